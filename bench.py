@@ -8,8 +8,13 @@ device inside the timed region, as a caller of the reference would pay it), then
 loss (-logProb.sum()/segments, train.py:187-189), which writes the dense [T,T,NBatch] score gradient and the
 [T-1,NBatch] noise gradient.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the headline line (metric, value, unit, higher_is_better,
+dtype, ms_per_step = milliseconds per timed step, ...).  Everything else it measures is behind --full (below).
+--dump-outputs DIR writes what the last timed step handed its caller as float32 .npy files (see _dump_outputs); the inputs
+are seeded, so two builds run with the same arguments can be compared output for output.
 
 One process per GPU.  Launched without torchrun and N > 1, bench.py spawns its N ranks itself
 (torch.multiprocessing, MASTER_ADDR=127.0.0.1); it never prints an N=1 line for N>1: the number of ranks in the
@@ -17,7 +22,7 @@ line is the world size the process group reports.  The chain (NBatch) axis is th
 own [T,T,352] problem (weak scaling: per-GPU work fixed), there is no data-path collective; with N > 1 each step also
 issues the fused 3-float loss/length/batch all-reduce of train.py:215-217 over RCCL.  Rank 0 prints ONE JSON line.
 
-Extra objects in the line:
+Extra objects in the line, with --full only:
   roofline     -- the log-partition forward sweep (semicrf_logz_fwd): algorithmic bytes 4*B*(T(T+1)/2 + T-1) per
                   launch / average launch time, HIP events on the launch stream.
   cpu_baseline -- the torch-CPU op-loop port of the reference's forward_backward (oracle/oracle.py), timed on this
@@ -26,7 +31,10 @@ Extra objects in the line:
                   decode (T=2048, NBatch=352, randn and model-like scores: device and end to end with Python lists),
                   the segment-shaped path at the model's real shape (T=691, 90 symbols, 1 and 4 segments: scorer + CRF
                   logProb fwd+bwd, decode + attribute features) and the train.py-shaped step (scorer + fused CRF
-                  log_prob -> (loss/50).backward() -> [3] all-reduce -> flat gradient all-reduce of 13.61 M parameters).
+                  log_prob -> (loss/50).backward() -> [3] all-reduce -> flat gradient all-reduce of 13.61 M parameters),
+                  and four more repetitions of the K timed steps (the spread of the headline).
+  decode       -- BASELINE.json's second metric (decode segments/s, T=2048, NBatch=352), taken from the extras.
+  multi_gpu_diagnostics -- N > 1: every rank's own time per step and the [3] loss all-reduce on its own.
 """
 from __future__ import annotations
 
@@ -65,6 +73,11 @@ def parse_args(argv=None):
     ap.add_argument("--T", type=int, default=1024)
     ap.add_argument("--nbatch", type=int, default=352)
     ap.add_argument("--impl", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure roofline, cpu_baseline, decode, extra (and multi_gpu_diagnostics at N > 1); the --no-* options "
+                         "below trim this set")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (logProb, score / noise gradients) to DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extra", action="store_true")
     ap.add_argument("--no-live-traffic", action="store_true", help="skip the two rocprofv3 --pmc passes behind roofline.traffic")
@@ -75,7 +88,10 @@ def parse_args(argv=None):
     ap.add_argument("--backend", default="nccl", help="process-group backend (nccl = RCCL; gloo only for --selftest-launch)")
     ap.add_argument("--selftest-launch", action="store_true",
                     help="CPU-only check of the launcher: form the process group, all-reduce, print the world size seen")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -185,6 +201,7 @@ def worker(args):
         if dist is not None:
             fused_loss_allreduce(loss, float(T), float(nseg))            # train.py:215-217, fused to one [3] over RCCL
         loss.backward()
+        return lp.detach()                                               # (what the caller got; the graph is not kept)
 
     def sync_all():
         torch.cuda.synchronize(dev)
@@ -199,12 +216,32 @@ def worker(args):
     log("warmup done")
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        lp_last = step()
     sync_all()
     elapsed_local = time.perf_counter() - t0
     elapsed = max_over_ranks(elapsed_local, dev)
     value = (1 if args.scaling == "strong" else seen_world) * args.steps / elapsed
     log(f"timed region done: {elapsed / args.steps * 1e3:.3f} ms/step")
+    if args.dump_outputs and rank == 0:
+        _dump_outputs(args.dump_outputs, lp_last, score.grad, noise.grad)
+        log(f"outputs of the last timed step written to {args.dump_outputs}")
+    line = {
+        "metric": "semi-CRF logProb+backward steps/sec at T=1024, NBatch=352" if (T, B_total) == (1024, 352)
+                  else f"semi-CRF logProb+backward steps/sec at T={T}, NBatch={B_total}",
+        "value": round(value, 3), "unit": "steps/s", "n_gpus": seen_world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True, "scaling": args.scaling,
+        "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": f"NeuralSemiCRFInterval(score, noise).logProb(intervals) fwd+bwd through the public API "
+                               f"(Python interval lists packed inside the timed region), T={T}, NBatch={B} per GPU"
+                               + (f" (= NBatch {B_total} cut across {seen_world} ranks)" if args.scaling == "strong" else "") + ", "
+                               f"fp32, exact-hash randn-like scores resident in HBM",
+                   "T": T, "NBatch": B, "impl": args.impl,
+                   "parallelism": f"chains sharded, {seen_world} rank(s) seen by the process group, no data-path collective"
+                                  + ("; [3] fp32 loss all-reduce per step over RCCL" if seen_world > 1 else "")},
+    }
+    if not args.full:
+        _emit(line, rank, dist)
+        return
     # the same K steps four more times (each bracketed like the timed region): the spread of the headline on THIS box.  `value`
     # stays the first region's.
     repeats = [elapsed / args.steps * 1e3]
@@ -289,26 +326,19 @@ def worker(args):
     if rank == 0 and seen_world == 1 and not args.no_cpu_baseline:
         cpu_baseline = _cpu_baseline(args, s_d, n_d, T, B, nseg)
 
+    line.update({
+        "roofline": roofline, "cpu_baseline": cpu_baseline,
+        # BASELINE.json's second metric ("decode segments/sec", configs[2]: T=2048, NBatch=352, forcedStartPos set) as a named field
+        "decode": extra.pop("_decode", None), "extra": extra,
+    })
+    if diag is not None:
+        line["multi_gpu_diagnostics"] = diag
+    _emit(line, rank, dist)
+
+
+def _emit(line, rank, dist):
+    """Rank 0 prints the ONE result line; every rank then leaves the process group."""
     if rank == 0:
-        line = {
-            "metric": "semi-CRF logProb+backward steps/sec at T=1024, NBatch=352" if (T, B_total) == (1024, 352)
-                      else f"semi-CRF logProb+backward steps/sec at T={T}, NBatch={B_total}",
-            "value": round(value, 3), "unit": "steps/s", "n_gpus": seen_world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True, "scaling": args.scaling,
-            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": f"NeuralSemiCRFInterval(score, noise).logProb(intervals) fwd+bwd through the public API "
-                                   f"(Python interval lists packed inside the timed region), T={T}, NBatch={B} per GPU"
-                                   + (f" (= NBatch {B_total} cut across {seen_world} ranks)" if args.scaling == "strong" else "") + ", "
-                                   f"fp32, exact-hash randn-like scores resident in HBM",
-                       "T": T, "NBatch": B, "impl": args.impl,
-                       "parallelism": f"chains sharded, {seen_world} rank(s) seen by the process group, no data-path collective"
-                                      + ("; [3] fp32 loss all-reduce per step over RCCL" if seen_world > 1 else "")},
-            "roofline": roofline, "cpu_baseline": cpu_baseline,
-            # BASELINE.json's second metric ("decode segments/sec", configs[2]: T=2048, NBatch=352, forcedStartPos set) as a named field
-            "decode": extra.pop("_decode", None), "extra": extra,
-        }
-        if diag is not None:
-            line["multi_gpu_diagnostics"] = diag
         print(json.dumps(line), flush=True)
     if dist is not None:
         dist.barrier()
@@ -318,6 +348,26 @@ def worker(args):
 # ---------------------------------------------------------------------------------------------------------------------
 # pieces
 # ---------------------------------------------------------------------------------------------------------------------
+
+DUMP_SAMPLE = 1 << 22          # at most this many cells per array written by --dump-outputs (16 MB of float32; three arrays)
+DUMP_SEED = 20261016
+
+
+def _dump_outputs(out_dir, lp, dscore, dnoise):
+    """What the last timed step handed its caller, as float32 arrays: logprob [B] and, after the backward pass, score_grad
+    [T, T, B] and noise_grad [T-1, B].  An array of more than DUMP_SAMPLE cells (the dense score gradient: 1.5 GB at T=1024,
+    NBatch=352) is written as <name>_sample.npy instead: its cells at DUMP_SAMPLE flat indices drawn with a fixed seed (sorted;
+    the zeros above the diagonal included), the same cells for the same T and NBatch in every run."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in (("logprob", lp), ("score_grad", dscore), ("noise_grad", dnoise)):
+        t = t.detach()
+        if t.numel() > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, t.numel(), size=DUMP_SAMPLE, dtype=np.int64))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+            name += "_sample"
+        np.save(os.path.join(out_dir, name + ".npy"), t.float().cpu().numpy())
+
 
 def _kernel_source_sha() -> str:
     h = hashlib.sha256()

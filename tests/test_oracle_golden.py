@@ -179,13 +179,12 @@ def test_segment_oracle(oracle, name):
     """The oracle's scorer + CRF composite (interval_score -> forward_backward / eval_path / viterbi -> the scorer's
     gradient in f64 numpy -> fetch_interval_features) against the reference's own modules run on the model glue
     (ModelTransformer.py:199-225, :256-266, :537-582): tests/golden/segment_*.npz."""
-    import torch
-    from segment_common import SEGMENT_CASES, check_segment_features, check_segment_grads, segment_inputs
+    from segment_common import SEGMENT_CASES, check_segment_features, check_segment_grads, linear_fp32_in_order, segment_inputs
     g = load_golden("segment_" + name)
     N, P, T, D = SEGMENT_CASES[name][:4]
     C = N * P
     ctx, W, bias, iv, gout, starts = segment_inputs(name)
-    y = torch.nn.functional.linear(ctx, W, bias)
+    y = linear_fp32_in_order(ctx, W, bias)
     q, k, diag = (t.reshape(C, T, -1).numpy() for t in y.split([D, D, 1], dim=-1))
     S = oracle.interval_score(q, k, diag[..., 0], "linear")
     Sd = S.astype(np.float64)

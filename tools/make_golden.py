@@ -618,6 +618,11 @@ def case_transcribe(names=None):
         for i in range(len(rec["velocity"])):
             d[f"head{i}_velocity_argmax"] = rec["velocity"][i].argmax(-1).astype(np.int32)
             d[f"head{i}_of"] = rec["of"][i].astype(np.float32)
+            # the refined onset / offset as the reference derives it (ModelTransformer.py:646-650), kept because its last bit
+            # depends on the host's math library and the tests compare the event times bit for bit
+            ofValue, _ = torch.from_numpy(d[f"head{i}_of"]).chunk(2, dim=-1)
+            ofValue = torch.clamp((torch.distributions.ContinuousBernoulli(logits=ofValue).mean - 0.5) / 0.99, -0.5, 0.5)
+            d[f"head{i}_ofValue"] = ofValue.contiguous().numpy()
         print(f"  transcribe {name}: {I['n_seg']} segments of T={T}, {len(final)} events after the merge ({len(kept['before'])} before "
               f"resolveOverlapping), {sum(len(p) for p in rec['pairs'])} decoded intervals, {time.time() - t0:.1f}s")
         save(f"transcribe_{name}", d)
