@@ -49,6 +49,7 @@ extern "C" {
 #define SEMICRF_OP_VITERBI 2
 #define SEMICRF_OP_EVAL_PATH 3
 #define SEMICRF_OP_INTERVAL_SCORE 4
+#define SEMICRF_OP_SAMPLE 5           /* B = nSample * NBatch of the semicrf_sample call */
 
 /* length scaling of the interval scorer (LayersTransformer.py:416-427) */
 #define SEMICRF_LEN_LINEAR 0
@@ -165,6 +166,26 @@ int semicrf_logz_bwd(const float* score, const float* noise, const float* v, con
 int semicrf_viterbi(const float* score, const float* noise, int T, int B, const int32_t* start,
                     int forward, int32_t* pairs, int64_t cap, int32_t* offsets,
                     void* ws, size_t ws_bytes, semicrf_stream_t stream);
+
+/*
+ * Exact posterior sampling of paths, p(y) = exp(evalPath(y) - logZ) (forward-filtering backward-sampling).  No counterpart in
+ * the reference (an extension of its surface, like decode_packed).  Adds nothing to the ABI's existing entry points (version 2).
+ *   v: alpha [T][B] of semicrf_logz_fwd on the same score / noise.
+ *   Draws k0 .. k0 + nSample - 1.  Draw k of chain c walks from t = T-1 (end == NULL) or end[c] down to frame 0; at a visited
+ *   frame t > 0 the predecessor is drawn from [skip, j = t-1, ..., 0] with weights exp(v[t-1] + n[t-1]), exp(v[j] + s[t,j]) by
+ *   inverse CDF over the row's own max-shifted sum Z (a candidate of weight 0 is never chosen; a threshold at or past the last
+ *   partial sum takes the last candidate of positive weight; a row without one takes the skip); at every visited frame (t,t)
+ *   is emitted iff u' < sigmoid(s[t,t]).
+ *   Uniforms: u = (splitmix64(idx, key) >> 40) * 2^-24, idx = ((k*B + c)*T + t)*2 + r, r = 0 predecessor, 1 singleton; the
+ *   result depends on (inputs, key, k) only -- not on nSample, k0 splits, grid or device.
+ *   pairs [cap][2], offsets [nSample*B + 1]: sample-major (chain c of draw k0 + k owns offsets[k*B + c] : offsets[k*B + c + 1]),
+ *   ascending by (begin, end) within a path, as semicrf_viterbi(forward = 1).  offsets[nSample*B] = -1 when v holds NaN in its
+ *   last row (a sweep that gave up on a bounded wait).
+ *   Workspace: semicrf_workspace_bytes(SEMICRF_OP_SAMPLE, T, nSample * B), about 5 * nSample * B * T int32.
+ */
+int semicrf_sample(const float* score, const float* noise, const float* v, int T, int B, int64_t k0, int nSample,
+                   uint64_t key, const int32_t* end, int32_t* pairs, int64_t cap, int32_t* offsets,
+                   void* ws, size_t ws_bytes, semicrf_stream_t stream);
 
 /*
  * Unnormalised path score.  Replaces: evalPath (:508-550).

@@ -16,6 +16,7 @@ What differs from the reference, invisibly at the API:
   * logProb() is ONE autograd node: its backward writes gout*(onehot(path) - marginal) in a single
     pass instead of summing two dense [T,T,B] gradients.
   * decode() backtracks on the device; only the packed (begin,end) pairs cross PCIe.
+EXTENSIONS of the reference's surface: decode_packed, and sample / sample_packed (exact posterior draws of paths).
 """
 from __future__ import annotations
 
@@ -647,6 +648,94 @@ def _decode(score, noiseScore, forcedStartPos: Optional[Sequence[int]], forward:
     return unpack_intervals(pairs_h, off_h, T)
 
 
+# --------------------------------------------------------------------------------------
+# posterior sampling (an extension of the reference's surface)
+# --------------------------------------------------------------------------------------
+
+_SAMPLE_CELLS = 1 << 24     # draws * chains * frames per device call: the workspace is ~20 B and the pairs buffer 16 B per cell
+
+
+def _sample_key(generator) -> int:
+    """The 64-bit key of a draw: one value of the (CPU) generator, so torch.manual_seed reproduces a draw."""
+    if generator is not None and torch.device(generator.device).type != "cpu":
+        raise ValueError(f"sample: the generator is on {generator.device}; pass a CPU torch.Generator (or None for torch's "
+                         "default one) -- it only makes the key, the draws themselves run where the scores live")
+    return int(torch.randint(0, 2 ** 63 - 1, (1,), generator=generator))
+
+
+def _sample_raw(score_c, noise_c, v, k0: int, n: int, key: int, end):
+    """Enqueue draws k0 .. k0+n-1 (code table + on-device walk + packing); returns (pairs [cap,2], offsets [n*B+1]) where the
+    scores live."""
+    T, B = score_c.shape[0], score_c.shape[2]
+    dev = score_c.device
+    pairs = torch.empty(n * B * 2 * T, 2, dtype=torch.int32, device=dev)
+    offsets = torch.empty(n * B + 1, dtype=torch.int32, device=dev)
+    ws = _lib.workspace(_lib.OP_SAMPLE, T, n * B, dev)
+    has = end is not None
+    _lib.ops().sample(score_c, noise_c, v, int(k0), int(n), int(key), end if has else offsets, has, pairs, offsets, ws)
+    return pairs, offsets
+
+
+def _sample(score, noiseScore, nSample: int, forcedEndPos: Optional[Sequence[int]], generator):
+    """(pairs [K,2], offsets [nSample*B+1]) as numpy int32, sample-major: chain c of draw k owns offsets[k*B+c]:offsets[k*B+c+1]."""
+    T, B = _check_inputs(score, noiseScore)
+    if int(nSample) != nSample or nSample < 1:
+        raise ValueError(f"sample: nSample must be a positive integer, got {nSample!r}")
+    nSample = int(nSample)
+    key = _sample_key(generator)
+    with torch.no_grad():
+        score_c, noise_c = _prep(score.detach()), _prep(noiseScore.detach())
+        dev = score_c.device
+        end = None
+        if forcedEndPos is not None:
+            if len(forcedEndPos) != B:
+                raise IndexError(f"forcedEndPos holds {len(forcedEndPos)} positions for {B} chains")
+            e = np.asarray(forcedEndPos, dtype=np.int64)
+            if (e < 0).any() or (e > T - 1).any():
+                raise IndexError(f"forcedEndPos out of range for T={T}")
+            end = torch.from_numpy(e.astype(np.int32)).to(dev, non_blocking=True)
+        _, v = _logz_fwd_raw(score_c, noise_c, want_v=True)
+        per = max(1, min(nSample, _SAMPLE_CELLS // (B * T)))
+        pair_parts, off_parts, base = [], [np.zeros(1, dtype=np.int32)], 0
+        for k0 in range(0, nSample, per):
+            n = min(per, nSample - k0)
+            pairs, offsets = _sample_raw(score_c, noise_c, v, k0, n, key, end)
+            off_h = offsets.cpu()                  # the one host sync per call
+            total = int(off_h[-1])
+            if total < 0:
+                _lib.async_error()                 # consumed here: the next call must not report this time-out again
+                raise RuntimeError("semicrf_sample: alpha holds NaN in its last row -- the inputs hold NaN (or -inf cells, which the "
+                                   "device's forward sweep does not take), or a bounded hand-off wait of the sweep timed out on the "
+                                   "device (GPU shared with work that kept part of the persistent kernel from running?); the draws are "
+                                   "invalid")
+            pair_parts.append(pairs[:total].cpu().numpy())
+            off_parts.append(off_h.numpy()[1:] + base)
+            base += total
+    pairs_np = np.concatenate(pair_parts).reshape(-1, 2).astype(np.int32, copy=False)
+    return pairs_np, np.concatenate(off_parts).astype(np.int32, copy=False)
+
+
+def sample_packed(score, noiseScore, nSample: int = 1, forcedEndPos: Optional[Sequence[int]] = None, generator=None):
+    """An EXTENSION of the reference's surface: `nSample` paths per chain drawn exactly from p(path) = exp(evalPath - logZ), as
+    two int32 arrays -- pairs [K, 2] of (begin, end) and offsets [nSample * nBatch + 1], sample-major (chain c of draw k owns
+    pairs[offsets[k * nBatch + c]:offsets[k * nBatch + c + 1]], ascending within a path, like decode_packed).
+
+    forcedEndPos: None or nBatch frames -- the path's END, as decode(forward=True, forcedStartPos=...): the prefix path on
+    [0, e] given a boundary at e.  generator: None (torch's default CPU generator: torch.manual_seed reproduces a draw) or a CPU
+    torch.Generator; it makes one 64-bit key, and the draws are a pure function of (inputs, key): the first m of n draws are
+    the m draws of nSample=m."""
+    return _sample(score, noiseScore, nSample, forcedEndPos, generator)
+
+
+def sample(score, noiseScore, nSample: int = 1, forcedEndPos: Optional[Sequence[int]] = None, generator=None) -> List[Intervals]:
+    """An EXTENSION of the reference's surface: `nSample` exact draws from p(path | score) (forward-filtering backward-sampling);
+    a list of nSample Intervals (one interval list per chain, the type decode returns).  Arguments as sample_packed."""
+    T, B = _check_inputs(score, noiseScore)
+    pairs, offsets = _sample(score, noiseScore, nSample, forcedEndPos, generator)
+    flat = unpack_intervals(torch.from_numpy(pairs), torch.from_numpy(offsets), T)
+    return [flat[k * B:(k + 1) * B] for k in range(len(flat) // B)]
+
+
 def viterbiBackward(score, noiseScore, forcedStartPos: Optional[List[int]] = None) -> Intervals:
     """Right-to-left Viterbi, the default decode (reference :13-104)."""
     return _decode(score, noiseScore, forcedStartPos, forward=False)
@@ -719,6 +808,18 @@ class NeuralSemiCRFInterval:
         ~25 ns of CPython object creation per interval on top of it (657 k intervals at T=2048, nBatch=352: 17 ms against 1 ms
         here); callers that go on with arrays anyway should take this one."""
         return _decode(self.score, self.noiseScore, forcedStartPos, bool(forward), packed=True)
+
+    def sample(self, nSample=1, forcedEndPos=None, generator=None):
+        """An EXTENSION of the reference's surface: a list of `nSample` Intervals drawn exactly from p(path) =
+        exp(evalPath(path) - computeLogZ()); each element plugs into logProb / evalPath.  forcedEndPos (None or nBatch frames) is
+        the path's END, as decode(forward=True, forcedStartPos=...); generator: None (torch's default CPU generator) or a CPU
+        torch.Generator.  Runs where the scores live (HIP kernels on the GPU, host kernels on the CPU); no gradient."""
+        return sample(self.score, self.noiseScore, nSample, forcedEndPos, generator)
+
+    def sample_packed(self, nSample=1, forcedEndPos=None, generator=None):
+        """`sample` as two int32 arrays, pairs [K, 2] and offsets [nSample * nBatch + 1] (sample-major), before the Python lists are
+        built -- see the module-level sample_packed."""
+        return sample_packed(self.score, self.noiseScore, nSample, forcedEndPos, generator)
 
     def evalPath(self, intervals):
         """compute the unnormalized score"""

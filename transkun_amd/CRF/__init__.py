@@ -2,4 +2,4 @@
 from .NeuralSemiCRFInterval import *  # noqa: F401,F403
 from .NeuralSemiCRFInterval import (NeuralSemiCRFInterval, viterbi, viterbiBackward, computeLogZ,  # noqa: F401
                                     forward_backward, evalPath, computeLogZFasterGrad,
-                                    ComputeLogZFasterGrad)
+                                    ComputeLogZFasterGrad, sample, sample_packed)

@@ -93,6 +93,9 @@ void launch_stage_linear(const float* W, const float* bias, int D, int size, int
 int launch_proj_tn(const float* A, long long lda, long long M, int R, int extra_col0, int total_rows, const float* X, long long ldx, int N,
                    float* dW, long long lddw, float* db, void* ws, size_t ws_bytes, hipStream_t stream);
 size_t persist_workspace_bytes(int T, int B);
+size_t sample_workspace_bytes(int T, int nB);
+void launch_sample(const float* score, const float* noise, const float* v, int T, int B, long long k0, int nSample,
+                   unsigned long long key, const int* end, int* pairs, long long cap, int* offsets, void* ws, hipStream_t stream);
 bool persist_supported(int T, int B);
 int launch_persist_sweep(int mode, int dir, const float* score, const float* noise, int T, int B, float* u_out,
                          float* last_out, int* code, void* ws, hipStream_t stream, int lease, unsigned lease_tag);
@@ -273,6 +276,7 @@ size_t semicrf_workspace_bytes(int op, int T, int B)
                    persist_workspace_bytes(T, B) + 4096;
         case SEMICRF_OP_EVAL_PATH: return 4096;
         case SEMICRF_OP_INTERVAL_SCORE: return 4096;
+        case SEMICRF_OP_SAMPLE: return sample_workspace_bytes(T, B);
         default: return 0;
     }
 }
@@ -476,6 +480,24 @@ int semicrf_viterbi(const float* score, const float* noise, int T, int B, const 
     const unsigned* err = fast ? persist_error_words(pws, &nerr, &estride) : nullptr;
     launch_backtrack(code, T, B, start, forward ? 1 : 0, region, counts, pairs, (long long)cap, offsets, st, err, nerr, estride);
     SEMICRF_CHECK_LAUNCH("semicrf_viterbi");
+    return SEMICRF_OK;
+}
+
+int semicrf_sample(const float* score, const float* noise, const float* v, int T, int B, int64_t k0, int nSample, uint64_t key,
+                   const int32_t* end, int32_t* pairs, int64_t cap, int32_t* offsets, void* ws, size_t ws_bytes,
+                   semicrf_stream_t stream)
+{
+    if (int rc = check_common(score, noise, T, B)) return rc;
+    SEMICRF_CHECK_ARG(v != nullptr, "v (alpha) is NULL");
+    SEMICRF_CHECK_ARG(nSample >= 1 && k0 >= 0, "nSample=%d must be >= 1 and k0=%lld >= 0", nSample, (long long)k0);
+    SEMICRF_CHECK_ARG(pairs && offsets && cap >= 0, "pairs/offsets must be non-NULL");
+    SEMICRF_CHECK_ARG((long long)nSample * B * 2 * T < (1ll << 31), "nSample*B*2T exceeds int32 offsets");
+    SEMICRF_CHECK_ARG((long long)T * ((B + 63) / 64) < (1ll << 31), "T*ceil(B/64) exceeds the grid");
+    SEMICRF_CHECK_ARG(ws != nullptr, "workspace is NULL");
+    if (ws_bytes < sample_workspace_bytes(T, nSample * B)) { set_error("workspace too small for sample"); return SEMICRF_EWORKSPACE; }
+    launch_sample(score, noise, v, T, B, (long long)k0, nSample, (unsigned long long)key, end, pairs, (long long)cap, offsets, ws,
+                  (hipStream_t)stream);
+    SEMICRF_CHECK_LAUNCH("semicrf_sample");
     return SEMICRF_OK;
 }
 

@@ -8,6 +8,7 @@
 //
 // Arithmetic: fp32 values as in the reference, sums of exponentials accumulated in double; decode is exact: one fp32 add
 // per candidate, first maximum in the reference's candidate order.
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -238,6 +239,80 @@ void viterbi(const float* score, const float* noise, int T, int B, const int32_t
             if (k < cap) { pairs[2 * k] = o[i]; pairs[2 * k + 1] = o[i + 1]; }
     }
     offsets[B] = (int32_t)k;
+}
+
+// Posterior sampling (include/semicrf_hip.h: semicrf_sample; the device kernel is sample.hip).  Per (frame, chain) the candidate
+// weights exp(x - max) in double and their running sums are built once; every draw that visits the frame takes the first candidate
+// whose running sum exceeds u * Z (binary search), or -- u * Z at or past the total -- the last one of positive weight.  The
+// uniforms are the device's: (splitmix64(((k*B + c)*T + t)*2 + r, key) >> 40) * 2^-24.
+namespace {
+inline uint64_t splitmix64(uint64_t idx, uint64_t key)
+{
+    uint64_t z = idx + key * 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+inline double uniform24(uint64_t idx, uint64_t key) { return (double)(splitmix64(idx, key) >> 40) * (1.0 / 16777216.0); }
+}  // namespace
+
+void sample(const float* score, const float* noise, const float* v, int T, int B, int64_t k0, int nSample, uint64_t key,
+            const int32_t* end, int32_t* pairs, int64_t cap, int32_t* offsets)
+{
+    const size_t Bs = (size_t)B;
+    const int64_t nB = (int64_t)nSample * B;
+    std::vector<std::vector<int32_t>> out((size_t)nB);
+#pragma omp parallel for schedule(dynamic, 1)
+    for (int c = 0; c < B; ++c) {
+        // cum[t][i]: running sums of the candidates of frame t (i = 0 skip, i >= 1 the interval (t - i, t)), built on first visit
+        std::vector<std::vector<double>> cum((size_t)T);
+        auto row = [&](int t) -> const std::vector<double>& {
+            std::vector<double>& r = cum[(size_t)t];
+            if (!r.empty() || t == 0) return r;
+            std::vector<float> x((size_t)t + 1);
+            x[0] = v[(size_t)(t - 1) * Bs + c] + noise[(size_t)(t - 1) * Bs + c];
+            for (int i = 1; i <= t; ++i) x[(size_t)i] = v[(size_t)(t - i) * Bs + c] + score[((size_t)t * T + (t - i)) * Bs + c];
+            float m = -INFINITY;
+            for (float xi : x) m = xi > m ? xi : m;
+            r.resize((size_t)t + 1);
+            double acc = 0.0;
+            for (int i = 0; i <= t; ++i) {
+                acc += m == -INFINITY ? 0.0 : exp((double)x[(size_t)i] - (double)m);
+                r[(size_t)i] = acc;
+            }
+            return r;
+        };
+        for (int k = 0; k < nSample; ++k) {
+            std::vector<int32_t> rev;
+            int t = end ? end[c] : T - 1;
+            for (;;) {
+                const uint64_t base = ((uint64_t)(k0 + k) * (uint64_t)B + (uint64_t)c) * (uint64_t)T + (uint64_t)t;
+                const double sg = 1.0 / (1.0 + exp(-(double)score[((size_t)t * T + t) * Bs + c]));
+                if (uniform24(2 * base + 1, key) < sg) { rev.push_back(t); rev.push_back(t); }
+                if (t == 0) break;
+                const std::vector<double>& r = row(t);
+                const double Z = r.back();
+                int pick = 0;                                       // no candidate of positive weight: the skip
+                if (Z > 0.0) {
+                    const double thr = uniform24(2 * base, key) * Z;
+                    if (thr < Z) pick = (int)(std::upper_bound(r.begin(), r.end(), thr) - r.begin());
+                    else pick = (int)(std::lower_bound(r.begin(), r.end(), Z) - r.begin());   // the last candidate of positive weight
+                }
+                if (pick == 0) t -= 1;
+                else { rev.push_back(t - pick); rev.push_back(t); t -= pick; }
+            }
+            std::vector<int32_t>& o = out[(size_t)k * Bs + c];
+            for (size_t i = rev.size(); i >= 2; i -= 2) { o.push_back(rev[i - 2]); o.push_back(rev[i - 1]); }
+        }
+    }
+    int64_t n = 0;
+    for (int64_t p = 0; p < nB; ++p) {
+        offsets[p] = (int32_t)n;
+        const std::vector<int32_t>& o = out[(size_t)p];
+        for (size_t i = 0; i + 1 < o.size(); i += 2, ++n)
+            if (n < cap) { pairs[2 * n] = o[i]; pairs[2 * n + 1] = o[i + 1]; }
+    }
+    offsets[nB] = (int32_t)n;
 }
 
 // evalPath (:508-550): sum of the path's interval scores plus the noise of every gap no interval covers

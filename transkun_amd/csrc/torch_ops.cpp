@@ -123,6 +123,20 @@ void viterbi(Tensor score, Tensor noise, Tensor start, bool has_start, bool forw
                           (size_t)ws.numel(), c.stream),
           "semicrf_viterbi");
 }
+// posterior sampling (semicrf_sample): key is the 64-bit key as a signed int (two's complement); end: B ints when has_end
+void sample(Tensor score, Tensor noise, Tensor v, int64_t k0, int64_t nSample, int64_t key, Tensor end, bool has_end, Tensor pairs,
+            Tensor offsets, Tensor ws)
+{
+    Ctx c(score); c.same(score, noise, v, pairs, offsets, ws);
+    if (has_end) c.same(score, end);
+    const Dims d = crf_dims(score, noise);
+    STD_TORCH_CHECK(nSample >= 1 && nSample < (1 << 30) && k0 >= 0, "semicrf: bad nSample / k0");
+    STD_TORCH_CHECK(pairs.dim() == 2 && pairs.size(1) == 2, "semicrf: pairs must be [cap, 2]");
+    check(semicrf_sample(cfp(score), cfp(noise), f32(v, (int64_t)d.T * d.B, "v"), d.T, d.B, k0, (int)nSample, (uint64_t)key,
+                         has_end ? i32(end, d.B, "end") : nullptr, i32(pairs, 0, "pairs"), (int64_t)pairs.size(0),
+                         i32(offsets, nSample * d.B + 1, "offsets"), bytes(ws, "ws"), (size_t)ws.numel(), c.stream),
+          "semicrf_sample");
+}
 void eval_path(Tensor score, Tensor noise, Tensor pairs, int64_t K, Tensor offsets, Tensor out, Tensor ws)
 {
     Ctx c(score); c.same(score, noise, pairs, offsets, out);
@@ -214,6 +228,21 @@ void viterbi_cpu(Tensor score, Tensor noise, Tensor start, bool has_start, bool 
         for (int c = 0; c < d.B; ++c) STD_TORCH_CHECK(st[c] >= 0 && st[c] < d.T, "semicrf: forcedStartPos out of range");
     semicrf_cpu::viterbi(cfp(score), cfp(noise), d.T, d.B, st, forward ? 1 : 0, i32(pairs, 0, "pairs"), (int64_t)pairs.size(0),
                          i32(offsets, d.B + 1, "offsets"));
+}
+void sample_cpu(Tensor score, Tensor noise, Tensor v, int64_t k0, int64_t nSample, int64_t key, Tensor end, bool has_end, Tensor pairs,
+                Tensor offsets, Tensor ws)
+{
+    all_cpu(score, noise, v, pairs, offsets);
+    if (has_end) all_cpu(end);
+    const Dims d = crf_dims(score, noise);
+    STD_TORCH_CHECK(nSample >= 1 && nSample < (1 << 30) && k0 >= 0, "semicrf: bad nSample / k0");
+    STD_TORCH_CHECK(nSample * d.B * 2 * d.T < (1ll << 31), "semicrf: nSample*B*2T exceeds int32 offsets");
+    STD_TORCH_CHECK(pairs.dim() == 2 && pairs.size(1) == 2, "semicrf: pairs must be [cap, 2]");
+    const int32_t* e = has_end ? i32(end, d.B, "end") : nullptr;
+    if (e)
+        for (int c = 0; c < d.B; ++c) STD_TORCH_CHECK(e[c] >= 0 && e[c] < d.T, "semicrf: forcedEndPos out of range");
+    semicrf_cpu::sample(cfp(score), cfp(noise), f32(v, (int64_t)d.T * d.B, "v"), d.T, d.B, k0, (int)nSample, (uint64_t)key, e,
+                        i32(pairs, 0, "pairs"), (int64_t)pairs.size(0), i32(offsets, nSample * d.B + 1, "offsets"));
 }
 inline void check_path(const int32_t* pairs, int64_t K, const int32_t* offsets, int T, int B)
 {
@@ -471,6 +500,8 @@ STABLE_TORCH_LIBRARY(semicrf, m)
     m.def("beta(Tensor score, Tensor noise, Tensor(a!) out, Tensor(b!) ws) -> ()");
     m.def("viterbi(Tensor score, Tensor noise, Tensor start, bool has_start, bool forward, Tensor(a!) pairs, Tensor(b!) offsets, "
           "Tensor(c!) ws) -> ()");
+    m.def("sample(Tensor score, Tensor noise, Tensor v, int k0, int nSample, int key, Tensor end, bool has_end, Tensor(a!) pairs, "
+          "Tensor(b!) offsets, Tensor(c!) ws) -> ()");
     m.def("eval_path(Tensor score, Tensor noise, Tensor pairs, int K, Tensor offsets, Tensor(a!) out, Tensor(b!) ws) -> ()");
     m.def("eval_path_bwd(Tensor gout, int T, int B, Tensor pairs, int K, Tensor offsets, Tensor(a!) dScore, bool has_ds, Tensor(b!) dNoise, "
           "bool has_dn) -> ()");
@@ -516,6 +547,7 @@ STABLE_TORCH_LIBRARY_IMPL(semicrf, CPU, m)
     m.impl("logz_bwd", TORCH_BOX(&logz_bwd_cpu));
     m.impl("beta", TORCH_BOX(&beta_cpu));
     m.impl("viterbi", TORCH_BOX(&viterbi_cpu));
+    m.impl("sample", TORCH_BOX(&sample_cpu));
     m.impl("eval_path", TORCH_BOX(&eval_path_cpu));
     m.impl("eval_path_bwd", TORCH_BOX(&eval_path_bwd_cpu));
     m.impl("logprob_fwd", TORCH_BOX(&logprob_fwd_cpu));
@@ -528,6 +560,7 @@ STABLE_TORCH_LIBRARY_IMPL(semicrf, CUDA, m)
     m.impl("logz_bwd", TORCH_BOX(&logz_bwd));
     m.impl("beta", TORCH_BOX(&beta));
     m.impl("viterbi", TORCH_BOX(&viterbi));
+    m.impl("sample", TORCH_BOX(&sample));
     m.impl("eval_path", TORCH_BOX(&eval_path));
     m.impl("eval_path_bwd", TORCH_BOX(&eval_path_bwd));
     m.impl("logprob_fwd", TORCH_BOX(&logprob_fwd));
