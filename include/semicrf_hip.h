@@ -50,6 +50,7 @@ extern "C" {
 #define SEMICRF_OP_EVAL_PATH 3
 #define SEMICRF_OP_INTERVAL_SCORE 4
 #define SEMICRF_OP_SAMPLE 5           /* B = nSample * NBatch of the semicrf_sample call */
+#define SEMICRF_OP_VITERBI_NBEST 6    /* B = k * NBatch of the semicrf_viterbi_nbest call */
 
 /* length scaling of the interval scorer (LayersTransformer.py:416-427) */
 #define SEMICRF_LEN_LINEAR 0
@@ -186,6 +187,24 @@ int semicrf_viterbi(const float* score, const float* noise, int T, int B, const 
 int semicrf_sample(const float* score, const float* noise, const float* v, int T, int B, int64_t k0, int nSample,
                    uint64_t key, const int32_t* end, int32_t* pairs, int64_t cap, int32_t* offsets,
                    void* ws, size_t ws_bytes, semicrf_stream_t stream);
+
+/*
+ * k-best Viterbi: the k highest-scoring paths of every chain, ranked.  No counterpart in the reference (an extension of its
+ * surface, like decode_packed).  Adds nothing to the ABI's existing entry points (version 2).
+ *   A path is what semicrf_viterbi returns for a chain; its value is the Viterbi recursion's: one fp32 add per candidate, the
+ *   singleton last (u = best + (singleton ? s[t,t] : 0)).  At every frame the partial paths are ordered by (1) value, descending,
+ *   (2) value before the singleton, descending, (3) candidate in semicrf_viterbi's tie order (skip first, then the smaller index
+ *   of the other endpoint), (4) predecessor rank, ascending, (5) the singleton, "on" first iff s[t,t] > 0; the first k are kept.
+ *   The order does not depend on k: k = 1 is semicrf_viterbi bit for bit, and the first m ranks of k are the m-best.
+ *   k: 1..16.  start, forward: as semicrf_viterbi (start is the END frame when forward = 1).
+ *   pairs [cap][2], offsets [k*B + 1]: rank-major (chain c of rank r owns offsets[r*B + c] : offsets[r*B + c + 1]), each path in
+ *   semicrf_viterbi's order.  scores [k][B]: the ranked values; npaths [B]: how many ranks exist (fewer than k paths at tiny T).
+ *   An absent rank has no intervals and score -inf; a real path of value -inf (-inf cells) is present.
+ *   Workspace: semicrf_workspace_bytes(SEMICRF_OP_VITERBI_NBEST, T, k * B), about 9 * k * B * T int32.
+ */
+int semicrf_viterbi_nbest(const float* score, const float* noise, int T, int B, int k, const int32_t* start, int forward,
+                          int32_t* pairs, int64_t cap, int32_t* offsets, float* scores, int32_t* npaths, void* ws, size_t ws_bytes,
+                          semicrf_stream_t stream);
 
 /*
  * Unnormalised path score.  Replaces: evalPath (:508-550).

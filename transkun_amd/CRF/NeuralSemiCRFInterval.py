@@ -16,7 +16,8 @@ What differs from the reference, invisibly at the API:
   * logProb() is ONE autograd node: its backward writes gout*(onehot(path) - marginal) in a single
     pass instead of summing two dense [T,T,B] gradients.
   * decode() backtracks on the device; only the packed (begin,end) pairs cross PCIe.
-EXTENSIONS of the reference's surface: decode_packed, and sample / sample_packed (exact posterior draws of paths).
+EXTENSIONS of the reference's surface: decode_packed, sample / sample_packed (exact posterior draws of paths), and
+  decode_nbest / decode_nbest_packed (the k best paths, ranked).
 """
 from __future__ import annotations
 
@@ -736,6 +737,80 @@ def sample(score, noiseScore, nSample: int = 1, forcedEndPos: Optional[Sequence[
     return [flat[k * B:(k + 1) * B] for k in range(len(flat) // B)]
 
 
+# --------------------------------------------------------------------------------------
+# k-best Viterbi (an extension of the reference's surface)
+# --------------------------------------------------------------------------------------
+
+NBEST_MAX = 16
+
+
+def _nbest_raw(score_c, noise_c, k: int, start, forward: bool):
+    """Enqueue semicrf_viterbi_nbest; returns device tensors pairs [cap, 2] and meta = offsets [k*B+1] | npaths [B] | the bits of
+    scores [k*B] (one int32 buffer: one copy back)."""
+    T, B = score_c.shape[0], score_c.shape[2]
+    dev = score_c.device
+    nB = k * B
+    pairs = torch.empty(nB * 2 * T, 2, dtype=torch.int32, device=dev)
+    meta = torch.empty(2 * nB + 1 + B, dtype=torch.int32, device=dev)
+    offsets, npaths = meta[:nB + 1], meta[nB + 1:nB + 1 + B]
+    scores = meta[nB + 1 + B:].view(torch.float32)
+    ws = _lib.workspace(_lib.OP_VITERBI_NBEST, T, nB, dev)
+    has = start is not None
+    _lib.ops().viterbi_nbest(score_c, noise_c, k, start if has else offsets, has, bool(forward), pairs, offsets, scores, npaths, ws)
+    return pairs, meta
+
+
+def _nbest(score, noiseScore, k, forcedStartPos: Optional[Sequence[int]], forward: bool):
+    """(pairs [K,2], offsets [k*B+1], scores [k,B] float32, npaths [B]) as numpy arrays, rank-major: chain c of rank r owns
+    pairs[offsets[r*B+c]:offsets[r*B+c+1]]."""
+    T, B = _check_inputs(score, noiseScore)
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+        raise ValueError(f"decode_nbest: k must be an integer in [1, {NBEST_MAX}], got {k!r}")
+    k = int(k)
+    if not 1 <= k <= NBEST_MAX:
+        raise ValueError(f"decode_nbest: k must be in [1, {NBEST_MAX}], got {k}")
+    with torch.no_grad():
+        score_c, noise_c = _prep(score.detach()), _prep(noiseScore.detach())
+        dev = score_c.device
+        start = None
+        if forcedStartPos is not None:
+            if len(forcedStartPos) != B:
+                raise IndexError(f"forcedStartPos holds {len(forcedStartPos)} positions for {B} chains")
+            st = np.asarray(forcedStartPos, dtype=np.int64)
+            if (st < 0).any() or (st > T - 1).any():
+                raise IndexError(f"forcedStartPos out of range for T={T}")
+            start = torch.from_numpy(st.astype(np.int32)).to(dev, non_blocking=True)
+        nB = k * B
+        pairs, meta = _nbest_raw(score_c, noise_c, k, start, forward)
+        meta_h = meta.cpu().numpy()                # the one host sync per call
+        total = int(meta_h[nB])
+        pairs_h = pairs[:total].cpu().numpy()
+    return (pairs_h, meta_h[:nB + 1].copy(), meta_h[nB + 1 + B:].view(np.float32).reshape(k, B).copy(),
+            meta_h[nB + 1:nB + 1 + B].copy())
+
+
+def viterbi_nbest_packed(score, noiseScore, k: int, forcedStartPos: Optional[Sequence[int]] = None, forward: bool = False):
+    """An EXTENSION of the reference's surface: the k highest-scoring paths of every chain as numpy arrays (pairs [K, 2] int32,
+    offsets [k * nBatch + 1] int32, scores [k, nBatch] float32, npaths [nBatch] int32).  Rank-major: chain c of rank r owns
+    pairs[offsets[r * nBatch + c]:offsets[r * nBatch + c + 1]], in decode's order.  scores are the Viterbi recursion's fp32
+    values; ranks past npaths[c] (fewer than k paths exist at tiny T) are empty with score -inf.  Ties are broken by a fixed
+    order (include/semicrf_hip.h: semicrf_viterbi_nbest), so k = 1 is decode bit for bit and the first m ranks of k are m-best.
+    forcedStartPos / forward: as decode (the END frame when forward=True).  1 <= k <= 16; no gradient."""
+    return _nbest(score, noiseScore, k, forcedStartPos, forward)
+
+
+def viterbi_nbest(score, noiseScore, k: int, forcedStartPos: Optional[Sequence[int]] = None, forward: bool = False):
+    """An EXTENSION of the reference's surface: (paths, scores) -- paths a list of k Intervals (rank r: one interval list per
+    chain, the type decode returns, None where chain c has fewer than r + 1 paths), scores a float32 numpy [k, nBatch].
+    Arguments as viterbi_nbest_packed; every present path plugs into evalPath / logProb."""
+    T, B = _check_inputs(score, noiseScore)
+    pairs, offsets, scores, npaths = _nbest(score, noiseScore, k, forcedStartPos, forward)
+    flat = unpack_intervals(torch.from_numpy(pairs), torch.from_numpy(offsets), T)
+    k = scores.shape[0]
+    paths = [[flat[r * B + c] if r < npaths[c] else None for c in range(B)] for r in range(k)]
+    return paths, scores
+
+
 def viterbiBackward(score, noiseScore, forcedStartPos: Optional[List[int]] = None) -> Intervals:
     """Right-to-left Viterbi, the default decode (reference :13-104)."""
     return _decode(score, noiseScore, forcedStartPos, forward=False)
@@ -820,6 +895,17 @@ class NeuralSemiCRFInterval:
         """`sample` as two int32 arrays, pairs [K, 2] and offsets [nSample * nBatch + 1] (sample-major), before the Python lists are
         built -- see the module-level sample_packed."""
         return sample_packed(self.score, self.noiseScore, nSample, forcedEndPos, generator)
+
+    def decode_nbest(self, k, forcedStartPos=None, forward=False):
+        """An EXTENSION of the reference's surface: the k highest-scoring paths of every chain, ranked -- (paths, scores) with
+        paths a list of k Intervals (None where a chain has fewer than k paths) and scores a float32 numpy [k, nBatch].  k = 1
+        is decode(forcedStartPos, forward) bit for bit; see the module-level viterbi_nbest.  No gradient."""
+        return viterbi_nbest(self.score, self.noiseScore, k, forcedStartPos, bool(forward))
+
+    def decode_nbest_packed(self, k, forcedStartPos=None, forward=False):
+        """`decode_nbest` as numpy arrays (pairs, offsets [k * nBatch + 1] rank-major, scores [k, nBatch], npaths [nBatch]) before
+        the Python lists are built -- see the module-level viterbi_nbest_packed."""
+        return viterbi_nbest_packed(self.score, self.noiseScore, k, forcedStartPos, bool(forward))
 
     def evalPath(self, intervals):
         """compute the unnormalized score"""

@@ -2,4 +2,5 @@
 from .NeuralSemiCRFInterval import *  # noqa: F401,F403
 from .NeuralSemiCRFInterval import (NeuralSemiCRFInterval, viterbi, viterbiBackward, computeLogZ,  # noqa: F401
                                     forward_backward, evalPath, computeLogZFasterGrad,
-                                    ComputeLogZFasterGrad, sample, sample_packed)
+                                    ComputeLogZFasterGrad, sample, sample_packed,
+                                    viterbi_nbest, viterbi_nbest_packed)

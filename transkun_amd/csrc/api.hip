@@ -94,6 +94,9 @@ int launch_proj_tn(const float* A, long long lda, long long M, int R, int extra_
                    float* dW, long long lddw, float* db, void* ws, size_t ws_bytes, hipStream_t stream);
 size_t persist_workspace_bytes(int T, int B);
 size_t sample_workspace_bytes(int T, int nB);
+size_t nbest_workspace_bytes(int T, int nB);
+void launch_viterbi_nbest(const float* score, const float* noise, int T, int B, int k, const int* start, int forward, int* pairs,
+                          long long cap, int* offsets, float* scores, int* npaths, void* ws, hipStream_t stream);
 void launch_sample(const float* score, const float* noise, const float* v, int T, int B, long long k0, int nSample,
                    unsigned long long key, const int* end, int* pairs, long long cap, int* offsets, void* ws, hipStream_t stream);
 bool persist_supported(int T, int B);
@@ -277,6 +280,7 @@ size_t semicrf_workspace_bytes(int op, int T, int B)
         case SEMICRF_OP_EVAL_PATH: return 4096;
         case SEMICRF_OP_INTERVAL_SCORE: return 4096;
         case SEMICRF_OP_SAMPLE: return sample_workspace_bytes(T, B);
+        case SEMICRF_OP_VITERBI_NBEST: return nbest_workspace_bytes(T, B);
         default: return 0;
     }
 }
@@ -498,6 +502,23 @@ int semicrf_sample(const float* score, const float* noise, const float* v, int T
     launch_sample(score, noise, v, T, B, (long long)k0, nSample, (unsigned long long)key, end, pairs, (long long)cap, offsets, ws,
                   (hipStream_t)stream);
     SEMICRF_CHECK_LAUNCH("semicrf_sample");
+    return SEMICRF_OK;
+}
+
+int semicrf_viterbi_nbest(const float* score, const float* noise, int T, int B, int k, const int32_t* start, int forward,
+                          int32_t* pairs, int64_t cap, int32_t* offsets, float* scores, int32_t* npaths, void* ws, size_t ws_bytes,
+                          semicrf_stream_t stream)
+{
+    if (int rc = check_common(score, noise, T, B)) return rc;
+    SEMICRF_CHECK_ARG(k >= 1 && k <= 16, "k=%d must be in [1, 16]", k);
+    SEMICRF_CHECK_ARG(pairs && offsets && cap >= 0, "pairs/offsets must be non-NULL");
+    SEMICRF_CHECK_ARG(scores && npaths, "scores/npaths must be non-NULL");
+    SEMICRF_CHECK_ARG((long long)k * B * 2 * T < (1ll << 31), "k*B*2T exceeds int32 offsets");
+    SEMICRF_CHECK_ARG(ws != nullptr, "workspace is NULL");
+    if (ws_bytes < nbest_workspace_bytes(T, k * B)) { set_error("workspace too small for viterbi_nbest"); return SEMICRF_EWORKSPACE; }
+    launch_viterbi_nbest(score, noise, T, B, k, start, forward ? 1 : 0, pairs, (long long)cap, offsets, scores, npaths, ws,
+                         (hipStream_t)stream);
+    SEMICRF_CHECK_LAUNCH("semicrf_viterbi_nbest");
     return SEMICRF_OK;
 }
 

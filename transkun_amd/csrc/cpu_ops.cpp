@@ -315,6 +315,137 @@ void sample(const float* score, const float* noise, const float* v, int T, int B
     offsets[nB] = (int32_t)n;
 }
 
+// k-best Viterbi (include/semicrf_hip.h: semicrf_viterbi_nbest; the device kernel is nbest.hip).  Per frame and chain a sorted
+// list of at most k partial paths, each (value, base, order word); a candidate's ranks are tried in ascending order and the scan of
+// a candidate stops at the first rank whose two singleton variants both fail to beat the list's k-th entry (later ranks of the
+// same candidate are no better).  Back-pointer word: (cidx << 5) | (rank << 1) | singleton, cidx 0 = skip, else the other
+// endpoint + 1; the order word is that ^ (s[t,t] > 0), so "on" sorts first exactly when decode would take it; -1 = absent rank.
+namespace {
+struct NbItem {
+    float v, b;
+    int32_t o;
+};
+inline bool nb_better(const NbItem& x, const NbItem& y)
+{
+    return x.v > y.v || (x.v == y.v && (x.b > y.b || (x.b == y.b && x.o < y.o)));
+}
+// insert into the sorted list L[0..n) of capacity k; false when x does not make the list
+inline bool nb_insert(NbItem* L, int& n, int k, const NbItem& x)
+{
+    if (n == k && !nb_better(x, L[k - 1])) return false;
+    int i = n < k ? n++ : k - 1;
+    while (i > 0 && nb_better(x, L[i - 1])) { L[i] = L[i - 1]; --i; }
+    L[i] = x;
+    return true;
+}
+}  // namespace
+
+void viterbi_nbest(const float* score, const float* noise, int T, int B, int k, const int32_t* start, int forward, int32_t* pairs,
+                   int64_t cap, int32_t* offsets, float* scores, int32_t* npaths)
+{
+    const size_t Bs = (size_t)B, K = (size_t)k;
+    std::vector<float> u((size_t)T * K * Bs);             // [frame][rank][chain]
+    std::vector<int32_t> code((size_t)T * K * Bs);
+    std::vector<int32_t> cnt((size_t)T * Bs);
+#pragma omp parallel for schedule(dynamic, 1)
+    for (int c0 = 0; c0 < B; c0 += CB) {
+        const int nc = B - c0 < CB ? B - c0 : CB;
+        NbItem L[CB][16];
+        int n[CB];
+        for (int p = 0; p < T; ++p) {
+            const int t = forward ? p : T - 1 - p;
+            const float* dg = score + ((size_t)t * T + t) * Bs + c0;
+            for (int c = 0; c < nc; ++c) n[c] = 0;
+            // candidate cidx with predecessor frame q and cell value x, for chain c of the block
+            auto push = [&](int c, int q, float x, int32_t cidx) {
+                const float d = dg[c];
+                const int32_t flip = d > 0.0f ? 1 : 0;
+                const int np = cnt[(size_t)q * Bs + c0 + c];
+                for (int r = 0; r < np; ++r) {
+                    const float base = u[((size_t)q * K + r) * Bs + c0 + c] + x;
+                    const int32_t w = (cidx << 5) | (r << 1);
+                    const NbItem on{base + d, base, (w | 1) ^ flip}, off{base + 0.0f, base, w ^ flip};
+                    const bool a = nb_insert(L[c], n[c], k, flip ? on : off);
+                    const bool b = nb_insert(L[c], n[c], k, flip ? off : on);
+                    if (!a && !b) break;
+                }
+            };
+            if (p == 0) {                                  // the terminal frame: the empty path, with or without (t,t)
+                for (int c = 0; c < nc; ++c) {
+                    const float d = dg[c];
+                    const int32_t flip = d > 0.0f ? 1 : 0;
+                    const NbItem on{0.0f + d, 0.0f, 1 ^ flip}, off{0.0f + 0.0f, 0.0f, 0 ^ flip};
+                    nb_insert(L[c], n[c], k, flip ? on : off);
+                    nb_insert(L[c], n[c], k, flip ? off : on);
+                }
+            } else if (forward) {
+                for (int c = 0; c < nc; ++c) push(c, t - 1, noise[(size_t)(t - 1) * Bs + c0 + c], 0);
+                for (int j = 0; j < t; ++j) {
+                    const float* cell = score + ((size_t)t * T + j) * Bs + c0;
+                    for (int c = 0; c < nc; ++c) push(c, j, cell[c], j + 1);
+                }
+            } else {
+                for (int c = 0; c < nc; ++c) push(c, t + 1, noise[(size_t)t * Bs + c0 + c], 0);
+                for (int e = t + 1; e < T; ++e) {
+                    const float* cell = score + ((size_t)e * T + t) * Bs + c0;
+                    for (int c = 0; c < nc; ++c) push(c, e, cell[c], e + 1);
+                }
+            }
+            for (int c = 0; c < nc; ++c) {
+                const int32_t flip = dg[c] > 0.0f ? 1 : 0;
+                cnt[(size_t)t * Bs + c0 + c] = n[c];
+                for (int r = 0; r < k; ++r) {
+                    const size_t at = ((size_t)t * K + r) * Bs + c0 + c;
+                    u[at] = r < n[c] ? L[c][r].v : -INFINITY;
+                    code[at] = r < n[c] ? (L[c][r].o ^ flip) : -1;
+                }
+            }
+        }
+    }
+    // the walks, one per (rank, chain), in decode's emission order
+    const int64_t nB = (int64_t)k * B;
+    std::vector<std::vector<int32_t>> out((size_t)nB);
+#pragma omp parallel for schedule(dynamic, 8)
+    for (int64_t idx = 0; idx < nB; ++idx) {
+        const int r0 = (int)(idx / B), c = (int)(idx % B);
+        const int st = start ? start[c] : (forward ? T - 1 : 0);
+        if (r0 == 0) npaths[c] = cnt[(size_t)st * Bs + c];
+        const bool present = r0 < cnt[(size_t)st * Bs + c];
+        scores[idx] = present ? u[((size_t)st * K + r0) * Bs + c] : -INFINITY;
+        if (!present) continue;
+        std::vector<int32_t>& o = out[(size_t)idx];
+        const int term = forward ? 0 : T - 1;
+        int j = st, r = r0;
+        for (;;) {
+            const int32_t w = code[((size_t)j * K + r) * Bs + c];
+            if (w & 1) { o.push_back(j); o.push_back(j); }
+            if (j == term) break;
+            const int32_t cidx = w >> 5;
+            r = (w >> 1) & 15;
+            if (cidx == 0) j += forward ? -1 : 1;
+            else {
+                const int q = cidx - 1;
+                o.push_back(forward ? q : j);
+                o.push_back(forward ? j : q);
+                j = q;
+            }
+        }
+        if (forward) {                                     // emitted descending: ascending like decode's
+            std::vector<int32_t> a;
+            for (size_t i = o.size(); i >= 2; i -= 2) { a.push_back(o[i - 2]); a.push_back(o[i - 1]); }
+            o.swap(a);
+        }
+    }
+    int64_t m = 0;
+    for (int64_t idx = 0; idx < nB; ++idx) {
+        offsets[idx] = (int32_t)m;
+        const std::vector<int32_t>& o = out[(size_t)idx];
+        for (size_t i = 0; i + 1 < o.size(); i += 2, ++m)
+            if (m < cap) { pairs[2 * m] = o[i]; pairs[2 * m + 1] = o[i + 1]; }
+    }
+    offsets[nB] = (int32_t)m;
+}
+
 // evalPath (:508-550): sum of the path's interval scores plus the noise of every gap no interval covers
 void eval_path(const float* score, const float* noise, int T, int B, const int32_t* pairs, const int32_t* offsets, float* out)
 {

@@ -11,6 +11,8 @@ void viterbi(const float* score, const float* noise, int T, int B, const int32_t
              int32_t* offsets);
 void sample(const float* score, const float* noise, const float* v, int T, int B, int64_t k0, int nSample, uint64_t key,
             const int32_t* end, int32_t* pairs, int64_t cap, int32_t* offsets);
+void viterbi_nbest(const float* score, const float* noise, int T, int B, int k, const int32_t* start, int forward, int32_t* pairs,
+                   int64_t cap, int32_t* offsets, float* scores /* [k][B] */, int32_t* npaths /* [B] */);
 void eval_path(const float* score, const float* noise, int T, int B, const int32_t* pairs, const int32_t* offsets, float* out);
 void eval_path_bwd(const float* gout, int T, int B, const int32_t* pairs, const int32_t* offsets, float* dScore, float* dNoise);
 }  // namespace semicrf_cpu

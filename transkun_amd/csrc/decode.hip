@@ -202,6 +202,9 @@ __global__ __launch_bounds__(256) void pack_kernel(const int* __restrict__ regio
     }
 }
 
+void launch_pack(const int* region, const int* counts, int T, int B, int forward, int* pairs, long long cap, int* offsets,
+                 hipStream_t stream, const unsigned* err, int nerr, int err_stride);
+
 void launch_backtrack(const int* code, int T, int B, const int* start, int forward, int* region,
                       int* counts, int* pairs, long long cap, int* offsets, hipStream_t stream,
                       const unsigned* err, int nerr, int err_stride)
@@ -227,6 +230,13 @@ void launch_backtrack(const int* code, int T, int B, const int* start, int forwa
     } else {
         hipLaunchKernelGGL(backtrack_kernel, dim3(B), dim3(64), lds, stream, code, T, B, start, forward, region, counts);
     }
+    launch_pack(region, counts, T, B, forward, pairs, cap, offsets, stream, err, nerr, err_stride);
+}
+
+// offsets and packing of B walks already in `region` / `counts` (the backtrack's layout; nbest.hip's walks write it too)
+void launch_pack(const int* region, const int* counts, int T, int B, int forward, int* pairs, long long cap, int* offsets,
+                 hipStream_t stream, const unsigned* err, int nerr, int err_stride)
+{
     hipLaunchKernelGGL(offsets_kernel, dim3(1), dim3(256), 0, stream, counts, B, offsets, err, nerr, err_stride);
     hipLaunchKernelGGL(pack_kernel, dim3(B), dim3(256), 0, stream, region, counts, offsets, T, B, forward, pairs,
                        cap);

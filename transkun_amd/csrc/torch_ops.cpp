@@ -137,6 +137,21 @@ void sample(Tensor score, Tensor noise, Tensor v, int64_t k0, int64_t nSample, i
                          i32(offsets, nSample * d.B + 1, "offsets"), bytes(ws, "ws"), (size_t)ws.numel(), c.stream),
           "semicrf_sample");
 }
+// k-best Viterbi (semicrf_viterbi_nbest): rank-major offsets [k*B+1], scores [k][B], npaths [B]
+void viterbi_nbest(Tensor score, Tensor noise, int64_t k, Tensor start, bool has_start, bool forward, Tensor pairs, Tensor offsets,
+                   Tensor scores, Tensor npaths, Tensor ws)
+{
+    Ctx c(score); c.same(score, noise, pairs, offsets, scores, npaths, ws);
+    if (has_start) c.same(score, start);
+    const Dims d = crf_dims(score, noise);
+    STD_TORCH_CHECK(k >= 1 && k <= 16, "semicrf: k must be in [1, 16]");
+    STD_TORCH_CHECK(pairs.dim() == 2 && pairs.size(1) == 2, "semicrf: pairs must be [cap, 2]");
+    check(semicrf_viterbi_nbest(cfp(score), cfp(noise), d.T, d.B, (int)k, has_start ? i32(start, d.B, "start") : nullptr,
+                                forward ? 1 : 0, i32(pairs, 0, "pairs"), (int64_t)pairs.size(0), i32(offsets, k * d.B + 1, "offsets"),
+                                f32w(scores, k * d.B, "scores"), i32(npaths, d.B, "npaths"), bytes(ws, "ws"), (size_t)ws.numel(),
+                                c.stream),
+          "semicrf_viterbi_nbest");
+}
 void eval_path(Tensor score, Tensor noise, Tensor pairs, int64_t K, Tensor offsets, Tensor out, Tensor ws)
 {
     Ctx c(score); c.same(score, noise, pairs, offsets, out);
@@ -243,6 +258,22 @@ void sample_cpu(Tensor score, Tensor noise, Tensor v, int64_t k0, int64_t nSampl
         for (int c = 0; c < d.B; ++c) STD_TORCH_CHECK(e[c] >= 0 && e[c] < d.T, "semicrf: forcedEndPos out of range");
     semicrf_cpu::sample(cfp(score), cfp(noise), f32(v, (int64_t)d.T * d.B, "v"), d.T, d.B, k0, (int)nSample, (uint64_t)key, e,
                         i32(pairs, 0, "pairs"), (int64_t)pairs.size(0), i32(offsets, nSample * d.B + 1, "offsets"));
+}
+void viterbi_nbest_cpu(Tensor score, Tensor noise, int64_t k, Tensor start, bool has_start, bool forward, Tensor pairs, Tensor offsets,
+                       Tensor scores, Tensor npaths, Tensor ws)
+{
+    all_cpu(score, noise, pairs, offsets, scores, npaths);
+    if (has_start) all_cpu(start);
+    const Dims d = crf_dims(score, noise);
+    STD_TORCH_CHECK(k >= 1 && k <= 16, "semicrf: k must be in [1, 16]");
+    STD_TORCH_CHECK(k * d.B * 2 * d.T < (1ll << 31), "semicrf: k*B*2T exceeds int32 offsets");
+    STD_TORCH_CHECK(pairs.dim() == 2 && pairs.size(1) == 2, "semicrf: pairs must be [cap, 2]");
+    const int32_t* st = has_start ? i32(start, d.B, "start") : nullptr;
+    if (st)
+        for (int c = 0; c < d.B; ++c) STD_TORCH_CHECK(st[c] >= 0 && st[c] < d.T, "semicrf: forcedStartPos out of range");
+    semicrf_cpu::viterbi_nbest(cfp(score), cfp(noise), d.T, d.B, (int)k, st, forward ? 1 : 0, i32(pairs, 0, "pairs"),
+                               (int64_t)pairs.size(0), i32(offsets, k * d.B + 1, "offsets"), f32w(scores, k * d.B, "scores"),
+                               i32(npaths, d.B, "npaths"));
 }
 inline void check_path(const int32_t* pairs, int64_t K, const int32_t* offsets, int T, int B)
 {
@@ -502,6 +533,8 @@ STABLE_TORCH_LIBRARY(semicrf, m)
           "Tensor(c!) ws) -> ()");
     m.def("sample(Tensor score, Tensor noise, Tensor v, int k0, int nSample, int key, Tensor end, bool has_end, Tensor(a!) pairs, "
           "Tensor(b!) offsets, Tensor(c!) ws) -> ()");
+    m.def("viterbi_nbest(Tensor score, Tensor noise, int k, Tensor start, bool has_start, bool forward, Tensor(a!) pairs, "
+          "Tensor(b!) offsets, Tensor(c!) scores, Tensor(d!) npaths, Tensor(e!) ws) -> ()");
     m.def("eval_path(Tensor score, Tensor noise, Tensor pairs, int K, Tensor offsets, Tensor(a!) out, Tensor(b!) ws) -> ()");
     m.def("eval_path_bwd(Tensor gout, int T, int B, Tensor pairs, int K, Tensor offsets, Tensor(a!) dScore, bool has_ds, Tensor(b!) dNoise, "
           "bool has_dn) -> ()");
@@ -548,6 +581,7 @@ STABLE_TORCH_LIBRARY_IMPL(semicrf, CPU, m)
     m.impl("beta", TORCH_BOX(&beta_cpu));
     m.impl("viterbi", TORCH_BOX(&viterbi_cpu));
     m.impl("sample", TORCH_BOX(&sample_cpu));
+    m.impl("viterbi_nbest", TORCH_BOX(&viterbi_nbest_cpu));
     m.impl("eval_path", TORCH_BOX(&eval_path_cpu));
     m.impl("eval_path_bwd", TORCH_BOX(&eval_path_bwd_cpu));
     m.impl("logprob_fwd", TORCH_BOX(&logprob_fwd_cpu));
@@ -561,6 +595,7 @@ STABLE_TORCH_LIBRARY_IMPL(semicrf, CUDA, m)
     m.impl("beta", TORCH_BOX(&beta));
     m.impl("viterbi", TORCH_BOX(&viterbi));
     m.impl("sample", TORCH_BOX(&sample));
+    m.impl("viterbi_nbest", TORCH_BOX(&viterbi_nbest));
     m.impl("eval_path", TORCH_BOX(&eval_path));
     m.impl("eval_path_bwd", TORCH_BOX(&eval_path_bwd));
     m.impl("logprob_fwd", TORCH_BOX(&logprob_fwd));
