@@ -51,6 +51,7 @@ extern "C" {
 #define SEMICRF_OP_INTERVAL_SCORE 4
 #define SEMICRF_OP_SAMPLE 5           /* B = nSample * NBatch of the semicrf_sample call */
 #define SEMICRF_OP_VITERBI_NBEST 6    /* B = k * NBatch of the semicrf_viterbi_nbest call */
+#define SEMICRF_OP_POSTERIORS 7       /* semicrf_posteriors */
 
 /* length scaling of the interval scorer (LayersTransformer.py:416-427) */
 #define SEMICRF_LEN_LINEAR 0
@@ -205,6 +206,36 @@ int semicrf_sample(const float* score, const float* noise, const float* v, int T
 int semicrf_viterbi_nbest(const float* score, const float* noise, int T, int B, int k, const int32_t* start, int forward,
                           int32_t* pairs, int64_t cap, int32_t* offsets, float* scores, int32_t* npaths, void* ws, size_t ws_bytes,
                           semicrf_stream_t stream);
+
+/*
+ * Posterior marginals and path entropy.  No counterpart in the reference (an extension of its surface, like semicrf_sample).
+ * Adds nothing to the ABI's existing entry points (version 2).
+ *   v: alpha [T][B] (semicrf_logz_fwd), q: beta [T][B] (semicrf_beta), logZ [B], all on the same score / noise.  q[t], like v[t],
+ *   includes softplus(s[t,t]) of its own frame.  sp = softplus (threshold 20), sigma = the logistic sigmoid,
+ *   R[t] = v[t] - sp(s[t,t]) (the log row total of alpha's recursion at t), mu[e,b] = dScore of semicrf_logz_bwd with gout = 1.
+ *   node   [T][B]   P(frame t is a node of the path, i.e. not strictly inside an interval) = exp(R[t] + q[t] - logZ); 1 at 0, T-1
+ *   single [T][B]   P((t,t) on the path) = node[t] sigma(s[t,t]) = mu[t,t]
+ *   begin  [T][B]   P(an interval (t,e), e > t, on the path) = sum_{e>t} mu[e,t]
+ *   end    [T][B]   P(an interval (b,t), b < t, on the path) = sum_{b<t} mu[t,b]
+ *   noiseP [T-1][B] dNoise of semicrf_logz_bwd with gout = 1: exp(v[t] + n[t] + q[t+1] - logZ)   (may be NULL when T = 1)
+ *   entropy [B]     H = sum_t node[t] (Hb(s[t,t]) + Hpred[t]) by the chain rule of semicrf_sample's backward walk:
+ *                   Hb(x) = sp(x) - x sigma(x) (the singleton's Bernoulli entropy); Hpred[0] = 0, Hpred[t] = -sum p lp over the
+ *                   candidates [skip, j = 0..t-1], lp_skip = v[t-1] + n[t-1] - R[t], lp_j = v[j] + s[t,j] - R[t]; a term of p = 0 is 0
+ *                   and every lp is clamped to <= 0, so no term is negative and nothing cancels.
+ *   Probabilities are clamped to <= 1 (NaN stays NaN).  One read of the lower triangle; no atomics: two calls are bit-identical.
+ *   Workspace: semicrf_workspace_bytes(SEMICRF_OP_POSTERIORS, T, B), about 2 * ceil(T/64) * T * B floats.
+ */
+int semicrf_posteriors(const float* score, const float* noise, const float* v, const float* q, const float* logZ, int T, int B,
+                       float* node, float* begin, float* end, float* single, float* noiseP, float* entropy, void* ws, size_t ws_bytes,
+                       semicrf_stream_t stream);
+
+/*
+ * Marginals of given intervals: out[i] = mu[e,b] of interval i = (b, e) (pairs / offsets / K as semicrf_eval_path; v, q, logZ as
+ * semicrf_posteriors): exp(v[b] + s[e,b] + q[e] - logZ) for b < e, single[t] for b = e, 0 for b > e (never on a path), NaN for an
+ * index outside [0, T).  No workspace.
+ */
+int semicrf_interval_marginals(const float* score, const float* v, const float* q, const float* logZ, int T, int B,
+                               const int32_t* pairs, int64_t K, const int32_t* offsets, float* out, semicrf_stream_t stream);
 
 /*
  * Unnormalised path score.  Replaces: evalPath (:508-550).

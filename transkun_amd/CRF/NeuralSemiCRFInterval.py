@@ -16,12 +16,14 @@ What differs from the reference, invisibly at the API:
   * logProb() is ONE autograd node: its backward writes gout*(onehot(path) - marginal) in a single
     pass instead of summing two dense [T,T,B] gradients.
   * decode() backtracks on the device; only the packed (begin,end) pairs cross PCIe.
-EXTENSIONS of the reference's surface: decode_packed, sample / sample_packed (exact posterior draws of paths), and
-  decode_nbest / decode_nbest_packed (the k best paths, ranked).
+EXTENSIONS of the reference's surface: decode_packed, sample / sample_packed (exact posterior draws of paths),
+  decode_nbest / decode_nbest_packed (the k best paths, ranked), and posteriors / interval_marginals /
+  interval_marginals_packed (posterior marginals and path entropy without the dense [T,T,B] tensor).
 """
 from __future__ import annotations
 
 import os
+from collections import namedtuple
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -811,6 +813,110 @@ def viterbi_nbest(score, noiseScore, k: int, forcedStartPos: Optional[Sequence[i
     return paths, scores
 
 
+# --------------------------------------------------------------------------------------
+# posterior marginals and path entropy (an extension of the reference's surface)
+# --------------------------------------------------------------------------------------
+
+Posteriors = namedtuple("Posteriors", "logZ entropy node begin end single noise")
+Posteriors.__doc__ = """Posterior summaries of every chain (float32, where the scores live; include/semicrf_hip.h: semicrf_posteriors).
+    logZ [B]; entropy [B]: the entropy of p(path) in nats; node [T, B]: P(frame t is not strictly inside an interval);
+    begin / end [T, B]: P(an interval of length > 1 begins / ends at t); single [T, B]: P(the singleton (t, t));
+    noise [T-1, B]: P(no interval covers the gap between t and t+1)."""
+
+
+def _beta_raw(score_c, noise_c):
+    T, B = score_c.shape[0], score_c.shape[2]
+    q = torch.empty(T, B, dtype=torch.float32, device=score_c.device)
+    ws = _lib.leased_workspace(_lib.OP_LOGZ_FWD, T, B, score_c.device, "beta")
+    _lib.ops().beta(score_c, noise_c, q, ws)
+    return q
+
+
+def _marginal_inputs(score_c, noise_c):
+    """(logZ, v, q) of the alpha and beta sweeps, enqueued on the current stream."""
+    logz, v = _logz_fwd_raw(score_c, noise_c, want_v=True)
+    return logz, v, _beta_raw(score_c, noise_c)
+
+
+def _posteriors_raw(score_c, noise_c, lvq=None) -> Posteriors:
+    """Enqueue the sweeps (unless lvq = (logZ, v, q) is given) and semicrf_posteriors; no host sync."""
+    if _odd_pad(score_c) and lvq is None:
+        P = _posteriors_raw(_pad1(score_c), _pad1(noise_c))
+        return Posteriors(*(x[..., :-1].contiguous() for x in P))
+    T, B = score_c.shape[0], score_c.shape[2]
+    dev = score_c.device
+    logz, v, q = _marginal_inputs(score_c, noise_c) if lvq is None else lvq
+    f = dict(dtype=torch.float32, device=dev)
+    node, begin, end, single = (torch.empty(T, B, **f) for _ in range(4))
+    noise, entropy = torch.empty(T - 1, B, **f), torch.empty(B, **f)
+    ws = _lib.workspace(_lib.OP_POSTERIORS, T, B, dev)
+    _lib.ops().posteriors(score_c, noise_c, v, q, logz, node, begin, end, single, noise, entropy, ws)
+    return Posteriors(logz, entropy, node, begin, end, single, noise)
+
+
+def _interval_marginals_raw(score_c, v, q, logz, pairs, K: int, offsets):
+    out = torch.empty(max(K, 1), dtype=torch.float32, device=score_c.device)
+    _lib.ops().interval_marginals(score_c, v, q, logz, pairs, int(K), offsets, out)
+    return out[:K]
+
+
+def _packed_on(pairs, offsets, T: int, B: int, device):
+    """decode_packed's arrays (numpy or tensors) -> (pairs int32 [K,2], offsets int32 [B+1], K) on `device`; host arrays are
+    checked with pack_intervals' errors, device tensors by the kernel (an index out of range gives NaN)."""
+    on_dev = isinstance(pairs, torch.Tensor) and isinstance(offsets, torch.Tensor) and pairs.device.type != "cpu"
+    p = pairs if isinstance(pairs, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(pairs))
+    o = offsets if isinstance(offsets, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(offsets))
+    assert o.dim() == 1 and o.numel() == B + 1, f"expected offsets of {B + 1} entries, got {tuple(o.shape)}"
+    p = p.reshape(-1, 2).to(torch.int32)
+    o = o.to(torch.int32)
+    K = int(p.shape[0])
+    if not on_dev:
+        pn, on = p.numpy(), o.numpy()
+        if on[0] != 0 or on[-1] != K or (np.diff(on) < 0).any():
+            raise ValueError("offsets not ascending or not matching the interval count")
+        if K and ((pn < 0).any() or (pn >= T).any()):
+            raise IndexError(f"interval index out of range for T={T}")
+    pin = torch.device(device).type == "cuda" and not on_dev
+    if pin:
+        p, o = p.pin_memory(), o.pin_memory()
+    return p.contiguous().to(device, non_blocking=True), o.contiguous().to(device, non_blocking=True), K
+
+
+def posteriors(score, noiseScore) -> Posteriors:
+    """An EXTENSION of the reference's surface: posterior marginals and path entropy of every chain, as a Posteriors namedtuple
+    (logZ, entropy, node, begin, end, single, noise) of float32 tensors where the scores live -- without the dense [T, T, B]
+    marginal tensor of forward_backward and without a host sync.  Runs the alpha and beta sweeps itself; no gradient."""
+    _check_inputs(score, noiseScore)
+    with torch.no_grad():
+        return _posteriors_raw(_prep(score.detach()), _prep(noiseScore.detach()))
+
+
+def interval_marginals_packed(score, noiseScore, pairs, offsets) -> torch.Tensor:
+    """An EXTENSION of the reference's surface: the posterior probability of each given interval, a float32 tensor [K] where the
+    scores live.  pairs [K, 2] (begin, end) and offsets [nBatch + 1] as decode_packed returns them (numpy arrays or tensors)."""
+    T, B = _check_inputs(score, noiseScore)
+    with torch.no_grad():
+        score_c, noise_c = _prep(score.detach()), _prep(noiseScore.detach())
+        p, o, K = _packed_on(pairs, offsets, T, B, score_c.device)
+        if _odd_pad(score_c):
+            s2, n2 = _pad1(score_c), _pad1(noise_c)
+            logz, v, q = _marginal_inputs(s2, n2)
+            return _interval_marginals_raw(s2, v, q, logz, p, K, torch.cat([o, o[-1:]]))
+        logz, v, q = _marginal_inputs(score_c, noise_c)
+        return _interval_marginals_raw(score_c, v, q, logz, p, K, o)
+
+
+def interval_marginals(score, noiseScore, intervals: Intervals) -> List[List[float]]:
+    """An EXTENSION of the reference's surface: the posterior probability of each interval of `intervals` (one list per chain,
+    e.g. what decode returns), as a list (len nBatch) of lists of floats in the given order."""
+    T, B = _check_inputs(score, noiseScore)
+    pairs, offsets = pack_intervals(intervals, T, B, "cpu")
+    K = pairs._semicrf_K
+    out = interval_marginals_packed(score, noiseScore, pairs[:K], offsets).cpu().tolist()
+    off = offsets.tolist()
+    return [out[off[c]:off[c + 1]] for c in range(B)]
+
+
 def viterbiBackward(score, noiseScore, forcedStartPos: Optional[List[int]] = None) -> Intervals:
     """Right-to-left Viterbi, the default decode (reference :13-104)."""
     return _decode(score, noiseScore, forcedStartPos, forward=False)
@@ -906,6 +1012,20 @@ class NeuralSemiCRFInterval:
         """`decode_nbest` as numpy arrays (pairs, offsets [k * nBatch + 1] rank-major, scores [k, nBatch], npaths [nBatch]) before
         the Python lists are built -- see the module-level viterbi_nbest_packed."""
         return viterbi_nbest_packed(self.score, self.noiseScore, k, forcedStartPos, bool(forward))
+
+    def posteriors(self):
+        """An EXTENSION of the reference's surface: a Posteriors namedtuple (logZ, entropy, node, begin, end, single, noise) of
+        float32 tensors where the scores live -- see the module-level posteriors.  No host sync, no gradient."""
+        return posteriors(self.score, self.noiseScore)
+
+    def interval_marginals(self, intervals):
+        """An EXTENSION of the reference's surface: the posterior probability of each interval of `intervals` (e.g. decode()'s
+        result), a list (len nBatch) of lists of floats in the given order."""
+        return interval_marginals(self.score, self.noiseScore, intervals)
+
+    def interval_marginals_packed(self, pairs, offsets):
+        """`interval_marginals` on decode_packed's arrays (numpy or tensors): a float32 tensor [K] where the scores live."""
+        return interval_marginals_packed(self.score, self.noiseScore, pairs, offsets)
 
     def evalPath(self, intervals):
         """compute the unnormalized score"""

@@ -3,4 +3,5 @@ from .NeuralSemiCRFInterval import *  # noqa: F401,F403
 from .NeuralSemiCRFInterval import (NeuralSemiCRFInterval, viterbi, viterbiBackward, computeLogZ,  # noqa: F401
                                     forward_backward, evalPath, computeLogZFasterGrad,
                                     ComputeLogZFasterGrad, sample, sample_packed,
-                                    viterbi_nbest, viterbi_nbest_packed)
+                                    viterbi_nbest, viterbi_nbest_packed, Posteriors, posteriors,
+                                    interval_marginals, interval_marginals_packed)

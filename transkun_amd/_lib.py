@@ -23,7 +23,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SEMICRF_LIB") or os.path.join(_HERE, "libsemicrf_hip.so")   # SEMICRF_LIB: development variants
 
-OP_LOGZ_FWD, OP_LOGZ_BWD, OP_VITERBI, OP_EVAL_PATH, OP_INTERVAL_SCORE, OP_SAMPLE, OP_VITERBI_NBEST = range(7)
+OP_LOGZ_FWD, OP_LOGZ_BWD, OP_VITERBI, OP_EVAL_PATH, OP_INTERVAL_SCORE, OP_SAMPLE, OP_VITERBI_NBEST, OP_POSTERIORS = range(8)
 LEN_MODES = {"linear": 0, "sqrt": 1, "none": 2}
 
 _vp = ctypes.c_void_p
@@ -50,6 +50,8 @@ _SIGS = {
     "semicrf_viterbi": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _i64, _vp, _vp, _sz, _vp]),
     "semicrf_sample": (_i, [_vp, _vp, _vp, _i, _i, _i64, _i, ctypes.c_uint64, _vp, _vp, _i64, _vp, _vp, _sz, _vp]),
     "semicrf_viterbi_nbest": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "semicrf_posteriors": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "semicrf_interval_marginals": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _i64, _vp, _vp, _vp]),
     "semicrf_eval_path": (_i, [_vp, _vp, _i, _i, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
     "semicrf_eval_path_bwd": (_i, [_vp, _i, _i, _vp, _i64, _vp, _vp, _vp, _vp]),
     "semicrf_logprob_fwd": (_i, [_vp, _vp, _i, _i, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),

@@ -94,6 +94,12 @@ int launch_proj_tn(const float* A, long long lda, long long M, int R, int extra_
                    float* dW, long long lddw, float* db, void* ws, size_t ws_bytes, hipStream_t stream);
 size_t persist_workspace_bytes(int T, int B);
 size_t sample_workspace_bytes(int T, int nB);
+size_t posterior_workspace_bytes(int T, int B);
+void launch_posteriors(const float* score, const float* noise, const float* v, const float* q, const float* logZ, int T, int B,
+                       float* node, float* begin, float* end, float* single, float* noiseP, float* entropy, void* ws,
+                       hipStream_t stream);
+void launch_interval_marginals(const float* score, const float* v, const float* q, const float* logZ, int T, int B, const int* pairs,
+                               int K, const int* offsets, float* out, hipStream_t stream);
 size_t nbest_workspace_bytes(int T, int nB);
 void launch_viterbi_nbest(const float* score, const float* noise, int T, int B, int k, const int* start, int forward, int* pairs,
                           long long cap, int* offsets, float* scores, int* npaths, void* ws, hipStream_t stream);
@@ -280,6 +286,7 @@ size_t semicrf_workspace_bytes(int op, int T, int B)
         case SEMICRF_OP_EVAL_PATH: return 4096;
         case SEMICRF_OP_INTERVAL_SCORE: return 4096;
         case SEMICRF_OP_SAMPLE: return sample_workspace_bytes(T, B);
+        case SEMICRF_OP_POSTERIORS: return posterior_workspace_bytes(T, B);
         case SEMICRF_OP_VITERBI_NBEST: return nbest_workspace_bytes(T, B);
         default: return 0;
     }
@@ -519,6 +526,33 @@ int semicrf_viterbi_nbest(const float* score, const float* noise, int T, int B, 
     launch_viterbi_nbest(score, noise, T, B, k, start, forward ? 1 : 0, pairs, (long long)cap, offsets, scores, npaths, ws,
                          (hipStream_t)stream);
     SEMICRF_CHECK_LAUNCH("semicrf_viterbi_nbest");
+    return SEMICRF_OK;
+}
+
+int semicrf_posteriors(const float* score, const float* noise, const float* v, const float* q, const float* logZ, int T, int B,
+                       float* node, float* begin, float* end, float* single, float* noiseP, float* entropy, void* ws, size_t ws_bytes,
+                       semicrf_stream_t stream)
+{
+    if (int rc = check_common(score, noise, T, B)) return rc;
+    SEMICRF_CHECK_ARG(v && q && logZ, "v (alpha), q (beta) and logZ must be non-NULL");
+    SEMICRF_CHECK_ARG(node && begin && end && single && entropy && (noiseP || T == 1), "an output is NULL");
+    SEMICRF_CHECK_ARG((long long)((T + 63) / 64) * ((T + 63) / 64 + 1) / 2 < 65536, "T=%d too large for the posterior pass", T);
+    SEMICRF_CHECK_ARG(ws != nullptr, "workspace is NULL");
+    if (ws_bytes < posterior_workspace_bytes(T, B)) { set_error("workspace too small for posteriors"); return SEMICRF_EWORKSPACE; }
+    launch_posteriors(score, noise, v, q, logZ, T, B, node, begin, end, single, noiseP, entropy, ws, (hipStream_t)stream);
+    SEMICRF_CHECK_LAUNCH("semicrf_posteriors");
+    return SEMICRF_OK;
+}
+
+int semicrf_interval_marginals(const float* score, const float* v, const float* q, const float* logZ, int T, int B,
+                               const int32_t* pairs, int64_t K, const int32_t* offsets, float* out, semicrf_stream_t stream)
+{
+    SEMICRF_CHECK_ARG(T >= 1 && B >= 1, "T=%d, B=%d must be >= 1", T, B);
+    SEMICRF_CHECK_ARG((long long)T * T * B < (1ll << 40), "T*T*B too large");
+    SEMICRF_CHECK_ARG(score && v && q && logZ && offsets, "score / v / q / logZ / offsets must be non-NULL");
+    SEMICRF_CHECK_ARG(K >= 0 && K < (1ll << 31) && (K == 0 || (pairs && out)), "bad interval count");
+    launch_interval_marginals(score, v, q, logZ, T, B, pairs, (int)K, offsets, out, (hipStream_t)stream);
+    SEMICRF_CHECK_LAUNCH("semicrf_interval_marginals");
     return SEMICRF_OK;
 }
 

@@ -315,6 +315,81 @@ void sample(const float* score, const float* noise, const float* v, int T, int B
     offsets[nB] = (int32_t)n;
 }
 
+// posterior marginals and path entropy (include/semicrf_hip.h: semicrf_posteriors; the device kernels are posterior.hip), every
+// sum and exponential in double from the fp32 v / q / logZ.
+namespace {
+inline double softplus_d(double x) { return x > 20.0 ? x : log1p(exp(x)); }
+inline double bern_entropy_d(double d)
+{
+    const double a = fabs(d), ea = exp(-a);
+    return log1p(ea) + (ea > 0.0 ? a * ea / (1.0 + ea) : 0.0);
+}
+inline double ent_term_d(double mu, double R, double y) { return mu > 0.0 ? mu * (R - y > 0.0 ? R - y : 0.0) : 0.0; }
+inline float clamp1(double x) { return x > 1.0 ? 1.0f : (float)x; }
+inline double single_d(double v, double q, double lz, double d) { return exp(v + q - lz + d - 2.0 * softplus_d(d)); }
+}  // namespace
+
+void posteriors(const float* score, const float* noise, const float* v, const float* q, const float* logZ, int T, int B, float* node,
+                float* begin, float* end, float* single, float* noiseP, float* entropy)
+{
+    const size_t Bs = (size_t)B;
+    const int nblk = (B + CB - 1) / CB;
+#pragma omp parallel for schedule(dynamic, 1)
+    for (int blk = 0; blk < nblk; ++blk) {
+        const int c0 = blk * CB;
+        const int nc = B - c0 < CB ? B - c0 : CB;
+        std::vector<double> bg((size_t)T * CB, 0.0);
+        double H[CB] = {0.0};
+        for (int e = 0; e < T; ++e) {
+            const float* row = score + (size_t)e * T * Bs;
+            for (int c = 0; c < nc; ++c) {
+                const size_t ec = (size_t)e * Bs + c0 + c;
+                const double lz = logZ[c0 + c], d = row[(size_t)e * Bs + c0 + c];
+                const double R = (double)v[ec] - softplus_d(d), A = (double)q[ec] - lz;
+                double en = 0.0, h = 0.0;
+                for (int b = 0; b < e; ++b) {
+                    const double y = (double)v[(size_t)b * Bs + c0 + c] + (double)row[(size_t)b * Bs + c0 + c];
+                    const double mu = exp(y + A);
+                    en += mu;
+                    bg[(size_t)b * CB + c] += mu;
+                    h += ent_term_d(mu, R, y);
+                }
+                const double nd = exp(R + A);
+                if (nd > 0.0) h += nd * bern_entropy_d(d);
+                if (e > 0) {
+                    const size_t pc = ec - Bs;
+                    const double y = (double)v[pc] + (double)noise[pc];
+                    h += ent_term_d(exp(y + A), R, y);
+                }
+                if (e + 1 < T) noiseP[ec] = clamp1(exp((double)v[ec] + (double)noise[ec] + (double)q[ec + Bs] - lz));
+                node[ec] = clamp1(nd);
+                single[ec] = clamp1(single_d(v[ec], q[ec], lz, d));
+                end[ec] = clamp1(en);
+                H[c] += h;
+            }
+        }
+        for (int t = 0; t < T; ++t)
+            for (int c = 0; c < nc; ++c) begin[(size_t)t * Bs + c0 + c] = clamp1(bg[(size_t)t * CB + c]);
+        for (int c = 0; c < nc; ++c) entropy[c0 + c] = (float)H[c];
+    }
+}
+
+// interval marginals (semicrf_interval_marginals): b > e gives 0; the caller has checked the indices
+void interval_marginals(const float* score, const float* v, const float* q, const float* logZ, int T, int B, const int32_t* pairs,
+                        const int32_t* offsets, float* out)
+{
+    const size_t Bs = (size_t)B;
+    for (int c = 0; c < B; ++c)
+        for (int32_t k = offsets[c]; k < offsets[c + 1]; ++k) {
+            const int b = pairs[2 * k], e = pairs[2 * k + 1];
+            const size_t ec = (size_t)e * Bs + c;
+            if (b > e) out[k] = 0.0f;
+            else if (b == e) out[k] = clamp1(single_d(v[ec], q[ec], logZ[c], score[((size_t)e * T + e) * Bs + c]));
+            else
+                out[k] = clamp1(exp((double)v[(size_t)b * Bs + c] + (double)score[((size_t)e * T + b) * Bs + c] + (double)q[ec] - logZ[c]));
+        }
+}
+
 // k-best Viterbi (include/semicrf_hip.h: semicrf_viterbi_nbest; the device kernel is nbest.hip).  Per frame and chain a sorted
 // list of at most k partial paths, each (value, base, order word); a candidate's ranks are tried in ascending order and the scan of
 // a candidate stops at the first rank whose two singleton variants both fail to beat the list's k-th entry (later ranks of the

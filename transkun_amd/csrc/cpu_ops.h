@@ -13,6 +13,10 @@ void sample(const float* score, const float* noise, const float* v, int T, int B
             const int32_t* end, int32_t* pairs, int64_t cap, int32_t* offsets);
 void viterbi_nbest(const float* score, const float* noise, int T, int B, int k, const int32_t* start, int forward, int32_t* pairs,
                    int64_t cap, int32_t* offsets, float* scores /* [k][B] */, int32_t* npaths /* [B] */);
+void posteriors(const float* score, const float* noise, const float* v, const float* q, const float* logZ, int T, int B, float* node,
+                float* begin, float* end, float* single, float* noiseP, float* entropy);
+void interval_marginals(const float* score, const float* v, const float* q, const float* logZ, int T, int B, const int32_t* pairs,
+                        const int32_t* offsets, float* out);
 void eval_path(const float* score, const float* noise, int T, int B, const int32_t* pairs, const int32_t* offsets, float* out);
 void eval_path_bwd(const float* gout, int T, int B, const int32_t* pairs, const int32_t* offsets, float* dScore, float* dNoise);
 }  // namespace semicrf_cpu

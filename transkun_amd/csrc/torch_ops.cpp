@@ -152,6 +152,40 @@ void viterbi_nbest(Tensor score, Tensor noise, int64_t k, Tensor start, bool has
                                 c.stream),
           "semicrf_viterbi_nbest");
 }
+// posterior marginals and entropy (semicrf_posteriors): v, q, logZ of the same score / noise
+void posteriors(Tensor score, Tensor noise, Tensor v, Tensor q, Tensor logZ, Tensor node, Tensor begin, Tensor end, Tensor single,
+                Tensor noiseP, Tensor entropy, Tensor ws)
+{
+    Ctx c(score); c.same(score, noise, v, q, logZ, node, begin, end, single, noiseP, entropy, ws);
+    const Dims d = crf_dims(score, noise);
+    const int64_t TB = (int64_t)d.T * d.B;
+    check(semicrf_posteriors(cfp(score), cfp(noise), f32(v, TB, "v"), f32(q, TB, "q"), f32(logZ, d.B, "logZ"), d.T, d.B,
+                             f32w(node, TB, "node"), f32w(begin, TB, "begin"), f32w(end, TB, "end"), f32w(single, TB, "single"),
+                             f32w(noiseP, TB - d.B, "noiseP"), f32w(entropy, d.B, "entropy"), bytes(ws, "ws"), (size_t)ws.numel(),
+                             c.stream),
+          "semicrf_posteriors");
+}
+inline Dims marg_dims(const Tensor& score, const Tensor& v, const Tensor& q, const Tensor& logZ)
+{
+    STD_TORCH_CHECK(score.dim() == 3 && score.size(0) == score.size(1), "semicrf: score must be [T, T, B]");
+    const int64_t T = score.size(0), B = score.size(2);
+    STD_TORCH_CHECK(T >= 1 && B >= 1 && T < (1 << 29) && B < (1ll << 31), "semicrf: bad score shape");
+    want(score, ScalarType::Float, T * T * B, "score");
+    want(v, ScalarType::Float, T * B, "v");
+    want(q, ScalarType::Float, T * B, "q");
+    want(logZ, ScalarType::Float, B, "logZ");
+    return Dims{(int)T, (int)B};
+}
+// interval marginals (semicrf_interval_marginals): pairs / offsets as eval_path
+void interval_marginals(Tensor score, Tensor v, Tensor q, Tensor logZ, Tensor pairs, int64_t K, Tensor offsets, Tensor out)
+{
+    Ctx c(score); c.same(score, v, q, logZ, pairs, offsets, out);
+    const Dims d = marg_dims(score, v, q, logZ);
+    STD_TORCH_CHECK(K >= 0, "semicrf: negative interval count");
+    check(semicrf_interval_marginals(cfp(score), cfp(v), cfp(q), cfp(logZ), d.T, d.B, i32(pairs, 2 * K, "pairs"), K,
+                                     i32(offsets, d.B + 1, "offsets"), f32w(out, K, "out"), c.stream),
+          "semicrf_interval_marginals");
+}
 void eval_path(Tensor score, Tensor noise, Tensor pairs, int64_t K, Tensor offsets, Tensor out, Tensor ws)
 {
     Ctx c(score); c.same(score, noise, pairs, offsets, out);
@@ -281,6 +315,28 @@ inline void check_path(const int32_t* pairs, int64_t K, const int32_t* offsets, 
     for (int c = 0; c < B; ++c) STD_TORCH_CHECK(offsets[c] <= offsets[c + 1], "semicrf: offsets must ascend");
     for (int64_t i = 0; i < K; ++i)
         STD_TORCH_CHECK(pairs[2 * i] >= 0 && pairs[2 * i] <= pairs[2 * i + 1] && pairs[2 * i + 1] < T, "semicrf: interval out of range");
+}
+void posteriors_cpu(Tensor score, Tensor noise, Tensor v, Tensor q, Tensor logZ, Tensor node, Tensor begin, Tensor end, Tensor single,
+                    Tensor noiseP, Tensor entropy, Tensor ws)
+{
+    all_cpu(score, noise, v, q, logZ, node, begin, end, single, noiseP, entropy);
+    const Dims d = crf_dims(score, noise);
+    const int64_t TB = (int64_t)d.T * d.B;
+    semicrf_cpu::posteriors(cfp(score), cfp(noise), f32(v, TB, "v"), f32(q, TB, "q"), f32(logZ, d.B, "logZ"), d.T, d.B,
+                            f32w(node, TB, "node"), f32w(begin, TB, "begin"), f32w(end, TB, "end"), f32w(single, TB, "single"),
+                            f32w(noiseP, TB - d.B, "noiseP"), f32w(entropy, d.B, "entropy"));
+}
+void interval_marginals_cpu(Tensor score, Tensor v, Tensor q, Tensor logZ, Tensor pairs, int64_t K, Tensor offsets, Tensor out)
+{
+    all_cpu(score, v, q, logZ, pairs, offsets, out);
+    const Dims d = marg_dims(score, v, q, logZ);
+    STD_TORCH_CHECK(K >= 0, "semicrf: negative interval count");
+    const int32_t* pp = i32(pairs, 2 * K, "pairs");
+    const int32_t* oo = i32(offsets, d.B + 1, "offsets");
+    STD_TORCH_CHECK(oo[0] == 0 && oo[d.B] == K, "semicrf: offsets do not match the interval count");
+    for (int c = 0; c < d.B; ++c) STD_TORCH_CHECK(oo[c] <= oo[c + 1], "semicrf: offsets must ascend");
+    for (int64_t i = 0; i < 2 * K; ++i) STD_TORCH_CHECK(pp[i] >= 0 && pp[i] < d.T, "semicrf: interval out of range");
+    semicrf_cpu::interval_marginals(cfp(score), cfp(v), cfp(q), cfp(logZ), d.T, d.B, pp, oo, f32w(out, K, "out"));
 }
 void eval_path_cpu(Tensor score, Tensor noise, Tensor pairs, int64_t K, Tensor offsets, Tensor out, Tensor ws)
 {
@@ -535,6 +591,9 @@ STABLE_TORCH_LIBRARY(semicrf, m)
           "Tensor(b!) offsets, Tensor(c!) ws) -> ()");
     m.def("viterbi_nbest(Tensor score, Tensor noise, int k, Tensor start, bool has_start, bool forward, Tensor(a!) pairs, "
           "Tensor(b!) offsets, Tensor(c!) scores, Tensor(d!) npaths, Tensor(e!) ws) -> ()");
+    m.def("posteriors(Tensor score, Tensor noise, Tensor v, Tensor q, Tensor logZ, Tensor(a!) node, Tensor(b!) begin, Tensor(c!) end, "
+          "Tensor(d!) single, Tensor(e!) noiseP, Tensor(f!) entropy, Tensor(g!) ws) -> ()");
+    m.def("interval_marginals(Tensor score, Tensor v, Tensor q, Tensor logZ, Tensor pairs, int K, Tensor offsets, Tensor(a!) out) -> ()");
     m.def("eval_path(Tensor score, Tensor noise, Tensor pairs, int K, Tensor offsets, Tensor(a!) out, Tensor(b!) ws) -> ()");
     m.def("eval_path_bwd(Tensor gout, int T, int B, Tensor pairs, int K, Tensor offsets, Tensor(a!) dScore, bool has_ds, Tensor(b!) dNoise, "
           "bool has_dn) -> ()");
@@ -582,6 +641,8 @@ STABLE_TORCH_LIBRARY_IMPL(semicrf, CPU, m)
     m.impl("viterbi", TORCH_BOX(&viterbi_cpu));
     m.impl("sample", TORCH_BOX(&sample_cpu));
     m.impl("viterbi_nbest", TORCH_BOX(&viterbi_nbest_cpu));
+    m.impl("posteriors", TORCH_BOX(&posteriors_cpu));
+    m.impl("interval_marginals", TORCH_BOX(&interval_marginals_cpu));
     m.impl("eval_path", TORCH_BOX(&eval_path_cpu));
     m.impl("eval_path_bwd", TORCH_BOX(&eval_path_bwd_cpu));
     m.impl("logprob_fwd", TORCH_BOX(&logprob_fwd_cpu));
@@ -596,6 +657,8 @@ STABLE_TORCH_LIBRARY_IMPL(semicrf, CUDA, m)
     m.impl("viterbi", TORCH_BOX(&viterbi));
     m.impl("sample", TORCH_BOX(&sample));
     m.impl("viterbi_nbest", TORCH_BOX(&viterbi_nbest));
+    m.impl("posteriors", TORCH_BOX(&posteriors));
+    m.impl("interval_marginals", TORCH_BOX(&interval_marginals));
     m.impl("eval_path", TORCH_BOX(&eval_path));
     m.impl("eval_path_bwd", TORCH_BOX(&eval_path_bwd));
     m.impl("logprob_fwd", TORCH_BOX(&logprob_fwd));
