@@ -52,6 +52,7 @@ extern "C" {
 #define SEMICRF_OP_SAMPLE 5           /* B = nSample * NBatch of the semicrf_sample call */
 #define SEMICRF_OP_VITERBI_NBEST 6    /* B = k * NBatch of the semicrf_viterbi_nbest call */
 #define SEMICRF_OP_POSTERIORS 7       /* semicrf_posteriors */
+#define SEMICRF_OP_MARGINAL_DECODE 8   /* semicrf_marginal_decode */
 
 /* length scaling of the interval scorer (LayersTransformer.py:416-427) */
 #define SEMICRF_LEN_LINEAR 0
@@ -236,6 +237,31 @@ int semicrf_posteriors(const float* score, const float* noise, const float* v, c
  */
 int semicrf_interval_marginals(const float* score, const float* v, const float* q, const float* logZ, int T, int B,
                                const int32_t* pairs, int64_t K, const int32_t* offsets, float* out, semicrf_stream_t stream);
+
+/*
+ * Marginal-threshold (posterior) decoding: every cell (e, b), b <= e, of chain c with m(e, b, c) >= tau[c * tau_stride], packed.
+ * No counterpart in the reference (an extension of its surface, like semicrf_posteriors).  Adds nothing to the ABI's existing
+ * entry points (version 2).
+ *   v, q, logZ: as semicrf_posteriors.  noise is not read (it is inside v and q); it may be NULL only when T = 1.
+ *   m(e, b, c) is the value semicrf_interval_marginals returns for (b, e) of chain c, bit for bit (both evaluate the same inline
+ *   functions).  The comparison is m >= tau in fp32; a NaN m or a NaN tau selects nothing.
+ *   tau: a DEVICE pointer; tau_stride 0 (one value for all chains) or 1 (per chain: per-symbol calibration).
+ *   pairs [cap][2] (begin, end), probs [cap] (probs[i] = m of interval i), offsets [B+1]: chain-major; within a chain ascending by
+ *   (begin, end), as semicrf_sample / semicrf_viterbi(forward = 1) order a path.  Two cells that overlap cannot lie on one path, so
+ *   their marginals sum to <= 1: for tau > 0.5 the selected cells of a chain are pairwise compatible -- a path in the sense of
+ *   semicrf_viterbi (then (begin, end) order is also ascending by end); for tau <= 0.5 they are a candidate lattice that may overlap.
+ *   offsets is exact even when offsets[B] > cap; pairs / probs then hold the first cap entries of that order and nothing is written
+ *   out of bounds (the semicrf_viterbi convention).  offsets[B] = -1 when v holds NaN in its last row (a sweep that gave up on a
+ *   bounded wait; the semicrf_sample convention).
+ *   Bound for callers: sum_{e > b} m(e, b) <= 1 for every b, so a chain has at most T * (floor(1 / tau) + 1) selected cells
+ *   (singletons included); for tau > 0.5 that is the 2 T of semicrf_viterbi.  T (T+1) / 2 * B must stay below 2^31.
+ *   No host synchronisation, no atomics: the result is a pure function of the inputs, two calls are bit-identical.  One read of the
+ *   lower triangle plus the rows that hold a selected cell.
+ *   Workspace: semicrf_workspace_bytes(SEMICRF_OP_MARGINAL_DECODE, T, B), about (1.5 * ceil(T/64) + 1) * T * B int32.
+ */
+int semicrf_marginal_decode(const float* score, const float* noise, const float* v, const float* q, const float* logZ, int T, int B,
+                            const float* tau, int tau_stride, int32_t* pairs, float* probs, int64_t cap, int32_t* offsets,
+                            void* ws, size_t ws_bytes, semicrf_stream_t stream);
 
 /*
  * Unnormalised path score.  Replaces: evalPath (:508-550).

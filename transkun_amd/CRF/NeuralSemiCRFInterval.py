@@ -17,8 +17,9 @@ What differs from the reference, invisibly at the API:
     pass instead of summing two dense [T,T,B] gradients.
   * decode() backtracks on the device; only the packed (begin,end) pairs cross PCIe.
 EXTENSIONS of the reference's surface: decode_packed, sample / sample_packed (exact posterior draws of paths),
-  decode_nbest / decode_nbest_packed (the k best paths, ranked), and posteriors / interval_marginals /
-  interval_marginals_packed (posterior marginals and path entropy without the dense [T,T,B] tensor).
+  decode_nbest / decode_nbest_packed (the k best paths, ranked), posteriors / interval_marginals /
+  interval_marginals_packed (posterior marginals and path entropy without the dense [T,T,B] tensor), and decode_marginal /
+  decode_marginal_packed (every interval whose posterior probability reaches a threshold).
 """
 from __future__ import annotations
 
@@ -917,6 +918,87 @@ def interval_marginals(score, noiseScore, intervals: Intervals) -> List[List[flo
     return [out[off[c]:off[c + 1]] for c in range(B)]
 
 
+# --------------------------------------------------------------------------------------
+# marginal-threshold (posterior) decoding (an extension of the reference's surface)
+# --------------------------------------------------------------------------------------
+
+def _marginal_decode_raw(score_c, noise_c, tau, cap: Optional[int] = None, lvq=None):
+    """Enqueue the sweeps (unless lvq = (logZ, v, q) is given) and semicrf_marginal_decode; no host sync.  tau: a float32 tensor
+    of 1 value or one per chain, where the scores live.  Returns device tensors (pairs [cap, 2], offsets [B+1], probs [cap]);
+    offsets is exact even past cap (default 2 T per chain: the bound for a threshold > 0.5)."""
+    if _odd_pad(score_c) and lvq is None:
+        t2 = tau if tau.numel() == 1 else torch.cat([tau, tau.new_full((1,), float("inf"))])     # the ghost chain selects nothing
+        pairs, offsets, probs = _marginal_decode_raw(_pad1(score_c), _pad1(noise_c), t2, cap)
+        return pairs, offsets[:-1], probs  # the ghost chain is last: its intervals lie behind offsets[B]
+    T, B = score_c.shape[0], score_c.shape[2]
+    dev = score_c.device
+    logz, v, q = _marginal_inputs(score_c, noise_c) if lvq is None else lvq
+    cap = max(int(cap), 1) if cap is not None else 2 * T * B
+    pairs = torch.empty(cap, 2, dtype=torch.int32, device=dev)
+    probs = torch.empty(cap, dtype=torch.float32, device=dev)
+    offsets = torch.empty(B + 1, dtype=torch.int32, device=dev)
+    ws = _lib.workspace(_lib.OP_MARGINAL_DECODE, T, B, dev)
+    _lib.ops().marginal_decode(score_c, noise_c, v, q, logz, tau, pairs, probs, offsets, ws)
+    return pairs, offsets, probs
+
+
+def _threshold_tensor(threshold, B: int, device) -> torch.Tensor:
+    if isinstance(threshold, torch.Tensor):
+        if not threshold.is_floating_point() or tuple(threshold.shape) != (B,):
+            raise ValueError(f"decode_marginal: a threshold tensor must be floating point of shape [{B}] (one value per chain), "
+                             f"got {threshold.dtype} {tuple(threshold.shape)}")
+        return threshold.detach().to(device=device, dtype=torch.float32).contiguous()       # not range-checked: that would synchronise
+    if isinstance(threshold, bool) or not isinstance(threshold, (int, float, np.floating, np.integer)):
+        raise ValueError(f"decode_marginal: threshold must be a float in (0, 1] or a float tensor [nBatch], got {threshold!r}")
+    t = float(threshold)
+    if not (0.0 < t <= 1.0):                   # NaN fails both comparisons
+        raise ValueError(f"decode_marginal: threshold must be in (0, 1], got {threshold!r}")
+    return torch.full((1,), t, dtype=torch.float32, device=device)
+
+
+def decode_marginal_packed(score, noiseScore, threshold):
+    """An EXTENSION of the reference's surface: every interval whose posterior probability P((begin, end) on the path | score) is
+    >= threshold, as host arrays like decode_packed plus the probabilities: (pairs int32 [K, 2], offsets int32 [nBatch + 1],
+    probs float32 [K]); chain c owns pairs[offsets[c]:offsets[c + 1]], ascending by (begin, end).  probs are the values
+    interval_marginals returns for those intervals, bit for bit.
+
+    threshold: a Python float in (0, 1], or a float tensor [nBatch] (one threshold per chain; not range-checked).  There is no
+    default: 0.5 is exactly where ties sit and the caller should choose a side.  For threshold > 0.5 the intervals of a chain
+    cannot overlap (overlapping intervals never share a path, so their probabilities sum to <= 1): the result is a path that
+    plugs into evalPath / logProb, the minimum-Bayes-risk decision for the gain (1 - threshold) per correct and -threshold per
+    wrong interval; for threshold <= 0.5 it is a candidate lattice that may overlap.  Runs the alpha and beta sweeps itself,
+    never builds the dense [T, T, nBatch] marginal tensor; one host sync; no gradient."""
+    T, B = _check_inputs(score, noiseScore)
+    with torch.no_grad():
+        score_c, noise_c = _prep(score.detach()), _prep(noiseScore.detach())
+        tau = _threshold_tensor(threshold, B, score_c.device)
+        lvq = None if _odd_pad(score_c) else _marginal_inputs(score_c, noise_c)    # (a single chain: the raw call pads and sweeps)
+        pairs, offsets, probs = _marginal_decode_raw(score_c, noise_c, tau, None, lvq)
+        off_h = offsets.cpu()                      # the one host sync
+        if int(off_h[-1]) > pairs.shape[0]:
+            # more cells than 2 T per chain (a threshold <= 0.5): once more with the exact size -- never a silent truncation
+            pairs, offsets, probs = _marginal_decode_raw(score_c, noise_c, tau, int(off_h[-1]), lvq)
+            off_h = offsets.cpu()
+        total = int(off_h[-1])
+        if total < 0:
+            _lib.async_error()                     # consumed here: the next call must not report this time-out again
+            raise RuntimeError("semicrf_marginal_decode: alpha holds NaN in its last row -- the inputs hold NaN (or -inf cells, which "
+                               "the device's forward sweep does not take), or a bounded hand-off wait of the sweep timed out on the "
+                               "device (GPU shared with work that kept part of the persistent kernel from running?); the result is invalid")
+        return pairs[:total].cpu().numpy(), off_h.numpy(), probs[:total].cpu().numpy()
+
+
+def decode_marginal(score, noiseScore, threshold):
+    """An EXTENSION of the reference's surface: (paths, probs) -- paths an Intervals (per chain the list of (begin, end) whose
+    posterior probability is >= threshold, ascending by (begin, end): the type decode returns), probs per chain the list of those
+    probabilities.  Arguments and properties as decode_marginal_packed."""
+    T, B = _check_inputs(score, noiseScore)
+    pairs, offsets, probs = decode_marginal_packed(score, noiseScore, threshold)
+    paths = unpack_intervals(torch.from_numpy(pairs), torch.from_numpy(offsets), T)
+    pl, off = probs.tolist(), offsets.tolist()
+    return paths, [pl[off[c]:off[c + 1]] for c in range(B)]
+
+
 def viterbiBackward(score, noiseScore, forcedStartPos: Optional[List[int]] = None) -> Intervals:
     """Right-to-left Viterbi, the default decode (reference :13-104)."""
     return _decode(score, noiseScore, forcedStartPos, forward=False)
@@ -1026,6 +1108,18 @@ class NeuralSemiCRFInterval:
     def interval_marginals_packed(self, pairs, offsets):
         """`interval_marginals` on decode_packed's arrays (numpy or tensors): a float32 tensor [K] where the scores live."""
         return interval_marginals_packed(self.score, self.noiseScore, pairs, offsets)
+
+    def decode_marginal(self, threshold):
+        """An EXTENSION of the reference's surface: (paths, probs) -- every interval whose posterior probability is >= threshold
+        (a float in (0, 1] or a float tensor [nBatch]; no default), per chain ascending by (begin, end), and those probabilities.
+        For threshold > 0.5 each chain's result is a path (plugs into evalPath / logProb) -- see the module-level
+        decode_marginal_packed.  No gradient."""
+        return decode_marginal(self.score, self.noiseScore, threshold)
+
+    def decode_marginal_packed(self, threshold):
+        """`decode_marginal` as host arrays (pairs int32 [K, 2], offsets int32 [nBatch + 1], probs float32 [K]) before the Python
+        lists are built; pairs / offsets feed interval_marginals_packed and attributes.attribute_input_packed as they are."""
+        return decode_marginal_packed(self.score, self.noiseScore, threshold)
 
     def evalPath(self, intervals):
         """compute the unnormalized score"""

@@ -4,4 +4,5 @@ from .NeuralSemiCRFInterval import (NeuralSemiCRFInterval, viterbi, viterbiBackw
                                     forward_backward, evalPath, computeLogZFasterGrad,
                                     ComputeLogZFasterGrad, sample, sample_packed,
                                     viterbi_nbest, viterbi_nbest_packed, Posteriors, posteriors,
-                                    interval_marginals, interval_marginals_packed)
+                                    interval_marginals, interval_marginals_packed,
+                                    decode_marginal, decode_marginal_packed)

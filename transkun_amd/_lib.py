@@ -24,6 +24,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SEMICRF_LIB") or os.path.join(_HERE, "libsemicrf_hip.so")   # SEMICRF_LIB: development variants
 
 OP_LOGZ_FWD, OP_LOGZ_BWD, OP_VITERBI, OP_EVAL_PATH, OP_INTERVAL_SCORE, OP_SAMPLE, OP_VITERBI_NBEST, OP_POSTERIORS = range(8)
+OP_MARGINAL_DECODE = 8
 LEN_MODES = {"linear": 0, "sqrt": 1, "none": 2}
 
 _vp = ctypes.c_void_p
@@ -52,6 +53,7 @@ _SIGS = {
     "semicrf_viterbi_nbest": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
     "semicrf_posteriors": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "semicrf_interval_marginals": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _i64, _vp, _vp, _vp]),
+    "semicrf_marginal_decode": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, _i64, _vp, _vp, _sz, _vp]),
     "semicrf_eval_path": (_i, [_vp, _vp, _i, _i, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
     "semicrf_eval_path_bwd": (_i, [_vp, _i, _i, _vp, _i64, _vp, _vp, _vp, _vp]),
     "semicrf_logprob_fwd": (_i, [_vp, _vp, _i, _i, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),

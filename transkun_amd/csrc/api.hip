@@ -100,6 +100,9 @@ void launch_posteriors(const float* score, const float* noise, const float* v, c
                        hipStream_t stream);
 void launch_interval_marginals(const float* score, const float* v, const float* q, const float* logZ, int T, int B, const int* pairs,
                                int K, const int* offsets, float* out, hipStream_t stream);
+size_t marginal_decode_workspace_bytes(int T, int B);
+void launch_marginal_decode(const float* score, const float* v, const float* q, const float* logZ, int T, int B, const float* tau,
+                            int tau_stride, int* pairs, float* probs, long long cap, int* offsets, void* ws, hipStream_t stream);
 size_t nbest_workspace_bytes(int T, int nB);
 void launch_viterbi_nbest(const float* score, const float* noise, int T, int B, int k, const int* start, int forward, int* pairs,
                           long long cap, int* offsets, float* scores, int* npaths, void* ws, hipStream_t stream);
@@ -288,6 +291,7 @@ size_t semicrf_workspace_bytes(int op, int T, int B)
         case SEMICRF_OP_SAMPLE: return sample_workspace_bytes(T, B);
         case SEMICRF_OP_POSTERIORS: return posterior_workspace_bytes(T, B);
         case SEMICRF_OP_VITERBI_NBEST: return nbest_workspace_bytes(T, B);
+        case SEMICRF_OP_MARGINAL_DECODE: return marginal_decode_workspace_bytes(T, B);
         default: return 0;
     }
 }
@@ -553,6 +557,23 @@ int semicrf_interval_marginals(const float* score, const float* v, const float* 
     SEMICRF_CHECK_ARG(K >= 0 && K < (1ll << 31) && (K == 0 || (pairs && out)), "bad interval count");
     launch_interval_marginals(score, v, q, logZ, T, B, pairs, (int)K, offsets, out, (hipStream_t)stream);
     SEMICRF_CHECK_LAUNCH("semicrf_interval_marginals");
+    return SEMICRF_OK;
+}
+
+int semicrf_marginal_decode(const float* score, const float* noise, const float* v, const float* q, const float* logZ, int T, int B,
+                            const float* tau, int tau_stride, int32_t* pairs, float* probs, int64_t cap, int32_t* offsets, void* ws,
+                            size_t ws_bytes, semicrf_stream_t stream)
+{
+    if (int rc = check_common(score, noise, T, B)) return rc;
+    SEMICRF_CHECK_ARG(v && q && logZ && tau, "v (alpha), q (beta), logZ and tau must be non-NULL");
+    SEMICRF_CHECK_ARG(tau_stride == 0 || tau_stride == 1, "tau stride must be 0 (one value for all chains) or 1");
+    SEMICRF_CHECK_ARG(pairs && probs && offsets && cap >= 0, "pairs/probs/offsets must be non-NULL and cap >= 0");
+    SEMICRF_CHECK_ARG((long long)T * (T + 1) / 2 * B < (1ll << 31), "T (T+1) / 2 * B exceeds int32 offsets");
+    SEMICRF_CHECK_ARG((long long)((T + 63) / 64) * ((T + 63) / 64 + 1) / 2 < 65536, "T=%d too large for the marginal decode", T);
+    SEMICRF_CHECK_ARG(ws != nullptr, "workspace is NULL");
+    if (ws_bytes < marginal_decode_workspace_bytes(T, B)) { set_error("workspace too small for marginal_decode"); return SEMICRF_EWORKSPACE; }
+    launch_marginal_decode(score, v, q, logZ, T, B, tau, tau_stride, pairs, probs, (long long)cap, offsets, ws, (hipStream_t)stream);
+    SEMICRF_CHECK_LAUNCH("semicrf_marginal_decode");
     return SEMICRF_OK;
 }
 

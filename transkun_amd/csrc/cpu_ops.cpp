@@ -327,6 +327,9 @@ inline double bern_entropy_d(double d)
 inline double ent_term_d(double mu, double R, double y) { return mu > 0.0 ? mu * (R - y > 0.0 ? R - y : 0.0) : 0.0; }
 inline float clamp1(double x) { return x > 1.0 ? 1.0f : (float)x; }
 inline double single_d(double v, double q, double lz, double d) { return exp(v + q - lz + d - 2.0 * softplus_d(d)); }
+// the marginal of ONE cell, rounded to fp32: what interval_marginals returns and what marginal_decode compares with its threshold
+inline float cell_marginal(float vb, float s, float qe, float lz) { return clamp1(exp((double)vb + (double)s + (double)qe - lz)); }
+inline float cell_marginal_single(float vt, float qt, float lz, float d) { return clamp1(single_d(vt, qt, lz, d)); }
 }  // namespace
 
 void posteriors(const float* score, const float* noise, const float* v, const float* q, const float* logZ, int T, int B, float* node,
@@ -384,10 +387,49 @@ void interval_marginals(const float* score, const float* v, const float* q, cons
             const int b = pairs[2 * k], e = pairs[2 * k + 1];
             const size_t ec = (size_t)e * Bs + c;
             if (b > e) out[k] = 0.0f;
-            else if (b == e) out[k] = clamp1(single_d(v[ec], q[ec], logZ[c], score[((size_t)e * T + e) * Bs + c]));
-            else
-                out[k] = clamp1(exp((double)v[(size_t)b * Bs + c] + (double)score[((size_t)e * T + b) * Bs + c] + (double)q[ec] - logZ[c]));
+            else if (b == e) out[k] = cell_marginal_single(v[ec], q[ec], logZ[c], score[((size_t)e * T + e) * Bs + c]);
+            else out[k] = cell_marginal(v[(size_t)b * Bs + c], score[((size_t)e * T + b) * Bs + c], q[ec], logZ[c]);
         }
+}
+
+// marginal-threshold decoding (include/semicrf_hip.h: semicrf_marginal_decode; the device kernels are marginal_decode.hip): every
+// cell b <= e with cell_marginal >= tau[c * tau_stride], chain-major, ascending by (begin, end).  Chain blocks in parallel, each
+// walking the triangle row by row (the chain axis is the contiguous one) into per-column lists; packed in order afterwards.
+void marginal_decode(const float* score, const float* v, const float* q, const float* logZ, int T, int B, const float* tau,
+                     int tau_stride, int32_t* pairs, float* probs, int64_t cap, int32_t* offsets)
+{
+    const size_t Bs = (size_t)B;
+    struct Hit { int32_t e; float m; };
+    std::vector<std::vector<Hit>> hits((size_t)T * Bs);            // [b][c]: the column's selected cells, e ascending
+    const int nblk = (B + CB - 1) / CB;
+#pragma omp parallel for schedule(dynamic, 1)
+    for (int blk = 0; blk < nblk; ++blk) {
+        const int c0 = blk * CB;
+        const int nc = B - c0 < CB ? B - c0 : CB;
+        for (int e = 0; e < T; ++e) {
+            const float* row = score + (size_t)e * T * Bs;
+            for (int b = 0; b <= e; ++b)
+                for (int c = c0; c < c0 + nc; ++c) {
+                    const size_t ec = (size_t)e * Bs + c;
+                    const float m = b == e ? cell_marginal_single(v[ec], q[ec], logZ[c], row[(size_t)e * Bs + c])
+                                           : cell_marginal(v[(size_t)b * Bs + c], row[(size_t)b * Bs + c], q[ec], logZ[c]);
+                    if (m >= tau[(size_t)c * tau_stride]) hits[(size_t)b * Bs + c].push_back(Hit{(int32_t)e, m});
+                }
+        }
+    }
+    int64_t n = 0;
+    bool bad = false;
+    for (int c = 0; c < B; ++c) {
+        offsets[c] = (int32_t)n;
+        for (int b = 0; b < T; ++b)
+            for (const Hit& h : hits[(size_t)b * Bs + c]) {
+                if (n < cap) { pairs[2 * n] = b; pairs[2 * n + 1] = h.e; probs[n] = h.m; }
+                ++n;
+            }
+        const float vl = v[(size_t)(T - 1) * Bs + c];
+        bad = bad || vl != vl;
+    }
+    offsets[B] = bad ? -1 : (int32_t)n;
 }
 
 // k-best Viterbi (include/semicrf_hip.h: semicrf_viterbi_nbest; the device kernel is nbest.hip).  Per frame and chain a sorted

@@ -17,6 +17,8 @@ void posteriors(const float* score, const float* noise, const float* v, const fl
                 float* begin, float* end, float* single, float* noiseP, float* entropy);
 void interval_marginals(const float* score, const float* v, const float* q, const float* logZ, int T, int B, const int32_t* pairs,
                         const int32_t* offsets, float* out);
+void marginal_decode(const float* score, const float* v, const float* q, const float* logZ, int T, int B, const float* tau,
+                     int tau_stride, int32_t* pairs, float* probs, int64_t cap, int32_t* offsets);
 void eval_path(const float* score, const float* noise, int T, int B, const int32_t* pairs, const int32_t* offsets, float* out);
 void eval_path_bwd(const float* gout, int T, int B, const int32_t* pairs, const int32_t* offsets, float* dScore, float* dNoise);
 }  // namespace semicrf_cpu

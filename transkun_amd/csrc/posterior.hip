@@ -21,6 +21,7 @@
 //   posterior_entropy_kernel  per chain the sum of those partials, in frame order.
 // The result is a pure function of the inputs (two calls are bit-identical).
 #include "common.h"
+#include "posterior_cell.h"
 
 namespace semicrf {
 
@@ -33,19 +34,6 @@ constexpr int PWAVES = 4;                   // waves per workgroup; each takes P
 constexpr int PROWS = PT / PWAVES;
 constexpr int PSUB = 4;                     // epilogue: workgroups per row band (16 frames each)
 
-typedef float f4 __attribute__((ext_vector_type(4)));
-typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));     // odd NBatch: 16-byte accesses at 4-byte aligned addresses
-
-// chains c0 .. c0+3 of row `p` (n = how many of them exist; the rest read as `fill`)
-__device__ __forceinline__ f4 ld4(const float* __restrict__ p, int n, float fill)
-{
-    if (n >= 4) return (f4)(*(const f4u*)p);
-    f4 r = {fill, fill, fill, fill};
-    if (n > 0) r.x = p[0];
-    if (n > 1) r.y = p[1];
-    if (n > 2) r.z = p[2];
-    return r;
-}
 __device__ __forceinline__ void st4(float* __restrict__ p, int n, f4 x)
 {
     if (n >= 4) { *(f4u*)p = (f4u)x; return; }
@@ -54,32 +42,19 @@ __device__ __forceinline__ void st4(float* __restrict__ p, int n, f4 x)
     if (n > 2) p[2] = x.z;
 }
 
-// the singleton's marginal exp(v + q - logZ + d - 2 sp(d)) (semicrf_logz_bwd's diagonal dScore)
-__device__ __forceinline__ float single_marg(float v, float q, float lz, float d)
-{
-    return __expf(v + q - lz + d - 2.0f * softplus_f(d));
-}
+// (clamp1, single_marg and the cell marginals shared with marginal_decode.hip: posterior_cell.h)
 // Bernoulli entropy of sigmoid(d), in the form that is symmetric in d and has no cancellation: sp(-|d|) + |d| sigmoid(-|d|)
 __device__ __forceinline__ float bern_entropy(float d)
 {
     const float a = fabsf(d), ea = __expf(-a);
     return log1pf(ea) + (ea > 0.0f ? a * ea / (1.0f + ea) : 0.0f);
 }
-__device__ __forceinline__ float clamp1(float x) { return x > 1.0f ? 1.0f : x; }     // rounding above 1; NaN stays NaN
 // one entropy term mu * (-lp), lp = y - R clamped to <= 0; a cell of zero probability adds exactly 0 (even with lp = -inf)
 __device__ __forceinline__ float ent_term(float mu, float R, float y)
 {
     return mu > 0.0f ? mu * fmaxf(R - y, 0.0f) : 0.0f;
 }
 
-__device__ __forceinline__ void tile_of(int k, int& i, int& j)      // k-th tile of the lower triangle, row-major: (i, j), j <= i
-{
-    int r = (int)((sqrtf(8.0f * (float)k + 1.0f) - 1.0f) * 0.5f);
-    while ((r + 1) * (r + 2) / 2 <= k) ++r;
-    while (r * (r + 1) / 2 > k) --r;
-    i = r;
-    j = k - r * (r + 1) / 2;
-}
 }  // namespace
 
 // grid (ceil(B/32), nI (nI+1)/2), block 256.  rowp [nI][T][B]: rowp[j][e] = sum over the columns of tile (e/64, j);
@@ -271,11 +246,8 @@ __global__ void interval_marginals_kernel(const float* __restrict__ score, const
     float r;
     if (b < 0 || e < 0 || b >= T || e >= T) r = __builtin_nanf("");
     else if (b > e) r = 0.0f;
-    else if (b == e) r = clamp1(single_marg(v[(size_t)e * Bs + c], q[(size_t)e * Bs + c], logZ[c], score[((size_t)e * T + e) * Bs + c]));
-    else {
-        const float y = v[(size_t)b * Bs + c] + score[((size_t)e * T + b) * Bs + c];
-        r = clamp1(__expf(y + (q[(size_t)e * Bs + c] - logZ[c])));
-    }
+    else if (b == e) r = cell_marginal_single(v[(size_t)e * Bs + c], q[(size_t)e * Bs + c], logZ[c], score[((size_t)e * T + e) * Bs + c]);
+    else r = cell_marginal(v[(size_t)b * Bs + c], score[((size_t)e * T + b) * Bs + c], q[(size_t)e * Bs + c] - logZ[c]);
     out[k] = r;
 }
 

@@ -186,6 +186,26 @@ void interval_marginals(Tensor score, Tensor v, Tensor q, Tensor logZ, Tensor pa
                                      i32(offsets, d.B + 1, "offsets"), f32w(out, K, "out"), c.stream),
           "semicrf_interval_marginals");
 }
+// marginal-threshold decoding (semicrf_marginal_decode): tau holds 1 value (all chains) or B (per chain); pairs [cap, 2], probs [cap]
+inline int tau_stride_of(const Tensor& tau, int B)
+{
+    want(tau, ScalarType::Float, 1, "tau");
+    STD_TORCH_CHECK(tau.numel() == 1 || tau.numel() == B, "semicrf: tau must hold 1 value or one per chain (", B, "), got ", tau.numel());
+    return tau.numel() == B && B > 1 ? 1 : 0;
+}
+void marginal_decode(Tensor score, Tensor noise, Tensor v, Tensor q, Tensor logZ, Tensor tau, Tensor pairs, Tensor probs, Tensor offsets,
+                     Tensor ws)
+{
+    Ctx c(score); c.same(score, noise, v, q, logZ, tau, pairs, probs, offsets, ws);
+    const Dims d = crf_dims(score, noise);
+    const int64_t TB = (int64_t)d.T * d.B;
+    STD_TORCH_CHECK(pairs.dim() == 2 && pairs.size(1) == 2 && pairs.size(0) >= 1, "semicrf: pairs must be [cap, 2], cap >= 1");
+    const int64_t cap = pairs.size(0);
+    check(semicrf_marginal_decode(cfp(score), cfp(noise), f32(v, TB, "v"), f32(q, TB, "q"), f32(logZ, d.B, "logZ"), d.T, d.B,
+                                  cfp(tau), tau_stride_of(tau, d.B), i32(pairs, 2 * cap, "pairs"), f32w(probs, cap, "probs"), cap,
+                                  i32(offsets, d.B + 1, "offsets"), bytes(ws, "ws"), (size_t)ws.numel(), c.stream),
+          "semicrf_marginal_decode");
+}
 void eval_path(Tensor score, Tensor noise, Tensor pairs, int64_t K, Tensor offsets, Tensor out, Tensor ws)
 {
     Ctx c(score); c.same(score, noise, pairs, offsets, out);
@@ -337,6 +357,19 @@ void interval_marginals_cpu(Tensor score, Tensor v, Tensor q, Tensor logZ, Tenso
     for (int c = 0; c < d.B; ++c) STD_TORCH_CHECK(oo[c] <= oo[c + 1], "semicrf: offsets must ascend");
     for (int64_t i = 0; i < 2 * K; ++i) STD_TORCH_CHECK(pp[i] >= 0 && pp[i] < d.T, "semicrf: interval out of range");
     semicrf_cpu::interval_marginals(cfp(score), cfp(v), cfp(q), cfp(logZ), d.T, d.B, pp, oo, f32w(out, K, "out"));
+}
+void marginal_decode_cpu(Tensor score, Tensor noise, Tensor v, Tensor q, Tensor logZ, Tensor tau, Tensor pairs, Tensor probs,
+                         Tensor offsets, Tensor ws)
+{
+    all_cpu(score, noise, v, q, logZ, tau, pairs, probs, offsets);
+    const Dims d = crf_dims(score, noise);
+    const int64_t TB = (int64_t)d.T * d.B;
+    STD_TORCH_CHECK((int64_t)d.T * (d.T + 1) / 2 * d.B < (1ll << 31), "semicrf: T (T+1) / 2 * B exceeds int32 offsets");
+    STD_TORCH_CHECK(pairs.dim() == 2 && pairs.size(1) == 2 && pairs.size(0) >= 1, "semicrf: pairs must be [cap, 2], cap >= 1");
+    const int64_t cap = pairs.size(0);
+    const int ts = tau_stride_of(tau, d.B);
+    semicrf_cpu::marginal_decode(cfp(score), f32(v, TB, "v"), f32(q, TB, "q"), f32(logZ, d.B, "logZ"), d.T, d.B, cfp(tau), ts,
+                                 i32(pairs, 2 * cap, "pairs"), f32w(probs, cap, "probs"), cap, i32(offsets, d.B + 1, "offsets"));
 }
 void eval_path_cpu(Tensor score, Tensor noise, Tensor pairs, int64_t K, Tensor offsets, Tensor out, Tensor ws)
 {
@@ -594,6 +627,8 @@ STABLE_TORCH_LIBRARY(semicrf, m)
     m.def("posteriors(Tensor score, Tensor noise, Tensor v, Tensor q, Tensor logZ, Tensor(a!) node, Tensor(b!) begin, Tensor(c!) end, "
           "Tensor(d!) single, Tensor(e!) noiseP, Tensor(f!) entropy, Tensor(g!) ws) -> ()");
     m.def("interval_marginals(Tensor score, Tensor v, Tensor q, Tensor logZ, Tensor pairs, int K, Tensor offsets, Tensor(a!) out) -> ()");
+    m.def("marginal_decode(Tensor score, Tensor noise, Tensor v, Tensor q, Tensor logZ, Tensor tau, Tensor(a!) pairs, Tensor(b!) probs, "
+          "Tensor(c!) offsets, Tensor(d!) ws) -> ()");
     m.def("eval_path(Tensor score, Tensor noise, Tensor pairs, int K, Tensor offsets, Tensor(a!) out, Tensor(b!) ws) -> ()");
     m.def("eval_path_bwd(Tensor gout, int T, int B, Tensor pairs, int K, Tensor offsets, Tensor(a!) dScore, bool has_ds, Tensor(b!) dNoise, "
           "bool has_dn) -> ()");
@@ -643,6 +678,7 @@ STABLE_TORCH_LIBRARY_IMPL(semicrf, CPU, m)
     m.impl("viterbi_nbest", TORCH_BOX(&viterbi_nbest_cpu));
     m.impl("posteriors", TORCH_BOX(&posteriors_cpu));
     m.impl("interval_marginals", TORCH_BOX(&interval_marginals_cpu));
+    m.impl("marginal_decode", TORCH_BOX(&marginal_decode_cpu));
     m.impl("eval_path", TORCH_BOX(&eval_path_cpu));
     m.impl("eval_path_bwd", TORCH_BOX(&eval_path_bwd_cpu));
     m.impl("logprob_fwd", TORCH_BOX(&logprob_fwd_cpu));
@@ -659,6 +695,7 @@ STABLE_TORCH_LIBRARY_IMPL(semicrf, CUDA, m)
     m.impl("viterbi_nbest", TORCH_BOX(&viterbi_nbest));
     m.impl("posteriors", TORCH_BOX(&posteriors));
     m.impl("interval_marginals", TORCH_BOX(&interval_marginals));
+    m.impl("marginal_decode", TORCH_BOX(&marginal_decode));
     m.impl("eval_path", TORCH_BOX(&eval_path));
     m.impl("eval_path_bwd", TORCH_BOX(&eval_path_bwd));
     m.impl("logprob_fwd", TORCH_BOX(&logprob_fwd));
