@@ -268,6 +268,12 @@ int semicrf_marginal_decode(const float* score, const float* noise, const float*
  *   pairs int32 [K][2] (begin,end), offsets int32 [B+1] (chain c owns pairs[offsets[c]:offsets[c+1]]).
  *   out[c] = sum_path ( s[end,begin,c] - (cum[end]-cum[begin]) ) + cum[T-1],  cum = prefix sums of noise.
  *   K = number of intervals in pairs (= offsets[B]).
+ * PRECONDITION (semicrf_eval_path, semicrf_eval_path_bwd, semicrf_logprob_fwd, semicrf_logprob_bwd[_f]): 0 <= begin <= end < T for
+ * every pair.  The device code takes pointers and does not check it: a pair with begin > end would read the cell [end][begin] of
+ * the upper triangle (which the scorer leaves unwritten) and its gradient would be added there, into cells that
+ * SEMICRF_GRAD_UPPER_IS_ZERO promises to be +0.0f.  The host that packs the pairs checks it (the Python entry points raise
+ * ValueError naming the pair before anything is launched; the CPU dispatch rejects the packed buffers).
+ * semicrf_interval_marginals is different: it accepts begin > end and returns 0 for it.
  */
 int semicrf_eval_path(const float* score, const float* noise, int T, int B,
                       const int32_t* pairs, int64_t K, const int32_t* offsets, float* out,

@@ -78,9 +78,12 @@ def _ready(pairs) -> None:
         pairs._semicrf_ready = None
 
 
-def pack_intervals(intervals: Sequence[Sequence[Tuple[int, int]]], T: int, B: int, device, overlap: bool = False):
+def pack_intervals(intervals: Sequence[Sequence[Tuple[int, int]]], T: int, B: int, device, overlap: bool = False, ordered: bool = True):
     """List[List[(begin,end)]] (len B) -> (pairs int32 [K,2], offsets int32 [B+1]) on `device`.
     One pass in C (csrc/pymarshal.c) into pinned host buffers, then two asynchronous copies.
+    ordered (the default: the paths of evalPath / logProb, whose kernels take begin <= end as a precondition and do not check it
+    on the device): ValueError naming the first interval with begin > end, raised here -- before anything is copied or launched.
+    ordered=False (interval_marginals, which returns 0 for such a pair) takes any pair inside [0, T).
     overlap=True: the copies go to a side stream (they need nothing from the GPU and would otherwise sit in front of the
     sweep that the caller enqueues next: 20-100 us per call); the caller must pass `pairs` to _ready() before its first use."""
     assert len(intervals) == B, f"expected {B} interval lists, got {len(intervals)}"
@@ -91,7 +94,7 @@ def pack_intervals(intervals: Sequence[Sequence[Tuple[int, int]]], T: int, B: in
     offsets_h = torch.empty(B + 1, dtype=torch.int32, pin_memory=pin)
     if K == 0:
         pairs_h.zero_()
-    k = mm.pack_into(intervals, pairs_h.data_ptr(), max(K, 1), offsets_h.data_ptr(), T)   # IndexError when out of range
+    k = mm.pack_into(intervals, pairs_h.data_ptr(), max(K, 1), offsets_h.data_ptr(), T, bool(ordered))   # IndexError when out of range
     assert k == K
     if overlap and pin:
         main = torch.cuda.current_stream(device)
@@ -911,7 +914,7 @@ def interval_marginals(score, noiseScore, intervals: Intervals) -> List[List[flo
     """An EXTENSION of the reference's surface: the posterior probability of each interval of `intervals` (one list per chain,
     e.g. what decode returns), as a list (len nBatch) of lists of floats in the given order."""
     T, B = _check_inputs(score, noiseScore)
-    pairs, offsets = pack_intervals(intervals, T, B, "cpu")
+    pairs, offsets = pack_intervals(intervals, T, B, "cpu", ordered=False)
     K = pairs._semicrf_K
     out = interval_marginals_packed(score, noiseScore, pairs[:K], offsets).cpu().tolist()
     off = offsets.tolist()

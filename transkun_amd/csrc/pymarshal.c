@@ -4,7 +4,8 @@
  * int32 buffers of the C ABI (pairs [K][2], offsets [B+1]).  Host-side only; no device code.
  *
  *   unpack(pairs_addr, offsets_addr, B, T) -> list of B lists of (begin, end) tuples
- *   pack_into(intervals, pairs_addr, cap, offsets_addr, T) -> K   (IndexError on an index outside [0, T))
+ *   pack_into(intervals, pairs_addr, cap, offsets_addr, T[, ordered]) -> K   (IndexError on an index outside [0, T);
+ *                                                        ordered != 0: ValueError naming the first interval with begin > end)
  *   count(intervals) -> total number of intervals
  *
  * The int objects 0..T-1 are created once per call and shared by all tuples (one allocation per interval instead of
@@ -87,7 +88,8 @@ static PyObject* m_pack_into(PyObject* self, PyObject* args)
     unsigned long long pa, oa;
     long long cap;
     long T;
-    if (!PyArg_ParseTuple(args, "OKLKl", &iv, &pa, &cap, &oa, &T)) return NULL;
+    int ordered = 0;                  /* the paths of evalPath / logProb: begin <= end (interval_marginals takes any pair) */
+    if (!PyArg_ParseTuple(args, "OKLKl|p", &iv, &pa, &cap, &oa, &T, &ordered)) return NULL;
     int32_t* pairs = (int32_t*)(uintptr_t)pa;
     int32_t* off = (int32_t*)(uintptr_t)oa;
     PyObject* seq = PySequence_Fast(iv, "intervals must be a sequence of sequences");
@@ -121,6 +123,11 @@ static PyObject* m_pack_into(PyObject* self, PyObject* args)
             if (b < 0 || b >= T || e < 0 || e >= T) {
                 Py_DECREF(lst); Py_DECREF(seq);
                 PyErr_Format(PyExc_IndexError, "interval index out of range for T=%ld", T);
+                return NULL;
+            }
+            if (ordered && b > e) {
+                Py_DECREF(lst); Py_DECREF(seq);
+                PyErr_Format(PyExc_ValueError, "interval (%ld, %ld) of chain %zd has begin > end", b, e, c);
                 return NULL;
             }
             if (k >= cap) { Py_DECREF(lst); Py_DECREF(seq); PyErr_SetString(PyExc_ValueError, "pairs buffer too small"); return NULL; }
@@ -577,7 +584,7 @@ static PyObject* m_tm_finish(PyObject* self, PyObject* args)
 
 static PyMethodDef methods[] = {
     {"unpack", m_unpack, METH_VARARGS, "packed int32 pairs/offsets (host addresses) -> list of lists of (begin, end)"},
-    {"pack_into", m_pack_into, METH_VARARGS, "list of lists of (begin, end) -> packed int32 buffers; returns K"},
+    {"pack_into", m_pack_into, METH_VARARGS, "list of lists of (begin, end) -> packed int32 buffers; returns K (ordered: begin <= end required)"},
     {"count", m_count, METH_O, "total number of intervals"},
     {"tm_new", m_tm_new, METH_VARARGS, "event merger for n_files recordings of P symbols"},
     {"tm_add", m_tm_add, METH_VARARGS, "merge the packed events of one step (rows of 7 doubles at a host address)"},
