@@ -53,6 +53,7 @@ extern "C" {
 #define SEMICRF_OP_VITERBI_NBEST 6    /* B = k * NBatch of the semicrf_viterbi_nbest call */
 #define SEMICRF_OP_POSTERIORS 7       /* semicrf_posteriors */
 #define SEMICRF_OP_MARGINAL_DECODE 8   /* semicrf_marginal_decode */
+#define SEMICRF_OP_EXPECTATION 9       /* semicrf_expectation / semicrf_covariance (one workspace for the pair) */
 
 /* length scaling of the interval scorer (LayersTransformer.py:416-427) */
 #define SEMICRF_LEN_LINEAR 0
@@ -262,6 +263,35 @@ int semicrf_interval_marginals(const float* score, const float* v, const float* 
 int semicrf_marginal_decode(const float* score, const float* noise, const float* v, const float* q, const float* logZ, int T, int B,
                             const float* tau, int tau_stride, int32_t* pairs, float* probs, int64_t cap, int32_t* offsets,
                             void* ws, size_t ws_bytes, semicrf_stream_t stream);
+
+/*
+ * Posterior expectation of an additive path functional, and its covariance with every cell of the lattice (the Hessian-vector
+ * product of logZ).  No counterpart in the reference (an extension of its surface, like semicrf_posteriors); its computeLogZ is
+ * plain torch and can be differentiated twice, which is what these two calls provide explicitly.  Adds nothing to the ABI's
+ * existing entry points (version 2).
+ *   weight [T][T][B] (the layout of score; only begin <= end is read) and noiseWeight [T-1][B] define
+ *     W(path) = sum of weight[e,b] over the intervals (b,e) of the path (singletons included) + sum of noiseWeight[t] over the
+ *     gaps t .. t+1 that no interval covers.
+ *   weight NULL or == score: the weights ARE the scores and the tensor is read once (pass noiseWeight = noise for the entropy:
+ *     then W = the path's score S and H = logZ - E_p[S]).  noiseWeight NULL: zeros.
+ *   v: alpha (semicrf_logz_fwd), q: beta (semicrf_beta) of the same score / noise.  They serve only as the shift of each row's
+ *     sum: the sweeps keep their own per-frame state -- the log-sums and the conditional expectations of W, forward and backward
+ *     -- in float64 (fp32 state cannot resolve the cancellation of a covariance; DESIGN.md "Posterior expectations"), every
+ *     per-cell exponential stays fp32 on an argument formed in float64.
+ * semicrf_expectation: E [B] = E_p[W]; H [B] = logZ - E (the path entropy when the weights are the scores); leaves the state in
+ *   ws.  Two reads of the lower triangle (rows forward, columns backward).
+ * semicrf_covariance: from the ws a semicrf_expectation call on the SAME score / noise / weight / noiseWeight filled (same T, B,
+ *   unchanged in between), one elementwise pass:
+ *     C [T][T][B]:  gout[c] Cov(1[(b,e) on path], W) for b <= e; exactly 0.0f for b > e (every element is written)
+ *     Cn [T-1][B]:  gout[c] Cov(1[gap t is noise], W)                (may be NULL when T = 1)
+ *   i.e. gout[c] dE[c] / dscore and gout[c] dE[c] / dnoise; with the weights = the scores, dH / dscore = -C, dH / dnoise = -Cn.
+ * No atomics, fixed summation order: two calls are bit-identical.  T < 65536.
+ * Workspace: semicrf_workspace_bytes(SEMICRF_OP_EXPECTATION, T, B), about 4 T B doubles.
+ */
+int semicrf_expectation(const float* score, const float* noise, const float* weight, const float* noiseWeight, const float* v,
+                        const float* q, int T, int B, float* E, float* H, void* ws, size_t ws_bytes, semicrf_stream_t stream);
+int semicrf_covariance(const float* score, const float* noise, const float* weight, const float* noiseWeight, const float* gout, int T,
+                       int B, float* C, float* Cn, const void* ws, size_t ws_bytes, semicrf_stream_t stream);
 
 /*
  * Unnormalised path score.  Replaces: evalPath (:508-550).

@@ -19,7 +19,8 @@ What differs from the reference, invisibly at the API:
 EXTENSIONS of the reference's surface: decode_packed, sample / sample_packed (exact posterior draws of paths),
   decode_nbest / decode_nbest_packed (the k best paths, ranked), posteriors / interval_marginals /
   interval_marginals_packed (posterior marginals and path entropy without the dense [T,T,B] tensor), and decode_marginal /
-  decode_marginal_packed (every interval whose posterior probability reaches a threshold).
+  decode_marginal_packed (every interval whose posterior probability reaches a threshold), and expectation / entropy /
+  covariance (posterior expectations of additive path functionals, the differentiable entropy, Hessian products of logZ).
 """
 from __future__ import annotations
 
@@ -922,6 +923,162 @@ def interval_marginals(score, noiseScore, intervals: Intervals) -> List[List[flo
 
 
 # --------------------------------------------------------------------------------------
+# posterior expectations, differentiable entropy, Hessian products of logZ (an extension of the reference's surface)
+# --------------------------------------------------------------------------------------
+
+def _expect_workspace(T: int, B: int, device) -> torch.Tensor:
+    """The float64 state semicrf_expectation leaves for semicrf_covariance (a fresh buffer: autograd may keep it)."""
+    if torch.device(device).type == "cpu":
+        return torch.empty((4 * T * B + 2 * B) * 8, dtype=torch.uint8)
+    return _lib.workspace(_lib.OP_EXPECTATION, T, B, device)
+
+
+def _expect_fwd(score_c, noise_c, weight_c, nweight_c):
+    """Enqueue the alpha / beta sweeps and semicrf_expectation; no host sync.  weight_c may BE score_c (read once); nweight_c None:
+    zeros.  Returns (E [B], H [B] = logZ - E, state); state feeds _expect_cov and _expect_marginals."""
+    pad = _odd_pad(score_c)
+    if pad:                                         # a single chain runs with a ghost chain, like every sweep
+        same = weight_c is score_c
+        nsame = nweight_c is noise_c
+        score_c, noise_c = _pad1(score_c), _pad1(noise_c)
+        weight_c = score_c if same else _pad1(weight_c)
+        if nweight_c is not None:
+            nweight_c = noise_c if nsame else _pad1(nweight_c)
+    T, B = score_c.shape[0], score_c.shape[2]
+    dev = score_c.device
+    logz, v, q = _marginal_inputs(score_c, noise_c)
+    E = torch.empty(B, dtype=torch.float32, device=dev)
+    H = torch.empty(B, dtype=torch.float32, device=dev)
+    ws = _expect_workspace(T, B, dev)
+    has_nw = nweight_c is not None
+    _lib.ops().expectation(score_c, noise_c, weight_c, nweight_c if has_nw else _empty(dev), has_nw, v, q, E, H, ws)
+    state = (score_c, noise_c, weight_c, nweight_c, ws, v, logz, pad)
+    if pad:
+        E, H = E[:-1].contiguous(), H[:-1].contiguous()
+    return E, H, state
+
+
+def _expect_cov(state, gout):
+    """semicrf_covariance on the state of _expect_fwd: (gout * C [T,T,B], gout * Cn [T-1,B]); the upper triangle is exact zeros."""
+    score_c, noise_c, weight_c, nweight_c, ws, _, _, pad = state
+    if pad:
+        gout = _pad1(gout)
+    T, B = score_c.shape[0], score_c.shape[2]
+    C = _empty_or_trim((T, T, B), score_c.device)
+    Cn = torch.empty_like(noise_c)
+    has_nw = nweight_c is not None
+    _lib.ops().covariance(score_c, noise_c, weight_c, nweight_c if has_nw else _empty(score_c.device), has_nw, gout, C, Cn, ws)
+    if pad:
+        C, Cn = C[:, :, :-1].contiguous(), Cn[:, :-1].contiguous()
+    return C, Cn
+
+
+def _expect_marginals(state, gout):
+    """gout * the marginals (the gradient of E with respect to weight / noiseWeight), by the existing gradient sweep."""
+    score_c, noise_c, _, _, _, v, logz, pad = state
+    if pad:
+        gout = _pad1(gout)
+    ds, dn, _ = _logz_bwd_raw(score_c, noise_c, v, logz, gout)
+    if pad:
+        ds, dn = ds[:, :, :-1].contiguous(), dn[:, :-1].contiguous()
+    return ds, dn
+
+
+def _check_weights(score, noiseScore, weight, noiseWeight):
+    T, B = _check_inputs(score, noiseScore)
+    assert tuple(weight.shape) == tuple(score.shape)
+    _lib.require_device(weight, "weight")
+    assert weight.device == score.device
+    if noiseWeight is not None:
+        assert tuple(noiseWeight.shape) == tuple(noiseScore.shape)
+        _lib.require_device(noiseWeight, "noiseWeight")
+        assert noiseWeight.device == score.device
+    return T, B
+
+
+class _Expectation(torch.autograd.Function):
+    """E_p[W] (entropy False) or H = logZ - E_p[S] (entropy True; weight / noiseWeight are then ignored) as one node.  The
+    backward is the covariance stream on the float64 state the forward left; it is once-differentiable."""
+
+    @staticmethod
+    def forward(ctx, score, noiseScore, weight, noiseWeight, entropy: bool):
+        score_c, noise_c = _prep(score), _prep(noiseScore)
+        if entropy:
+            weight_c, nweight_c = score_c, noise_c
+        else:
+            weight_c = _prep(weight)
+            nweight_c = _prep(noiseWeight) if noiseWeight is not None else None
+        E, H, state = _expect_fwd(score_c, noise_c, weight_c, nweight_c)
+        ctx.entropy = entropy
+        ctx.has_nw = noiseWeight is not None
+        ctx.in_dtypes = tuple(t.dtype if t is not None else None for t in (score, noiseScore, weight, noiseWeight))
+        if any(ctx.needs_input_grad[:4]):
+            ctx.state_meta = state[7]
+            ctx.save_for_backward(*(t for t in state[:7] if t is not None))
+        return H if entropy else E
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        saved = list(ctx.saved_tensors)
+        if ctx.entropy or ctx.has_nw:
+            score_c, noise_c, weight_c, nweight_c, ws, v, logz = saved
+        else:
+            score_c, noise_c, weight_c, ws, v, logz = saved
+            nweight_c = None
+        if weight_c.data_ptr() == score_c.data_ptr():
+            weight_c = score_c                      # (saved tensors are unpacked as distinct objects)
+        state = (score_c, noise_c, weight_c, nweight_c, ws, v, logz, ctx.state_meta)
+        B = score_c.shape[2] - (1 if ctx.state_meta else 0)
+        g = _gout(grad_output, B)
+        ds = dn = dw = dnw = None
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            C, Cn = _expect_cov(state, -g if ctx.entropy else g)            # dH/dscore = -C with the weights = the scores
+            ds = C.to(ctx.in_dtypes[0]) if ctx.needs_input_grad[0] else None
+            dn = Cn.to(ctx.in_dtypes[1]) if ctx.needs_input_grad[1] else None
+        if not ctx.entropy and (ctx.needs_input_grad[2] or (ctx.has_nw and ctx.needs_input_grad[3])):
+            mw, mn = _expect_marginals(state, g)
+            dw = mw.to(ctx.in_dtypes[2]) if ctx.needs_input_grad[2] else None
+            dnw = mn.to(ctx.in_dtypes[3]) if ctx.has_nw and ctx.needs_input_grad[3] else None
+        return ds, dn, dw, dnw, None
+
+
+def expectation(score, noiseScore, weight, noiseWeight=None) -> torch.Tensor:
+    """An EXTENSION of the reference's surface: E_p[W] of every chain (float32 [nBatch], where the scores live) for the additive
+    path functional W(path) = sum of weight[end, begin] over the path's intervals (singletons included) + sum of noiseWeight[t]
+    over the gaps no interval covers.  weight [T, T, nBatch] has the layout of score (only begin <= end is read), noiseWeight
+    [T-1, nBatch] defaults to zeros.  Differentiable once: the gradients to score / noiseScore are the covariances
+    Cov(1[cell on path], W) (see covariance), those to weight / noiseWeight the marginals of forward_backward; a second
+    differentiation raises.  Without a gradient no dense [T, T, nBatch] tensor is allocated.  No host sync."""
+    _check_weights(score, noiseScore, weight, noiseWeight)
+    return _Expectation.apply(score, noiseScore, weight, noiseWeight, False)
+
+
+def entropy(score, noiseScore) -> torch.Tensor:
+    """An EXTENSION of the reference's surface: the entropy H = logZ - E_p[score of the path] of p(path) in nats, float32 [nBatch],
+    differentiable once (dH/dscore = -Cov(1[cell on path], S)): an entropy regulariser, minimum-entropy training, a confidence
+    penalty.  posteriors().entropy is the same number without a gradient."""
+    _check_inputs(score, noiseScore)
+    return _Expectation.apply(score, noiseScore, None, None, True)
+
+
+def covariance(score, noiseScore, weight, noiseWeight=None):
+    """An EXTENSION of the reference's surface: (E [nBatch], C [T, T, nBatch], Cn [T-1, nBatch]) with E = E_p[W] as expectation,
+    C[end, begin] = Cov(1[(begin, end) on path], W) (exact zeros for begin > end) and Cn[t] = Cov(1[gap t is noise], W): the
+    product of the Hessian of logZ with (weight, noiseWeight), i.e. the explicit second-order route (the reference's computeLogZ
+    is plain torch and can be differentiated twice; computeLogZ here cannot).  float32 where the scores live; no gradient."""
+    _check_weights(score, noiseScore, weight, noiseWeight)
+    with torch.no_grad():
+        score_c, noise_c = _prep(score.detach()), _prep(noiseScore.detach())
+        same = weight is score
+        weight_c = score_c if same else _prep(weight.detach())
+        nweight_c = None if noiseWeight is None else (noise_c if noiseWeight is noiseScore else _prep(noiseWeight.detach()))
+        E, _, state = _expect_fwd(score_c, noise_c, weight_c, nweight_c)
+        C, Cn = _expect_cov(state, torch.ones(E.shape[0], dtype=torch.float32, device=E.device))
+    return E, C, Cn
+
+
+# --------------------------------------------------------------------------------------
 # marginal-threshold (posterior) decoding (an extension of the reference's surface)
 # --------------------------------------------------------------------------------------
 
@@ -1111,6 +1268,21 @@ class NeuralSemiCRFInterval:
     def interval_marginals_packed(self, pairs, offsets):
         """`interval_marginals` on decode_packed's arrays (numpy or tensors): a float32 tensor [K] where the scores live."""
         return interval_marginals_packed(self.score, self.noiseScore, pairs, offsets)
+
+    def expectation(self, weight, noiseWeight=None):
+        """An EXTENSION of the reference's surface: E_p[W] [nBatch] of the additive path functional given by weight [T, T, nBatch]
+        and noiseWeight [T-1, nBatch] (default zeros), float32, differentiable once -- see the module-level expectation."""
+        return expectation(self.score, self.noiseScore, weight, noiseWeight)
+
+    def entropy(self):
+        """An EXTENSION of the reference's surface: the path entropy [nBatch] in nats, float32, differentiable once -- see the
+        module-level entropy."""
+        return entropy(self.score, self.noiseScore)
+
+    def covariance(self, weight, noiseWeight=None):
+        """An EXTENSION of the reference's surface: (E, C, Cn), the covariances of every cell with the path functional, i.e. the
+        Hessian of logZ times (weight, noiseWeight) -- see the module-level covariance.  No gradient."""
+        return covariance(self.score, self.noiseScore, weight, noiseWeight)
 
     def decode_marginal(self, threshold):
         """An EXTENSION of the reference's surface: (paths, probs) -- every interval whose posterior probability is >= threshold

@@ -5,4 +5,5 @@ from .NeuralSemiCRFInterval import (NeuralSemiCRFInterval, viterbi, viterbiBackw
                                     ComputeLogZFasterGrad, sample, sample_packed,
                                     viterbi_nbest, viterbi_nbest_packed, Posteriors, posteriors,
                                     interval_marginals, interval_marginals_packed,
-                                    decode_marginal, decode_marginal_packed)
+                                    decode_marginal, decode_marginal_packed,
+                                    expectation, entropy, covariance)

@@ -95,6 +95,11 @@ int launch_proj_tn(const float* A, long long lda, long long M, int R, int extra_
 size_t persist_workspace_bytes(int T, int B);
 size_t sample_workspace_bytes(int T, int nB);
 size_t posterior_workspace_bytes(int T, int B);
+size_t expectation_workspace_bytes(int T, int B);
+void launch_expectation(const float* score, const float* noise, const float* weight, const float* nweight, const float* v, const float* q,
+                        int T, int B, float* E, float* H, void* ws, hipStream_t stream);
+void launch_covariance(const float* score, const float* noise, const float* weight, const float* nweight, const float* gout, int T, int B,
+                       float* C, float* Cn, const void* ws, hipStream_t stream);
 void launch_posteriors(const float* score, const float* noise, const float* v, const float* q, const float* logZ, int T, int B,
                        float* node, float* begin, float* end, float* single, float* noiseP, float* entropy, void* ws,
                        hipStream_t stream);
@@ -292,6 +297,7 @@ size_t semicrf_workspace_bytes(int op, int T, int B)
         case SEMICRF_OP_POSTERIORS: return posterior_workspace_bytes(T, B);
         case SEMICRF_OP_VITERBI_NBEST: return nbest_workspace_bytes(T, B);
         case SEMICRF_OP_MARGINAL_DECODE: return marginal_decode_workspace_bytes(T, B);
+        case SEMICRF_OP_EXPECTATION: return expectation_workspace_bytes(T, B);
         default: return 0;
     }
 }
@@ -545,6 +551,33 @@ int semicrf_posteriors(const float* score, const float* noise, const float* v, c
     if (ws_bytes < posterior_workspace_bytes(T, B)) { set_error("workspace too small for posteriors"); return SEMICRF_EWORKSPACE; }
     launch_posteriors(score, noise, v, q, logZ, T, B, node, begin, end, single, noiseP, entropy, ws, (hipStream_t)stream);
     SEMICRF_CHECK_LAUNCH("semicrf_posteriors");
+    return SEMICRF_OK;
+}
+
+int semicrf_expectation(const float* score, const float* noise, const float* weight, const float* noiseWeight, const float* v,
+                        const float* q, int T, int B, float* E, float* H, void* ws, size_t ws_bytes, semicrf_stream_t stream)
+{
+    if (int rc = check_common(score, noise, T, B)) return rc;
+    SEMICRF_CHECK_ARG(v && q, "v (alpha) and q (beta) must be non-NULL");
+    SEMICRF_CHECK_ARG(E && H, "an output is NULL");
+    SEMICRF_CHECK_ARG(ws != nullptr, "workspace is NULL");
+    if (ws_bytes < expectation_workspace_bytes(T, B)) { set_error("workspace too small for expectation"); return SEMICRF_EWORKSPACE; }
+    launch_expectation(score, noise, weight ? weight : score, noiseWeight, v, q, T, B, E, H, ws, (hipStream_t)stream);
+    SEMICRF_CHECK_LAUNCH("semicrf_expectation");
+    return SEMICRF_OK;
+}
+
+int semicrf_covariance(const float* score, const float* noise, const float* weight, const float* noiseWeight, const float* gout, int T,
+                       int B, float* C, float* Cn, const void* ws, size_t ws_bytes, semicrf_stream_t stream)
+{
+    if (int rc = check_common(score, noise, T, B)) return rc;
+    SEMICRF_CHECK_ARG(gout != nullptr, "gout is NULL");
+    SEMICRF_CHECK_ARG(C && (Cn || T == 1), "an output is NULL");
+    SEMICRF_CHECK_ARG(T < 65536, "T=%d too large for the covariance pass", T);
+    SEMICRF_CHECK_ARG(ws != nullptr, "workspace is NULL");
+    if (ws_bytes < expectation_workspace_bytes(T, B)) { set_error("workspace too small for covariance"); return SEMICRF_EWORKSPACE; }
+    launch_covariance(score, noise, weight ? weight : score, noiseWeight, gout, T, B, C, Cn, ws, (hipStream_t)stream);
+    SEMICRF_CHECK_LAUNCH("semicrf_covariance");
     return SEMICRF_OK;
 }
 

@@ -377,6 +377,121 @@ void posteriors(const float* score, const float* noise, const float* v, const fl
     }
 }
 
+// posterior expectations and covariances (include/semicrf_hip.h: semicrf_expectation, semicrf_covariance; the device kernels are
+// expectation.hip), everything in double: the per-frame log-sums v64 / q64 and the conditional expectations
+//   a[t]    = E[W of the prefix up to node t, its singleton included | t is a node]
+//   binc[t] = E[W of the suffix from node t on, its singleton included | t is a node]
+// by rows (forward) and by columns (backward), chain blocks in parallel; then one pass over the triangle.
+namespace {
+inline double sigmoid_d(double x) { return x > 20.0 ? 1.0 : 1.0 / (1.0 + exp(-x)); }      // d softplus_d / dx
+
+// one direction for the chains c0 .. c0 + nc: fwd: frame t = k, cell (t, p) = s[t][p]; else t = T-1-k, cell = s[p][t]
+void expectation_sweep(const float* score, const float* noise, const float* weight, const float* nweight, int T, int B, int c0, int nc,
+                       bool fwd, double* L, double* X)
+{
+    const size_t Bs = (size_t)B;
+    for (int k = 0; k < T; ++k) {
+        const int t = fwd ? k : T - 1 - k;
+        double m[CB], Z[CB], A[CB];
+        if (k > 0) {
+            const int pn = fwd ? t - 1 : t + 1;
+            const size_t gc = (size_t)(fwd ? t - 1 : t) * Bs + c0;
+            for (int c = 0; c < nc; ++c) m[c] = L[(size_t)pn * Bs + c0 + c] + (double)noise[gc + c];
+            for (int j = 0; j < k; ++j) {
+                const int p = fwd ? j : T - 1 - j;
+                const float* cell = score + (fwd ? (size_t)t * T + p : (size_t)p * T + t) * Bs + c0;
+                const double* Lp = L + (size_t)p * Bs + c0;
+                for (int c = 0; c < nc; ++c) { const double x = Lp[c] + (double)cell[c]; m[c] = x > m[c] ? x : m[c]; }
+            }
+            for (int c = 0; c < nc; ++c) {
+                if (!(m[c] > -INFINITY)) m[c] = 0.0;
+                const double ex = exp(L[(size_t)pn * Bs + c0 + c] + (double)noise[gc + c] - m[c]);
+                Z[c] = ex;
+                A[c] = ex * (X[(size_t)pn * Bs + c0 + c] + (nweight ? (double)nweight[gc + c] : 0.0));
+            }
+            for (int j = 0; j < k; ++j) {
+                const int p = fwd ? j : T - 1 - j;
+                const size_t off = (fwd ? (size_t)t * T + p : (size_t)p * T + t) * Bs + c0;
+                const float* cell = score + off;
+                const float* wc = weight + off;
+                const double* Lp = L + (size_t)p * Bs + c0;
+                const double* Xp = X + (size_t)p * Bs + c0;
+                for (int c = 0; c < nc; ++c) {
+                    const double ex = exp(Lp[c] + (double)cell[c] - m[c]);
+                    Z[c] += ex;
+                    A[c] += ex * (Xp[c] + (double)wc[c]);
+                }
+            }
+        }
+        const size_t dc = ((size_t)t * T + t) * Bs + c0;
+        for (int c = 0; c < nc; ++c) {
+            const double d = score[dc + c];
+            double Lt = softplus_d(d), Xt = sigmoid_d(d) * (double)weight[dc + c];
+            if (k > 0) {
+                Lt += m[c] + log(Z[c]);
+                Xt += Z[c] > 0.0 ? A[c] / Z[c] : 0.0;
+            }
+            L[(size_t)t * Bs + c0 + c] = Lt;
+            X[(size_t)t * Bs + c0 + c] = Xt;
+        }
+    }
+}
+}  // namespace
+
+void expectation(const float* score, const float* noise, const float* weight, const float* nweight, int T, int B, float* E, float* H,
+                 double* state)
+{
+    if (!weight) weight = score;
+    const size_t TB = (size_t)T * B;
+    double *v64 = state, *a = state + TB, *q64 = state + 2 * TB, *binc = state + 3 * TB, *E64 = state + 4 * TB, *lz64 = E64 + B;
+    const int nblk = (B + CB - 1) / CB;
+#pragma omp parallel for schedule(dynamic, 1)
+    for (int job = 0; job < 2 * nblk; ++job) {
+        const int c0 = (job >> 1) * CB;
+        const int nc = B - c0 < CB ? B - c0 : CB;
+        if (job & 1) expectation_sweep(score, noise, weight, nweight, T, B, c0, nc, false, q64, binc);
+        else expectation_sweep(score, noise, weight, nweight, T, B, c0, nc, true, v64, a);
+    }
+    for (int c = 0; c < B; ++c) {
+        E64[c] = a[(size_t)(T - 1) * B + c];
+        lz64[c] = v64[(size_t)(T - 1) * B + c];
+        E[c] = (float)E64[c];
+        H[c] = (float)(lz64[c] - E64[c]);
+    }
+}
+
+void covariance(const float* score, const float* noise, const float* weight, const float* nweight, const float* gout, int T, int B,
+                const double* state, float* C, float* Cn)
+{
+    if (!weight) weight = score;
+    const size_t TB = (size_t)T * B, Bs = (size_t)B;
+    const double *v64 = state, *a = state + TB, *q64 = state + 2 * TB, *binc = state + 3 * TB, *E64 = state + 4 * TB, *lz64 = E64 + B;
+#pragma omp parallel for schedule(dynamic, 4)
+    for (int e = 0; e < T; ++e) {
+        const size_t row = (size_t)e * T * Bs;
+        for (int b = 0; b < e; ++b)
+            for (int c = 0; c < B; ++c) {
+                const size_t cell = row + (size_t)b * Bs + c, bc = (size_t)b * Bs + c, ec = (size_t)e * Bs + c;
+                const double mu = exp(v64[bc] + (double)score[cell] + q64[ec] - lz64[c]);
+                C[cell] = (float)(mu * (a[bc] + (double)weight[cell] + binc[ec] - E64[c]) * (double)gout[c]);
+            }
+        for (int c = 0; c < B; ++c) {                                   // the singleton: P = node sigma(d), given weight w[t,t]
+            const size_t ec = (size_t)e * Bs + c, cell = row + ec;
+            const double d = score[cell], w = weight[cell];
+            const double mu = exp(v64[ec] + q64[ec] - 2.0 * softplus_d(d) + d - lz64[c]);
+            C[cell] = (float)(mu * (a[ec] + binc[ec] + (1.0 - 2.0 * sigmoid_d(d)) * w - E64[c]) * (double)gout[c]);
+        }
+        if (e + 1 < T) {
+            memset(C + row + (size_t)(e + 1) * Bs, 0, (size_t)(T - 1 - e) * Bs * sizeof(float));        // begin > end: exact zeros
+            for (int c = 0; c < B; ++c) {
+                const size_t ec = (size_t)e * Bs + c;
+                const double mu = exp(v64[ec] + (double)noise[ec] + q64[ec + Bs] - lz64[c]);
+                Cn[ec] = (float)(mu * (a[ec] + (nweight ? (double)nweight[ec] : 0.0) + binc[ec + Bs] - E64[c]) * (double)gout[c]);
+            }
+        }
+    }
+}
+
 // interval marginals (semicrf_interval_marginals): b > e gives 0; the caller has checked the indices
 void interval_marginals(const float* score, const float* v, const float* q, const float* logZ, int T, int B, const int32_t* pairs,
                         const int32_t* offsets, float* out)

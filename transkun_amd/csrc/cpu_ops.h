@@ -19,6 +19,11 @@ void interval_marginals(const float* score, const float* v, const float* q, cons
                         const int32_t* offsets, float* out);
 void marginal_decode(const float* score, const float* v, const float* q, const float* logZ, int T, int B, const float* tau,
                      int tau_stride, int32_t* pairs, float* probs, int64_t cap, int32_t* offsets);
+// state: (4 T B + 2 B) doubles, filled by expectation and read by covariance (v64, a, q64, binc [T][B] each, then E, logZ [B])
+void expectation(const float* score, const float* noise, const float* weight /* or null: score */, const float* nweight /* or null: 0 */,
+                 int T, int B, float* E, float* H, double* state);
+void covariance(const float* score, const float* noise, const float* weight, const float* nweight, const float* gout, int T, int B,
+                const double* state, float* C, float* Cn /* or null when T = 1 */);
 void eval_path(const float* score, const float* noise, int T, int B, const int32_t* pairs, const int32_t* offsets, float* out);
 void eval_path_bwd(const float* gout, int T, int B, const int32_t* pairs, const int32_t* offsets, float* dScore, float* dNoise);
 }  // namespace semicrf_cpu

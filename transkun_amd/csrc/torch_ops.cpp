@@ -165,6 +165,37 @@ void posteriors(Tensor score, Tensor noise, Tensor v, Tensor q, Tensor logZ, Ten
                              c.stream),
           "semicrf_posteriors");
 }
+// posterior expectation / covariance (semicrf_expectation, semicrf_covariance): weight may BE score (read once); nweight is
+// read when has_nw.  ws: the state the pair shares (semicrf_workspace_bytes(SEMICRF_OP_EXPECTATION); the host kernels:
+// (4 T B + 2 B) doubles)
+inline const float* weight_of(const Tensor& weight, const Tensor& score, int64_t n)
+{
+    const float* w = f32(weight, n, "weight");
+    STD_TORCH_CHECK(weight.numel() == score.numel(), "semicrf: weight must have the shape of score");
+    return w;
+}
+void expectation(Tensor score, Tensor noise, Tensor weight, Tensor nweight, bool has_nw, Tensor v, Tensor q, Tensor E, Tensor H, Tensor ws)
+{
+    Ctx c(score); c.same(score, noise, weight, v, q, E, H, ws);
+    if (has_nw) c.same(score, nweight);
+    const Dims d = crf_dims(score, noise);
+    const int64_t TB = (int64_t)d.T * d.B;
+    check(semicrf_expectation(cfp(score), cfp(noise), weight_of(weight, score, TB * d.T), has_nw ? f32(nweight, TB - d.B, "noiseWeight") : nullptr,
+                              f32(v, TB, "v"), f32(q, TB, "q"), d.T, d.B, f32w(E, d.B, "E"), f32w(H, d.B, "H"), bytes(ws, "ws"),
+                              (size_t)ws.numel(), c.stream),
+          "semicrf_expectation");
+}
+void covariance(Tensor score, Tensor noise, Tensor weight, Tensor nweight, bool has_nw, Tensor gout, Tensor C, Tensor Cn, Tensor ws)
+{
+    Ctx c(score); c.same(score, noise, weight, gout, C, Cn, ws);
+    if (has_nw) c.same(score, nweight);
+    const Dims d = crf_dims(score, noise);
+    const int64_t TB = (int64_t)d.T * d.B;
+    check(semicrf_covariance(cfp(score), cfp(noise), weight_of(weight, score, TB * d.T), has_nw ? f32(nweight, TB - d.B, "noiseWeight") : nullptr,
+                             f32(gout, d.B, "gout"), d.T, d.B, f32w(C, TB * d.T, "C"), f32w(Cn, TB - d.B, "Cn"), bytes(ws, "ws"),
+                             (size_t)ws.numel(), c.stream),
+          "semicrf_covariance");
+}
 inline Dims marg_dims(const Tensor& score, const Tensor& v, const Tensor& q, const Tensor& logZ)
 {
     STD_TORCH_CHECK(score.dim() == 3 && score.size(0) == score.size(1), "semicrf: score must be [T, T, B]");
@@ -345,6 +376,29 @@ void posteriors_cpu(Tensor score, Tensor noise, Tensor v, Tensor q, Tensor logZ,
     semicrf_cpu::posteriors(cfp(score), cfp(noise), f32(v, TB, "v"), f32(q, TB, "q"), f32(logZ, d.B, "logZ"), d.T, d.B,
                             f32w(node, TB, "node"), f32w(begin, TB, "begin"), f32w(end, TB, "end"), f32w(single, TB, "single"),
                             f32w(noiseP, TB - d.B, "noiseP"), f32w(entropy, d.B, "entropy"));
+}
+inline double* state_cpu(const Tensor& ws, const Dims& d)
+{
+    want(ws, ScalarType::Byte, (int64_t)((4 * (int64_t)d.T * d.B + 2 * d.B) * sizeof(double)), "ws");
+    STD_TORCH_CHECK(((uintptr_t)ws.data_ptr() & 7) == 0, "semicrf: `ws` must be 8-byte aligned");
+    return (double*)ws.data_ptr();
+}
+void expectation_cpu(Tensor score, Tensor noise, Tensor weight, Tensor nweight, bool has_nw, Tensor v, Tensor q, Tensor E, Tensor H,
+                     Tensor ws)
+{
+    all_cpu(score, noise, weight, nweight, v, q, E, H, ws);
+    const Dims d = crf_dims(score, noise);
+    const int64_t TB = (int64_t)d.T * d.B;
+    semicrf_cpu::expectation(cfp(score), cfp(noise), weight_of(weight, score, TB * d.T), has_nw ? f32(nweight, TB - d.B, "noiseWeight") : nullptr,
+                             d.T, d.B, f32w(E, d.B, "E"), f32w(H, d.B, "H"), state_cpu(ws, d));
+}
+void covariance_cpu(Tensor score, Tensor noise, Tensor weight, Tensor nweight, bool has_nw, Tensor gout, Tensor C, Tensor Cn, Tensor ws)
+{
+    all_cpu(score, noise, weight, nweight, gout, C, Cn, ws);
+    const Dims d = crf_dims(score, noise);
+    const int64_t TB = (int64_t)d.T * d.B;
+    semicrf_cpu::covariance(cfp(score), cfp(noise), weight_of(weight, score, TB * d.T), has_nw ? f32(nweight, TB - d.B, "noiseWeight") : nullptr,
+                            f32(gout, d.B, "gout"), d.T, d.B, state_cpu(ws, d), f32w(C, TB * d.T, "C"), f32w(Cn, TB - d.B, "Cn"));
 }
 void interval_marginals_cpu(Tensor score, Tensor v, Tensor q, Tensor logZ, Tensor pairs, int64_t K, Tensor offsets, Tensor out)
 {
@@ -626,6 +680,10 @@ STABLE_TORCH_LIBRARY(semicrf, m)
           "Tensor(b!) offsets, Tensor(c!) scores, Tensor(d!) npaths, Tensor(e!) ws) -> ()");
     m.def("posteriors(Tensor score, Tensor noise, Tensor v, Tensor q, Tensor logZ, Tensor(a!) node, Tensor(b!) begin, Tensor(c!) end, "
           "Tensor(d!) single, Tensor(e!) noiseP, Tensor(f!) entropy, Tensor(g!) ws) -> ()");
+    m.def("expectation(Tensor score, Tensor noise, Tensor weight, Tensor nweight, bool has_nw, Tensor v, Tensor q, Tensor(a!) E, Tensor(b!) H, "
+          "Tensor(c!) ws) -> ()");
+    m.def("covariance(Tensor score, Tensor noise, Tensor weight, Tensor nweight, bool has_nw, Tensor gout, Tensor(a!) C, Tensor(b!) Cn, "
+          "Tensor ws) -> ()");
     m.def("interval_marginals(Tensor score, Tensor v, Tensor q, Tensor logZ, Tensor pairs, int K, Tensor offsets, Tensor(a!) out) -> ()");
     m.def("marginal_decode(Tensor score, Tensor noise, Tensor v, Tensor q, Tensor logZ, Tensor tau, Tensor(a!) pairs, Tensor(b!) probs, "
           "Tensor(c!) offsets, Tensor(d!) ws) -> ()");
@@ -678,6 +736,8 @@ STABLE_TORCH_LIBRARY_IMPL(semicrf, CPU, m)
     m.impl("viterbi_nbest", TORCH_BOX(&viterbi_nbest_cpu));
     m.impl("posteriors", TORCH_BOX(&posteriors_cpu));
     m.impl("interval_marginals", TORCH_BOX(&interval_marginals_cpu));
+    m.impl("expectation", TORCH_BOX(&expectation_cpu));
+    m.impl("covariance", TORCH_BOX(&covariance_cpu));
     m.impl("marginal_decode", TORCH_BOX(&marginal_decode_cpu));
     m.impl("eval_path", TORCH_BOX(&eval_path_cpu));
     m.impl("eval_path_bwd", TORCH_BOX(&eval_path_bwd_cpu));
@@ -695,6 +755,8 @@ STABLE_TORCH_LIBRARY_IMPL(semicrf, CUDA, m)
     m.impl("viterbi_nbest", TORCH_BOX(&viterbi_nbest));
     m.impl("posteriors", TORCH_BOX(&posteriors));
     m.impl("interval_marginals", TORCH_BOX(&interval_marginals));
+    m.impl("expectation", TORCH_BOX(&expectation));
+    m.impl("covariance", TORCH_BOX(&covariance));
     m.impl("marginal_decode", TORCH_BOX(&marginal_decode));
     m.impl("eval_path", TORCH_BOX(&eval_path));
     m.impl("eval_path_bwd", TORCH_BOX(&eval_path_bwd));
