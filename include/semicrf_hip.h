@@ -54,6 +54,7 @@ extern "C" {
 #define SEMICRF_OP_POSTERIORS 7       /* semicrf_posteriors */
 #define SEMICRF_OP_MARGINAL_DECODE 8   /* semicrf_marginal_decode */
 #define SEMICRF_OP_EXPECTATION 9       /* semicrf_expectation / semicrf_covariance (one workspace for the pair) */
+#define SEMICRF_OP_MBR_SELECT 10       /* semicrf_mbr_select */
 
 /* length scaling of the interval scorer (LayersTransformer.py:416-427) */
 #define SEMICRF_LEN_LINEAR 0
@@ -263,6 +264,38 @@ int semicrf_interval_marginals(const float* score, const float* v, const float* 
 int semicrf_marginal_decode(const float* score, const float* noise, const float* v, const float* q, const float* logZ, int T, int B,
                             const float* tau, int tau_stride, int32_t* pairs, float* probs, int64_t cap, int32_t* offsets,
                             void* ws, size_t ws_bytes, semicrf_stream_t stream);
+
+/*
+ * Posterior (minimum-Bayes-risk) PATH decoding at any threshold: among all paths of a chain, the one that maximises the sum over
+ * its intervals of (m(e, b) - tau) -- the gain 1 - tau per correct and -tau per wrong interval, solved for every tau (for
+ * tau > 0.5 it is the set {m > tau} itself).  An interval with m <= tau can be replaced by noise gaps without loss, so the optimum
+ * uses only the cells a semicrf_marginal_decode call at the same tau emits: the call is a weighted-interval-scheduling dynamic
+ * program over that packed lattice; it reads neither the scores nor a [T][T][B] tensor.  No counterpart in the reference (an
+ * extension of its surface, like semicrf_marginal_decode).  Adds nothing to the ABI's existing entry points (version 2).
+ *   pairs [K][2] (begin, end), weight [K], offsets [B+1]: a lattice in semicrf_marginal_decode's format (its pairs / probs /
+ *   offsets), ascending by (begin, end) within a chain, 0 <= begin <= end < T; K = the lattice's capacity (the `cap` of that call).
+ *   tau, tau_stride: as semicrf_marginal_decode; chain c uses tau[c * tau_stride].
+ *   Eligibility: entry i is eligible iff weight[i] > tau (a strict fp32 compare; NaN is never eligible; an entry outside
+ *   0 <= begin <= end < T is never eligible).  Its gain is g_i = weight[i] - tau, one fp32 subtraction.
+ *   gS(t) = g of the eligible entry (t, t), else +0.0f.
+ *   Recursion (all fp32, every sum one add):  F[T-1] = gS(T-1);  for t = T-2 .. 0: best = F[t+1], choice "skip"; for the eligible
+ *   entries (t, e), e > t, in ascending e: c = g_i + F[e]; if c > best (strict): best = c, choice i;  F[t] = best + gS(t).
+ *   Among equal maxima the skip wins, after it the smallest e (the values do not depend on the order the maximum is taken in).
+ *   Trace from t = 0: at a visited frame emit (t, t) if it is eligible; stop at t = T-1; on "skip" go to t + 1, otherwise emit
+ *   (t, e) and go to e.  The output is ascending by (begin, end), the order of semicrf_viterbi(forward = 1).
+ *   pairs_out [cap][2], probs_out [cap]: the selected entries and their weights, bit for bit; offsets_out [B+1], exact even when
+ *   offsets_out[B] > cap, nothing is written out of bounds (a path has at most 2 T - 1 cells: cap = 2 T B always suffices);
+ *   gain [B] = F[0].
+ *   offsets[B] is read on the DEVICE: when it is negative (semicrf_marginal_decode's NaN convention) or exceeds K (a truncated
+ *   lattice), offsets_out[B] = -1, the other offsets and gain are 0 and nothing is selected -- the two calls chain without a host
+ *   synchronisation in between.
+ *   No atomics, fixed order: two calls are bit-identical.  2 T B must stay below 2^31.
+ *   Workspace: semicrf_workspace_bytes(SEMICRF_OP_MBR_SELECT, T, B), about 7 T B int32 (8 T B for T > 4096, where the recursion's
+ *   values do not stay on chip).  pairs must be 8-byte aligned.
+ */
+int semicrf_mbr_select(const int32_t* pairs, const float* weight, const int32_t* offsets, int64_t K, int T, int B, const float* tau,
+                       int tau_stride, int32_t* pairs_out, float* probs_out, int64_t cap, int32_t* offsets_out, float* gain,
+                       void* ws, size_t ws_bytes, semicrf_stream_t stream);
 
 /*
  * Posterior expectation of an additive path functional, and its covariance with every cell of the lattice (the Hessian-vector

@@ -1102,17 +1102,17 @@ def _marginal_decode_raw(score_c, noise_c, tau, cap: Optional[int] = None, lvq=N
     return pairs, offsets, probs
 
 
-def _threshold_tensor(threshold, B: int, device) -> torch.Tensor:
+def _threshold_tensor(threshold, B: int, device, name: str = "decode_marginal") -> torch.Tensor:
     if isinstance(threshold, torch.Tensor):
         if not threshold.is_floating_point() or tuple(threshold.shape) != (B,):
-            raise ValueError(f"decode_marginal: a threshold tensor must be floating point of shape [{B}] (one value per chain), "
+            raise ValueError(f"{name}: a threshold tensor must be floating point of shape [{B}] (one value per chain), "
                              f"got {threshold.dtype} {tuple(threshold.shape)}")
         return threshold.detach().to(device=device, dtype=torch.float32).contiguous()       # not range-checked: that would synchronise
     if isinstance(threshold, bool) or not isinstance(threshold, (int, float, np.floating, np.integer)):
-        raise ValueError(f"decode_marginal: threshold must be a float in (0, 1] or a float tensor [nBatch], got {threshold!r}")
+        raise ValueError(f"{name}: threshold must be a float in (0, 1] or a float tensor [nBatch], got {threshold!r}")
     t = float(threshold)
     if not (0.0 < t <= 1.0):                   # NaN fails both comparisons
-        raise ValueError(f"decode_marginal: threshold must be in (0, 1], got {threshold!r}")
+        raise ValueError(f"{name}: threshold must be in (0, 1], got {threshold!r}")
     return torch.full((1,), t, dtype=torch.float32, device=device)
 
 
@@ -1157,6 +1157,79 @@ def decode_marginal(score, noiseScore, threshold):
     paths = unpack_intervals(torch.from_numpy(pairs), torch.from_numpy(offsets), T)
     pl, off = probs.tolist(), offsets.tolist()
     return paths, [pl[off[c]:off[c + 1]] for c in range(B)]
+
+
+# --------------------------------------------------------------------------------------
+# MBR path decoding at any threshold (an extension of the reference's surface)
+# --------------------------------------------------------------------------------------
+
+def _mbr_select_raw(pairs, probs, offsets, T: int, tau):
+    """Enqueue semicrf_mbr_select on a device lattice (_marginal_decode_raw's result); no host sync.  Returns device tensors
+    (pairs [2 T B, 2], offsets [B+1], probs [2 T B], gain [B]); offsets[B] = -1 when the lattice is truncated or invalid."""
+    B = offsets.shape[0] - 1
+    dev = offsets.device
+    cap = 2 * T * B                                # a path has at most 2 T - 1 cells
+    pairs_out = torch.empty(cap, 2, dtype=torch.int32, device=dev)
+    probs_out = torch.empty(cap, dtype=torch.float32, device=dev)
+    offsets_out = torch.empty(B + 1, dtype=torch.int32, device=dev)
+    gain = torch.empty(B, dtype=torch.float32, device=dev)
+    ws = _lib.workspace(_lib.OP_MBR_SELECT, T, B, dev)
+    _lib.ops().mbr_select(pairs, probs, offsets, T, tau, pairs_out, probs_out, offsets_out, gain, ws)
+    return pairs_out, offsets_out, probs_out, gain
+
+
+def decode_mbr_packed(score, noiseScore, threshold):
+    """An EXTENSION of the reference's surface: the minimum-Bayes-risk PATH for the gain (1 - threshold) per correct and -threshold
+    per wrong interval, at ANY threshold: among all paths of a chain the one that maximises the sum over its intervals of
+    (P((begin, end) on the path | score) - threshold).  Returns host arrays (pairs int32 [K, 2], offsets int32 [nBatch + 1], probs
+    float32 [K], gain float32 [nBatch]): chain c owns pairs[offsets[c]:offsets[c + 1]], ascending by (begin, end) -- always a path
+    that plugs into evalPath / logProb -- probs are those intervals' posterior probabilities (interval_marginals' values, bit for
+    bit) and gain[c] the maximised sum.  For threshold > 0.5 it is decode_marginal_packed's set without the probabilities equal to
+    the threshold; below, where that set is a lattice that may overlap, this is the consistent decision (lower the threshold for
+    recall).
+
+    threshold: as decode_marginal_packed (a Python float in (0, 1] or a float tensor [nBatch], not range-checked).  Runs the alpha
+    and beta sweeps once, semicrf_marginal_decode into a device lattice and semicrf_mbr_select on it; never builds a dense
+    [T, T, nBatch] tensor; one host sync; no gradient."""
+    T, B = _check_inputs(score, noiseScore)
+    with torch.no_grad():
+        score_c, noise_c = _prep(score.detach()), _prep(noiseScore.detach())
+        tau = _threshold_tensor(threshold, B, score_c.device, "decode_mbr")
+        pad = _odd_pad(score_c)
+        lvq = None if pad else _marginal_inputs(score_c, noise_c)
+        nB = B + 1 if pad else B                   # (a single chain: the raw call pads and sweeps; the ghost's cells come last)
+        if isinstance(threshold, torch.Tensor):
+            cap = 2 * T * nB
+        else:                                      # sum_{e > b} m(e, b) <= 1: at most floor(1 / tau) + 1 cells per begin
+            cap = min((int(1.0 / float(threshold)) + 1) * T, T * (T + 1) // 2) * nB
+        lat = _marginal_decode_raw(score_c, noise_c, tau, cap, lvq)
+        pairs, offsets, probs, gain = _mbr_select_raw(lat[0], lat[2], lat[1], T, tau)
+        off_h = offsets.cpu()                      # the one host sync
+        if int(off_h[-1]) < 0:
+            lat_total = int(lat[1][-1])
+            if lat_total > lat[0].shape[0]:
+                # the lattice did not fit (a threshold tensor with small values): once more with the exact size -- never a silent truncation
+                lat = _marginal_decode_raw(score_c, noise_c, tau, lat_total + (cap // nB if pad else 0), lvq)
+                pairs, offsets, probs, gain = _mbr_select_raw(lat[0], lat[2], lat[1], T, tau)
+                off_h = offsets.cpu()
+        total = int(off_h[-1])
+        if total < 0:
+            _lib.async_error()                     # consumed here: the next call must not report this time-out again
+            raise RuntimeError("semicrf_mbr_select: alpha holds NaN in its last row -- the inputs hold NaN (or -inf cells, which "
+                               "the device's forward sweep does not take), or a bounded hand-off wait of the sweep timed out on the "
+                               "device (GPU shared with work that kept part of the persistent kernel from running?); the result is invalid")
+        return pairs[:total].cpu().numpy(), off_h.numpy(), probs[:total].cpu().numpy(), gain.cpu().numpy()
+
+
+def decode_mbr(score, noiseScore, threshold):
+    """An EXTENSION of the reference's surface: (paths, probs, gain) -- paths an Intervals (per chain the minimum-Bayes-risk path
+    at `threshold`, the type decode returns), probs per chain the list of its intervals' posterior probabilities, gain a float32
+    numpy [nBatch].  Arguments and properties as decode_mbr_packed."""
+    T, B = _check_inputs(score, noiseScore)
+    pairs, offsets, probs, gain = decode_mbr_packed(score, noiseScore, threshold)
+    paths = unpack_intervals(torch.from_numpy(pairs), torch.from_numpy(offsets), T)
+    pl, off = probs.tolist(), offsets.tolist()
+    return paths, [pl[off[c]:off[c + 1]] for c in range(B)], gain
 
 
 def viterbiBackward(score, noiseScore, forcedStartPos: Optional[List[int]] = None) -> Intervals:
@@ -1295,6 +1368,18 @@ class NeuralSemiCRFInterval:
         """`decode_marginal` as host arrays (pairs int32 [K, 2], offsets int32 [nBatch + 1], probs float32 [K]) before the Python
         lists are built; pairs / offsets feed interval_marginals_packed and attributes.attribute_input_packed as they are."""
         return decode_marginal_packed(self.score, self.noiseScore, threshold)
+
+    def decode_mbr(self, threshold):
+        """An EXTENSION of the reference's surface: (paths, probs, gain) -- per chain the minimum-Bayes-risk PATH at `threshold` (the
+        path maximising the sum over its intervals of (posterior probability - threshold); a float in (0, 1] or a float tensor
+        [nBatch]; no default), its intervals' probabilities and the maximised sum.  Always a path (plugs into evalPath / logProb),
+        also for threshold <= 0.5 where decode_marginal gives a lattice -- see the module-level decode_mbr_packed.  No gradient."""
+        return decode_mbr(self.score, self.noiseScore, threshold)
+
+    def decode_mbr_packed(self, threshold):
+        """`decode_mbr` as host arrays (pairs int32 [K, 2], offsets int32 [nBatch + 1], probs float32 [K], gain float32 [nBatch])
+        before the Python lists are built."""
+        return decode_mbr_packed(self.score, self.noiseScore, threshold)
 
     def evalPath(self, intervals):
         """compute the unnormalized score"""

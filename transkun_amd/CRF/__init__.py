@@ -6,4 +6,5 @@ from .NeuralSemiCRFInterval import (NeuralSemiCRFInterval, viterbi, viterbiBackw
                                     viterbi_nbest, viterbi_nbest_packed, Posteriors, posteriors,
                                     interval_marginals, interval_marginals_packed,
                                     decode_marginal, decode_marginal_packed,
+                                    decode_mbr, decode_mbr_packed,
                                     expectation, entropy, covariance)

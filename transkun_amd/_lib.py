@@ -26,6 +26,7 @@ LIB_PATH = os.environ.get("SEMICRF_LIB") or os.path.join(_HERE, "libsemicrf_hip.
 OP_LOGZ_FWD, OP_LOGZ_BWD, OP_VITERBI, OP_EVAL_PATH, OP_INTERVAL_SCORE, OP_SAMPLE, OP_VITERBI_NBEST, OP_POSTERIORS = range(8)
 OP_MARGINAL_DECODE = 8
 OP_EXPECTATION = 9
+OP_MBR_SELECT = 10
 LEN_MODES = {"linear": 0, "sqrt": 1, "none": 2}
 
 _vp = ctypes.c_void_p
@@ -55,6 +56,7 @@ _SIGS = {
     "semicrf_posteriors": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "semicrf_interval_marginals": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _i64, _vp, _vp, _vp]),
     "semicrf_marginal_decode": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, _i64, _vp, _vp, _sz, _vp]),
+    "semicrf_mbr_select": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp, _i, _vp, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
     "semicrf_expectation": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "semicrf_covariance": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "semicrf_eval_path": (_i, [_vp, _vp, _i, _i, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),

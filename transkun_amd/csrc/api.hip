@@ -108,6 +108,10 @@ void launch_interval_marginals(const float* score, const float* v, const float* 
 size_t marginal_decode_workspace_bytes(int T, int B);
 void launch_marginal_decode(const float* score, const float* v, const float* q, const float* logZ, int T, int B, const float* tau,
                             int tau_stride, int* pairs, float* probs, long long cap, int* offsets, void* ws, hipStream_t stream);
+size_t mbr_select_workspace_bytes(int T, int B);
+void launch_mbr_select(const int* pairs, const float* weight, const int* offsets, long long K, int T, int B, const float* tau,
+                       int tau_stride, int* pairs_out, float* probs_out, long long cap, int* offsets_out, float* gain, void* ws,
+                       hipStream_t stream);
 size_t nbest_workspace_bytes(int T, int nB);
 void launch_viterbi_nbest(const float* score, const float* noise, int T, int B, int k, const int* start, int forward, int* pairs,
                           long long cap, int* offsets, float* scores, int* npaths, void* ws, hipStream_t stream);
@@ -298,6 +302,7 @@ size_t semicrf_workspace_bytes(int op, int T, int B)
         case SEMICRF_OP_VITERBI_NBEST: return nbest_workspace_bytes(T, B);
         case SEMICRF_OP_MARGINAL_DECODE: return marginal_decode_workspace_bytes(T, B);
         case SEMICRF_OP_EXPECTATION: return expectation_workspace_bytes(T, B);
+        case SEMICRF_OP_MBR_SELECT: return mbr_select_workspace_bytes(T, B);
         default: return 0;
     }
 }
@@ -607,6 +612,25 @@ int semicrf_marginal_decode(const float* score, const float* noise, const float*
     if (ws_bytes < marginal_decode_workspace_bytes(T, B)) { set_error("workspace too small for marginal_decode"); return SEMICRF_EWORKSPACE; }
     launch_marginal_decode(score, v, q, logZ, T, B, tau, tau_stride, pairs, probs, (long long)cap, offsets, ws, (hipStream_t)stream);
     SEMICRF_CHECK_LAUNCH("semicrf_marginal_decode");
+    return SEMICRF_OK;
+}
+
+int semicrf_mbr_select(const int32_t* pairs, const float* weight, const int32_t* offsets, int64_t K, int T, int B, const float* tau,
+                       int tau_stride, int32_t* pairs_out, float* probs_out, int64_t cap, int32_t* offsets_out, float* gain, void* ws,
+                       size_t ws_bytes, semicrf_stream_t stream)
+{
+    SEMICRF_CHECK_ARG(T >= 1 && B >= 1, "T=%d, B=%d must be >= 1", T, B);
+    SEMICRF_CHECK_ARG(T < (1 << 29) && (long long)2 * T * B < (1ll << 31), "2 T B exceeds int32 offsets");
+    SEMICRF_CHECK_ARG(K >= 0 && K < (1ll << 31) && (K == 0 || (pairs && weight)), "bad lattice capacity");
+    SEMICRF_CHECK_ARG(((uintptr_t)pairs & 7) == 0, "pairs must be 8-byte aligned");
+    SEMICRF_CHECK_ARG(offsets && tau, "offsets and tau must be non-NULL");
+    SEMICRF_CHECK_ARG(tau_stride == 0 || tau_stride == 1, "tau stride must be 0 (one value for all chains) or 1");
+    SEMICRF_CHECK_ARG(pairs_out && probs_out && offsets_out && gain && cap >= 0, "pairs_out/probs_out/offsets_out/gain must be non-NULL and cap >= 0");
+    SEMICRF_CHECK_ARG(ws != nullptr, "workspace is NULL");
+    if (ws_bytes < mbr_select_workspace_bytes(T, B)) { set_error("workspace too small for mbr_select"); return SEMICRF_EWORKSPACE; }
+    launch_mbr_select(pairs, weight, offsets, (long long)K, T, B, tau, tau_stride, pairs_out, probs_out, (long long)cap, offsets_out, gain,
+                      ws, (hipStream_t)stream);
+    SEMICRF_CHECK_LAUNCH("semicrf_mbr_select");
     return SEMICRF_OK;
 }
 

@@ -547,6 +547,70 @@ void marginal_decode(const float* score, const float* v, const float* q, const f
     offsets[B] = bad ? -1 : (int32_t)n;
 }
 
+// MBR path decoding (include/semicrf_hip.h: semicrf_mbr_select; the device kernels are mbr_decode.hip): per chain the recursion
+// F[t] = max(F[t+1], max over the eligible (t, e), e > t, of g + F[e]) + gS(t) over the packed lattice, walked backwards, then the
+// trace from frame 0.  Ties: the skip, then the smallest e (the strict compare in ascending order).  Chains in parallel; packed in
+// chain order afterwards.
+void mbr_select(const int32_t* pairs, const float* weight, const int32_t* offsets, int64_t K, int T, int B, const float* tau,
+                int tau_stride, int32_t* pairs_out, float* probs_out, int64_t cap, int32_t* offsets_out, float* gain)
+{
+    const int64_t total = offsets[B];
+    if (total < 0 || total > K) {                                   // the NaN convention of the sweeps / a truncated lattice
+        for (int c = 0; c < B; ++c) { offsets_out[c] = 0; gain[c] = 0.0f; }
+        offsets_out[B] = -1;
+        return;
+    }
+    std::vector<std::vector<int32_t>> sel((size_t)B);               // the selected lattice indices of every chain, in path order
+#pragma omp parallel for schedule(dynamic, 4)
+    for (int c = 0; c < B; ++c) {
+        const float th = tau[(size_t)c * tau_stride];
+        int64_t lo = std::min<int64_t>(std::max<int64_t>(offsets[c], 0), total);
+        int64_t hi = std::min<int64_t>(std::max<int64_t>(offsets[c + 1], lo), total);
+        std::vector<float> F((size_t)T + 1, 0.0f);                  // F[T] = +0: F[T-1] = 0 + gS(T-1)
+        std::vector<int32_t> ch((size_t)T, -1), sg((size_t)T, -1), nx((size_t)T, 0);
+        int64_t i = hi;
+        for (int t = T - 1; t >= 0; --t) {
+            while (i > lo && pairs[2 * (i - 1)] > t) --i;           // (an unsorted lattice: entries above the frame are dropped)
+            int64_t j = i;
+            while (j > lo && pairs[2 * (j - 1)] == t) --j;          // the frame's entries: [j, i), ascending by end
+            float best = F[t + 1], gs = 0.0f;
+            int32_t key = -1;
+            for (int64_t k = j; k < i; ++k) {
+                const int32_t e = pairs[2 * k + 1];
+                const float w = weight[k];
+                if (!(w > th) || e < t || e >= T) continue;         // NaN on either side: not eligible
+                const float g = w - th;
+                if (e == t) {
+                    if (sg[t] < 0) { sg[t] = (int32_t)k; gs = g; }
+                    continue;
+                }
+                const float cv = g + F[e];
+                if (cv > best) { best = cv; key = (int32_t)k; }
+            }
+            ch[t] = key;
+            nx[t] = key < 0 ? t + 1 : pairs[2 * key + 1];
+            F[t] = best + gs;
+            i = j;
+        }
+        gain[c] = F[0];
+        std::vector<int32_t>& out = sel[(size_t)c];
+        for (int t = 0;; t = nx[t]) {
+            if (sg[t] >= 0) out.push_back(sg[t]);
+            if (t == T - 1) break;
+            if (ch[t] >= 0) out.push_back(ch[t]);
+        }
+    }
+    int64_t n = 0;
+    for (int c = 0; c < B; ++c) {
+        offsets_out[c] = (int32_t)n;
+        for (const int32_t k : sel[(size_t)c]) {
+            if (n < cap) { pairs_out[2 * n] = pairs[2 * k]; pairs_out[2 * n + 1] = pairs[2 * k + 1]; probs_out[n] = weight[k]; }
+            ++n;
+        }
+    }
+    offsets_out[B] = (int32_t)n;
+}
+
 // k-best Viterbi (include/semicrf_hip.h: semicrf_viterbi_nbest; the device kernel is nbest.hip).  Per frame and chain a sorted
 // list of at most k partial paths, each (value, base, order word); a candidate's ranks are tried in ascending order and the scan of
 // a candidate stops at the first rank whose two singleton variants both fail to beat the list's k-th entry (later ranks of the

@@ -19,6 +19,8 @@ void interval_marginals(const float* score, const float* v, const float* q, cons
                         const int32_t* offsets, float* out);
 void marginal_decode(const float* score, const float* v, const float* q, const float* logZ, int T, int B, const float* tau,
                      int tau_stride, int32_t* pairs, float* probs, int64_t cap, int32_t* offsets);
+void mbr_select(const int32_t* pairs, const float* weight, const int32_t* offsets, int64_t K, int T, int B, const float* tau,
+                int tau_stride, int32_t* pairs_out, float* probs_out, int64_t cap, int32_t* offsets_out, float* gain /* [B] */);
 // state: (4 T B + 2 B) doubles, filled by expectation and read by covariance (v64, a, q64, binc [T][B] each, then E, logZ [B])
 void expectation(const float* score, const float* noise, const float* weight /* or null: score */, const float* nweight /* or null: 0 */,
                  int T, int B, float* E, float* H, double* state);

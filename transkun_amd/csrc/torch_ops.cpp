@@ -237,6 +237,34 @@ void marginal_decode(Tensor score, Tensor noise, Tensor v, Tensor q, Tensor logZ
                                   i32(offsets, d.B + 1, "offsets"), bytes(ws, "ws"), (size_t)ws.numel(), c.stream),
           "semicrf_marginal_decode");
 }
+// MBR path decoding (semicrf_mbr_select) over a lattice of marginal_decode: pairs [K, 2], weight [K], offsets [B + 1]; tau as above;
+// pairs_out [cap, 2], probs_out [cap], offsets_out [B + 1], gain [B]
+struct MbrDims { int64_t K, cap; int B; };
+inline MbrDims mbr_dims(const Tensor& pairs, const Tensor& weight, const Tensor& offsets, int64_t T, const Tensor& pairs_out,
+                        const Tensor& probs_out, const Tensor& offsets_out, const Tensor& gain)
+{
+    STD_TORCH_CHECK(pairs.dim() == 2 && pairs.size(1) == 2, "semicrf: pairs must be [K, 2]");
+    STD_TORCH_CHECK(pairs_out.dim() == 2 && pairs_out.size(1) == 2 && pairs_out.size(0) >= 1, "semicrf: pairs_out must be [cap, 2], cap >= 1");
+    const int64_t K = pairs.size(0), cap = pairs_out.size(0), B = offsets.numel() - 1;
+    STD_TORCH_CHECK(T >= 1 && B >= 1 && T < (1 << 29) && 2 * T * B < (1ll << 31), "semicrf: bad T / offsets size");
+    want(pairs, ScalarType::Int, 2 * K, "pairs");
+    want(weight, ScalarType::Float, K, "weight");
+    want(offsets, ScalarType::Int, B + 1, "offsets");
+    want(pairs_out, ScalarType::Int, 2 * cap, "pairs_out");
+    want(probs_out, ScalarType::Float, cap, "probs_out");
+    want(offsets_out, ScalarType::Int, B + 1, "offsets_out");
+    want(gain, ScalarType::Float, B, "gain");
+    return MbrDims{K, cap, (int)B};
+}
+void mbr_select(Tensor pairs, Tensor weight, Tensor offsets, int64_t T, Tensor tau, Tensor pairs_out, Tensor probs_out, Tensor offsets_out,
+                Tensor gain, Tensor ws)
+{
+    Ctx c(offsets); c.same(offsets, pairs, weight, tau, pairs_out, probs_out, offsets_out, gain, ws);
+    const MbrDims d = mbr_dims(pairs, weight, offsets, T, pairs_out, probs_out, offsets_out, gain);
+    check(semicrf_mbr_select(ip(pairs), cfp(weight), ip(offsets), d.K, (int)T, d.B, cfp(tau), tau_stride_of(tau, d.B), ip(pairs_out),
+                             fp(probs_out), d.cap, ip(offsets_out), fp(gain), bytes(ws, "ws"), (size_t)ws.numel(), c.stream),
+          "semicrf_mbr_select");
+}
 void eval_path(Tensor score, Tensor noise, Tensor pairs, int64_t K, Tensor offsets, Tensor out, Tensor ws)
 {
     Ctx c(score); c.same(score, noise, pairs, offsets, out);
@@ -424,6 +452,15 @@ void marginal_decode_cpu(Tensor score, Tensor noise, Tensor v, Tensor q, Tensor 
     const int ts = tau_stride_of(tau, d.B);
     semicrf_cpu::marginal_decode(cfp(score), f32(v, TB, "v"), f32(q, TB, "q"), f32(logZ, d.B, "logZ"), d.T, d.B, cfp(tau), ts,
                                  i32(pairs, 2 * cap, "pairs"), f32w(probs, cap, "probs"), cap, i32(offsets, d.B + 1, "offsets"));
+}
+void mbr_select_cpu(Tensor pairs, Tensor weight, Tensor offsets, int64_t T, Tensor tau, Tensor pairs_out, Tensor probs_out,
+                    Tensor offsets_out, Tensor gain, Tensor ws)
+{
+    all_cpu(pairs, weight, offsets, tau, pairs_out, probs_out, offsets_out, gain);
+    const MbrDims d = mbr_dims(pairs, weight, offsets, T, pairs_out, probs_out, offsets_out, gain);
+    const int ts = tau_stride_of(tau, d.B);
+    semicrf_cpu::mbr_select(ip(pairs), cfp(weight), ip(offsets), d.K, (int)T, d.B, cfp(tau), ts, ip(pairs_out), fp(probs_out), d.cap,
+                            ip(offsets_out), fp(gain));
 }
 void eval_path_cpu(Tensor score, Tensor noise, Tensor pairs, int64_t K, Tensor offsets, Tensor out, Tensor ws)
 {
@@ -687,6 +724,8 @@ STABLE_TORCH_LIBRARY(semicrf, m)
     m.def("interval_marginals(Tensor score, Tensor v, Tensor q, Tensor logZ, Tensor pairs, int K, Tensor offsets, Tensor(a!) out) -> ()");
     m.def("marginal_decode(Tensor score, Tensor noise, Tensor v, Tensor q, Tensor logZ, Tensor tau, Tensor(a!) pairs, Tensor(b!) probs, "
           "Tensor(c!) offsets, Tensor(d!) ws) -> ()");
+    m.def("mbr_select(Tensor pairs, Tensor weight, Tensor offsets, int T, Tensor tau, Tensor(a!) pairs_out, Tensor(b!) probs_out, "
+          "Tensor(c!) offsets_out, Tensor(d!) gain, Tensor(e!) ws) -> ()");
     m.def("eval_path(Tensor score, Tensor noise, Tensor pairs, int K, Tensor offsets, Tensor(a!) out, Tensor(b!) ws) -> ()");
     m.def("eval_path_bwd(Tensor gout, int T, int B, Tensor pairs, int K, Tensor offsets, Tensor(a!) dScore, bool has_ds, Tensor(b!) dNoise, "
           "bool has_dn) -> ()");
@@ -739,6 +778,7 @@ STABLE_TORCH_LIBRARY_IMPL(semicrf, CPU, m)
     m.impl("expectation", TORCH_BOX(&expectation_cpu));
     m.impl("covariance", TORCH_BOX(&covariance_cpu));
     m.impl("marginal_decode", TORCH_BOX(&marginal_decode_cpu));
+    m.impl("mbr_select", TORCH_BOX(&mbr_select_cpu));
     m.impl("eval_path", TORCH_BOX(&eval_path_cpu));
     m.impl("eval_path_bwd", TORCH_BOX(&eval_path_bwd_cpu));
     m.impl("logprob_fwd", TORCH_BOX(&logprob_fwd_cpu));
@@ -758,6 +798,7 @@ STABLE_TORCH_LIBRARY_IMPL(semicrf, CUDA, m)
     m.impl("expectation", TORCH_BOX(&expectation));
     m.impl("covariance", TORCH_BOX(&covariance));
     m.impl("marginal_decode", TORCH_BOX(&marginal_decode));
+    m.impl("mbr_select", TORCH_BOX(&mbr_select));
     m.impl("eval_path", TORCH_BOX(&eval_path));
     m.impl("eval_path_bwd", TORCH_BOX(&eval_path_bwd));
     m.impl("logprob_fwd", TORCH_BOX(&logprob_fwd));
