@@ -16,6 +16,7 @@ import pytest
 import torch
 
 from conftest import EDGE_CASES, edge_inputs, unpack_lists
+from mbr_common import _mbr_reference
 from transkun_amd import CRF, _lib, synth
 
 crf_mod = importlib.import_module("transkun_amd.CRF.NeuralSemiCRFInterval")
@@ -38,56 +39,7 @@ def _tau_array(thr, B):
     return thr.numpy().astype(np.float32) if isinstance(thr, torch.Tensor) else np.full(B, thr, np.float32)
 
 
-# ---- the restatement -------------------------------------------------------------------------------------------------------
-
-def _mbr_reference(pairs, offsets, weight, T, tau):
-    """semicrf_mbr_select as the header states it, in numpy float32 (np.float32 + np.float32 is one fp32 add)."""
-    B = len(offsets) - 1
-    zero = np.float32(0.0)
-    sel, off, gain = [], [0], np.zeros(B, np.float32)
-    for c in range(B):
-        lo, hi = int(offsets[c]), int(offsets[c + 1])
-        th = np.float32(tau[c])
-        w, b, e = weight[lo:hi], pairs[lo:hi, 0], pairs[lo:hi, 1]
-        with np.errstate(invalid="ignore"):
-            elig = w > th                                     # strict; NaN is never eligible
-        g = w - th
-        assert g.dtype == np.float32
-        single, begins = {}, {}
-        for i in np.nonzero(elig)[0]:
-            if b[i] == e[i]:
-                single.setdefault(int(b[i]), int(i))
-            else:
-                begins.setdefault(int(b[i]), []).append(int(i))          # the lattice is ascending by (begin, end)
-        gS = lambda t: g[single[t]] if t in single else zero
-        F = np.zeros(T, np.float32)
-        choice = [-1] * T
-        F[T - 1] = gS(T - 1)
-        for t in range(T - 2, -1, -1):
-            best, ch = F[t + 1], -1
-            for i in begins.get(t, ()):
-                cv = g[i] + F[e[i]]
-                if cv > best:
-                    best, ch = cv, i
-            F[t] = best + gS(t)
-            choice[t] = ch
-        assert F.dtype == np.float32
-        t = 0
-        while True:
-            if t in single:
-                sel.append(lo + single[t])
-            if t == T - 1:
-                break
-            if choice[t] < 0:
-                t += 1
-            else:
-                sel.append(lo + choice[t])
-                t = int(e[choice[t]])
-        off.append(len(sel))
-        gain[c] = F[0]
-    sel = np.asarray(sel, np.int64)
-    return pairs[sel].reshape(-1, 2), np.asarray(off, np.int32), weight[sel], gain
-
+# ---- the restatement (_mbr_reference: tests/mbr_common.py) -------------------------------------------------------------------
 
 def _check_structure(crf, T, B, tau, got, what):
     pairs, offsets, probs, gain = got
