@@ -55,6 +55,9 @@ extern "C" {
 #define SEMICRF_OP_MARGINAL_DECODE 8   /* semicrf_marginal_decode */
 #define SEMICRF_OP_EXPECTATION 9       /* semicrf_expectation / semicrf_covariance (one workspace for the pair) */
 #define SEMICRF_OP_MBR_SELECT 10       /* semicrf_mbr_select */
+#define SEMICRF_OP_MARGINAL_DECODE_TOL 11   /* semicrf_marginal_decode_tol */
+
+#define SEMICRF_TOL_MAX 8              /* largest onset / offset tolerance (frames) of the *_tol entry points */
 
 /* length scaling of the interval scorer (LayersTransformer.py:416-427) */
 #define SEMICRF_LEN_LINEAR 0
@@ -296,6 +299,49 @@ int semicrf_marginal_decode(const float* score, const float* noise, const float*
 int semicrf_mbr_select(const int32_t* pairs, const float* weight, const int32_t* offsets, int64_t K, int T, int B, const float* tau,
                        int tau_stride, int32_t* pairs_out, float* probs_out, int64_t cap, int32_t* offsets_out, float* gain,
                        void* ws, size_t ws_bytes, semicrf_stream_t stream);
+
+/*
+ * Onset/offset-tolerant interval posteriors and marginal-threshold decoding.  No counterpart in the reference (an extension of its
+ * surface, like semicrf_marginal_decode).  Adds nothing to the ABI's existing entry points (version 2).
+ *
+ * Tolerances are tol_begin = db and tol_end = de, in frames, with 0 <= db, de <= SEMICRF_TOL_MAX = 8.  For a cell 0 <= b <= e < T
+ * of chain c:
+ *
+ *   row(e') = sum over b' = max(0, b-db) .. min(b+db, e'), ascending, of m(e', b')     (fp32, one add per term)
+ *   M(e,b)  = clamp1( sum over e' = max(0, e-de) .. min(T-1, e+de), ascending, of row(e') )
+ *
+ *   - m(e', b') is the value semicrf_interval_marginals returns for (b', e'), bit for bit.
+ *     - That means cell_marginal / cell_marginal_single of posterior_cell.h, each clamped on its own.
+ *     - Singletons (t,t) are ordinary cells of the box.
+ *   - Rows without a cell (e' < b - db) contribute nothing.
+ *   - clamp1 is the existing one: values above 1 become 1 and NaN stays NaN.
+ *   - A NaN term makes M NaN, which selects nothing.
+ *
+ * Meaning: M is the expected number of path intervals whose begin is within db of b and whose end is within de of e, capped at 1.
+ *   - For e - b > db + de all cells of the box share an interior frame, so at most one of them lies on a path.  The uncapped sum is
+ *     then already a probability: P(some interval of the path matches (b,e) within the tolerance).
+ *   - For shorter cells it is the union bound of that probability.
+ *   - db = de = 0 gives M = m.
+ * The order above is the contract.  It is chosen so that a separable stencil (row sums, then a sum of rows) and a direct gather give
+ * the same bits.  Both must sum the 2 db + 1 and 2 de + 1 terms directly, never with a sliding add/subtract.
+ *
+ * semicrf_interval_marginals_tol: out[i] = M of interval i; arguments as semicrf_interval_marginals; b > e gives 0 and an index
+ * outside [0, T) gives NaN.  No workspace.
+ * semicrf_marginal_decode_tol: semicrf_marginal_decode with M >= tau in place of m >= tau and probs[i] = M -- chain-major, ascending
+ * by (begin, end); offsets exact past cap, nothing written out of bounds; offsets[B] = -1 on a NaN in v's last row; no atomics, no
+ * host synchronisation, two calls are bit-identical.  With a tolerance the selected cells of a chain are NOT a path even for
+ * tau > 0.5 (neighbouring cells pass together; a box holds up to 2 (2 db + 1)(2 de + 1) of mass per begin): the result is a lattice
+ * for semicrf_mbr_select.  The triangle is read once per tile plus the tile's halo of de rows and db columns, plus the boxes of the
+ * rows that hold a selected cell.
+ * A tolerance outside [0, 8] returns SEMICRF_EINVAL.  With (0, 0) both calls forward to the entry points they extend.
+ * Workspace: semicrf_workspace_bytes(SEMICRF_OP_MARGINAL_DECODE_TOL, T, B), the size of SEMICRF_OP_MARGINAL_DECODE.
+ */
+int semicrf_interval_marginals_tol(const float* score, const float* v, const float* q, const float* logZ, int T, int B,
+                                   const int32_t* pairs, int64_t K, const int32_t* offsets, int tol_begin, int tol_end, float* out,
+                                   semicrf_stream_t stream);
+int semicrf_marginal_decode_tol(const float* score, const float* noise, const float* v, const float* q, const float* logZ, int T, int B,
+                                const float* tau, int tau_stride, int tol_begin, int tol_end, int32_t* pairs, float* probs, int64_t cap,
+                                int32_t* offsets, void* ws, size_t ws_bytes, semicrf_stream_t stream);
 
 /*
  * Posterior expectation of an additive path functional, and its covariance with every cell of the lattice (the Hessian-vector

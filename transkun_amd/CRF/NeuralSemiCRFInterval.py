@@ -21,6 +21,8 @@ EXTENSIONS of the reference's surface: decode_packed, sample / sample_packed (ex
   interval_marginals_packed (posterior marginals and path entropy without the dense [T,T,B] tensor), and decode_marginal /
   decode_marginal_packed (every interval whose posterior probability reaches a threshold), and expectation / entropy /
   covariance (posterior expectations of additive path functionals, the differentiable entropy, Hessian products of logZ).
+  interval_marginals, decode_marginal and decode_mbr (and their _packed forms) take tolerance=(onset, offset) in frames: the
+  probability that the path holds an interval within that window of the given one, the currency of note-level metrics.
 """
 from __future__ import annotations
 
@@ -859,9 +861,30 @@ def _posteriors_raw(score_c, noise_c, lvq=None) -> Posteriors:
     return Posteriors(logz, entropy, node, begin, end, single, noise)
 
 
-def _interval_marginals_raw(score_c, v, q, logz, pairs, K: int, offsets):
+def _tolerance(tolerance, name: str) -> Tuple[int, int]:
+    """The `tolerance` keyword of the posterior calls -> (onset, offset) in frames: None is (0, 0), an int t is (t, t), a pair of
+    ints is taken as it is; each in 0 .. 8 (SEMICRF_TOL_MAX).  Anything else (bool, float, negative, > 8, wrong length): ValueError."""
+    if tolerance is None:
+        return 0, 0
+    is_int = lambda x: isinstance(x, (int, np.integer)) and not isinstance(x, (bool, np.bool_))
+    if is_int(tolerance):
+        pair = (int(tolerance), int(tolerance))
+    elif isinstance(tolerance, (tuple, list)) and len(tolerance) == 2 and all(is_int(x) for x in tolerance):
+        pair = (int(tolerance[0]), int(tolerance[1]))
+    else:
+        raise ValueError(f"{name}: tolerance must be None, an int or a pair (onset, offset) of ints in 0..{_lib.TOL_MAX} (frames), "
+                         f"got {tolerance!r}")
+    if not all(0 <= x <= _lib.TOL_MAX for x in pair):
+        raise ValueError(f"{name}: tolerance must lie in 0..{_lib.TOL_MAX} frames, got {tolerance!r}")
+    return pair
+
+
+def _interval_marginals_raw(score_c, v, q, logz, pairs, K: int, offsets, tol: Tuple[int, int] = (0, 0)):
     out = torch.empty(max(K, 1), dtype=torch.float32, device=score_c.device)
-    _lib.ops().interval_marginals(score_c, v, q, logz, pairs, int(K), offsets, out)
+    if tol == (0, 0):
+        _lib.ops().interval_marginals(score_c, v, q, logz, pairs, int(K), offsets, out)
+    else:
+        _lib.ops().interval_marginals_tol(score_c, v, q, logz, pairs, int(K), offsets, tol[0], tol[1], out)
     return out[:K]
 
 
@@ -896,28 +919,38 @@ def posteriors(score, noiseScore) -> Posteriors:
         return _posteriors_raw(_prep(score.detach()), _prep(noiseScore.detach()))
 
 
-def interval_marginals_packed(score, noiseScore, pairs, offsets) -> torch.Tensor:
+def interval_marginals_packed(score, noiseScore, pairs, offsets, tolerance=None) -> torch.Tensor:
     """An EXTENSION of the reference's surface: the posterior probability of each given interval, a float32 tensor [K] where the
-    scores live.  pairs [K, 2] (begin, end) and offsets [nBatch + 1] as decode_packed returns them (numpy arrays or tensors)."""
+    scores live.  pairs [K, 2] (begin, end) and offsets [nBatch + 1] as decode_packed returns them (numpy arrays or tensors).
+
+    tolerance: None, an int t (meaning (t, t)) or a pair (onset, offset) of ints in 0..8, in frames.  With a tolerance (db, de) the
+    value of (b, e) is M = min(1, the sum of the exact-cell probabilities over the box |b' - b| <= db, |e' - e| <= de): the expected
+    number of path intervals that match (b, e) within the tolerance -- for e - b > db + de the probability that one does, the
+    quantity a note-level metric with an onset / offset window asks for (include/semicrf_hip.h: semicrf_interval_marginals_tol).
+    None and (0, 0) are the exact-cell probabilities."""
     T, B = _check_inputs(score, noiseScore)
+    tol = _tolerance(tolerance, "interval_marginals")
     with torch.no_grad():
         score_c, noise_c = _prep(score.detach()), _prep(noiseScore.detach())
         p, o, K = _packed_on(pairs, offsets, T, B, score_c.device)
         if _odd_pad(score_c):
             s2, n2 = _pad1(score_c), _pad1(noise_c)
             logz, v, q = _marginal_inputs(s2, n2)
-            return _interval_marginals_raw(s2, v, q, logz, p, K, torch.cat([o, o[-1:]]))
+            return _interval_marginals_raw(s2, v, q, logz, p, K, torch.cat([o, o[-1:]]), tol)
         logz, v, q = _marginal_inputs(score_c, noise_c)
-        return _interval_marginals_raw(score_c, v, q, logz, p, K, o)
+        return _interval_marginals_raw(score_c, v, q, logz, p, K, o, tol)
 
 
-def interval_marginals(score, noiseScore, intervals: Intervals) -> List[List[float]]:
+def interval_marginals(score, noiseScore, intervals: Intervals, tolerance=None) -> List[List[float]]:
     """An EXTENSION of the reference's surface: the posterior probability of each interval of `intervals` (one list per chain,
-    e.g. what decode returns), as a list (len nBatch) of lists of floats in the given order."""
+    e.g. what decode returns), as a list (len nBatch) of lists of floats in the given order.  tolerance: as
+    interval_marginals_packed (None, an int or a pair (onset, offset) of frames in 0..8): the probability that the path holds an
+    interval within that many frames of the given one."""
     T, B = _check_inputs(score, noiseScore)
+    _tolerance(tolerance, "interval_marginals")
     pairs, offsets = pack_intervals(intervals, T, B, "cpu", ordered=False)
     K = pairs._semicrf_K
-    out = interval_marginals_packed(score, noiseScore, pairs[:K], offsets).cpu().tolist()
+    out = interval_marginals_packed(score, noiseScore, pairs[:K], offsets, tolerance).cpu().tolist()
     off = offsets.tolist()
     return [out[off[c]:off[c + 1]] for c in range(B)]
 
@@ -1082,13 +1115,14 @@ def covariance(score, noiseScore, weight, noiseWeight=None):
 # marginal-threshold (posterior) decoding (an extension of the reference's surface)
 # --------------------------------------------------------------------------------------
 
-def _marginal_decode_raw(score_c, noise_c, tau, cap: Optional[int] = None, lvq=None):
-    """Enqueue the sweeps (unless lvq = (logZ, v, q) is given) and semicrf_marginal_decode; no host sync.  tau: a float32 tensor
-    of 1 value or one per chain, where the scores live.  Returns device tensors (pairs [cap, 2], offsets [B+1], probs [cap]);
-    offsets is exact even past cap (default 2 T per chain: the bound for a threshold > 0.5)."""
+def _marginal_decode_raw(score_c, noise_c, tau, cap: Optional[int] = None, lvq=None, tol: Tuple[int, int] = (0, 0)):
+    """Enqueue the sweeps (unless lvq = (logZ, v, q) is given) and semicrf_marginal_decode (semicrf_marginal_decode_tol for a
+    tolerance tol = (onset, offset) other than (0, 0)); no host sync.  tau: a float32 tensor of 1 value or one per chain, where the
+    scores live.  Returns device tensors (pairs [cap, 2], offsets [B+1], probs [cap]); offsets is exact even past cap (default 2 T
+    per chain: the bound for a threshold > 0.5 without a tolerance)."""
     if _odd_pad(score_c) and lvq is None:
         t2 = tau if tau.numel() == 1 else torch.cat([tau, tau.new_full((1,), float("inf"))])     # the ghost chain selects nothing
-        pairs, offsets, probs = _marginal_decode_raw(_pad1(score_c), _pad1(noise_c), t2, cap)
+        pairs, offsets, probs = _marginal_decode_raw(_pad1(score_c), _pad1(noise_c), t2, cap, None, tol)
         return pairs, offsets[:-1], probs  # the ghost chain is last: its intervals lie behind offsets[B]
     T, B = score_c.shape[0], score_c.shape[2]
     dev = score_c.device
@@ -1097,8 +1131,12 @@ def _marginal_decode_raw(score_c, noise_c, tau, cap: Optional[int] = None, lvq=N
     pairs = torch.empty(cap, 2, dtype=torch.int32, device=dev)
     probs = torch.empty(cap, dtype=torch.float32, device=dev)
     offsets = torch.empty(B + 1, dtype=torch.int32, device=dev)
-    ws = _lib.workspace(_lib.OP_MARGINAL_DECODE, T, B, dev)
-    _lib.ops().marginal_decode(score_c, noise_c, v, q, logz, tau, pairs, probs, offsets, ws)
+    if tol == (0, 0):
+        ws = _lib.workspace(_lib.OP_MARGINAL_DECODE, T, B, dev)
+        _lib.ops().marginal_decode(score_c, noise_c, v, q, logz, tau, pairs, probs, offsets, ws)
+    else:
+        ws = _lib.workspace(_lib.OP_MARGINAL_DECODE_TOL, T, B, dev)
+        _lib.ops().marginal_decode_tol(score_c, noise_c, v, q, logz, tau, tol[0], tol[1], pairs, probs, offsets, ws)
     return pairs, offsets, probs
 
 
@@ -1116,7 +1154,7 @@ def _threshold_tensor(threshold, B: int, device, name: str = "decode_marginal") 
     return torch.full((1,), t, dtype=torch.float32, device=device)
 
 
-def decode_marginal_packed(score, noiseScore, threshold):
+def decode_marginal_packed(score, noiseScore, threshold, tolerance=None):
     """An EXTENSION of the reference's surface: every interval whose posterior probability P((begin, end) on the path | score) is
     >= threshold, as host arrays like decode_packed plus the probabilities: (pairs int32 [K, 2], offsets int32 [nBatch + 1],
     probs float32 [K]); chain c owns pairs[offsets[c]:offsets[c + 1]], ascending by (begin, end).  probs are the values
@@ -1127,17 +1165,25 @@ def decode_marginal_packed(score, noiseScore, threshold):
     cannot overlap (overlapping intervals never share a path, so their probabilities sum to <= 1): the result is a path that
     plugs into evalPath / logProb, the minimum-Bayes-risk decision for the gain (1 - threshold) per correct and -threshold per
     wrong interval; for threshold <= 0.5 it is a candidate lattice that may overlap.  Runs the alpha and beta sweeps itself,
-    never builds the dense [T, T, nBatch] marginal tensor; one host sync; no gradient."""
+    never builds the dense [T, T, nBatch] marginal tensor; one host sync; no gradient.
+
+    tolerance: None, an int t (meaning (t, t)) or a pair (onset, offset) of ints in 0..8, in frames; None and (0, 0) are the call
+    above, unchanged.  With a tolerance the compared and returned value is interval_marginals(..., tolerance)'s M (bit for bit):
+    every interval that the path matches within the tolerance with probability >= threshold.  That set is NO LONGER a path, even
+    for threshold > 0.5 -- the neighbours of a confident interval pass together with it (up to (2 onset + 1)(2 offset + 1) cells
+    per note): it is a lattice, and decode_mbr(threshold, tolerance) is the call that returns one path.  A single chain runs with a
+    ghost chain appended, as without a tolerance; the ghost's cells never show."""
     T, B = _check_inputs(score, noiseScore)
+    tol = _tolerance(tolerance, "decode_marginal")
     with torch.no_grad():
         score_c, noise_c = _prep(score.detach()), _prep(noiseScore.detach())
         tau = _threshold_tensor(threshold, B, score_c.device)
         lvq = None if _odd_pad(score_c) else _marginal_inputs(score_c, noise_c)    # (a single chain: the raw call pads and sweeps)
-        pairs, offsets, probs = _marginal_decode_raw(score_c, noise_c, tau, None, lvq)
+        pairs, offsets, probs = _marginal_decode_raw(score_c, noise_c, tau, None, lvq, tol)
         off_h = offsets.cpu()                      # the one host sync
         if int(off_h[-1]) > pairs.shape[0]:
-            # more cells than 2 T per chain (a threshold <= 0.5): once more with the exact size -- never a silent truncation
-            pairs, offsets, probs = _marginal_decode_raw(score_c, noise_c, tau, int(off_h[-1]), lvq)
+            # more cells than 2 T per chain (a threshold <= 0.5, a tolerance): once more with the exact size -- never a silent truncation
+            pairs, offsets, probs = _marginal_decode_raw(score_c, noise_c, tau, int(off_h[-1]), lvq, tol)
             off_h = offsets.cpu()
         total = int(off_h[-1])
         if total < 0:
@@ -1148,12 +1194,12 @@ def decode_marginal_packed(score, noiseScore, threshold):
         return pairs[:total].cpu().numpy(), off_h.numpy(), probs[:total].cpu().numpy()
 
 
-def decode_marginal(score, noiseScore, threshold):
+def decode_marginal(score, noiseScore, threshold, tolerance=None):
     """An EXTENSION of the reference's surface: (paths, probs) -- paths an Intervals (per chain the list of (begin, end) whose
     posterior probability is >= threshold, ascending by (begin, end): the type decode returns), probs per chain the list of those
-    probabilities.  Arguments and properties as decode_marginal_packed."""
+    probabilities.  Arguments and properties as decode_marginal_packed (with a tolerance the lists are a lattice, not a path)."""
     T, B = _check_inputs(score, noiseScore)
-    pairs, offsets, probs = decode_marginal_packed(score, noiseScore, threshold)
+    pairs, offsets, probs = decode_marginal_packed(score, noiseScore, threshold, tolerance)
     paths = unpack_intervals(torch.from_numpy(pairs), torch.from_numpy(offsets), T)
     pl, off = probs.tolist(), offsets.tolist()
     return paths, [pl[off[c]:off[c + 1]] for c in range(B)]
@@ -1178,7 +1224,7 @@ def _mbr_select_raw(pairs, probs, offsets, T: int, tau):
     return pairs_out, offsets_out, probs_out, gain
 
 
-def decode_mbr_packed(score, noiseScore, threshold):
+def decode_mbr_packed(score, noiseScore, threshold, tolerance=None):
     """An EXTENSION of the reference's surface: the minimum-Bayes-risk PATH for the gain (1 - threshold) per correct and -threshold
     per wrong interval, at ANY threshold: among all paths of a chain the one that maximises the sum over its intervals of
     (P((begin, end) on the path | score) - threshold).  Returns host arrays (pairs int32 [K, 2], offsets int32 [nBatch + 1], probs
@@ -1190,8 +1236,17 @@ def decode_mbr_packed(score, noiseScore, threshold):
 
     threshold: as decode_marginal_packed (a Python float in (0, 1] or a float tensor [nBatch], not range-checked).  Runs the alpha
     and beta sweeps once, semicrf_marginal_decode into a device lattice and semicrf_mbr_select on it; never builds a dense
-    [T, T, nBatch] tensor; one host sync; no gradient."""
+    [T, T, nBatch] tensor; one host sync; no gradient.
+
+    tolerance: None, an int t (meaning (t, t)) or a pair (onset, offset) of ints in 0..8, in frames; None and (0, 0) are the call
+    above, unchanged.  With a tolerance the lattice is semicrf_marginal_decode_tol's and the recursion is the same: the path
+    maximises the sum over its intervals of (M - threshold), M = interval_marginals(..., tolerance)'s value -- the probability that
+    the true path holds an interval within the tolerance of the chosen one -- and probs are the M of its intervals, bit for bit.
+    This is the call that turns the tolerance-aware set of decode_marginal (a lattice: neighbouring cells pass together) into one
+    path: a note whose onset the model spreads over two frames is returned once, with the probability of the pair.  A single chain
+    runs with a ghost chain appended, as without a tolerance."""
     T, B = _check_inputs(score, noiseScore)
+    tol = _tolerance(tolerance, "decode_mbr")
     with torch.no_grad():
         score_c, noise_c = _prep(score.detach()), _prep(noiseScore.detach())
         tau = _threshold_tensor(threshold, B, score_c.device, "decode_mbr")
@@ -1200,16 +1255,23 @@ def decode_mbr_packed(score, noiseScore, threshold):
         nB = B + 1 if pad else B                   # (a single chain: the raw call pads and sweeps; the ghost's cells come last)
         if isinstance(threshold, torch.Tensor):
             cap = 2 * T * nB
+        elif tol != (0, 0):
+            # a box holds up to 2 (2 db + 1)(2 de + 1) of mass per begin (every column of it <= 1 in intervals + 1 as a singleton,
+            # every cell in 2 de + 1 boxes of a begin): at most that / tau cells per begin, or the whole column; start from 2 T per
+            # chain when that is smaller (it is, for every tolerance > 0 and T > 4) and let the retry below take the exact count
+            per_begin = int(2 * (2 * tol[0] + 1) * (2 * tol[1] + 1) / float(threshold)) + 1
+            cap = min(min(per_begin * T, T * (T + 1) // 2), 2 * T) * nB
         else:                                      # sum_{e > b} m(e, b) <= 1: at most floor(1 / tau) + 1 cells per begin
             cap = min((int(1.0 / float(threshold)) + 1) * T, T * (T + 1) // 2) * nB
-        lat = _marginal_decode_raw(score_c, noise_c, tau, cap, lvq)
+        lat = _marginal_decode_raw(score_c, noise_c, tau, cap, lvq, tol)
         pairs, offsets, probs, gain = _mbr_select_raw(lat[0], lat[2], lat[1], T, tau)
         off_h = offsets.cpu()                      # the one host sync
         if int(off_h[-1]) < 0:
             lat_total = int(lat[1][-1])
             if lat_total > lat[0].shape[0]:
-                # the lattice did not fit (a threshold tensor with small values): once more with the exact size -- never a silent truncation
-                lat = _marginal_decode_raw(score_c, noise_c, tau, lat_total + (cap // nB if pad else 0), lvq)
+                # the lattice did not fit (a threshold tensor with small values, a tolerance): once more with the exact size -- never
+                # a silent truncation
+                lat = _marginal_decode_raw(score_c, noise_c, tau, lat_total + (cap // nB if pad else 0), lvq, tol)
                 pairs, offsets, probs, gain = _mbr_select_raw(lat[0], lat[2], lat[1], T, tau)
                 off_h = offsets.cpu()
         total = int(off_h[-1])
@@ -1221,12 +1283,12 @@ def decode_mbr_packed(score, noiseScore, threshold):
         return pairs[:total].cpu().numpy(), off_h.numpy(), probs[:total].cpu().numpy(), gain.cpu().numpy()
 
 
-def decode_mbr(score, noiseScore, threshold):
+def decode_mbr(score, noiseScore, threshold, tolerance=None):
     """An EXTENSION of the reference's surface: (paths, probs, gain) -- paths an Intervals (per chain the minimum-Bayes-risk path
     at `threshold`, the type decode returns), probs per chain the list of its intervals' posterior probabilities, gain a float32
-    numpy [nBatch].  Arguments and properties as decode_mbr_packed."""
+    numpy [nBatch].  Arguments and properties as decode_mbr_packed (tolerance: the onset / offset window in frames)."""
     T, B = _check_inputs(score, noiseScore)
-    pairs, offsets, probs, gain = decode_mbr_packed(score, noiseScore, threshold)
+    pairs, offsets, probs, gain = decode_mbr_packed(score, noiseScore, threshold, tolerance)
     paths = unpack_intervals(torch.from_numpy(pairs), torch.from_numpy(offsets), T)
     pl, off = probs.tolist(), offsets.tolist()
     return paths, [pl[off[c]:off[c + 1]] for c in range(B)], gain
@@ -1333,14 +1395,15 @@ class NeuralSemiCRFInterval:
         float32 tensors where the scores live -- see the module-level posteriors.  No host sync, no gradient."""
         return posteriors(self.score, self.noiseScore)
 
-    def interval_marginals(self, intervals):
+    def interval_marginals(self, intervals, tolerance=None):
         """An EXTENSION of the reference's surface: the posterior probability of each interval of `intervals` (e.g. decode()'s
-        result), a list (len nBatch) of lists of floats in the given order."""
-        return interval_marginals(self.score, self.noiseScore, intervals)
+        result), a list (len nBatch) of lists of floats in the given order.  tolerance (None, an int or (onset, offset) in frames,
+        0..8): the probability of an interval within that window -- see the module-level interval_marginals_packed."""
+        return interval_marginals(self.score, self.noiseScore, intervals, tolerance)
 
-    def interval_marginals_packed(self, pairs, offsets):
+    def interval_marginals_packed(self, pairs, offsets, tolerance=None):
         """`interval_marginals` on decode_packed's arrays (numpy or tensors): a float32 tensor [K] where the scores live."""
-        return interval_marginals_packed(self.score, self.noiseScore, pairs, offsets)
+        return interval_marginals_packed(self.score, self.noiseScore, pairs, offsets, tolerance)
 
     def expectation(self, weight, noiseWeight=None):
         """An EXTENSION of the reference's surface: E_p[W] [nBatch] of the additive path functional given by weight [T, T, nBatch]
@@ -1357,29 +1420,31 @@ class NeuralSemiCRFInterval:
         Hessian of logZ times (weight, noiseWeight) -- see the module-level covariance.  No gradient."""
         return covariance(self.score, self.noiseScore, weight, noiseWeight)
 
-    def decode_marginal(self, threshold):
+    def decode_marginal(self, threshold, tolerance=None):
         """An EXTENSION of the reference's surface: (paths, probs) -- every interval whose posterior probability is >= threshold
         (a float in (0, 1] or a float tensor [nBatch]; no default), per chain ascending by (begin, end), and those probabilities.
         For threshold > 0.5 each chain's result is a path (plugs into evalPath / logProb) -- see the module-level
-        decode_marginal_packed.  No gradient."""
-        return decode_marginal(self.score, self.noiseScore, threshold)
+        decode_marginal_packed.  With a tolerance (None, an int or (onset, offset) in frames, 0..8) the result is a lattice, not a
+        path: decode_mbr is the call that returns one.  No gradient."""
+        return decode_marginal(self.score, self.noiseScore, threshold, tolerance)
 
-    def decode_marginal_packed(self, threshold):
+    def decode_marginal_packed(self, threshold, tolerance=None):
         """`decode_marginal` as host arrays (pairs int32 [K, 2], offsets int32 [nBatch + 1], probs float32 [K]) before the Python
         lists are built; pairs / offsets feed interval_marginals_packed and attributes.attribute_input_packed as they are."""
-        return decode_marginal_packed(self.score, self.noiseScore, threshold)
+        return decode_marginal_packed(self.score, self.noiseScore, threshold, tolerance)
 
-    def decode_mbr(self, threshold):
+    def decode_mbr(self, threshold, tolerance=None):
         """An EXTENSION of the reference's surface: (paths, probs, gain) -- per chain the minimum-Bayes-risk PATH at `threshold` (the
         path maximising the sum over its intervals of (posterior probability - threshold); a float in (0, 1] or a float tensor
         [nBatch]; no default), its intervals' probabilities and the maximised sum.  Always a path (plugs into evalPath / logProb),
-        also for threshold <= 0.5 where decode_marginal gives a lattice -- see the module-level decode_mbr_packed.  No gradient."""
-        return decode_mbr(self.score, self.noiseScore, threshold)
+        also for threshold <= 0.5 where decode_marginal gives a lattice -- see the module-level decode_mbr_packed.  tolerance (None,
+        an int or (onset, offset) in frames, 0..8): the probabilities count an interval within that window.  No gradient."""
+        return decode_mbr(self.score, self.noiseScore, threshold, tolerance)
 
-    def decode_mbr_packed(self, threshold):
+    def decode_mbr_packed(self, threshold, tolerance=None):
         """`decode_mbr` as host arrays (pairs int32 [K, 2], offsets int32 [nBatch + 1], probs float32 [K], gain float32 [nBatch])
         before the Python lists are built."""
-        return decode_mbr_packed(self.score, self.noiseScore, threshold)
+        return decode_mbr_packed(self.score, self.noiseScore, threshold, tolerance)
 
     def evalPath(self, intervals):
         """compute the unnormalized score"""

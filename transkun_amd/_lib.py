@@ -27,6 +27,8 @@ OP_LOGZ_FWD, OP_LOGZ_BWD, OP_VITERBI, OP_EVAL_PATH, OP_INTERVAL_SCORE, OP_SAMPLE
 OP_MARGINAL_DECODE = 8
 OP_EXPECTATION = 9
 OP_MBR_SELECT = 10
+OP_MARGINAL_DECODE_TOL = 11
+TOL_MAX = 8                                     # SEMICRF_TOL_MAX
 LEN_MODES = {"linear": 0, "sqrt": 1, "none": 2}
 
 _vp = ctypes.c_void_p
@@ -56,6 +58,8 @@ _SIGS = {
     "semicrf_posteriors": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "semicrf_interval_marginals": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _i64, _vp, _vp, _vp]),
     "semicrf_marginal_decode": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, _i64, _vp, _vp, _sz, _vp]),
+    "semicrf_interval_marginals_tol": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _i64, _vp, _i, _i, _vp, _vp]),
+    "semicrf_marginal_decode_tol": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _vp, _vp, _i64, _vp, _vp, _sz, _vp]),
     "semicrf_mbr_select": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp, _i, _vp, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
     "semicrf_expectation": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "semicrf_covariance": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),

@@ -108,6 +108,12 @@ void launch_interval_marginals(const float* score, const float* v, const float* 
 size_t marginal_decode_workspace_bytes(int T, int B);
 void launch_marginal_decode(const float* score, const float* v, const float* q, const float* logZ, int T, int B, const float* tau,
                             int tau_stride, int* pairs, float* probs, long long cap, int* offsets, void* ws, hipStream_t stream);
+size_t marginal_decode_tol_workspace_bytes(int T, int B);
+void launch_interval_marginals_tol(const float* score, const float* v, const float* q, const float* logZ, int T, int B, const int* pairs,
+                                   int K, const int* offsets, int db, int de, float* out, hipStream_t stream);
+void launch_marginal_decode_tol(const float* score, const float* v, const float* q, const float* logZ, int T, int B, const float* tau,
+                                int tau_stride, int db, int de, int* pairs, float* probs, long long cap, int* offsets, void* ws,
+                                hipStream_t stream);
 size_t mbr_select_workspace_bytes(int T, int B);
 void launch_mbr_select(const int* pairs, const float* weight, const int* offsets, long long K, int T, int B, const float* tau,
                        int tau_stride, int* pairs_out, float* probs_out, long long cap, int* offsets_out, float* gain, void* ws,
@@ -303,6 +309,7 @@ size_t semicrf_workspace_bytes(int op, int T, int B)
         case SEMICRF_OP_MARGINAL_DECODE: return marginal_decode_workspace_bytes(T, B);
         case SEMICRF_OP_EXPECTATION: return expectation_workspace_bytes(T, B);
         case SEMICRF_OP_MBR_SELECT: return mbr_select_workspace_bytes(T, B);
+        case SEMICRF_OP_MARGINAL_DECODE_TOL: return marginal_decode_tol_workspace_bytes(T, B);
         default: return 0;
     }
 }
@@ -612,6 +619,44 @@ int semicrf_marginal_decode(const float* score, const float* noise, const float*
     if (ws_bytes < marginal_decode_workspace_bytes(T, B)) { set_error("workspace too small for marginal_decode"); return SEMICRF_EWORKSPACE; }
     launch_marginal_decode(score, v, q, logZ, T, B, tau, tau_stride, pairs, probs, (long long)cap, offsets, ws, (hipStream_t)stream);
     SEMICRF_CHECK_LAUNCH("semicrf_marginal_decode");
+    return SEMICRF_OK;
+}
+
+int semicrf_interval_marginals_tol(const float* score, const float* v, const float* q, const float* logZ, int T, int B,
+                                   const int32_t* pairs, int64_t K, const int32_t* offsets, int tol_begin, int tol_end, float* out,
+                                   semicrf_stream_t stream)
+{
+    SEMICRF_CHECK_ARG(tol_begin >= 0 && tol_begin <= SEMICRF_TOL_MAX && tol_end >= 0 && tol_end <= SEMICRF_TOL_MAX,
+                      "tolerance (%d, %d) outside [0, %d]", tol_begin, tol_end, SEMICRF_TOL_MAX);
+    if (tol_begin == 0 && tol_end == 0) return semicrf_interval_marginals(score, v, q, logZ, T, B, pairs, K, offsets, out, stream);
+    SEMICRF_CHECK_ARG(T >= 1 && B >= 1, "T=%d, B=%d must be >= 1", T, B);
+    SEMICRF_CHECK_ARG((long long)T * T * B < (1ll << 40), "T*T*B too large");
+    SEMICRF_CHECK_ARG(score && v && q && logZ && offsets, "score / v / q / logZ / offsets must be non-NULL");
+    SEMICRF_CHECK_ARG(K >= 0 && K < (1ll << 31) && (K == 0 || (pairs && out)), "bad interval count");
+    launch_interval_marginals_tol(score, v, q, logZ, T, B, pairs, (int)K, offsets, tol_begin, tol_end, out, (hipStream_t)stream);
+    SEMICRF_CHECK_LAUNCH("semicrf_interval_marginals_tol");
+    return SEMICRF_OK;
+}
+
+int semicrf_marginal_decode_tol(const float* score, const float* noise, const float* v, const float* q, const float* logZ, int T, int B,
+                                const float* tau, int tau_stride, int tol_begin, int tol_end, int32_t* pairs, float* probs, int64_t cap,
+                                int32_t* offsets, void* ws, size_t ws_bytes, semicrf_stream_t stream)
+{
+    SEMICRF_CHECK_ARG(tol_begin >= 0 && tol_begin <= SEMICRF_TOL_MAX && tol_end >= 0 && tol_end <= SEMICRF_TOL_MAX,
+                      "tolerance (%d, %d) outside [0, %d]", tol_begin, tol_end, SEMICRF_TOL_MAX);
+    if (tol_begin == 0 && tol_end == 0)
+        return semicrf_marginal_decode(score, noise, v, q, logZ, T, B, tau, tau_stride, pairs, probs, cap, offsets, ws, ws_bytes, stream);
+    if (int rc = check_common(score, noise, T, B)) return rc;
+    SEMICRF_CHECK_ARG(v && q && logZ && tau, "v (alpha), q (beta), logZ and tau must be non-NULL");
+    SEMICRF_CHECK_ARG(tau_stride == 0 || tau_stride == 1, "tau stride must be 0 (one value for all chains) or 1");
+    SEMICRF_CHECK_ARG(pairs && probs && offsets && cap >= 0, "pairs/probs/offsets must be non-NULL and cap >= 0");
+    SEMICRF_CHECK_ARG((long long)T * (T + 1) / 2 * B < (1ll << 31), "T (T+1) / 2 * B exceeds int32 offsets");
+    SEMICRF_CHECK_ARG((long long)((T + 63) / 64) * ((T + 63) / 64 + 1) / 2 < 65536, "T=%d too large for the marginal decode", T);
+    SEMICRF_CHECK_ARG(ws != nullptr, "workspace is NULL");
+    if (ws_bytes < marginal_decode_tol_workspace_bytes(T, B)) { set_error("workspace too small for marginal_decode_tol"); return SEMICRF_EWORKSPACE; }
+    launch_marginal_decode_tol(score, v, q, logZ, T, B, tau, tau_stride, tol_begin, tol_end, pairs, probs, (long long)cap, offsets, ws,
+                               (hipStream_t)stream);
+    SEMICRF_CHECK_LAUNCH("semicrf_marginal_decode_tol");
     return SEMICRF_OK;
 }
 

@@ -547,6 +547,99 @@ void marginal_decode(const float* score, const float* v, const float* q, const f
     offsets[B] = bad ? -1 : (int32_t)n;
 }
 
+// tolerance-aware interval marginals (include/semicrf_hip.h: semicrf_interval_marginals_tol), the definition evaluated literally:
+// rows e' ascending, inside a row b' ascending, one fp32 add per term.  b > e gives 0; the caller has checked the indices
+void interval_marginals_tol(const float* score, const float* v, const float* q, const float* logZ, int T, int B, const int32_t* pairs,
+                            const int32_t* offsets, int db, int de, float* out)
+{
+    const size_t Bs = (size_t)B;
+#pragma omp parallel for schedule(dynamic, 1)
+    for (int c = 0; c < B; ++c)
+        for (int32_t k = offsets[c]; k < offsets[c + 1]; ++k) {
+            const int b = pairs[2 * k], e = pairs[2 * k + 1];
+            if (b > e) { out[k] = 0.0f; continue; }
+            const int elo = std::max(0, e - de), ehi = std::min(T - 1, e + de), blo = std::max(0, b - db);
+            float acc = 0.0f;
+            for (int er = elo; er <= ehi; ++er) {
+                const int bhi = std::min(b + db, er);
+                if (bhi < blo) continue;
+                const size_t ec = (size_t)er * Bs + c;
+                float row = 0.0f;
+                for (int bc = blo; bc <= bhi; ++bc)
+                    row += bc == er ? cell_marginal_single(v[ec], q[ec], logZ[c], score[((size_t)er * T + er) * Bs + c])
+                                    : cell_marginal(v[(size_t)bc * Bs + c], score[((size_t)er * T + bc) * Bs + c], q[ec], logZ[c]);
+                acc += row;
+            }
+            out[k] = acc > 1.0f ? 1.0f : acc;
+        }
+}
+
+// tolerance-aware marginal-threshold decoding (include/semicrf_hip.h: semicrf_marginal_decode_tol; the device kernels are
+// marginal_tol.hip): marginal_decode with M in place of m.  Per chain block the triangle is walked row by row: the row's m, then its
+// row sums around every column (ascending b'; a cell outside the triangle is +0.0f, and x + 0.0f == x for x >= 0 and NaN) into a
+// ring of 2 de + 1 rows; M(e, .) is the sum of the ring in ascending row order once row e + de is in it.
+void marginal_decode_tol(const float* score, const float* v, const float* q, const float* logZ, int T, int B, const float* tau,
+                         int tau_stride, int db, int de, int32_t* pairs, float* probs, int64_t cap, int32_t* offsets)
+{
+    const size_t Bs = (size_t)B;
+    struct Hit { int32_t e; float m; };
+    std::vector<std::vector<Hit>> hits((size_t)T * Bs);            // [b][c]: the column's selected cells, e ascending
+    const int nblk = (B + CB - 1) / CB, R = 2 * de + 1;
+#pragma omp parallel for schedule(dynamic, 1)
+    for (int blk = 0; blk < nblk; ++blk) {
+        const int c0 = blk * CB;
+        const int nc = B - c0 < CB ? B - c0 : CB;
+        std::vector<float> mrow((size_t)T * CB), ring((size_t)R * T * CB, 0.0f);
+        for (int er = 0; er < T + de; ++er) {
+            float* rs = ring.data() + (size_t)(er % R) * T * CB;
+            if (er < T) {
+                const float* row = score + (size_t)er * T * Bs;
+                for (int b = 0; b <= er; ++b)
+                    for (int cc = 0; cc < nc; ++cc) {
+                        const int c = c0 + cc;
+                        const size_t ec = (size_t)er * Bs + c;
+                        mrow[(size_t)b * CB + cc] = b == er ? cell_marginal_single(v[ec], q[ec], logZ[c], row[(size_t)er * Bs + c])
+                                                            : cell_marginal(v[(size_t)b * Bs + c], row[(size_t)b * Bs + c], q[ec], logZ[c]);
+                    }
+                for (int b = 0; b < T; ++b) {
+                    const int blo = std::max(0, b - db), bhi = std::min(b + db, er);
+                    for (int cc = 0; cc < nc; ++cc) {
+                        float a = 0.0f;
+                        for (int bc = blo; bc <= bhi; ++bc) a += mrow[(size_t)bc * CB + cc];
+                        rs[(size_t)b * CB + cc] = a;
+                    }
+                }
+            } else {
+                std::fill(rs, rs + (size_t)T * CB, 0.0f);          // a row past the last frame
+            }
+            const int e = er - de;
+            if (e < 0) continue;
+            const int elo = std::max(0, e - de), ehi = std::min(T - 1, e + de);
+            for (int b = 0; b <= e; ++b)
+                for (int cc = 0; cc < nc; ++cc) {
+                    float a = 0.0f;
+                    for (int x = elo; x <= ehi; ++x) a += ring[((size_t)(x % R) * T + b) * CB + cc];
+                    const float M = a > 1.0f ? 1.0f : a;
+                    const int c = c0 + cc;
+                    if (M >= tau[(size_t)c * tau_stride]) hits[(size_t)b * Bs + c].push_back(Hit{(int32_t)e, M});
+                }
+        }
+    }
+    int64_t n = 0;
+    bool bad = false;
+    for (int c = 0; c < B; ++c) {
+        offsets[c] = (int32_t)n;
+        for (int b = 0; b < T; ++b)
+            for (const Hit& h : hits[(size_t)b * Bs + c]) {
+                if (n < cap) { pairs[2 * n] = b; pairs[2 * n + 1] = h.e; probs[n] = h.m; }
+                ++n;
+            }
+        const float vl = v[(size_t)(T - 1) * Bs + c];
+        bad = bad || vl != vl;
+    }
+    offsets[B] = bad ? -1 : (int32_t)n;
+}
+
 // MBR path decoding (include/semicrf_hip.h: semicrf_mbr_select; the device kernels are mbr_decode.hip): per chain the recursion
 // F[t] = max(F[t+1], max over the eligible (t, e), e > t, of g + F[e]) + gS(t) over the packed lattice, walked backwards, then the
 // trace from frame 0.  Ties: the skip, then the smallest e (the strict compare in ascending order).  Chains in parallel; packed in

@@ -19,6 +19,10 @@ void interval_marginals(const float* score, const float* v, const float* q, cons
                         const int32_t* offsets, float* out);
 void marginal_decode(const float* score, const float* v, const float* q, const float* logZ, int T, int B, const float* tau,
                      int tau_stride, int32_t* pairs, float* probs, int64_t cap, int32_t* offsets);
+void interval_marginals_tol(const float* score, const float* v, const float* q, const float* logZ, int T, int B, const int32_t* pairs,
+                            const int32_t* offsets, int tol_begin, int tol_end, float* out);
+void marginal_decode_tol(const float* score, const float* v, const float* q, const float* logZ, int T, int B, const float* tau,
+                         int tau_stride, int tol_begin, int tol_end, int32_t* pairs, float* probs, int64_t cap, int32_t* offsets);
 void mbr_select(const int32_t* pairs, const float* weight, const int32_t* offsets, int64_t K, int T, int B, const float* tau,
                 int tau_stride, int32_t* pairs_out, float* probs_out, int64_t cap, int32_t* offsets_out, float* gain /* [B] */);
 // state: (4 T B + 2 B) doubles, filled by expectation and read by covariance (v64, a, q64, binc [T][B] each, then E, logZ [B])

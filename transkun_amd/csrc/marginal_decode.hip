@@ -22,6 +22,7 @@
 //                        tile column = offsets[c] + prefix[b][c] + bandprefix[ti][b][c]; the rows of the mask in ascending order.
 // The order (begin, end) -- not (end, begin) -- is what makes the rank inside a tile column a running count of one lane.
 // No atomics: every word has one writer and every sum a fixed order; the result is a pure function of the inputs.
+// marginal_tol.hip (semicrf_marginal_decode_tol) reuses the scans and the workspace layout with a count and a write pass of its own.
 #include "common.h"
 #include "posterior_cell.h"
 
@@ -38,39 +39,7 @@ constexpr int MRB = 2;                      // rows whose loads are issued toget
 constexpr int MSEG = 64;                    // rowscan: segments of b per chain
 constexpr int MRC = 16;                     // rowscan: chains per workgroup
 
-typedef int i4 __attribute__((ext_vector_type(4)));
-typedef int i4u __attribute__((ext_vector_type(4), aligned(4)));
-typedef unsigned long long u64;
-
-// (f4, ld4, tile_of: posterior_cell.h)
-__device__ __forceinline__ i4 ldi4(const int* __restrict__ p, int n)
-{
-    if (n >= 4) return (i4)(*(const i4u*)p);
-    i4 r = {0, 0, 0, 0};
-    if (n > 0) r.x = p[0];
-    if (n > 1) r.y = p[1];
-    if (n > 2) r.z = p[2];
-    return r;
-}
-__device__ __forceinline__ void sti4(int* __restrict__ p, int n, i4 x)
-{
-    if (n >= 4) { *(i4u*)p = (i4u)x; return; }
-    if (n > 0) p[0] = x.x;
-    if (n > 1) p[1] = x.y;
-    if (n > 2) p[2] = x.z;
-}
-// the thresholds of chains c0 .. c0+3; a chain that does not exist gets +inf (m <= 1 never reaches it)
-__device__ __forceinline__ f4 ld_tau(const float* __restrict__ tau, int tau_stride, int c0, int n)
-{
-    const float inf = __builtin_huge_valf();
-    f4 r = {inf, inf, inf, inf};
-    if (n > 0) r.x = tau[(size_t)c0 * tau_stride];
-    if (n > 1) r.y = tau[(size_t)(c0 + 1) * tau_stride];
-    if (n > 2) r.z = tau[(size_t)(c0 + 2) * tau_stride];
-    if (n > 3) r.w = tau[(size_t)(c0 + 3) * tau_stride];
-    return r;
-}
-
+// (f4, ld4, tile_of, i4, u64, ldi4, sti4, ld_tau: posterior_cell.h)
 }  // namespace
 
 // grid (ceil(B/32), nI (nI+1)/2), block 256.  cnt [nI][T][B]: cnt[i][b] = selected cells of tile column (i, b);
@@ -297,6 +266,14 @@ size_t marginal_decode_workspace_bytes(int T, int B)
     return align_up(nI * T * Bs * 4) + align_up(nI * T * NQ * 8) + align_up((size_t)T * Bs * 4) + align_up(Bs * 4);
 }
 
+// the scans between a count pass and a write pass (also marginal_tol.hip's): cnt and coltot become exclusive prefixes, offsets is final
+void marginal_decode_scans(int* cnt, int* coltot, int* tot, const float* v, int T, int B, int* offsets, hipStream_t stream)
+{
+    mdec_colscan_kernel<<<(unsigned)(((size_t)T * B + 255) / 256), 256, 0, stream>>>(cnt, T, B, band_count(T), coltot);
+    mdec_rowscan_kernel<<<(B + MRC - 1) / MRC, MRC * MSEG, 0, stream>>>(coltot, T, B, tot);
+    mdec_offsets_kernel<<<1, 1024, 0, stream>>>(tot, v, T, B, offsets);
+}
+
 void launch_marginal_decode(const float* score, const float* v, const float* q, const float* logZ, int T, int B, const float* tau,
                             int tau_stride, int* pairs, float* probs, long long cap, int* offsets, void* ws, hipStream_t stream)
 {
@@ -311,9 +288,7 @@ void launch_marginal_decode(const float* score, const float* v, const float* q, 
     w += align_up((size_t)T * Bs * 4);
     int* tot = (int*)w;
     mdec_count_kernel<<<dim3((B + MCH - 1) / MCH, ntiles), 64 * MWAVES, 0, stream>>>(score, v, q, logZ, T, B, tau, tau_stride, NQ, cnt, mask);
-    mdec_colscan_kernel<<<(unsigned)(((size_t)T * Bs + 255) / 256), 256, 0, stream>>>(cnt, T, B, nI, coltot);
-    mdec_rowscan_kernel<<<(B + MRC - 1) / MRC, MRC * MSEG, 0, stream>>>(coltot, T, B, tot);
-    mdec_offsets_kernel<<<1, 1024, 0, stream>>>(tot, v, T, B, offsets);
+    marginal_decode_scans(cnt, coltot, tot, v, T, B, offsets, stream);
     mdec_write_kernel<<<dim3((MT * NQ + 255) / 256, ntiles), 256, 0, stream>>>(score, v, q, logZ, T, B, tau, tau_stride, NQ, cnt, coltot, mask,
                                                                              offsets, pairs, probs, cap);
 }

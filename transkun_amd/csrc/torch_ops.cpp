@@ -237,6 +237,38 @@ void marginal_decode(Tensor score, Tensor noise, Tensor v, Tensor q, Tensor logZ
                                   i32(offsets, d.B + 1, "offsets"), bytes(ws, "ws"), (size_t)ws.numel(), c.stream),
           "semicrf_marginal_decode");
 }
+// the tolerance-aware forms (semicrf_interval_marginals_tol / semicrf_marginal_decode_tol): tol_begin, tol_end in 0 .. SEMICRF_TOL_MAX
+inline void check_tol(int64_t tb, int64_t te)
+{
+    STD_TORCH_CHECK(tb >= 0 && tb <= SEMICRF_TOL_MAX && te >= 0 && te <= SEMICRF_TOL_MAX, "semicrf: tolerance (", tb, ", ", te,
+                    ") outside [0, ", SEMICRF_TOL_MAX, "]");
+}
+void interval_marginals_tol(Tensor score, Tensor v, Tensor q, Tensor logZ, Tensor pairs, int64_t K, Tensor offsets, int64_t tol_begin,
+                            int64_t tol_end, Tensor out)
+{
+    Ctx c(score); c.same(score, v, q, logZ, pairs, offsets, out);
+    const Dims d = marg_dims(score, v, q, logZ);
+    STD_TORCH_CHECK(K >= 0, "semicrf: negative interval count");
+    check_tol(tol_begin, tol_end);
+    check(semicrf_interval_marginals_tol(cfp(score), cfp(v), cfp(q), cfp(logZ), d.T, d.B, i32(pairs, 2 * K, "pairs"), K,
+                                         i32(offsets, d.B + 1, "offsets"), (int)tol_begin, (int)tol_end, f32w(out, K, "out"), c.stream),
+          "semicrf_interval_marginals_tol");
+}
+void marginal_decode_tol(Tensor score, Tensor noise, Tensor v, Tensor q, Tensor logZ, Tensor tau, int64_t tol_begin, int64_t tol_end,
+                         Tensor pairs, Tensor probs, Tensor offsets, Tensor ws)
+{
+    Ctx c(score); c.same(score, noise, v, q, logZ, tau, pairs, probs, offsets, ws);
+    const Dims d = crf_dims(score, noise);
+    const int64_t TB = (int64_t)d.T * d.B;
+    STD_TORCH_CHECK(pairs.dim() == 2 && pairs.size(1) == 2 && pairs.size(0) >= 1, "semicrf: pairs must be [cap, 2], cap >= 1");
+    check_tol(tol_begin, tol_end);
+    const int64_t cap = pairs.size(0);
+    check(semicrf_marginal_decode_tol(cfp(score), cfp(noise), f32(v, TB, "v"), f32(q, TB, "q"), f32(logZ, d.B, "logZ"), d.T, d.B,
+                                      cfp(tau), tau_stride_of(tau, d.B), (int)tol_begin, (int)tol_end, i32(pairs, 2 * cap, "pairs"),
+                                      f32w(probs, cap, "probs"), cap, i32(offsets, d.B + 1, "offsets"), bytes(ws, "ws"),
+                                      (size_t)ws.numel(), c.stream),
+          "semicrf_marginal_decode_tol");
+}
 // MBR path decoding (semicrf_mbr_select) over a lattice of marginal_decode: pairs [K, 2], weight [K], offsets [B + 1]; tau as above;
 // pairs_out [cap, 2], probs_out [cap], offsets_out [B + 1], gain [B]
 struct MbrDims { int64_t K, cap; int B; };
@@ -452,6 +484,43 @@ void marginal_decode_cpu(Tensor score, Tensor noise, Tensor v, Tensor q, Tensor 
     const int ts = tau_stride_of(tau, d.B);
     semicrf_cpu::marginal_decode(cfp(score), f32(v, TB, "v"), f32(q, TB, "q"), f32(logZ, d.B, "logZ"), d.T, d.B, cfp(tau), ts,
                                  i32(pairs, 2 * cap, "pairs"), f32w(probs, cap, "probs"), cap, i32(offsets, d.B + 1, "offsets"));
+}
+void interval_marginals_tol_cpu(Tensor score, Tensor v, Tensor q, Tensor logZ, Tensor pairs, int64_t K, Tensor offsets, int64_t tol_begin,
+                                int64_t tol_end, Tensor out)
+{
+    all_cpu(score, v, q, logZ, pairs, offsets, out);
+    const Dims d = marg_dims(score, v, q, logZ);
+    STD_TORCH_CHECK(K >= 0, "semicrf: negative interval count");
+    check_tol(tol_begin, tol_end);
+    const int32_t* pp = i32(pairs, 2 * K, "pairs");
+    const int32_t* oo = i32(offsets, d.B + 1, "offsets");
+    STD_TORCH_CHECK(oo[0] == 0 && oo[d.B] == K, "semicrf: offsets do not match the interval count");
+    for (int c = 0; c < d.B; ++c) STD_TORCH_CHECK(oo[c] <= oo[c + 1], "semicrf: offsets must ascend");
+    for (int64_t i = 0; i < 2 * K; ++i) STD_TORCH_CHECK(pp[i] >= 0 && pp[i] < d.T, "semicrf: interval out of range");
+    if (tol_begin == 0 && tol_end == 0)
+        semicrf_cpu::interval_marginals(cfp(score), cfp(v), cfp(q), cfp(logZ), d.T, d.B, pp, oo, f32w(out, K, "out"));
+    else
+        semicrf_cpu::interval_marginals_tol(cfp(score), cfp(v), cfp(q), cfp(logZ), d.T, d.B, pp, oo, (int)tol_begin, (int)tol_end,
+                                            f32w(out, K, "out"));
+}
+void marginal_decode_tol_cpu(Tensor score, Tensor noise, Tensor v, Tensor q, Tensor logZ, Tensor tau, int64_t tol_begin, int64_t tol_end,
+                             Tensor pairs, Tensor probs, Tensor offsets, Tensor ws)
+{
+    all_cpu(score, noise, v, q, logZ, tau, pairs, probs, offsets);
+    const Dims d = crf_dims(score, noise);
+    const int64_t TB = (int64_t)d.T * d.B;
+    STD_TORCH_CHECK((int64_t)d.T * (d.T + 1) / 2 * d.B < (1ll << 31), "semicrf: T (T+1) / 2 * B exceeds int32 offsets");
+    STD_TORCH_CHECK(pairs.dim() == 2 && pairs.size(1) == 2 && pairs.size(0) >= 1, "semicrf: pairs must be [cap, 2], cap >= 1");
+    check_tol(tol_begin, tol_end);
+    const int64_t cap = pairs.size(0);
+    const int ts = tau_stride_of(tau, d.B);
+    if (tol_begin == 0 && tol_end == 0)
+        semicrf_cpu::marginal_decode(cfp(score), f32(v, TB, "v"), f32(q, TB, "q"), f32(logZ, d.B, "logZ"), d.T, d.B, cfp(tau), ts,
+                                     i32(pairs, 2 * cap, "pairs"), f32w(probs, cap, "probs"), cap, i32(offsets, d.B + 1, "offsets"));
+    else
+        semicrf_cpu::marginal_decode_tol(cfp(score), f32(v, TB, "v"), f32(q, TB, "q"), f32(logZ, d.B, "logZ"), d.T, d.B, cfp(tau), ts,
+                                         (int)tol_begin, (int)tol_end, i32(pairs, 2 * cap, "pairs"), f32w(probs, cap, "probs"), cap,
+                                         i32(offsets, d.B + 1, "offsets"));
 }
 void mbr_select_cpu(Tensor pairs, Tensor weight, Tensor offsets, int64_t T, Tensor tau, Tensor pairs_out, Tensor probs_out,
                     Tensor offsets_out, Tensor gain, Tensor ws)
@@ -724,6 +793,10 @@ STABLE_TORCH_LIBRARY(semicrf, m)
     m.def("interval_marginals(Tensor score, Tensor v, Tensor q, Tensor logZ, Tensor pairs, int K, Tensor offsets, Tensor(a!) out) -> ()");
     m.def("marginal_decode(Tensor score, Tensor noise, Tensor v, Tensor q, Tensor logZ, Tensor tau, Tensor(a!) pairs, Tensor(b!) probs, "
           "Tensor(c!) offsets, Tensor(d!) ws) -> ()");
+    m.def("interval_marginals_tol(Tensor score, Tensor v, Tensor q, Tensor logZ, Tensor pairs, int K, Tensor offsets, int tol_begin, "
+          "int tol_end, Tensor(a!) out) -> ()");
+    m.def("marginal_decode_tol(Tensor score, Tensor noise, Tensor v, Tensor q, Tensor logZ, Tensor tau, int tol_begin, int tol_end, "
+          "Tensor(a!) pairs, Tensor(b!) probs, Tensor(c!) offsets, Tensor(d!) ws) -> ()");
     m.def("mbr_select(Tensor pairs, Tensor weight, Tensor offsets, int T, Tensor tau, Tensor(a!) pairs_out, Tensor(b!) probs_out, "
           "Tensor(c!) offsets_out, Tensor(d!) gain, Tensor(e!) ws) -> ()");
     m.def("eval_path(Tensor score, Tensor noise, Tensor pairs, int K, Tensor offsets, Tensor(a!) out, Tensor(b!) ws) -> ()");
@@ -778,6 +851,8 @@ STABLE_TORCH_LIBRARY_IMPL(semicrf, CPU, m)
     m.impl("expectation", TORCH_BOX(&expectation_cpu));
     m.impl("covariance", TORCH_BOX(&covariance_cpu));
     m.impl("marginal_decode", TORCH_BOX(&marginal_decode_cpu));
+    m.impl("interval_marginals_tol", TORCH_BOX(&interval_marginals_tol_cpu));
+    m.impl("marginal_decode_tol", TORCH_BOX(&marginal_decode_tol_cpu));
     m.impl("mbr_select", TORCH_BOX(&mbr_select_cpu));
     m.impl("eval_path", TORCH_BOX(&eval_path_cpu));
     m.impl("eval_path_bwd", TORCH_BOX(&eval_path_bwd_cpu));
@@ -798,6 +873,8 @@ STABLE_TORCH_LIBRARY_IMPL(semicrf, CUDA, m)
     m.impl("expectation", TORCH_BOX(&expectation));
     m.impl("covariance", TORCH_BOX(&covariance));
     m.impl("marginal_decode", TORCH_BOX(&marginal_decode));
+    m.impl("interval_marginals_tol", TORCH_BOX(&interval_marginals_tol));
+    m.impl("marginal_decode_tol", TORCH_BOX(&marginal_decode_tol));
     m.impl("mbr_select", TORCH_BOX(&mbr_select));
     m.impl("eval_path", TORCH_BOX(&eval_path));
     m.impl("eval_path_bwd", TORCH_BOX(&eval_path_bwd));
