@@ -373,6 +373,39 @@ int semicrf_covariance(const float* score, const float* noise, const float* weig
                        int B, float* C, float* Cn, const void* ws, size_t ws_bytes, semicrf_stream_t stream);
 
 /*
+ * Decoded paths against target paths: the counts behind note-level and frame-level precision / recall, per chain.
+ * Replaces: the host loops of TransKun.computeStats (ModelTransformer.py:403-438) -- decode() to Python lists, then compareBracket
+ * (Evaluation.py:10-18) and compareFramewise (:67-74) chain by chain -- on the packed lists where semicrf_viterbi left them.  Adds
+ * nothing to the ABI's existing entry points (version 2).
+ *   est_pairs / est_offsets, ref_pairs / ref_offsets: two packed lists in the format of semicrf_viterbi and semicrf_eval_path
+ *   (pairs int32 [K][2] (begin, end), chain-major; offsets int32 [B+1], offsets[B] = the total).  A pairs buffer holds at least
+ *   offsets[B] entries (the caller's promise: the call has no capacity argument) and is 8-byte aligned -- every pair is one 8-byte
+ *   load; it may be NULL when its total is 0.  The two lists may be the same buffers.
+ *   stats int32 [B][7], per chain c:
+ *     [0] nRef, [1] nEst   the list lengths
+ *     [2] nExact           the number of pairs present in both lists (with multiplicity, should a list repeat a pair); on lists
+ *                          without repeats -- every decoded path -- compareBracket's nCorrect
+ *     [3] nRefFrames, [4] nEstFrames, [5] nBothFrames
+ *                          what compareFramewise(est, ref) returns with countZero = True, bit for bit.  A list's frame count is the
+ *                          recurrence s += end - begin + (prevEnd < begin), prevEnd = end (prevEnd = -1 at the start): an interval
+ *                          that touches its predecessor shares that frame with it.  nBothFrames is the same recurrence over the
+ *                          non-empty closed intersections [max(b, b*), min(e, e*)] of a merge walk over the two lists that advances
+ *                          the list whose current interval ends first, the reference list on a tie.
+ *     [6] nMatchTol        the size of a maximum matching between the two lists where (b, e) and (b*, e*) can be matched iff
+ *                          |b - b*| <= tol_begin and |e - e*| <= tol_end; with (0, 0) it is nExact.
+ *   tol_begin, tol_end: 0 .. SEMICRF_TOL_MAX frames; anything else returns SEMICRF_EINVAL.
+ * Preconditions are checked on the DEVICE (the lists come from other kernels): every index lies in [0, T), begin <= end, and begin
+ * and end are each non-decreasing along a chain's list (singletons and touching intervals included), offsets are non-decreasing
+ * within [0, offsets[B]].  A chain that violates one gets all seven entries -1; nothing outside [0, offsets[B]) is read.  When
+ * est_offsets[B] or ref_offsets[B] is negative (the NaN / time-out marker of semicrf_viterbi and semicrf_marginal_decode) every
+ * entry of every chain is -1: a decode and the comparison chain without a host look in between, as semicrf_mbr_select does.
+ * All counts are int32: a chain's lists hold fewer than 2^31 / T entries (a path has at most 2 T - 1).
+ * No workspace, no atomics, no host synchronisation; one thread per chain.
+ */
+int semicrf_compare_paths(const int32_t* est_pairs, const int32_t* est_offsets, const int32_t* ref_pairs, const int32_t* ref_offsets,
+                          int T, int B, int tol_begin, int tol_end, int32_t* stats /* [B][7] */, semicrf_stream_t stream);
+
+/*
  * Unnormalised path score.  Replaces: evalPath (:508-550).
  *   pairs int32 [K][2] (begin,end), offsets int32 [B+1] (chain c owns pairs[offsets[c]:offsets[c+1]]).
  *   out[c] = sum_path ( s[end,begin,c] - (cum[end]-cum[begin]) ) + cum[T-1],  cum = prefix sums of noise.

@@ -23,6 +23,8 @@ EXTENSIONS of the reference's surface: decode_packed, sample / sample_packed (ex
   covariance (posterior expectations of additive path functionals, the differentiable entropy, Hessian products of logZ).
   interval_marginals, decode_marginal and decode_mbr (and their _packed forms) take tolerance=(onset, offset) in frames: the
   probability that the path holds an interval within that window of the given one, the currency of note-level metrics.
+  compare_paths / compare_paths_packed / decode_stats count in that currency: per chain the matches (exact and within a tolerance)
+  and the frame overlaps between a decoded path and a target, on the device, without Python lists.
 """
 from __future__ import annotations
 
@@ -631,20 +633,24 @@ def _viterbi_raw(score_c, noise_c, start, forward: bool):
     return pairs, offsets
 
 
+def _start_tensor(forcedStartPos: Optional[Sequence[int]], T: int, B: int, device):
+    """forcedStartPos (None or B frames) as the int32 device vector semicrf_viterbi takes; IndexError when out of range."""
+    if forcedStartPos is None:
+        return None
+    assert len(forcedStartPos) == B
+    st = np.asarray(forcedStartPos, dtype=np.int64)
+    if (st < 0).any() or (st > T - 1).any():
+        raise IndexError(f"forcedStartPos out of range for T={T}")
+    return torch.from_numpy(st.astype(np.int32)).to(device, non_blocking=True)
+
+
 def _decode(score, noiseScore, forcedStartPos: Optional[Sequence[int]], forward: bool, packed: bool = False):
     assert len(score.shape) == 3
     assert score.shape[0] == score.shape[1]
     T, B = _check_inputs(score, noiseScore)
     with torch.no_grad():
         score_c, noise_c = _prep(score.detach()), _prep(noiseScore.detach())
-        dev = score_c.device
-        start = None
-        if forcedStartPos is not None:
-            assert len(forcedStartPos) == B
-            st = np.asarray(forcedStartPos, dtype=np.int64)
-            if (st < 0).any() or (st > T - 1).any():
-                raise IndexError(f"forcedStartPos out of range for T={T}")
-            start = torch.from_numpy(st.astype(np.int32)).to(dev, non_blocking=True)
+        start = _start_tensor(forcedStartPos, T, B, score_c.device)
         pairs, offsets = _viterbi_raw(score_c, noise_c, start, forward)
         off_h = offsets.cpu()                      # the one host sync of decode
         total = int(off_h[-1])
@@ -1294,6 +1300,110 @@ def decode_mbr(score, noiseScore, threshold, tolerance=None):
     return paths, [pl[off[c]:off[c + 1]] for c in range(B)], gain
 
 
+# --------------------------------------------------------------------------------------
+# path comparison: decoded paths against target paths (the counts of the reference's computeStats)
+# --------------------------------------------------------------------------------------
+
+# column indices of the [nBatch, 7] tensor the comparison returns: stats[:, PathStats.nExact]
+PathStats = namedtuple("PathStats", "nRef nEst nExact nRefFrames nEstFrames nBothFrames nMatchTol")(*range(7))
+
+
+def _compare_paths_raw(est_pairs, est_offsets, ref_pairs, ref_offsets, T: int, tol: Tuple[int, int]):
+    """Enqueue semicrf_compare_paths on packed int32 tensors of one device; no host sync.  Returns stats int32 [B, 7]."""
+    B = est_offsets.shape[0] - 1
+    stats = torch.empty(B, 7, dtype=torch.int32, device=est_offsets.device)
+    _lib.ops().compare_paths(est_pairs, est_offsets, ref_pairs, ref_offsets, int(T), tol[0], tol[1], stats)
+    return stats
+
+
+def _packed_list(pairs, offsets, side: str):
+    """One packed list of compare_paths_packed as it is: int32, contiguous, pairs [K, 2] 8-byte aligned -- nothing is converted or
+    copied (a conversion would hide a wrong buffer, and a copy of a device tensor is a launch)."""
+    p = torch.from_numpy(pairs) if isinstance(pairs, np.ndarray) else pairs
+    o = torch.from_numpy(offsets) if isinstance(offsets, np.ndarray) else offsets
+    for t, name in ((p, f"{side}_pairs"), (o, f"{side}_offsets")):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"compare_paths: {name} must be a tensor or a numpy array, got {type(t).__name__}")
+        if t.dtype != torch.int32:
+            raise TypeError(f"compare_paths: {name} must be int32, got {t.dtype}")
+        if not t.is_contiguous():
+            raise ValueError(f"compare_paths: {name} must be contiguous")
+        _lib.require_device(t, name)
+    if p.dim() != 2 or p.shape[1] != 2:
+        raise ValueError(f"compare_paths: {side}_pairs must be [K, 2], got {tuple(p.shape)}")
+    if o.dim() != 1 or o.numel() < 2:
+        raise ValueError(f"compare_paths: {side}_offsets must be [nBatch + 1], got {tuple(o.shape)}")
+    if p.numel() and p.data_ptr() % 8:
+        raise ValueError(f"compare_paths: {side}_pairs must be 8-byte aligned (every pair is one 8-byte load)")
+    if p.device != o.device:
+        raise ValueError(f"compare_paths: {side}_pairs and {side}_offsets are on different devices")
+    if p.is_cuda:
+        # the total lives on the device and the kernel reads pairs[: total]: a total beyond the buffer becomes the invalid marker
+        o = torch.where(o[-1:] > p.shape[0], torch.full_like(o, -1), o)
+    return p, o
+
+
+def compare_paths_packed(est_pairs, est_offsets, ref_pairs, ref_offsets, T: int, tolerance=None) -> torch.Tensor:
+    """An EXTENSION of the reference's surface: per chain the counts that note-level and frame-level precision / recall are made
+    of, an int32 tensor [nBatch, 7] on the inputs' device with the columns of PathStats:
+
+      nRef, nEst                            the lengths of the two lists
+      nExact                                pairs present in both -- compareBracket's nCorrect (Evaluation.py:10-18)
+      nRefFrames, nEstFrames, nBothFrames   compareFramewise(est, ref) (Evaluation.py:67-74), bit for bit
+      nMatchTol                             the largest number of estimate / reference pairs that can be matched one to one with
+                                            onsets within tolerance[0] and offsets within tolerance[1] frames; nExact at (0, 0)
+
+    est_* and ref_* are packed lists as decode_packed returns them (pairs int32 [K, 2], offsets int32 [nBatch + 1]; tensors or
+    numpy arrays, all on one device, contiguous, pairs 8-byte aligned: TypeError / ValueError otherwise, before anything is
+    launched).  T: the number of frames.  tolerance: None, an int or a pair (onset, offset) of ints in 0..8, as decode_mbr takes it.
+
+    The lists are checked where they live: a chain with an index outside [0, T), begin > end or a begin or end that decreases
+    along the list has all seven entries -1; a negative offsets[-1] (the marker a decode leaves when it gave up) makes every
+    entry -1.  Never synchronises: on the GPU one kernel (semicrf_compare_paths), on the CPU the host kernel of the same contract."""
+    tol = _tolerance(tolerance, "compare_paths")
+    T = int(T)
+    if T < 1:
+        raise ValueError(f"compare_paths: T must be >= 1, got {T}")
+    with torch.no_grad():
+        ep, eo = _packed_list(est_pairs, est_offsets, "est")
+        rp, ro = _packed_list(ref_pairs, ref_offsets, "ref")
+        if eo.shape != ro.shape:
+            raise ValueError(f"compare_paths: the two lists hold {eo.numel() - 1} and {ro.numel() - 1} chains")
+        if ep.device != rp.device:
+            raise ValueError("compare_paths: the two lists are on different devices")
+        return _compare_paths_raw(ep, eo, rp, ro, T, tol)
+
+
+def compare_paths(est: Intervals, ref: Intervals, T: int, tolerance=None) -> torch.Tensor:
+    """compare_paths_packed on Python lists (what decode returns and what logProb takes): packs both with
+    pack_intervals(..., ordered=True) -- IndexError / ValueError for an index outside [0, T) or begin > end -- and returns the
+    int32 [nBatch, 7] tensor on the CPU, where the lists are (the host kernel)."""
+    tol = _tolerance(tolerance, "compare_paths")
+    assert len(est) == len(ref), f"{len(est)} estimated lists against {len(ref)} reference lists"
+    B = len(est)
+    ep, eo = pack_intervals(est, int(T), B, "cpu", ordered=True)
+    rp, ro = pack_intervals(ref, int(T), B, "cpu", ordered=True)
+    with torch.no_grad():
+        return _compare_paths_raw(ep, eo, rp, ro, int(T), tol)
+
+
+def decode_stats(score, noiseScore, intervals: Intervals, forcedStartPos=None, forward: bool = False, tolerance=None) -> torch.Tensor:
+    """An EXTENSION of the reference's surface: decode(forcedStartPos, forward) compared with the target `intervals`, as
+    compare_paths_packed's int32 [nBatch, 7] tensor where the scores live (columns: PathStats) -- what the reference's
+    computeStats gets from decode() + compareBracket + compareFramewise (ModelTransformer.py:403-438), without the Python lists:
+    the decoded path stays packed on the device and the comparison kernel reads it there.  Nothing waits for the device: a decode
+    that gave up on a bounded wait shows as -1 in every entry.  tolerance: as compare_paths_packed.  No gradient."""
+    T, B = _check_inputs(score, noiseScore)
+    tol = _tolerance(tolerance, "decode_stats")
+    with torch.no_grad():
+        score_c, noise_c = _prep(score.detach()), _prep(noiseScore.detach())
+        dev = score_c.device
+        ref_pairs, ref_offsets = pack_intervals(intervals, T, B, dev, ordered=True)
+        start = _start_tensor(forcedStartPos, T, B, dev)
+        pairs, offsets = _viterbi_raw(score_c, noise_c, start, bool(forward))
+        return _compare_paths_raw(pairs, offsets, ref_pairs, ref_offsets, T, tol)
+
+
 def viterbiBackward(score, noiseScore, forcedStartPos: Optional[List[int]] = None) -> Intervals:
     """Right-to-left Viterbi, the default decode (reference :13-104)."""
     return _decode(score, noiseScore, forcedStartPos, forward=False)
@@ -1366,6 +1476,13 @@ class NeuralSemiCRFInterval:
         ~25 ns of CPython object creation per interval on top of it (657 k intervals at T=2048, nBatch=352: 17 ms against 1 ms
         here); callers that go on with arrays anyway should take this one."""
         return _decode(self.score, self.noiseScore, forcedStartPos, bool(forward), packed=True)
+
+    def decode_stats(self, intervals, forcedStartPos=None, forward=False, tolerance=None):
+        """An EXTENSION of the reference's surface: decode_packed(forcedStartPos, forward) followed by the comparison with the
+        target `intervals` on the same device: an int32 tensor [nBatch, 7] with the columns of PathStats (list lengths, exact
+        matches, the three frame counts of the reference's compareFramewise, matches within `tolerance`) -- see the module-level
+        decode_stats and compare_paths_packed.  Builds no Python lists and never waits for the device; no gradient."""
+        return decode_stats(self.score, self.noiseScore, intervals, forcedStartPos, bool(forward), tolerance)
 
     def sample(self, nSample=1, forcedEndPos=None, generator=None):
         """An EXTENSION of the reference's surface: a list of `nSample` Intervals drawn exactly from p(path) =

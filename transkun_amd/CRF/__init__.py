@@ -7,4 +7,5 @@ from .NeuralSemiCRFInterval import (NeuralSemiCRFInterval, viterbi, viterbiBackw
                                     interval_marginals, interval_marginals_packed,
                                     decode_marginal, decode_marginal_packed,
                                     decode_mbr, decode_mbr_packed,
-                                    expectation, entropy, covariance)
+                                    expectation, entropy, covariance,
+                                    PathStats, compare_paths, compare_paths_packed, decode_stats)

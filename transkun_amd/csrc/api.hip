@@ -114,6 +114,8 @@ void launch_interval_marginals_tol(const float* score, const float* v, const flo
 void launch_marginal_decode_tol(const float* score, const float* v, const float* q, const float* logZ, int T, int B, const float* tau,
                                 int tau_stride, int db, int de, int* pairs, float* probs, long long cap, int* offsets, void* ws,
                                 hipStream_t stream);
+void launch_compare_paths(const int* est_pairs, const int* est_offsets, const int* ref_pairs, const int* ref_offsets, int T, int B,
+                          int tb, int te, int* stats, hipStream_t stream);
 size_t mbr_select_workspace_bytes(int T, int B);
 void launch_mbr_select(const int* pairs, const float* weight, const int* offsets, long long K, int T, int B, const float* tau,
                        int tau_stride, int* pairs_out, float* probs_out, long long cap, int* offsets_out, float* gain, void* ws,
@@ -676,6 +678,21 @@ int semicrf_mbr_select(const int32_t* pairs, const float* weight, const int32_t*
     launch_mbr_select(pairs, weight, offsets, (long long)K, T, B, tau, tau_stride, pairs_out, probs_out, (long long)cap, offsets_out, gain,
                       ws, (hipStream_t)stream);
     SEMICRF_CHECK_LAUNCH("semicrf_mbr_select");
+    return SEMICRF_OK;
+}
+
+int semicrf_compare_paths(const int32_t* est_pairs, const int32_t* est_offsets, const int32_t* ref_pairs, const int32_t* ref_offsets,
+                          int T, int B, int tol_begin, int tol_end, int32_t* stats, semicrf_stream_t stream)
+{
+    SEMICRF_CHECK_ARG(T >= 1 && B >= 1, "T=%d, B=%d must be >= 1", T, B);
+    SEMICRF_CHECK_ARG(T < (1 << 29) && (long long)7 * B < (1ll << 31), "T or B too large");
+    SEMICRF_CHECK_ARG(tol_begin >= 0 && tol_begin <= SEMICRF_TOL_MAX && tol_end >= 0 && tol_end <= SEMICRF_TOL_MAX,
+                      "tolerance (%d, %d) outside 0..%d", tol_begin, tol_end, SEMICRF_TOL_MAX);
+    SEMICRF_CHECK_ARG(est_offsets && ref_offsets && stats, "est_offsets/ref_offsets/stats must be non-NULL");
+    SEMICRF_CHECK_ARG((((uintptr_t)est_pairs | (uintptr_t)ref_pairs) & 7) == 0, "pairs must be 8-byte aligned");
+    SEMICRF_CHECK_ARG((((uintptr_t)est_offsets | (uintptr_t)ref_offsets | (uintptr_t)stats) & 3) == 0, "offsets/stats must be 4-byte aligned");
+    launch_compare_paths(est_pairs, est_offsets, ref_pairs, ref_offsets, T, B, tol_begin, tol_end, stats, (hipStream_t)stream);
+    SEMICRF_CHECK_LAUNCH("semicrf_compare_paths");
     return SEMICRF_OK;
 }
 

@@ -11,6 +11,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <cstdlib>
 #include <cstring>
 #include <vector>
 
@@ -702,6 +703,87 @@ void mbr_select(const int32_t* pairs, const float* weight, const int32_t* offset
         }
     }
     offsets_out[B] = (int32_t)n;
+}
+
+// Path comparison (include/semicrf_hip.h: semicrf_compare_paths; the device kernel is pathstats.hip): per chain the list lengths,
+// the exact matches, the three frame counts of the reference's compareFramewise and the maximum matching under a tolerance.  The
+// walks are written one after the other here (the device kernel runs them in one loop); the tolerant walk at (0, 0) is the exact one.
+namespace {
+struct PairList {
+    const int32_t* p;
+    int64_t lo, hi;
+    int64_t size() const { return hi - lo; }
+    int32_t b(int64_t i) const { return p[2 * (lo + i)]; }
+    int32_t e(int64_t i) const { return p[2 * (lo + i) + 1]; }
+};
+bool list_valid(const PairList& l, int T)
+{
+    int32_t pb = 0, pe = -1;
+    for (int64_t i = 0; i < l.size(); ++i) {
+        if (l.b(i) < pb || l.b(i) > l.e(i) || l.e(i) >= T || l.e(i) < pe) return false;
+        pb = l.b(i); pe = l.e(i);
+    }
+    return true;
+}
+// s += end - begin, + 1 unless the piece starts at or before the previous piece's end
+struct FrameSum {
+    uint32_t s = 0;
+    int32_t prev_end = -1;
+    void add(int32_t l, int32_t r) { s += (uint32_t)(r - l) + (prev_end < l ? 1u : 0u); prev_end = r; }
+};
+int32_t list_frames(const PairList& l)
+{
+    FrameSum f;
+    for (int64_t i = 0; i < l.size(); ++i) f.add(l.b(i), l.e(i));
+    return (int32_t)f.s;
+}
+int32_t both_frames(const PairList& est, const PairList& ref)
+{
+    FrameSum f;                                     // (a piece that the reference merges into its predecessor is one without the + 1)
+    int64_t i = 0, j = 0;
+    while (i < est.size() && j < ref.size()) {
+        const int32_t l = std::max(est.b(i), ref.b(j)), r = std::min(est.e(i), ref.e(j));
+        if (r >= l) f.add(l, r);
+        if (est.e(i) < ref.e(j)) ++i; else ++j;
+    }
+    return (int32_t)f.s;
+}
+int32_t match_count(const PairList& est, const PairList& ref, int tb, int te)
+{
+    int32_t n = 0;
+    int64_t i = 0, j = 0;
+    while (i < est.size() && j < ref.size()) {
+        const int32_t b = est.b(i), e = est.e(i), rb = ref.b(j), re = ref.e(j);
+        if (std::abs(b - rb) <= tb && std::abs(e - re) <= te) { ++n; ++i; ++j; }
+        else if (rb > b + tb || re > e + te) ++i;   // the reference's head is too late for this estimate: so is all that follows it
+        else ++j;                                   // it is too early for this estimate and for every later one
+    }
+    return n;
+}
+}  // namespace
+
+void compare_paths(const int32_t* est_pairs, const int32_t* est_offsets, const int32_t* ref_pairs, const int32_t* ref_offsets, int T,
+                   int B, int tol_begin, int tol_end, int32_t* stats)
+{
+    const int64_t etot = est_offsets[B], rtot = ref_offsets[B];
+#pragma omp parallel for schedule(dynamic, 8)
+    for (int c = 0; c < B; ++c) {
+        int32_t* out = stats + (size_t)7 * c;
+        const PairList est{est_pairs, est_offsets[c], est_offsets[c + 1]}, ref{ref_pairs, ref_offsets[c], ref_offsets[c + 1]};
+        const bool ok = etot >= 0 && rtot >= 0 && est.lo >= 0 && est.lo <= est.hi && est.hi <= etot && ref.lo >= 0 && ref.lo <= ref.hi &&
+                        ref.hi <= rtot && list_valid(est, T) && list_valid(ref, T);
+        if (!ok) {
+            for (int k = 0; k < 7; ++k) out[k] = -1;
+            continue;
+        }
+        out[0] = (int32_t)ref.size();
+        out[1] = (int32_t)est.size();
+        out[2] = match_count(est, ref, 0, 0);
+        out[3] = list_frames(ref);
+        out[4] = list_frames(est);
+        out[5] = both_frames(est, ref);
+        out[6] = tol_begin == 0 && tol_end == 0 ? out[2] : match_count(est, ref, tol_begin, tol_end);
+    }
 }
 
 // k-best Viterbi (include/semicrf_hip.h: semicrf_viterbi_nbest; the device kernel is nbest.hip).  Per frame and chain a sorted

@@ -25,6 +25,8 @@ void marginal_decode_tol(const float* score, const float* v, const float* q, con
                          int tau_stride, int tol_begin, int tol_end, int32_t* pairs, float* probs, int64_t cap, int32_t* offsets);
 void mbr_select(const int32_t* pairs, const float* weight, const int32_t* offsets, int64_t K, int T, int B, const float* tau,
                 int tau_stride, int32_t* pairs_out, float* probs_out, int64_t cap, int32_t* offsets_out, float* gain /* [B] */);
+void compare_paths(const int32_t* est_pairs, const int32_t* est_offsets, const int32_t* ref_pairs, const int32_t* ref_offsets, int T,
+                   int B, int tol_begin, int tol_end, int32_t* stats /* [B][7] */);
 // state: (4 T B + 2 B) doubles, filled by expectation and read by covariance (v64, a, q64, binc [T][B] each, then E, logZ [B])
 void expectation(const float* score, const float* noise, const float* weight /* or null: score */, const float* nweight /* or null: 0 */,
                  int T, int B, float* E, float* H, double* state);

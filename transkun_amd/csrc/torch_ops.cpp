@@ -297,6 +297,34 @@ void mbr_select(Tensor pairs, Tensor weight, Tensor offsets, int64_t T, Tensor t
                              fp(probs_out), d.cap, ip(offsets_out), fp(gain), bytes(ws, "ws"), (size_t)ws.numel(), c.stream),
           "semicrf_mbr_select");
 }
+// path comparison (semicrf_compare_paths): two packed lists, pairs [K, 2] / offsets [B + 1] each; stats [B, 7].  The pairs buffers
+// must hold offsets[B] entries -- the total lives on the device, so the caller vouches for it (the Python mirror does)
+inline int cmp_dims(const Tensor& est_pairs, const Tensor& est_offsets, const Tensor& ref_pairs, const Tensor& ref_offsets, int64_t T,
+                    int64_t tol_begin, int64_t tol_end, const Tensor& stats)
+{
+    STD_TORCH_CHECK(est_pairs.dim() == 2 && est_pairs.size(1) == 2 && ref_pairs.dim() == 2 && ref_pairs.size(1) == 2,
+                    "semicrf: pairs must be [K, 2]");
+    const int64_t B = est_offsets.numel() - 1;
+    STD_TORCH_CHECK(T >= 1 && B >= 1 && T < (1 << 29) && 7 * B < (1ll << 31), "semicrf: bad T / offsets size");
+    STD_TORCH_CHECK(ref_offsets.numel() == B + 1, "semicrf: est_offsets and ref_offsets must have the same length");
+    want(est_pairs, ScalarType::Int, 0, "est_pairs");
+    want(ref_pairs, ScalarType::Int, 0, "ref_pairs");
+    want(est_offsets, ScalarType::Int, B + 1, "est_offsets");
+    want(ref_offsets, ScalarType::Int, B + 1, "ref_offsets");
+    want(stats, ScalarType::Int, 7 * B, "stats");
+    check_tol(tol_begin, tol_end);
+    STD_TORCH_CHECK((((uintptr_t)ip(est_pairs) | (uintptr_t)ip(ref_pairs)) & 7) == 0, "semicrf: pairs must be 8-byte aligned");
+    return (int)B;
+}
+void compare_paths(Tensor est_pairs, Tensor est_offsets, Tensor ref_pairs, Tensor ref_offsets, int64_t T, int64_t tol_begin,
+                   int64_t tol_end, Tensor stats)
+{
+    Ctx c(est_offsets); c.same(est_offsets, est_pairs, ref_pairs, ref_offsets, stats);
+    const int B = cmp_dims(est_pairs, est_offsets, ref_pairs, ref_offsets, T, tol_begin, tol_end, stats);
+    check(semicrf_compare_paths(ip(est_pairs), ip(est_offsets), ip(ref_pairs), ip(ref_offsets), (int)T, B, (int)tol_begin, (int)tol_end,
+                                ip(stats), c.stream),
+          "semicrf_compare_paths");
+}
 void eval_path(Tensor score, Tensor noise, Tensor pairs, int64_t K, Tensor offsets, Tensor out, Tensor ws)
 {
     Ctx c(score); c.same(score, noise, pairs, offsets, out);
@@ -530,6 +558,16 @@ void mbr_select_cpu(Tensor pairs, Tensor weight, Tensor offsets, int64_t T, Tens
     const int ts = tau_stride_of(tau, d.B);
     semicrf_cpu::mbr_select(ip(pairs), cfp(weight), ip(offsets), d.K, (int)T, d.B, cfp(tau), ts, ip(pairs_out), fp(probs_out), d.cap,
                             ip(offsets_out), fp(gain));
+}
+void compare_paths_cpu(Tensor est_pairs, Tensor est_offsets, Tensor ref_pairs, Tensor ref_offsets, int64_t T, int64_t tol_begin,
+                       int64_t tol_end, Tensor stats)
+{
+    all_cpu(est_pairs, est_offsets, ref_pairs, ref_offsets, stats);
+    const int B = cmp_dims(est_pairs, est_offsets, ref_pairs, ref_offsets, T, tol_begin, tol_end, stats);
+    // on the host the totals can be looked at: the promise the device entry point takes from its caller is checked here
+    const int32_t *eo = ip(est_offsets), *ro = ip(ref_offsets);
+    STD_TORCH_CHECK(eo[B] <= est_pairs.size(0) && ro[B] <= ref_pairs.size(0), "semicrf: offsets[B] exceeds the pairs buffer");
+    semicrf_cpu::compare_paths(ip(est_pairs), eo, ip(ref_pairs), ro, (int)T, B, (int)tol_begin, (int)tol_end, ip(stats));
 }
 void eval_path_cpu(Tensor score, Tensor noise, Tensor pairs, int64_t K, Tensor offsets, Tensor out, Tensor ws)
 {
@@ -799,6 +837,8 @@ STABLE_TORCH_LIBRARY(semicrf, m)
           "Tensor(a!) pairs, Tensor(b!) probs, Tensor(c!) offsets, Tensor(d!) ws) -> ()");
     m.def("mbr_select(Tensor pairs, Tensor weight, Tensor offsets, int T, Tensor tau, Tensor(a!) pairs_out, Tensor(b!) probs_out, "
           "Tensor(c!) offsets_out, Tensor(d!) gain, Tensor(e!) ws) -> ()");
+    m.def("compare_paths(Tensor est_pairs, Tensor est_offsets, Tensor ref_pairs, Tensor ref_offsets, int T, int tol_begin, int tol_end, "
+          "Tensor(a!) stats) -> ()");
     m.def("eval_path(Tensor score, Tensor noise, Tensor pairs, int K, Tensor offsets, Tensor(a!) out, Tensor(b!) ws) -> ()");
     m.def("eval_path_bwd(Tensor gout, int T, int B, Tensor pairs, int K, Tensor offsets, Tensor(a!) dScore, bool has_ds, Tensor(b!) dNoise, "
           "bool has_dn) -> ()");
@@ -854,6 +894,7 @@ STABLE_TORCH_LIBRARY_IMPL(semicrf, CPU, m)
     m.impl("interval_marginals_tol", TORCH_BOX(&interval_marginals_tol_cpu));
     m.impl("marginal_decode_tol", TORCH_BOX(&marginal_decode_tol_cpu));
     m.impl("mbr_select", TORCH_BOX(&mbr_select_cpu));
+    m.impl("compare_paths", TORCH_BOX(&compare_paths_cpu));
     m.impl("eval_path", TORCH_BOX(&eval_path_cpu));
     m.impl("eval_path_bwd", TORCH_BOX(&eval_path_bwd_cpu));
     m.impl("logprob_fwd", TORCH_BOX(&logprob_fwd_cpu));
@@ -876,6 +917,7 @@ STABLE_TORCH_LIBRARY_IMPL(semicrf, CUDA, m)
     m.impl("interval_marginals_tol", TORCH_BOX(&interval_marginals_tol));
     m.impl("marginal_decode_tol", TORCH_BOX(&marginal_decode_tol));
     m.impl("mbr_select", TORCH_BOX(&mbr_select));
+    m.impl("compare_paths", TORCH_BOX(&compare_paths));
     m.impl("eval_path", TORCH_BOX(&eval_path));
     m.impl("eval_path_bwd", TORCH_BOX(&eval_path_bwd));
     m.impl("logprob_fwd", TORCH_BOX(&logprob_fwd));

@@ -193,22 +193,13 @@ class SegmentTranscriber(nn.Module):
     # ------------------------------------------------------------------------------------------------------------------
     # one step on the device
     # ------------------------------------------------------------------------------------------------------------------
-    @torch.no_grad()
-    def decode_step(self, ctxBatch: torch.Tensor, start: Optional[torch.Tensor], beginTime: torch.Tensor, lastFrameIdx: int,
-                    stepFrames: int, onsetBound: Optional[int] = None, velocityCriteron: str = "hamming", k_cap: Optional[int] = None):
-        """ctxBatch [F, P, T, D] (one segment of each of F recordings); start: int32 [F*P] forced start positions on the device
-        or None; beginTime: float64 [F] on the device.  Returns a dict of DEVICE tensors: pairs [K,2], offsets [F*P+1],
-        symIdx [K], scatterIdx [K], velocity [K], times [K,2] f64, flags [K,2] u8, lastP [F*P], nextStart [F*P], and K.
-
-        k_cap: run WITHOUT the host synchronisation for K: everything behind the decode is sized for k_cap intervals (the rows
-        behind the real count hold harmless values), `K` in the result is None and `Kdev` is the count on the device; the caller
-        checks it later (it must not exceed k_cap: beyond it the chains' events -- and `nextStart` -- are cut off)."""
-        assert ctxBatch.dim() == 4
+    def _decode_packed(self, ctxBatch: torch.Tensor, start: Optional[torch.Tensor]):
+        """Scorer and Viterbi decode of one batch of segments, nothing synchronised: ctxBatch [F, P, T, D] -> the decoded paths
+        packed on the device, (pairs int32 [cap, 2], offsets int32 [F*P + 1]), chain-indexed (c = segment * P + symbol).  start:
+        int32 [F*P] forced start positions on the device or None."""
         Fn, P, T, D = ctxBatch.shape
-        assert P == len(self.targetMIDIPitch)
         B = Fn * P
         dev = ctxBatch.device
-        ops = _lib.ops()
         # processFramesBatch :199-222.  S stays inside this step, so its chain axis uses the slot layout (include/semicrf_hip.h):
         # the P symbols of a segment in `pitch` slots (96 for 90) -- whole 128-byte lines for the CRF kernels -- with all-zero
         # ghost chains that decode to nothing; the packed result is chain-indexed again before anything else sees it
@@ -240,6 +231,25 @@ class SegmentTranscriber(nn.Module):
             offsets = torch.cat([offsets_s.index_select(0, real), offsets_s[-1:]])
         else:
             pairs, offsets = _nsci._viterbi_raw(score, noise, start, False)              # transcribeFrames :549
+        return pairs, offsets
+
+    @torch.no_grad()
+    def decode_step(self, ctxBatch: torch.Tensor, start: Optional[torch.Tensor], beginTime: torch.Tensor, lastFrameIdx: int,
+                    stepFrames: int, onsetBound: Optional[int] = None, velocityCriteron: str = "hamming", k_cap: Optional[int] = None):
+        """ctxBatch [F, P, T, D] (one segment of each of F recordings); start: int32 [F*P] forced start positions on the device
+        or None; beginTime: float64 [F] on the device.  Returns a dict of DEVICE tensors: pairs [K,2], offsets [F*P+1],
+        symIdx [K], scatterIdx [K], velocity [K], times [K,2] f64, flags [K,2] u8, lastP [F*P], nextStart [F*P], and K.
+
+        k_cap: run WITHOUT the host synchronisation for K: everything behind the decode is sized for k_cap intervals (the rows
+        behind the real count hold harmless values), `K` in the result is None and `Kdev` is the count on the device; the caller
+        checks it later (it must not exceed k_cap: beyond it the chains' events -- and `nextStart` -- are cut off)."""
+        assert ctxBatch.dim() == 4
+        Fn, P, T, D = ctxBatch.shape
+        assert P == len(self.targetMIDIPitch)
+        B = Fn * P
+        dev = ctxBatch.device
+        ops = _lib.ops()
+        pairs, offsets = self._decode_packed(ctxBatch, start)
         if onsetBound is not None:                                                       # :554-555
             pairs2 = torch.empty_like(pairs)
             offsets2 = torch.empty_like(offsets)
@@ -280,6 +290,86 @@ class SegmentTranscriber(nn.Module):
                            beginTime, int(stepFrames), times, flags, lastP, nextStart)
         return dict(K=K if k_cap is None else None, Kdev=Kdev, k_cap=k_cap, pairs=pairs[:K], offsets=offsets, symIdx=sym, scatterIdx=sc,
                     velocity=velocity, times=times, flags=flags, lastP=lastP, nextStart=nextStart, ofValue=ofValue, ofPresence=ofPresence)
+
+    # ------------------------------------------------------------------------------------------------------------------
+    # the validation statistic
+    # ------------------------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def computeStats(self, ctxBatch: torch.Tensor, intervalsBatch, velocityBatch, ofRefinedGTBatch, tolerance=None) -> dict:
+        """ModelTransformer.py:388-495 from `ctx` on (the backbone's output in the place of the audio, as in decode_step): decode
+        without a forced start, compare the decoded paths with the target intervals (compareBracket and compareFramewise, :426-438)
+        and evaluate the two attribute heads on the TARGET intervals (:445-481).  The decoded paths never leave the device: the
+        counts are column sums of semicrf_compare_paths' per-chain rows (CRF.decode_stats), and ONE host synchronisation at the
+        end fetches the eight numbers.
+
+        ctxBatch [N, P, T, D]; the targets as prepareIntervals yields them, per segment and symbol: intervalsBatch[n][p] a list of
+        (begin, end), velocityBatch[n][p] the velocities and ofRefinedGTBatch[n][p] the (onset, offset) refinements of those
+        intervals (the reference's data["intervals"], data["velocity"], data["endPointRefine"]); the last two may also be given
+        flat, in chain order (a sequence or tensor of K values / [K, 2]).
+        Returns the reference's dict: nGT, nEst, nCorrect, nGTFramewise, nEstFramewise, nCorrectFramewise (ints), seVelocityForced,
+        seOFForced (floats: the squared error of the softmax-weighted mean velocity, and of the ContinuousBernoulli mean shifted
+        back and clamped to +-0.5; evaluated in float64 from the heads' fp32 logits).  With tolerance (None, an int or
+        (onset, offset) in frames, 0..8) also nCorrectTolerant: the matches within that window.  Without a single target interval the heads are not run and both errors are 0."""
+        assert ctxBatch.dim() == 4
+        Fn, P, T, D = ctxBatch.shape
+        assert P == len(self.targetMIDIPitch)
+        assert len(intervalsBatch) == Fn
+        B = Fn * P
+        dev = ctxBatch.device
+        tol = _nsci._tolerance(tolerance, "computeStats")
+        flat = [sym for seg in intervalsBatch for sym in seg]                            # :415-416
+        assert len(flat) == B
+        # everything the host has to say goes first: the copies need nothing from the GPU and nothing below waits for them
+        ref_pairs, ref_offsets = _nsci.pack_intervals(flat, T, B, dev)
+        K = ref_pairs._semicrf_K
+        if K > 0:
+            vel_gt = self._target_tensor(velocityBatch, torch.float32, (K,), dev, "velocityBatch")           # :471-472 (exact: 0..127)
+            of_gt = self._target_tensor(ofRefinedGTBatch, torch.float32, (K, 2), dev, "ofRefinedGTBatch")    # :474-475
+        pairs, offsets = self._decode_packed(ctxBatch, None)                             # :403
+        stats = _nsci._compare_paths_raw(pairs, offsets, ref_pairs, ref_offsets, T, tol)
+        out = torch.zeros(10, dtype=torch.float64, device=dev)
+        out[:7] = stats.sum(0, dtype=torch.int64)                                        # :428-438
+        out[7] = stats.min()                                                             # -1: a chain the kernel rejected
+        if K > 0:
+            attributeInput, _, _ = attributes.attribute_input_packed(ctxBatch, ref_pairs, ref_offsets, K)   # :445-450
+            # The heads run in fp32 as in the reference; what follows their logits runs in float64 (K x 128 values).  The closed form
+            # of the ContinuousBernoulli mean, p / (2p - 1) + 1 / (log(1 - p) - log p), is the difference of two terms that grow like
+            # 1 / |logit| towards logit 0: in fp32 it loses up to 1e-5 absolute there, 1e-4 of seOFForced on heads with small logits.
+            logitsVelocity = self.velocityPredictor(attributeInput).double()             # :454
+            pVelocity = F.softmax(logitsVelocity, dim=-1)                                # :455
+            velocity = (pVelocity * torch.arange(128, device=dev, dtype=torch.float64)).sum(-1)   # :459-460
+            ofValue, _ = self.refinedOFPredictor(attributeInput).double().chunk(2, dim=-1)        # :463
+            ofDist = torch.distributions.ContinuousBernoulli(logits=ofValue, validate_args=False)   # (the argument check is a host sync)
+            ofValue = torch.clamp((ofDist.mean - 0.5) / 0.99, -0.5, 0.5)                 # :467-468
+            out[8] = (velocity - vel_gt).pow(2).sum()                                    # :481
+            out[9] = (ofValue - of_gt).pow(2).sum()                                      # :480
+        h = out.cpu().tolist()                                                           # the one host sync
+        if h[7] < 0:
+            _lib.async_error()                   # consumed here: the next library call must not report a time-out again
+            raise RuntimeError("computeStats: the comparison rejected a chain -- the decode gave up on a bounded wait on the device, or "
+                               "a target list is not ascending in begin and in end")
+        c = _nsci.PathStats
+        res = {"nGT": int(h[c.nRef]), "nEst": int(h[c.nEst]), "nCorrect": int(h[c.nExact]), "nGTFramewise": int(h[c.nRefFrames]),
+               "nEstFramewise": int(h[c.nEstFrames]), "nCorrectFramewise": int(h[c.nBothFrames]), "seVelocityForced": h[8],
+               "seOFForced": h[9]}
+        if tolerance is not None:
+            res["nCorrectTolerant"] = int(h[c.nMatchTol])
+        return res
+
+    @staticmethod
+    def _target_tensor(x, dtype, shape, dev, name: str) -> torch.Tensor:
+        """A target of computeStats -- nested per segment and symbol as prepareIntervals yields it, or flat -- as one tensor on
+        `dev`, uploaded from pinned memory without waiting for the device."""
+        if not isinstance(x, torch.Tensor):
+            x = list(x)
+            if x and isinstance(x[0], (list, tuple)) and (len(x[0]) == 0 or isinstance(x[0][0], (list, tuple))):
+                x = [v for seg in x for sym in seg for v in sym]                         # sum(sum(..., []), []), :412-413, :471-474
+            x = torch.tensor(x, dtype=dtype).reshape(-1, *shape[1:])
+        x = x.to(dtype)
+        assert tuple(x.shape) == tuple(shape), f"{name}: expected {tuple(shape)} values for the target intervals, got {tuple(x.shape)}"
+        if x.device.type == "cpu" and torch.device(dev).type == "cuda":
+            x = x.pin_memory()
+        return x.to(dev, non_blocking=True)
 
     @staticmethod
     def _velocity(logitsVelocity: torch.Tensor, criterion: str) -> torch.Tensor:
