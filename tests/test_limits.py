@@ -32,8 +32,9 @@ def grad_tol(logz):
 
 # ---- A. backtrack switch points on synthetic lattices ----------------------------------------------------------------------
 
-SWITCH_T = [8191, 8192, 8193, 16384, 16385, 20011]           # both sides of BT_PAR_MAX and BT_LDS_MAX, and an odd long row
-SWITCH_T_CPU = [8193, 16385]
+# both sides of MBR_LDS_T (4096: F in LDS up to there), of BT_PAR_MAX and of BT_LDS_MAX, and an odd long row
+SWITCH_T = [4095, 4096, 4097, 8191, 8192, 8193, 16384, 16385, 20011]
+SWITCH_T_CPU = [4097, 8193, 16385]
 TAU_ALL = 0.3
 TAU_PER_CHAIN = (0.3, 0.25, 0.35, 0.2)
 

@@ -2,14 +2,15 @@
 
 CPU tests check the host kernel against exact enumeration of every path (tiny T), against the reference decode (k = 1) on the
 edge goldens, for the prefix property, and against a numpy-fp32 restatement of the recursion and its order; GPU tests check the
-device against the host kernel bit for bit, and k = 1 against the device decode."""
+device against the host kernel bit for bit (on both sides of the walk's LDS limit too), and k = 1 against the device decode."""
 import ctypes
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import EDGE_CASES, edge_inputs, load_golden
+from conftest import EDGE_CASES, edge_inputs, load_golden, rel_err
+from path_targets_common import path_reference
 from transkun_amd import CRF, _lib, synth
 
 DIRS = [False, True]
@@ -373,6 +374,73 @@ def test_full_size_device_equals_host(gpu, shape):
     for fwd in DIRS:
         st = _starts(T, B, 12 + fwd, fwd)
         _assert_same(*_both(score, noise, k, st, fwd, gpu), (shape, fwd))
+
+
+# ---- both sides of the walk's LDS limit ------------------------------------------------------------------------------------
+
+LOGZ_TOL = 1e-5                                               # tests/test_gpu_parity.py: the suite's tolerance for path scores
+
+# T, B, k: the code table (T * k int32) is the last that fits the walk's 128 KB of LDS (with a ragged last workgroup of the
+# sweep's four chains), the first walked in global memory, a long one in global memory, and a long row that is back in LDS
+WALK_CASES = [(2048, 5, 16), (2050, 5, 16), (4100, 3, 8), (4100, 3, 4)]
+
+
+def _path_scores64(score, noise, segs, B, st, forward):
+    """float64 score of every path (rank-major list) over its walk's range: path_reference's sum on [lo, hi] = [0, start]
+    (forward) or [start, T - 1]"""
+    T = score.shape[0]
+    out = np.empty(len(segs))
+    for c in range(B):
+        lo, hi = (0, T - 1) if st is None else ((0, st[c]) if forward else (st[c], T - 1))
+        sub_s, sub_n = score[lo:hi + 1, lo:hi + 1, c:c + 1], noise[lo:hi, c:c + 1]
+        for r in range(len(segs) // B):
+            path = segs[r * B + c]
+            assert all(lo <= b <= e <= hi for b, e in path), (r, c)
+            out[r * B + c] = path_reference(sub_s, sub_n, [[(b - lo, e - lo) for b, e in path]])[0][0]
+    return out
+
+
+_WALK_INPUTS = {}                                             # the last shape's inputs only (200 MB at T = 4100)
+
+
+def _walk_inputs(shape, gpu):
+    if shape not in _WALK_INPUTS:
+        _WALK_INPUTS.clear()
+        T, B, k = shape
+        sg, ng = synth.crf_inputs(T, B, T + k, gpu, "randn")
+        _WALK_INPUTS[shape] = (sg.cpu(), ng.cpu(), sg, ng)
+    return _WALK_INPUTS[shape]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("forced", [False, True])
+@pytest.mark.parametrize("fwd", DIRS)
+@pytest.mark.parametrize("shape", WALK_CASES, ids=str)
+def test_walk_lds_limit_device_equals_host(gpu, shape, fwd, forced):
+    """Device == host bit for bit where the device's walk changes from a code table staged in LDS to one read from global memory
+    (the host kernel has no such switch), and on the same results what needs no second kernel: rank 0 is decode, the scores
+    do not increase, the paths of a chain are distinct, and every score is the float64 score of its path.  (One device call per
+    case: the sweep of k = 16 takes seconds at these lengths whatever the number of chains)"""
+    T, B, k = shape
+    score, noise, sg, ng = _walk_inputs(shape, gpu)
+    st = _starts(T, B, k + 5 * fwd, fwd) if forced else None
+    what = (shape, fwd, forced)
+    host = CRF.viterbi_nbest_packed(score, noise, k, st, fwd)
+    devr = CRF.viterbi_nbest_packed(sg, ng, k, st, fwd)
+    _assert_same(host, devr, what)
+    pairs, offsets, scores, npaths = devr
+    assert (npaths == k).all(), what                                      # (no start is within a few frames of the walk's end)
+    dp, do = CRF.NeuralSemiCRFInterval(sg, ng).decode_packed(forcedStartPos=st, forward=fwd)
+    assert np.array_equal(offsets[:B + 1], do) and np.array_equal(pairs[:offsets[B]], dp), what
+    assert (scores[:-1] >= scores[1:]).all(), what
+    segs = _segments(pairs, offsets)
+    for c in range(B):
+        assert len({tuple(segs[r * B + c]) for r in range(k)}) == k, (what, c)
+    want = _path_scores64(score, noise, segs, B, st, fwd)
+    assert rel_err(scores.reshape(-1), want) < LOGZ_TOL, what
+    if (shape, fwd, forced) == (WALK_CASES[-1], DIRS[-1], True):
+        _WALK_INPUTS.clear()
+        torch.cuda.empty_cache()
 
 
 @pytest.mark.gpu

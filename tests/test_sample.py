@@ -2,7 +2,8 @@
 
 The draws are a pure function of (inputs, key), so every test here is deterministic: a fixed generator seed makes the key.
 CPU tests check the distribution itself (exact enumeration for tiny T, marginals against forward_backward, a float64
-restatement of the contract); GPU tests check the device against the same properties and against the host kernel."""
+restatement of the contract); GPU tests check the device against the same properties, against the host kernel, and step by step
+against the float64 CDF of every visited row (tests/sample_common.py)."""
 import importlib
 import math
 import types
@@ -12,7 +13,9 @@ import pytest
 import torch
 
 from conftest import edge_inputs
-from transkun_amd import CRF, synth
+from sample_common import (StepCase, _alpha64, _check_valid, _restated_sample, _restated_walk, _segments, _steps_to_path, _u, _uniforms,
+                           check_steps, flat_inputs, pack_paths)
+from transkun_amd import CRF, _lib, synth
 
 crf_mod = importlib.import_module("transkun_amd.CRF.NeuralSemiCRFInterval")     # the module (the package exports the class by that name)
 
@@ -25,94 +28,10 @@ def _key(seed):
     return int(torch.randint(0, 2 ** 63 - 1, (1,), generator=_gen(seed)))
 
 
-def _segments(pairs, offsets):
-    return [[tuple(int(x) for x in p) for p in pairs[offsets[i]:offsets[i + 1]]] for i in range(len(offsets) - 1)]
-
-
 def _mixed_inputs(T, seeds=(3, 4, 5)):
     """Three chains with different constructions (randn, model, ties)."""
     parts = [synth.crf_inputs(T, 1, s, "cpu", kind) for s, kind in zip(seeds, ("randn", "model", "ties"))]
     return (torch.cat([p[0] for p in parts], 2).contiguous(), torch.cat([p[1] for p in parts], 1).contiguous())
-
-
-def _check_valid(pairs, offsets, T, ends=None, B=None):
-    """Every segment is a path a walk can produce: 0 <= b <= e < T (e <= forced end), strictly ascending (begin, end), intervals
-    that at most touch, and no singleton strictly inside an interval."""
-    pairs = np.asarray(pairs, np.int64).reshape(-1, 2)
-    offsets = np.asarray(offsets, np.int64)
-    K = int(offsets[-1])
-    assert offsets[0] == 0 and (np.diff(offsets) >= 0).all() and pairs.shape[0] == K
-    if K == 0:
-        return
-    b, e = pairs[:, 0], pairs[:, 1]
-    seg = np.repeat(np.arange(len(offsets) - 1), np.diff(offsets))
-    assert (b >= 0).all() and (b <= e).all() and (e < T).all()
-    if ends is not None:
-        lim = np.asarray(ends, np.int64)[seg % B]
-        assert (e <= lim).all()
-    same = seg[1:] == seg[:-1]
-    asc = (b[1:] > b[:-1]) | ((b[1:] == b[:-1]) & (e[1:] > e[:-1]))
-    assert asc[same].all(), "not strictly ascending within a path"
-    # the last interval (b < e) before each entry, in the same path: its end must not pass the entry's begin
-    idx = np.where(b < e, np.arange(K), -1)
-    last = np.maximum.accumulate(idx)
-    prev = np.concatenate([[-1], last[:-1]])
-    ok = prev >= 0
-    ok &= seg[np.maximum(prev, 0)] == seg
-    assert (e[prev[ok]] <= b[ok]).all(), "overlapping intervals or a singleton inside an interval"
-
-
-# ---- float64 restatement of the contract ---------------------------------------------------------------------------------
-
-def _u(idx, key):
-    return (synth.hash_u64_numpy(np.asarray(idx, np.uint64), key) >> np.uint64(40)).astype(np.float64) * 2.0 ** -24
-
-
-def _alpha64(s, n):
-    T, B = s.shape[0], s.shape[2]
-    v = np.zeros((T, B))
-    sp = lambda x: np.logaddexp(0.0, x)
-    v[0] = sp(s[0, 0])
-    for t in range(1, T):
-        cand = np.concatenate([(v[t - 1] + n[t - 1])[None], v[:t] + s[t, :t]], 0)
-        v[t] = np.logaddexp.reduce(cand, 0) + sp(s[t, t])
-    return v
-
-
-def _restated_sample(s, n, v, nSample, key, ends=None):
-    """List of nSample*B paths (sample-major) from the contract: float64, sequential running sums, first sum > u*Z."""
-    T, B = s.shape[0], s.shape[2]
-    s = s.astype(np.float64); n = n.astype(np.float64)
-    out = []
-    cums = {}
-    for k in range(nSample):
-        for c in range(B):
-            t = T - 1 if ends is None else int(ends[c])
-            rev = []
-            while True:
-                base = ((k * B + c) * T + t) * 2
-                u = _u([base, base + 1], key)
-                if u[1] < 1.0 / (1.0 + math.exp(-s[t, t, c])):
-                    rev.append((t, t))
-                if t == 0:
-                    break
-                if (t, c) not in cums:
-                    x = np.concatenate([[v[t - 1, c] + n[t - 1, c]], v[t - 1::-1, c] + s[t, t - 1::-1, c]])
-                    m = x.max()
-                    cums[(t, c)] = np.cumsum(np.exp(x - m)) if m > -np.inf else np.zeros_like(x)
-                cs = cums[(t, c)]
-                Z = cs[-1]
-                pick = 0
-                if Z > 0:
-                    thr = u[0] * Z
-                    pick = int(np.searchsorted(cs, thr, side="right")) if thr < Z else int(np.searchsorted(cs, Z, side="left"))
-                if pick == 0:
-                    t -= 1
-                else:
-                    rev.append((t - pick, t))
-                    t -= pick
-            out.append(sorted(rev))
-    return out
 
 
 # ---- exact distribution --------------------------------------------------------------------------------------------------
@@ -253,6 +172,125 @@ def test_restatement_agreement_cpu():
     want = _restated_sample(s.numpy(), n.numpy(), v, N, key, ends)
     got = _segments(*CRF.sample_packed(s, n, N, forcedEndPos=ends, generator=_gen(7)))
     assert _agreement(got, want) >= 0.99
+
+
+# ---- step by step ------------------------------------------------------------------------------------------------------------
+# sample_common.StepCase holds the reference side of a case (the float64 restatement's draws, the band delta from the plain-fp32
+# restatement's own error, the ambiguous share); a sampler's draws of the same case go through StepCase.check.
+
+def _step_inputs(T, B, seed, kind, device="cpu"):
+    """(score, noise, alpha) as fp32 numpy; alpha is the float64 recursion on these inputs, rounded once.  device: where the hash
+    of synth.crf_inputs runs (the same bits on either)"""
+    if kind == "flat":
+        return flat_inputs(T, B, seed)
+    s, n = synth.crf_inputs(T, B, seed, device, kind)
+    s, n = s.cpu().numpy(), n.cpu().numpy()
+    return s, n, _alpha64(s, n).astype(np.float32)
+
+
+def _mixed_ends(T, B):
+    """0, 1 and T - 1 first, then a mixed set"""
+    return ([0, 1, T - 1] + [int(x) for x in (np.arange(B) * 7 + 3) % T])[:B]
+
+
+def _raw_draws(st, nt, vt, k0, N, key, ends):
+    """semicrf_sample alone, where the tensors live, on the alpha handed in: (pairs, offsets) as numpy"""
+    e = torch.tensor(ends, dtype=torch.int32, device=st.device) if ends is not None else None
+    p, o = crf_mod._sample_raw(st, nt, vt, k0, N, key, e)
+    o = o.cpu().numpy()
+    return p[:int(o[-1])].cpu().numpy(), o
+
+
+def _run_case(case, tensors):
+    """the case's draws from the sampler where `tensors` (score, noise, alpha) live: zero violations"""
+    pairs, offsets = _raw_draws(*tensors, case.k0, case.nSample, case.key, case.ends)
+    bad, steps, amb = case.check(pairs, offsets)
+    assert not bad, (case.name, len(bad), bad[:5])
+    assert steps > 0
+    return pairs, offsets
+
+
+def _tensors(arrays, device):
+    return tuple(torch.from_numpy(x).to(device) for x in arrays)
+
+
+def _coins_in_band(case):
+    _, u1 = _uniforms(case.T, case.B, case.nSample, case.key, case.k0)
+    n = 0
+    for i, walk in enumerate(case.walks):
+        k, c = divmod(i, case.B)
+        for t, _, _ in walk:
+            p = 1.0 / (1.0 + math.exp(-float(case.score[t, t, c])))
+            n += abs(u1[k, c, t] - p) <= 8 * 2.0 ** -24
+    return n
+
+
+STEP_KINDS = ["randn", "model", "flat"]
+
+
+@pytest.mark.parametrize("kind", STEP_KINDS)
+@pytest.mark.parametrize("forced", [False, True])
+def test_steps_restatement_cpu(kind, forced):
+    """The restatement's own draws: admissible at every step (StepCase asserts it at its band), and with NO band -- delta = 0 --
+    still without a violation and without an ambiguous pick: what is ambiguous there is a coin inside its exception, nothing else."""
+    T, B, N = 64, 20, 16
+    arrays = _step_inputs(T, B, 31, kind)
+    case = StepCase(f"restatement {kind}", *arrays, _key(7), 0, N, _mixed_ends(T, B) if forced else None)
+    assert case.paths == _restated_sample(*arrays, N, case.key, case.ends)
+    bad, steps, amb = check_steps(*arrays, case.key, 0, N, case.ends, *pack_paths(case.paths), 0.0)
+    assert not bad and steps == sum(len(w) for w in case.walks)
+    assert amb == _coins_in_band(case)
+
+
+def test_steps_mutation_cpu():
+    """One clear pick moved by one candidate and one clear coin flipped: the checker reports exactly those two steps."""
+    T, B, N = 64, 20, 4
+    arrays = _step_inputs(T, B, 33, "randn")
+    case = StepCase("mutation", *arrays, _key(8), 0, N)
+    u0, u1 = _uniforms(T, B, N, case.key)
+    moved = flipped = None
+    paths = list(case.paths)
+    for i, walk in enumerate(case.walks):
+        k, c = divmod(i, B)
+        for pos, (t, pick, single) in enumerate(walk):
+            if moved is None and t >= 8 and pick is not None:
+                cs = case.cums[t][c]
+                u = u0[k, c, t] * cs[-1]
+                d = case.delta * cs[-1]
+                alt = pick + 1
+                # clear: the pick is the only admissible candidate, with room to spare, and its neighbour exists
+                if alt <= t and (pick == 0 or cs[pick - 1] < u - 2 * d) and cs[pick] > u + 2 * d:
+                    tail = _restated_walk(*arrays, u0[k, c], u1[k, c], c, t - alt, case.cums)
+                    paths[i] = _steps_to_path(walk[:pos] + [(t, alt, single)] + tail)
+                    moved = (k, c, t, "pick")
+                    break
+            if flipped is None and moved is not None and (k, c) != moved[:2]:
+                p = 1.0 / (1.0 + math.exp(-float(arrays[0][t, t, c])))
+                if abs(u1[k, c, t] - p) > 0.01:
+                    paths[i] = _steps_to_path(walk[:pos] + [(t, pick, not single)] + walk[pos + 1:])
+                    flipped = (k, c, t, "coin")
+                    break
+        if moved and flipped:
+            break
+    assert moved and flipped
+    bad, steps, amb = case.check(*pack_paths(paths))
+    assert sorted(b[:4] for b in bad) == sorted([moved, flipped])
+    # and the unchanged draws stay clean
+    assert not case.check(*pack_paths(case.paths))[0]
+
+
+HOST_STEP_CASES = [(64, 20, 16, kind, forced) for kind in STEP_KINDS for forced in (False, True)] + [(2050, 2, 2, "flat", False)]
+
+
+@pytest.mark.parametrize("T,B,N,kind,forced", HOST_STEP_CASES, ids=str)
+def test_steps_host_kernel_cpu(T, B, N, kind, forced):
+    """The host kernel (float64 sums of fp32 log-weights) through the same checker, at the band of the case."""
+    arrays = _step_inputs(T, B, 35 + T, kind)
+    case = StepCase(f"host {kind} T={T}", *arrays, _key(T + forced), 0, N, _mixed_ends(T, B) if forced else None)
+    _run_case(case, _tensors(arrays, "cpu"))
+    if T > 2048:
+        share, count = case.far_chunk_share()
+        assert count > 0 and share > 0.5, (share, count)
 
 
 # ---- low temperature -----------------------------------------------------------------------------------------------------
@@ -523,3 +561,100 @@ def test_full_size_gpu(gpu, T, B, N):
     for path in crf.sample(N, generator=_gen(T)):
         lp = crf.logProb(path)
         assert torch.isfinite(lp).all() and (lp <= 1e-3).all()
+
+
+# ---- GPU: every step of every draw against the float64 CDF of its row ------------------------------------------------------------
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("B", [1, 64, 65, 130])
+def test_steps_chain_tiles_gpu(gpu, B):
+    """One lane per chain, 64 chains per workgroup: one chain, a full tile, a ragged second tile, a ragged third."""
+    T, N = 50, 9
+    arrays = _step_inputs(T, B, 90 + B, "randn" if B != 64 else "model")
+    tensors = _tensors(arrays, gpu)
+    for ends in (None, _mixed_ends(T, B)):
+        _run_case(StepCase(f"tiles B={B} ends={ends is not None}", *arrays, _key(B), 0, N, ends), tensors)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("N", [1, 8, 9, 17])
+def test_steps_draw_loop_gpu(gpu, N):
+    """The draws of a (row, chain) are dealt to 8 waves: fewer draws than waves, one each, one more, two rounds and one."""
+    T, B = 50, 5
+    arrays = _step_inputs(T, B, 95, "randn")
+    tensors = _tensors(arrays, gpu)
+    for ends in (None, _mixed_ends(T, B)):
+        _run_case(StepCase(f"draws N={N} ends={ends is not None}", *arrays, _key(N), 0, N, ends), tensors)
+
+
+@pytest.mark.gpu
+def test_steps_split_call_gpu(gpu):
+    """Nine draws as two calls (k0 = 0 and k0 = 5) are the nine draws of one call, bit for bit, and each call passes on its own."""
+    T, B, N = 50, 5, 9
+    arrays = _step_inputs(T, B, 96, "randn")
+    tensors = _tensors(arrays, gpu)
+    key = _key(96)
+    for ends in (None, _mixed_ends(T, B)):
+        whole = _run_case(StepCase("split 0..8", *arrays, key, 0, N, ends), tensors)
+        lo = _run_case(StepCase("split 0..4", *arrays, key, 0, 5, ends), tensors)
+        hi = _run_case(StepCase("split 5..8", *arrays, key, 5, 4, ends), tensors)
+        assert np.array_equal(np.concatenate([lo[0], hi[0]]), whole[0])
+        assert np.array_equal(np.concatenate([lo[1], hi[1][1:] + lo[1][-1]]), whole[1])
+
+
+def _long_case(gpu, T, B, N, kind, seed, end_sets, first_row):
+    arrays = _step_inputs(T, B, seed, kind, gpu)
+    tensors = _tensors(arrays, gpu)
+    for ends in end_sets:
+        case = StepCase(f"{kind} T={T} ends={ends}", *arrays, _key(T + B), 0, N, ends)
+        if kind == "flat" and (ends is None or max(ends) >= first_row):
+            share, count = case.far_chunk_share(first_row)              # from the reference's picks alone
+            print(f"{case.name}: {count} picks on rows >= {first_row}, {100 * share:.3g} % beyond the first chunk, "
+                  f"{case.chunks_hit(first_row)} distinct chunks")
+            assert count > 0 and share > 0.5, (share, count)
+        _run_case(case, tensors)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", ["flat", "randn"])
+def test_steps_chunk_switch_gpu(gpu, kind):
+    """Rows 2047 (2048 candidates: 128 chunks of one batch, every summary slot used) and 2048, 2049 (chunks of two batches: the
+    rescale between the batches of a chunk, the rescan of a two-batch chunk) in one launch.  Forced ends put a walk's first
+    step on each of the three rows; the flat rows send the picks into every part of the row."""
+    T = 2050
+    try:
+        end_sets = (None, [T - 1, 2048, 2047, 0, 1, 1033])
+        if kind == "flat":                                                  # a flat walk is ~10 steps: eighteen more first steps per row
+            end_sets += ([2049] * 6, [2048] * 6, [2047] * 6)
+        _long_case(gpu, T, 6, 3, kind, 97, end_sets, 2048)
+    finally:
+        torch.cuda.empty_cache()
+
+
+@pytest.mark.gpu
+def test_steps_three_batches_gpu(gpu):
+    """Chunks of three batches (48 candidates) from row 4096 on."""
+    T = 4100
+    try:
+        _long_case(gpu, T, 3, 2, "flat", 98, (None, [T - 1, 4096, 4095], [0, 1, 2048], [4098, 4097, 4096], [4095] * 3), 4096)
+    finally:
+        torch.cuda.empty_cache()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("alpha", ["restated", "device"])
+def test_steps_model_shape_gpu(gpu, alpha):
+    """The model's row length on three chain tiles: the sampler alone on the restated alpha, and end to end on the alpha of the
+    device's own forward sweep, read back and handed to the checker."""
+    T, B, N = 691, 130, 2
+    st, nt = synth.crf_inputs(T, B, 99, gpu, "model")
+    s, n = st.cpu(), nt.cpu()
+    if alpha == "device":
+        _lib.device_status()
+        _, vt = crf_mod._logz_fwd_raw(st, nt, True)
+        v = vt.cpu().numpy()
+        assert _lib.device_status() == 0
+    else:
+        v = _alpha64(s.numpy(), n.numpy()).astype(np.float32)
+        vt = torch.from_numpy(v).to(gpu)
+    _run_case(StepCase(f"model shape, {alpha} alpha", s.numpy(), n.numpy(), v, _key(691), 0, N), (st, nt, vt))
