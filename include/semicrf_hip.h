@@ -373,6 +373,29 @@ int semicrf_covariance(const float* score, const float* noise, const float* weig
                        int B, float* C, float* Cn, const void* ws, size_t ws_bytes, semicrf_stream_t stream);
 
 /*
+ * The alpha sweep from a forced start: alpha of the semi-CRF restricted to the frames start[c] .. T-1 of chain c -- the model whose
+ * MAP path semicrf_viterbi(start) returns.  No counterpart in the reference (its forced start exists for decode only); adds nothing
+ * to the ABI's existing entry points (version 2).  With d[t] = score[t,t,c], sp = softplus, S[e,b] = score[e,b,c], n[t] = noise[t,c],
+ * s = start[c]:
+ *     v[t][c] = -inf                                                                          t <  s
+ *     v[s][c] = sp(d[s])
+ *     v[t][c] = logaddexp(v[t-1] + n[t-1], logsumexp_{s <= b < t}(v[b] + S[t,b])) + sp(d[t])     t >  s
+ *     logZ[c] = v[T-1][c]      (= beta[s] of semicrf_beta up to fp32 rounding: beta[t] depends on the frames >= t only)
+ * (logZ, v, beta) are what semicrf_posteriors, semicrf_interval_marginals(_tol) and semicrf_marginal_decode(_tol) take: with this v
+ * they describe the conditional model, and every marginal of a cell with begin < start[c] is exactly 0.0f.
+ *   start [B], device, int32.  A start[c] outside [0, T-1] gives NaN for logZ[c] and for that chain's column of v; it never causes an
+ *     out-of-range access.
+ *   Reads only cells begin <= end, and nothing in columns before the chain's start.  Any T >= 1, any B >= 1 (odd B: 16-byte
+ *     accesses at 4-byte aligned addresses).  fp32 arithmetic (running-maximum log-sum-exp), fixed summation order: two calls are
+ *     bit-identical.  No atomics.
+ *   No communication between workgroups: a workgroup owns 16 chains for the whole recurrence -- no flags, no spins, no grid barrier,
+ *     no lease; nothing in this call can time out or hang, and it never touches semicrf_async_error's word.
+ *   Workspace: none (ws may be NULL, ws_bytes 0).
+ */
+int semicrf_alpha_from(const float* score, const float* noise, const int32_t* start, int T, int B, float* v, float* logZ, void* ws,
+                       size_t ws_bytes, semicrf_stream_t stream);
+
+/*
  * Decoded paths against target paths: the counts behind note-level and frame-level precision / recall, per chain.
  * Replaces: the host loops of TransKun.computeStats (ModelTransformer.py:403-438) -- decode() to Python lists, then compareBracket
  * (Evaluation.py:10-18) and compareFramewise (:67-74) chain by chain -- on the packed lists where semicrf_viterbi left them.  Adds

@@ -25,6 +25,8 @@ EXTENSIONS of the reference's surface: decode_packed, sample / sample_packed (ex
   probability that the path holds an interval within that window of the given one, the currency of note-level metrics.
   compare_paths / compare_paths_packed / decode_stats count in that currency: per chain the matches (exact and within a tolerance)
   and the frame overlaps between a decoded path and a target, on the device, without Python lists.
+  posteriors, interval_marginals, decode_marginal and decode_mbr (and their _packed forms) take forcedStartPos= like decode: the
+  posterior of the model restricted to the frames from each chain's start on, the one decode(forcedStartPos) maximises.
 """
 from __future__ import annotations
 
@@ -845,20 +847,61 @@ def _beta_raw(score_c, noise_c):
     return q
 
 
-def _marginal_inputs(score_c, noise_c):
-    """(logZ, v, q) of the alpha and beta sweeps, enqueued on the current stream."""
+def _alpha_from_raw(score_c, noise_c, start):
+    """(logZ_s [B], alpha_s [T, B]) of semicrf_alpha_from: the alpha sweep of the model restricted to the frames start[c] .. T-1
+    (start: int32 [B] where the scores live); alpha_s is -inf before the start.  Enqueued on the current stream, no workspace."""
+    T, B = score_c.shape[0], score_c.shape[2]
+    logz = torch.empty(B, dtype=torch.float32, device=score_c.device)
+    v = torch.empty(T, B, dtype=torch.float32, device=score_c.device)
+    _lib.ops().alpha_from(score_c, noise_c, start, v, logz, torch.empty(0, dtype=torch.uint8, device=score_c.device))
+    return logz, v
+
+
+def _marginal_inputs_from(score_c, noise_c, start):
+    """(logZ_s, alpha_s, q) of the model that starts chain c at frame start[c]: the forced-start alpha sweep and the ordinary beta
+    sweep (q[t] depends on the frames >= t only, so it is the conditional model's beta as it stands).  With these in the place
+    of _marginal_inputs' triple every posterior kernel describes the conditional model: alpha_s = -inf before the start makes each
+    marginal there an exact 0."""
+    logz, v = _alpha_from_raw(score_c, noise_c, start)
+    return logz, v, _beta_raw(score_c, noise_c)
+
+
+def _marginal_inputs(score_c, noise_c, start=None):
+    """(logZ, v, q) of the alpha and beta sweeps, enqueued on the current stream.  start (int32 [B] on the device): from a forced
+    start, _marginal_inputs_from."""
+    if start is not None:
+        return _marginal_inputs_from(score_c, noise_c, start)
     logz, v = _logz_fwd_raw(score_c, noise_c, want_v=True)
     return logz, v, _beta_raw(score_c, noise_c)
 
 
-def _posteriors_raw(score_c, noise_c, lvq=None) -> Posteriors:
-    """Enqueue the sweeps (unless lvq = (logZ, v, q) is given) and semicrf_posteriors; no host sync."""
+def _start_arg(forcedStartPos, T: int, B: int, device, name: str):
+    """The forcedStartPos keyword of the posterior calls -> None or an int32 vector [B] where the scores live.  A sequence of B
+    ints is checked like decode's (IndexError for a wrong length or a frame outside [0, T-1], TypeError for anything but ints); an
+    int32 tensor [B] is taken as it is and NOT range-checked (that would synchronise): a start out of range gives NaN for its chain."""
+    if forcedStartPos is None:
+        return None
+    if isinstance(forcedStartPos, torch.Tensor):
+        if forcedStartPos.dtype != torch.int32 or tuple(forcedStartPos.shape) != (B,):
+            raise TypeError(f"{name}: a forcedStartPos tensor must be int32 of shape [{B}], got {forcedStartPos.dtype} "
+                            f"{tuple(forcedStartPos.shape)}")
+        return forcedStartPos.detach().to(device).contiguous()
+    st = list(forcedStartPos)
+    if len(st) != B:
+        raise IndexError(f"{name}: forcedStartPos holds {len(st)} entries for {B} chains")
+    if not all(isinstance(x, (int, np.integer)) and not isinstance(x, (bool, np.bool_)) for x in st):
+        raise TypeError(f"{name}: forcedStartPos must hold ints (frames), got {forcedStartPos!r}")
+    return _start_tensor(st, T, B, device)
+
+
+def _posteriors_raw(score_c, noise_c, lvq=None, start=None) -> Posteriors:
+    """Enqueue the sweeps (unless lvq = (logZ, v, q) is given; from `start` when that is given) and semicrf_posteriors; no host sync."""
     if _odd_pad(score_c) and lvq is None:
-        P = _posteriors_raw(_pad1(score_c), _pad1(noise_c))
+        P = _posteriors_raw(_pad1(score_c), _pad1(noise_c), None, _pad1(start) if start is not None else None)
         return Posteriors(*(x[..., :-1].contiguous() for x in P))
     T, B = score_c.shape[0], score_c.shape[2]
     dev = score_c.device
-    logz, v, q = _marginal_inputs(score_c, noise_c) if lvq is None else lvq
+    logz, v, q = _marginal_inputs(score_c, noise_c, start) if lvq is None else lvq
     f = dict(dtype=torch.float32, device=dev)
     node, begin, end, single = (torch.empty(T, B, **f) for _ in range(4))
     noise, entropy = torch.empty(T - 1, B, **f), torch.empty(B, **f)
@@ -885,12 +928,18 @@ def _tolerance(tolerance, name: str) -> Tuple[int, int]:
     return pair
 
 
-def _interval_marginals_raw(score_c, v, q, logz, pairs, K: int, offsets, tol: Tuple[int, int] = (0, 0)):
+def _interval_marginals_raw(score_c, v, q, logz, pairs, K: int, offsets, tol: Tuple[int, int] = (0, 0), start=None):
+    """start (int32 per chain of `offsets`, or None): with a tolerance an interval with begin < start is given an exact 0 here -- its
+    box still holds cells at or behind the start, but the model from the start has no such interval (without a tolerance alpha =
+    -inf before the start makes the kernel's own value the exact 0)."""
     out = torch.empty(max(K, 1), dtype=torch.float32, device=score_c.device)
     if tol == (0, 0):
         _lib.ops().interval_marginals(score_c, v, q, logz, pairs, int(K), offsets, out)
     else:
         _lib.ops().interval_marginals_tol(score_c, v, q, logz, pairs, int(K), offsets, tol[0], tol[1], out)
+        if start is not None and K > 0:
+            before = pairs[:K, 0] < start.index_select(0, _chain_of_rows(offsets, K))
+            out = torch.where(before, torch.zeros_like(out[:K]), out[:K])
     return out[:K]
 
 
@@ -916,16 +965,22 @@ def _packed_on(pairs, offsets, T: int, B: int, device):
     return p.contiguous().to(device, non_blocking=True), o.contiguous().to(device, non_blocking=True), K
 
 
-def posteriors(score, noiseScore) -> Posteriors:
+def posteriors(score, noiseScore, forcedStartPos=None) -> Posteriors:
     """An EXTENSION of the reference's surface: posterior marginals and path entropy of every chain, as a Posteriors namedtuple
     (logZ, entropy, node, begin, end, single, noise) of float32 tensors where the scores live -- without the dense [T, T, B]
-    marginal tensor of forward_backward and without a host sync.  Runs the alpha and beta sweeps itself; no gradient."""
-    _check_inputs(score, noiseScore)
+    marginal tensor of forward_backward and without a host sync.  Runs the alpha and beta sweeps itself; no gradient.
+
+    forcedStartPos: None, or one start frame per chain as decode takes it (a sequence of nBatch ints, IndexError when out of range;
+    or an int32 tensor [nBatch] where the scores live, not range-checked).  The result then describes the model restricted to
+    the frames start .. T-1 of each chain, the one whose MAP path decode(forcedStartPos) returns: logZ is that model's, entropy
+    its path entropy, and node / begin / end / single / noise are exactly 0 before the start."""
+    T, B = _check_inputs(score, noiseScore)
     with torch.no_grad():
-        return _posteriors_raw(_prep(score.detach()), _prep(noiseScore.detach()))
+        score_c, noise_c = _prep(score.detach()), _prep(noiseScore.detach())
+        return _posteriors_raw(score_c, noise_c, None, _start_arg(forcedStartPos, T, B, score_c.device, "posteriors"))
 
 
-def interval_marginals_packed(score, noiseScore, pairs, offsets, tolerance=None) -> torch.Tensor:
+def interval_marginals_packed(score, noiseScore, pairs, offsets, tolerance=None, forcedStartPos=None) -> torch.Tensor:
     """An EXTENSION of the reference's surface: the posterior probability of each given interval, a float32 tensor [K] where the
     scores live.  pairs [K, 2] (begin, end) and offsets [nBatch + 1] as decode_packed returns them (numpy arrays or tensors).
 
@@ -933,30 +988,36 @@ def interval_marginals_packed(score, noiseScore, pairs, offsets, tolerance=None)
     value of (b, e) is M = min(1, the sum of the exact-cell probabilities over the box |b' - b| <= db, |e' - e| <= de): the expected
     number of path intervals that match (b, e) within the tolerance -- for e - b > db + de the probability that one does, the
     quantity a note-level metric with an onset / offset window asks for (include/semicrf_hip.h: semicrf_interval_marginals_tol).
-    None and (0, 0) are the exact-cell probabilities."""
+    None and (0, 0) are the exact-cell probabilities.
+
+    forcedStartPos: as posteriors (None, nBatch ints or an int32 tensor [nBatch]): the probabilities under the model that starts
+    chain c at that frame; an interval with begin < start has probability exactly 0 (with a tolerance: the cells of its box at or
+    behind the start still count)."""
     T, B = _check_inputs(score, noiseScore)
     tol = _tolerance(tolerance, "interval_marginals")
     with torch.no_grad():
         score_c, noise_c = _prep(score.detach()), _prep(noiseScore.detach())
+        start = _start_arg(forcedStartPos, T, B, score_c.device, "interval_marginals")
         p, o, K = _packed_on(pairs, offsets, T, B, score_c.device)
         if _odd_pad(score_c):
             s2, n2 = _pad1(score_c), _pad1(noise_c)
-            logz, v, q = _marginal_inputs(s2, n2)
-            return _interval_marginals_raw(s2, v, q, logz, p, K, torch.cat([o, o[-1:]]), tol)
-        logz, v, q = _marginal_inputs(score_c, noise_c)
-        return _interval_marginals_raw(score_c, v, q, logz, p, K, o, tol)
+            st2 = _pad1(start) if start is not None else None
+            logz, v, q = _marginal_inputs(s2, n2, st2)
+            return _interval_marginals_raw(s2, v, q, logz, p, K, torch.cat([o, o[-1:]]), tol, st2)
+        logz, v, q = _marginal_inputs(score_c, noise_c, start)
+        return _interval_marginals_raw(score_c, v, q, logz, p, K, o, tol, start)
 
 
-def interval_marginals(score, noiseScore, intervals: Intervals, tolerance=None) -> List[List[float]]:
+def interval_marginals(score, noiseScore, intervals: Intervals, tolerance=None, forcedStartPos=None) -> List[List[float]]:
     """An EXTENSION of the reference's surface: the posterior probability of each interval of `intervals` (one list per chain,
     e.g. what decode returns), as a list (len nBatch) of lists of floats in the given order.  tolerance: as
     interval_marginals_packed (None, an int or a pair (onset, offset) of frames in 0..8): the probability that the path holds an
-    interval within that many frames of the given one."""
+    interval within that many frames of the given one.  forcedStartPos: as interval_marginals_packed."""
     T, B = _check_inputs(score, noiseScore)
     _tolerance(tolerance, "interval_marginals")
     pairs, offsets = pack_intervals(intervals, T, B, "cpu", ordered=False)
     K = pairs._semicrf_K
-    out = interval_marginals_packed(score, noiseScore, pairs[:K], offsets, tolerance).cpu().tolist()
+    out = interval_marginals_packed(score, noiseScore, pairs[:K], offsets, tolerance, forcedStartPos).cpu().tolist()
     off = offsets.tolist()
     return [out[off[c]:off[c + 1]] for c in range(B)]
 
@@ -1121,18 +1182,20 @@ def covariance(score, noiseScore, weight, noiseWeight=None):
 # marginal-threshold (posterior) decoding (an extension of the reference's surface)
 # --------------------------------------------------------------------------------------
 
-def _marginal_decode_raw(score_c, noise_c, tau, cap: Optional[int] = None, lvq=None, tol: Tuple[int, int] = (0, 0)):
+def _marginal_decode_raw(score_c, noise_c, tau, cap: Optional[int] = None, lvq=None, tol: Tuple[int, int] = (0, 0), start=None):
     """Enqueue the sweeps (unless lvq = (logZ, v, q) is given) and semicrf_marginal_decode (semicrf_marginal_decode_tol for a
     tolerance tol = (onset, offset) other than (0, 0)); no host sync.  tau: a float32 tensor of 1 value or one per chain, where the
     scores live.  Returns device tensors (pairs [cap, 2], offsets [B+1], probs [cap]); offsets is exact even past cap (default 2 T
-    per chain: the bound for a threshold > 0.5 without a tolerance)."""
+    per chain: the bound for a threshold > 0.5 without a tolerance).  start (int32 [B] on the device, or None): the sweeps run from
+    that forced start (_marginal_inputs_from)."""
     if _odd_pad(score_c) and lvq is None:
         t2 = tau if tau.numel() == 1 else torch.cat([tau, tau.new_full((1,), float("inf"))])     # the ghost chain selects nothing
-        pairs, offsets, probs = _marginal_decode_raw(_pad1(score_c), _pad1(noise_c), t2, cap, None, tol)
+        st2 = _pad1(start) if start is not None else None
+        pairs, offsets, probs = _marginal_decode_raw(_pad1(score_c), _pad1(noise_c), t2, cap, None, tol, st2)
         return pairs, offsets[:-1], probs  # the ghost chain is last: its intervals lie behind offsets[B]
     T, B = score_c.shape[0], score_c.shape[2]
     dev = score_c.device
-    logz, v, q = _marginal_inputs(score_c, noise_c) if lvq is None else lvq
+    logz, v, q = _marginal_inputs(score_c, noise_c, start) if lvq is None else lvq
     cap = max(int(cap), 1) if cap is not None else 2 * T * B
     pairs = torch.empty(cap, 2, dtype=torch.int32, device=dev)
     probs = torch.empty(cap, dtype=torch.float32, device=dev)
@@ -1143,7 +1206,38 @@ def _marginal_decode_raw(score_c, noise_c, tau, cap: Optional[int] = None, lvq=N
     else:
         ws = _lib.workspace(_lib.OP_MARGINAL_DECODE_TOL, T, B, dev)
         _lib.ops().marginal_decode_tol(score_c, noise_c, v, q, logz, tau, tol[0], tol[1], pairs, probs, offsets, ws)
+        if start is not None:
+            return _drop_before_start(pairs, offsets, probs, start)
     return pairs, offsets, probs
+
+
+def _chain_of_rows(offsets, n: int):
+    """The chain of each of the first n rows of a packed list (rows behind offsets[B] get the last chain); no host sync."""
+    B = offsets.shape[0] - 1
+    rows = torch.arange(n, device=offsets.device)
+    return torch.bucketize(rows, offsets[1:].long(), right=True).clamp_(max=B - 1)
+
+
+def _drop_before_start(pairs, offsets, probs, start):
+    """A tolerance-aware lattice from a forced start: the box of a cell with begin < start still holds cells at or behind the
+    start, so semicrf_marginal_decode_tol (which knows nothing of the start) can select it; the model has no such interval.  Drops
+    those rows and packs the rest in order, on the device and without a host sync (a prefix sum over the rows).
+    The kernel's markers in offsets[B] are handed on untouched: -1 (alpha's last row holds NaN: the result is invalid) and a count
+    > cap (a truncated lattice: the count is the size to come back with).  In both cases the ORIGINAL offsets are returned next to
+    the filtered pairs / probs, which then do not belong together -- that is harmless only because nothing reads such a result:
+    every caller raises on the first and retries on the second."""
+    cap, B = pairs.shape[0], offsets.shape[0] - 1
+    total = offsets[-1]
+    rows = torch.arange(cap, device=pairs.device)
+    chain = _chain_of_rows(offsets, cap)
+    keep = (rows < total) & (pairs[:, 0] >= start.index_select(0, chain))
+    dest = torch.where(keep, torch.cumsum(keep, 0) - 1, torch.full_like(rows, cap))      # dropped rows land in a spare last row
+    pairs_f = torch.empty(cap + 1, 2, dtype=pairs.dtype, device=pairs.device).index_copy_(0, dest, pairs)[:cap]
+    probs_f = torch.empty(cap + 1, dtype=probs.dtype, device=probs.device).index_copy_(0, dest, probs)[:cap]
+    counts = torch.zeros(B + 1, dtype=torch.int64, device=pairs.device).index_add_(0, chain + 1, keep.long())
+    offsets_f = torch.cumsum(counts, 0).to(offsets.dtype)
+    fits = (total >= 0) & (total <= cap)
+    return pairs_f, torch.where(fits, offsets_f, offsets), probs_f
 
 
 def _threshold_tensor(threshold, B: int, device, name: str = "decode_marginal") -> torch.Tensor:
@@ -1160,7 +1254,7 @@ def _threshold_tensor(threshold, B: int, device, name: str = "decode_marginal") 
     return torch.full((1,), t, dtype=torch.float32, device=device)
 
 
-def decode_marginal_packed(score, noiseScore, threshold, tolerance=None):
+def decode_marginal_packed(score, noiseScore, threshold, tolerance=None, forcedStartPos=None):
     """An EXTENSION of the reference's surface: every interval whose posterior probability P((begin, end) on the path | score) is
     >= threshold, as host arrays like decode_packed plus the probabilities: (pairs int32 [K, 2], offsets int32 [nBatch + 1],
     probs float32 [K]); chain c owns pairs[offsets[c]:offsets[c + 1]], ascending by (begin, end).  probs are the values
@@ -1178,18 +1272,23 @@ def decode_marginal_packed(score, noiseScore, threshold, tolerance=None):
     every interval that the path matches within the tolerance with probability >= threshold.  That set is NO LONGER a path, even
     for threshold > 0.5 -- the neighbours of a confident interval pass together with it (up to (2 onset + 1)(2 offset + 1) cells
     per note): it is a lattice, and decode_mbr(threshold, tolerance) is the call that returns one path.  A single chain runs with a
-    ghost chain appended, as without a tolerance; the ghost's cells never show."""
+    ghost chain appended, as without a tolerance; the ghost's cells never show.
+
+    forcedStartPos: as posteriors (None, nBatch ints or an int32 tensor [nBatch]): the probabilities are those of the model that
+    starts chain c at that frame; only intervals with begin >= start are returned, and probs stay interval_marginals(...,
+    forcedStartPos=...)'s values bit for bit."""
     T, B = _check_inputs(score, noiseScore)
     tol = _tolerance(tolerance, "decode_marginal")
     with torch.no_grad():
         score_c, noise_c = _prep(score.detach()), _prep(noiseScore.detach())
         tau = _threshold_tensor(threshold, B, score_c.device)
-        lvq = None if _odd_pad(score_c) else _marginal_inputs(score_c, noise_c)    # (a single chain: the raw call pads and sweeps)
-        pairs, offsets, probs = _marginal_decode_raw(score_c, noise_c, tau, None, lvq, tol)
+        start = _start_arg(forcedStartPos, T, B, score_c.device, "decode_marginal")
+        lvq = None if _odd_pad(score_c) else _marginal_inputs(score_c, noise_c, start)    # (a single chain: the raw call pads and sweeps)
+        pairs, offsets, probs = _marginal_decode_raw(score_c, noise_c, tau, None, lvq, tol, start)
         off_h = offsets.cpu()                      # the one host sync
         if int(off_h[-1]) > pairs.shape[0]:
             # more cells than 2 T per chain (a threshold <= 0.5, a tolerance): once more with the exact size -- never a silent truncation
-            pairs, offsets, probs = _marginal_decode_raw(score_c, noise_c, tau, int(off_h[-1]), lvq, tol)
+            pairs, offsets, probs = _marginal_decode_raw(score_c, noise_c, tau, int(off_h[-1]), lvq, tol, start)
             off_h = offsets.cpu()
         total = int(off_h[-1])
         if total < 0:
@@ -1200,12 +1299,12 @@ def decode_marginal_packed(score, noiseScore, threshold, tolerance=None):
         return pairs[:total].cpu().numpy(), off_h.numpy(), probs[:total].cpu().numpy()
 
 
-def decode_marginal(score, noiseScore, threshold, tolerance=None):
+def decode_marginal(score, noiseScore, threshold, tolerance=None, forcedStartPos=None):
     """An EXTENSION of the reference's surface: (paths, probs) -- paths an Intervals (per chain the list of (begin, end) whose
     posterior probability is >= threshold, ascending by (begin, end): the type decode returns), probs per chain the list of those
     probabilities.  Arguments and properties as decode_marginal_packed (with a tolerance the lists are a lattice, not a path)."""
     T, B = _check_inputs(score, noiseScore)
-    pairs, offsets, probs = decode_marginal_packed(score, noiseScore, threshold, tolerance)
+    pairs, offsets, probs = decode_marginal_packed(score, noiseScore, threshold, tolerance, forcedStartPos)
     paths = unpack_intervals(torch.from_numpy(pairs), torch.from_numpy(offsets), T)
     pl, off = probs.tolist(), offsets.tolist()
     return paths, [pl[off[c]:off[c + 1]] for c in range(B)]
@@ -1230,7 +1329,47 @@ def _mbr_select_raw(pairs, probs, offsets, T: int, tau):
     return pairs_out, offsets_out, probs_out, gain
 
 
-def decode_mbr_packed(score, noiseScore, threshold, tolerance=None):
+def _mbr_decode_raw(score_c, noise_c, tau, threshold, tol: Tuple[int, int] = (0, 0), start=None, retry: bool = True):
+    """The device part of decode_mbr: the sweeps (from `start`, int32 [B] on the device, when given), semicrf_marginal_decode(_tol)
+    into a device lattice and semicrf_mbr_select on it.  Returns (pairs [2 T B, 2], offsets [B+1], probs [2 T B], gain [B],
+    offsets_host): four device tensors and the host copy of the offsets (None with retry=False); offsets[B] = -1 marks an invalid
+    result.
+    tau: the float32 threshold tensor (1 value or one per chain); threshold: the caller's scalar (a Python float: it sizes the
+    lattice) or anything else (a tensor: 2 T cells per chain).  Without a tolerance and with a scalar threshold the lattice bound
+    (floor(1 / threshold) + 1) T cells per chain is exact -- nothing can be truncated -- and retry=False enqueues everything
+    without a host sync.  retry=True reads the offsets once (the one host sync; returned as the fifth element) and, where the
+    lattice did not fit, runs both kernels once more with the exact size: never a silent truncation."""
+    T, B = score_c.shape[0], score_c.shape[2]
+    pad = _odd_pad(score_c)
+    lvq = None if pad else _marginal_inputs(score_c, noise_c, start)
+    nB = B + 1 if pad else B                   # (a single chain: the raw call pads and sweeps; the ghost's cells come last)
+    if not isinstance(threshold, (int, float, np.floating, np.integer)):
+        cap = 2 * T * nB
+    elif tol != (0, 0):
+        # a box holds up to 2 (2 db + 1)(2 de + 1) of mass per begin (every column of it <= 1 in intervals + 1 as a singleton,
+        # every cell in 2 de + 1 boxes of a begin): at most that / tau cells per begin, or the whole column; start from 2 T per
+        # chain when that is smaller (it is, for every tolerance > 0 and T > 4) and let the retry below take the exact count
+        per_begin = int(2 * (2 * tol[0] + 1) * (2 * tol[1] + 1) / float(threshold)) + 1
+        cap = min(min(per_begin * T, T * (T + 1) // 2), 2 * T) * nB
+    else:                                      # sum_{e > b} m(e, b) <= 1: at most floor(1 / tau) + 1 cells per begin
+        cap = min((int(1.0 / float(threshold)) + 1) * T, T * (T + 1) // 2) * nB
+    lat = _marginal_decode_raw(score_c, noise_c, tau, cap, lvq, tol, start)
+    pairs, offsets, probs, gain = _mbr_select_raw(lat[0], lat[2], lat[1], T, tau)
+    off_h = None
+    if retry:
+        off_h = offsets.cpu()                  # the one host sync
+        if int(off_h[-1]) < 0:
+            lat_total = int(lat[1][-1])
+            if lat_total > lat[0].shape[0]:
+                # the lattice did not fit (a threshold tensor with small values, a tolerance): once more with the exact size -- never
+                # a silent truncation
+                lat = _marginal_decode_raw(score_c, noise_c, tau, lat_total + (cap // nB if pad else 0), lvq, tol, start)
+                pairs, offsets, probs, gain = _mbr_select_raw(lat[0], lat[2], lat[1], T, tau)
+                off_h = offsets.cpu()
+    return pairs, offsets, probs, gain, off_h
+
+
+def decode_mbr_packed(score, noiseScore, threshold, tolerance=None, forcedStartPos=None):
     """An EXTENSION of the reference's surface: the minimum-Bayes-risk PATH for the gain (1 - threshold) per correct and -threshold
     per wrong interval, at ANY threshold: among all paths of a chain the one that maximises the sum over its intervals of
     (P((begin, end) on the path | score) - threshold).  Returns host arrays (pairs int32 [K, 2], offsets int32 [nBatch + 1], probs
@@ -1250,36 +1389,17 @@ def decode_mbr_packed(score, noiseScore, threshold, tolerance=None):
     the true path holds an interval within the tolerance of the chosen one -- and probs are the M of its intervals, bit for bit.
     This is the call that turns the tolerance-aware set of decode_marginal (a lattice: neighbouring cells pass together) into one
     path: a note whose onset the model spreads over two frames is returned once, with the probability of the pair.  A single chain
-    runs with a ghost chain appended, as without a tolerance."""
+    runs with a ghost chain appended, as without a tolerance.
+
+    forcedStartPos: as posteriors (None, nBatch ints or an int32 tensor [nBatch]): the MBR path of the model that starts chain c at
+    that frame -- the posterior counterpart of decode(forcedStartPos); every returned interval has begin >= start."""
     T, B = _check_inputs(score, noiseScore)
     tol = _tolerance(tolerance, "decode_mbr")
     with torch.no_grad():
         score_c, noise_c = _prep(score.detach()), _prep(noiseScore.detach())
         tau = _threshold_tensor(threshold, B, score_c.device, "decode_mbr")
-        pad = _odd_pad(score_c)
-        lvq = None if pad else _marginal_inputs(score_c, noise_c)
-        nB = B + 1 if pad else B                   # (a single chain: the raw call pads and sweeps; the ghost's cells come last)
-        if isinstance(threshold, torch.Tensor):
-            cap = 2 * T * nB
-        elif tol != (0, 0):
-            # a box holds up to 2 (2 db + 1)(2 de + 1) of mass per begin (every column of it <= 1 in intervals + 1 as a singleton,
-            # every cell in 2 de + 1 boxes of a begin): at most that / tau cells per begin, or the whole column; start from 2 T per
-            # chain when that is smaller (it is, for every tolerance > 0 and T > 4) and let the retry below take the exact count
-            per_begin = int(2 * (2 * tol[0] + 1) * (2 * tol[1] + 1) / float(threshold)) + 1
-            cap = min(min(per_begin * T, T * (T + 1) // 2), 2 * T) * nB
-        else:                                      # sum_{e > b} m(e, b) <= 1: at most floor(1 / tau) + 1 cells per begin
-            cap = min((int(1.0 / float(threshold)) + 1) * T, T * (T + 1) // 2) * nB
-        lat = _marginal_decode_raw(score_c, noise_c, tau, cap, lvq, tol)
-        pairs, offsets, probs, gain = _mbr_select_raw(lat[0], lat[2], lat[1], T, tau)
-        off_h = offsets.cpu()                      # the one host sync
-        if int(off_h[-1]) < 0:
-            lat_total = int(lat[1][-1])
-            if lat_total > lat[0].shape[0]:
-                # the lattice did not fit (a threshold tensor with small values, a tolerance): once more with the exact size -- never
-                # a silent truncation
-                lat = _marginal_decode_raw(score_c, noise_c, tau, lat_total + (cap // nB if pad else 0), lvq, tol)
-                pairs, offsets, probs, gain = _mbr_select_raw(lat[0], lat[2], lat[1], T, tau)
-                off_h = offsets.cpu()
+        start = _start_arg(forcedStartPos, T, B, score_c.device, "decode_mbr")
+        pairs, offsets, probs, gain, off_h = _mbr_decode_raw(score_c, noise_c, tau, threshold, tol, start)     # (its one host sync)
         total = int(off_h[-1])
         if total < 0:
             _lib.async_error()                     # consumed here: the next call must not report this time-out again
@@ -1289,12 +1409,12 @@ def decode_mbr_packed(score, noiseScore, threshold, tolerance=None):
         return pairs[:total].cpu().numpy(), off_h.numpy(), probs[:total].cpu().numpy(), gain.cpu().numpy()
 
 
-def decode_mbr(score, noiseScore, threshold, tolerance=None):
+def decode_mbr(score, noiseScore, threshold, tolerance=None, forcedStartPos=None):
     """An EXTENSION of the reference's surface: (paths, probs, gain) -- paths an Intervals (per chain the minimum-Bayes-risk path
     at `threshold`, the type decode returns), probs per chain the list of its intervals' posterior probabilities, gain a float32
     numpy [nBatch].  Arguments and properties as decode_mbr_packed (tolerance: the onset / offset window in frames)."""
     T, B = _check_inputs(score, noiseScore)
-    pairs, offsets, probs, gain = decode_mbr_packed(score, noiseScore, threshold, tolerance)
+    pairs, offsets, probs, gain = decode_mbr_packed(score, noiseScore, threshold, tolerance, forcedStartPos)
     paths = unpack_intervals(torch.from_numpy(pairs), torch.from_numpy(offsets), T)
     pl, off = probs.tolist(), offsets.tolist()
     return paths, [pl[off[c]:off[c + 1]] for c in range(B)], gain
@@ -1507,20 +1627,23 @@ class NeuralSemiCRFInterval:
         the Python lists are built -- see the module-level viterbi_nbest_packed."""
         return viterbi_nbest_packed(self.score, self.noiseScore, k, forcedStartPos, bool(forward))
 
-    def posteriors(self):
+    def posteriors(self, forcedStartPos=None):
         """An EXTENSION of the reference's surface: a Posteriors namedtuple (logZ, entropy, node, begin, end, single, noise) of
-        float32 tensors where the scores live -- see the module-level posteriors.  No host sync, no gradient."""
-        return posteriors(self.score, self.noiseScore)
+        float32 tensors where the scores live -- see the module-level posteriors.  No host sync, no gradient.  forcedStartPos (as
+        decode's, or an int32 tensor [nBatch] on the device): the posterior of the model restricted to the frames from each chain's
+        start on -- the one decode(forcedStartPos) maximises; the same keyword on interval_marginals, decode_marginal, decode_mbr
+        and their _packed forms."""
+        return posteriors(self.score, self.noiseScore, forcedStartPos)
 
-    def interval_marginals(self, intervals, tolerance=None):
+    def interval_marginals(self, intervals, tolerance=None, forcedStartPos=None):
         """An EXTENSION of the reference's surface: the posterior probability of each interval of `intervals` (e.g. decode()'s
         result), a list (len nBatch) of lists of floats in the given order.  tolerance (None, an int or (onset, offset) in frames,
         0..8): the probability of an interval within that window -- see the module-level interval_marginals_packed."""
-        return interval_marginals(self.score, self.noiseScore, intervals, tolerance)
+        return interval_marginals(self.score, self.noiseScore, intervals, tolerance, forcedStartPos)
 
-    def interval_marginals_packed(self, pairs, offsets, tolerance=None):
+    def interval_marginals_packed(self, pairs, offsets, tolerance=None, forcedStartPos=None):
         """`interval_marginals` on decode_packed's arrays (numpy or tensors): a float32 tensor [K] where the scores live."""
-        return interval_marginals_packed(self.score, self.noiseScore, pairs, offsets, tolerance)
+        return interval_marginals_packed(self.score, self.noiseScore, pairs, offsets, tolerance, forcedStartPos)
 
     def expectation(self, weight, noiseWeight=None):
         """An EXTENSION of the reference's surface: E_p[W] [nBatch] of the additive path functional given by weight [T, T, nBatch]
@@ -1537,31 +1660,31 @@ class NeuralSemiCRFInterval:
         Hessian of logZ times (weight, noiseWeight) -- see the module-level covariance.  No gradient."""
         return covariance(self.score, self.noiseScore, weight, noiseWeight)
 
-    def decode_marginal(self, threshold, tolerance=None):
+    def decode_marginal(self, threshold, tolerance=None, forcedStartPos=None):
         """An EXTENSION of the reference's surface: (paths, probs) -- every interval whose posterior probability is >= threshold
         (a float in (0, 1] or a float tensor [nBatch]; no default), per chain ascending by (begin, end), and those probabilities.
         For threshold > 0.5 each chain's result is a path (plugs into evalPath / logProb) -- see the module-level
         decode_marginal_packed.  With a tolerance (None, an int or (onset, offset) in frames, 0..8) the result is a lattice, not a
         path: decode_mbr is the call that returns one.  No gradient."""
-        return decode_marginal(self.score, self.noiseScore, threshold, tolerance)
+        return decode_marginal(self.score, self.noiseScore, threshold, tolerance, forcedStartPos)
 
-    def decode_marginal_packed(self, threshold, tolerance=None):
+    def decode_marginal_packed(self, threshold, tolerance=None, forcedStartPos=None):
         """`decode_marginal` as host arrays (pairs int32 [K, 2], offsets int32 [nBatch + 1], probs float32 [K]) before the Python
         lists are built; pairs / offsets feed interval_marginals_packed and attributes.attribute_input_packed as they are."""
-        return decode_marginal_packed(self.score, self.noiseScore, threshold, tolerance)
+        return decode_marginal_packed(self.score, self.noiseScore, threshold, tolerance, forcedStartPos)
 
-    def decode_mbr(self, threshold, tolerance=None):
+    def decode_mbr(self, threshold, tolerance=None, forcedStartPos=None):
         """An EXTENSION of the reference's surface: (paths, probs, gain) -- per chain the minimum-Bayes-risk PATH at `threshold` (the
         path maximising the sum over its intervals of (posterior probability - threshold); a float in (0, 1] or a float tensor
         [nBatch]; no default), its intervals' probabilities and the maximised sum.  Always a path (plugs into evalPath / logProb),
         also for threshold <= 0.5 where decode_marginal gives a lattice -- see the module-level decode_mbr_packed.  tolerance (None,
         an int or (onset, offset) in frames, 0..8): the probabilities count an interval within that window.  No gradient."""
-        return decode_mbr(self.score, self.noiseScore, threshold, tolerance)
+        return decode_mbr(self.score, self.noiseScore, threshold, tolerance, forcedStartPos)
 
-    def decode_mbr_packed(self, threshold, tolerance=None):
+    def decode_mbr_packed(self, threshold, tolerance=None, forcedStartPos=None):
         """`decode_mbr` as host arrays (pairs int32 [K, 2], offsets int32 [nBatch + 1], probs float32 [K], gain float32 [nBatch])
         before the Python lists are built."""
-        return decode_mbr_packed(self.score, self.noiseScore, threshold, tolerance)
+        return decode_mbr_packed(self.score, self.noiseScore, threshold, tolerance, forcedStartPos)
 
     def evalPath(self, intervals):
         """compute the unnormalized score"""

@@ -96,6 +96,7 @@ size_t persist_workspace_bytes(int T, int B);
 size_t sample_workspace_bytes(int T, int nB);
 size_t posterior_workspace_bytes(int T, int B);
 size_t expectation_workspace_bytes(int T, int B);
+void launch_alpha_from(const float* score, const float* noise, const int* start, int T, int B, float* v, float* logZ, hipStream_t stream);
 void launch_expectation(const float* score, const float* noise, const float* weight, const float* nweight, const float* v, const float* q,
                         int T, int B, float* E, float* H, void* ws, hipStream_t stream);
 void launch_covariance(const float* score, const float* noise, const float* weight, const float* nweight, const float* gout, int T, int B,
@@ -578,6 +579,18 @@ int semicrf_expectation(const float* score, const float* noise, const float* wei
     if (ws_bytes < expectation_workspace_bytes(T, B)) { set_error("workspace too small for expectation"); return SEMICRF_EWORKSPACE; }
     launch_expectation(score, noise, weight ? weight : score, noiseWeight, v, q, T, B, E, H, ws, (hipStream_t)stream);
     SEMICRF_CHECK_LAUNCH("semicrf_expectation");
+    return SEMICRF_OK;
+}
+
+int semicrf_alpha_from(const float* score, const float* noise, const int32_t* start, int T, int B, float* v, float* logZ, void* ws,
+                       size_t ws_bytes, semicrf_stream_t stream)
+{
+    (void)ws; (void)ws_bytes;                      // no workspace: NULL is fine
+    if (int rc = check_common(score, noise, T, B)) return rc;
+    SEMICRF_CHECK_ARG(start != nullptr, "start is NULL");
+    SEMICRF_CHECK_ARG(v && logZ, "an output is NULL");
+    launch_alpha_from(score, noise, start, T, B, v, logZ, (hipStream_t)stream);
+    SEMICRF_CHECK_LAUNCH("semicrf_alpha_from");
     return SEMICRF_OK;
 }
 

@@ -86,6 +86,35 @@ void logz_fwd(const float* score, const float* noise, int T, int B, float* logZ,
     }
 }
 
+// alpha sweep from a forced start (semicrf_alpha_from): chain c runs on the frames start[c] .. T-1, v = -inf before.
+// A thread owns whole chains (the recurrence of a chain is sequential and short next to logz_fwd's: no row-wise sharing).
+void alpha_from(const float* score, const float* noise, const int32_t* start, int T, int B, float* v, float* logZ)
+{
+    const size_t Bs = (size_t)B;
+#pragma omp parallel for schedule(static)
+    for (int c = 0; c < B; ++c) {
+        const int s = start[c];
+        if (s < 0 || s > T - 1) {
+            for (int t = 0; t < T; ++t) v[(size_t)t * Bs + c] = NAN;
+            logZ[c] = NAN;
+            continue;
+        }
+        for (int t = 0; t < s; ++t) v[(size_t)t * Bs + c] = -INFINITY;
+        for (int t = s; t < T; ++t) {
+            const float* row = score + (size_t)t * T * Bs + c;
+            float a = softplus(row[(size_t)t * Bs]);
+            if (t > s) {
+                Lse acc{-INFINITY, 0.0};
+                acc.push(v[(size_t)(t - 1) * Bs + c] + noise[(size_t)(t - 1) * Bs + c]);
+                for (int b = s; b < t; ++b) acc.push(v[(size_t)b * Bs + c] + row[(size_t)b * Bs]);
+                a += acc.value();
+            }
+            v[(size_t)t * Bs + c] = a;
+        }
+        logZ[c] = v[(size_t)(T - 1) * Bs + c];
+    }
+}
+
 // beta sweep by frames (the flipped half of forward_backward :386-414) and, when dScore is given, the marginals
 // (:424-447) times gout (:469-472).  Row e is visited once, right after q[e] is final: its cells are pushed into the
 // accumulators of the frames t < e and turned into marginals in the same pass.

@@ -5,6 +5,8 @@
 
 namespace semicrf_cpu {
 void logz_fwd(const float* score, const float* noise, int T, int B, float* logZ, float* v /* [T][B], required */);
+// alpha of the semi-CRF restricted to the frames start[c] .. T-1 (semicrf_alpha_from); a start out of range gives a NaN column
+void alpha_from(const float* score, const float* noise, const int32_t* start, int T, int B, float* v /* [T][B] */, float* logZ);
 void logz_bwd(const float* score, const float* noise, const float* v, const float* logZ, const float* gout, int T, int B,
               float* dScore /* or null: beta only */, float* dNoise /* or null */, float* q /* [T][B], required */);
 void viterbi(const float* score, const float* noise, int T, int B, const int32_t* start, int forward, int32_t* pairs, int64_t cap,

@@ -112,6 +112,14 @@ void beta(Tensor score, Tensor noise, Tensor out, Tensor ws)
     check(semicrf_beta(cfp(score), cfp(noise), d.T, d.B, f32w(out, (int64_t)d.T * d.B, "beta"), bytes(ws, "ws"), (size_t)ws.numel(), c.stream),
           "semicrf_beta");
 }
+void alpha_from(Tensor score, Tensor noise, Tensor start, Tensor v, Tensor logZ, Tensor ws)
+{
+    Ctx c(score); c.same(score, noise, start, v, logZ, ws);
+    const Dims d = crf_dims(score, noise);
+    check(semicrf_alpha_from(cfp(score), cfp(noise), i32(start, d.B, "start"), d.T, d.B, f32w(v, (int64_t)d.T * d.B, "v"),
+                             f32w(logZ, d.B, "logZ"), bytes(ws, "ws"), (size_t)ws.numel(), c.stream),
+          "semicrf_alpha_from");
+}
 void viterbi(Tensor score, Tensor noise, Tensor start, bool has_start, bool forward, Tensor pairs, Tensor offsets, Tensor ws)
 {
     Ctx c(score); c.same(score, noise, pairs, offsets, ws);
@@ -404,6 +412,13 @@ void beta_cpu(Tensor score, Tensor noise, Tensor out, Tensor ws)
     all_cpu(score, noise, out);
     const Dims d = crf_dims(score, noise);
     semicrf_cpu::logz_bwd(cfp(score), cfp(noise), nullptr, nullptr, nullptr, d.T, d.B, nullptr, nullptr, f32w(out, (int64_t)d.T * d.B, "beta"));
+}
+void alpha_from_cpu(Tensor score, Tensor noise, Tensor start, Tensor v, Tensor logZ, Tensor ws)
+{
+    all_cpu(score, noise, start, v, logZ);
+    const Dims d = crf_dims(score, noise);
+    semicrf_cpu::alpha_from(cfp(score), cfp(noise), i32(start, d.B, "start"), d.T, d.B, f32w(v, (int64_t)d.T * d.B, "v"),
+                            f32w(logZ, d.B, "logZ"));
 }
 void viterbi_cpu(Tensor score, Tensor noise, Tensor start, bool has_start, bool forward, Tensor pairs, Tensor offsets, Tensor ws)
 {
@@ -816,6 +831,7 @@ STABLE_TORCH_LIBRARY(semicrf, m)
     m.def("logz_bwd(Tensor score, Tensor noise, Tensor v, Tensor logZ, Tensor gout, Tensor(a!) dScore, Tensor(b!) dNoise, Tensor(c!) q, "
           "bool want_q, int flags, Tensor(d!) ws) -> ()");
     m.def("beta(Tensor score, Tensor noise, Tensor(a!) out, Tensor(b!) ws) -> ()");
+    m.def("alpha_from(Tensor score, Tensor noise, Tensor start, Tensor(a!) v, Tensor(b!) logz, Tensor(c!) ws) -> ()");
     m.def("viterbi(Tensor score, Tensor noise, Tensor start, bool has_start, bool forward, Tensor(a!) pairs, Tensor(b!) offsets, "
           "Tensor(c!) ws) -> ()");
     m.def("sample(Tensor score, Tensor noise, Tensor v, int k0, int nSample, int key, Tensor end, bool has_end, Tensor(a!) pairs, "
@@ -883,6 +899,7 @@ STABLE_TORCH_LIBRARY_IMPL(semicrf, CPU, m)
     m.impl("logz_fwd", TORCH_BOX(&logz_fwd_cpu));
     m.impl("logz_bwd", TORCH_BOX(&logz_bwd_cpu));
     m.impl("beta", TORCH_BOX(&beta_cpu));
+    m.impl("alpha_from", TORCH_BOX(&alpha_from_cpu));
     m.impl("viterbi", TORCH_BOX(&viterbi_cpu));
     m.impl("sample", TORCH_BOX(&sample_cpu));
     m.impl("viterbi_nbest", TORCH_BOX(&viterbi_nbest_cpu));
@@ -906,6 +923,7 @@ STABLE_TORCH_LIBRARY_IMPL(semicrf, CUDA, m)
     m.impl("logz_fwd", TORCH_BOX(&logz_fwd));
     m.impl("logz_bwd", TORCH_BOX(&logz_bwd));
     m.impl("beta", TORCH_BOX(&beta));
+    m.impl("alpha_from", TORCH_BOX(&alpha_from));
     m.impl("viterbi", TORCH_BOX(&viterbi));
     m.impl("sample", TORCH_BOX(&sample));
     m.impl("viterbi_nbest", TORCH_BOX(&viterbi_nbest));

@@ -178,6 +178,10 @@ class SegmentTranscriber(nn.Module):
         self.capFactor, self.capFloor = 1.5, 4096     # transcribe_many: rows for the heads = capFactor x the largest count seen, at least capFloor
         self.projection = "separate"    # "merged": the scorer's two projections as one (see decode_step); scores then differ from
                                         # the reference's by fp32 reassociation, so the default keeps its operation order
+        self.decoder = "viterbi"        # "mbr": every segment is decoded by decode_mbr from its forced start (the posterior of the
+                                        # model restricted to the frames from the start on) instead of the MAP path
+        self.mbrThreshold = 0.5         # decoder == "mbr": the threshold of decode_mbr, a float in (0, 1]
+        self.mbrTolerance = None        # decoder == "mbr": decode_mbr's tolerance (None, an int or (onset, offset) in frames)
         self._merged = None
         self.velocityPredictor = _head(size * 3, velocityPredictorHiddenSize, 128, velocityDropoutProb)           # :109-115
         self.refinedOFPredictor = _head(size * 3, refinedOFPredictorHiddenSize, 4, refinedOFDropoutProb)          # :119-125
@@ -194,9 +198,16 @@ class SegmentTranscriber(nn.Module):
     # one step on the device
     # ------------------------------------------------------------------------------------------------------------------
     def _decode_packed(self, ctxBatch: torch.Tensor, start: Optional[torch.Tensor]):
-        """Scorer and Viterbi decode of one batch of segments, nothing synchronised: ctxBatch [F, P, T, D] -> the decoded paths
-        packed on the device, (pairs int32 [cap, 2], offsets int32 [F*P + 1]), chain-indexed (c = segment * P + symbol).  start:
-        int32 [F*P] forced start positions on the device or None."""
+        """Scorer and decode of one batch of segments: ctxBatch [F, P, T, D] -> the decoded paths packed on the device,
+        (pairs int32 [cap, 2], offsets int32 [F*P + 1]), chain-indexed (c = segment * P + symbol).  start: int32 [F*P] forced start
+        positions on the device or None (frame 0 for every chain).
+
+        decoder "viterbi" (the default): the MAP path from the forced start, nothing synchronised.  "mbr": decode_mbr's path at
+        mbrThreshold from the same forced start (CRF._mbr_decode_raw on semicrf_alpha_from's alpha); without a tolerance the
+        lattice bound is exact and nothing is synchronised either; with mbrTolerance set the lattice may need its retry, which
+        reads one count from the device (transcribe_many then runs its synchronous route)."""
+        if self.decoder not in ("viterbi", "mbr"):
+            raise ValueError(f"decoder must be 'viterbi' or 'mbr', not {self.decoder!r}")
         Fn, P, T, D = ctxBatch.shape
         B = Fn * P
         dev = ctxBatch.device
@@ -221,6 +232,8 @@ class SegmentTranscriber(nn.Module):
             finally:
                 self.scorer.slotPitch = None
             score, noise = S.flatten(-2, -1), b.flatten(-2, -1)
+        if self.decoder == "mbr":
+            return self._decode_mbr(score, noise, start, Fn, P, pitch)
         if pitch != P:
             real, _ = slot_maps(Fn, P, pitch, dev)
             start_s = None
@@ -232,6 +245,36 @@ class SegmentTranscriber(nn.Module):
         else:
             pairs, offsets = _nsci._viterbi_raw(score, noise, start, False)              # transcribeFrames :549
         return pairs, offsets
+
+    def _invalid_decode_message(self) -> str:
+        """What offsets[-1] = -1 behind _decode_packed means, by decoder."""
+        if self.decoder == "mbr":
+            return ("decoder 'mbr': the decode result is invalid -- alpha holds NaN in its last row (the scores hold NaN, or a forced "
+                    "start lies outside [0, T-1]), or the beta sweep's bounded hand-off wait timed out on the device")
+        return "semicrf_viterbi: a bounded hand-off wait timed out on the device; the decode result is invalid"
+
+    def _decode_mbr(self, score, noise, start: Optional[torch.Tensor], Fn: int, P: int, pitch: int):
+        """The "mbr" branch of _decode_packed on the scorer's output (slot layout when pitch != P): (pairs, offsets) by chain, in
+        decode_packed's format.  Ghost slots get start 0 and the threshold +inf (they select nothing), and the offsets are
+        re-indexed by chain exactly as the Viterbi branch does."""
+        dev = score.device
+        thr = _nsci._threshold_tensor(self.mbrThreshold, Fn * P, dev, "decoder 'mbr'")
+        if thr.numel() != 1:
+            raise ValueError("mbrThreshold must be a float in (0, 1]")
+        tol = _nsci._tolerance(self.mbrTolerance, "decoder 'mbr'")
+        nslot = Fn * pitch
+        if start is None:
+            start = torch.zeros(Fn * P, dtype=torch.int32, device=dev)
+        tau = thr
+        if pitch != P:
+            real, _ = slot_maps(Fn, P, pitch, dev)
+            start = torch.zeros(nslot, dtype=torch.int32, device=dev).index_copy_(0, real, start)
+            tau = torch.full((nslot,), float("inf"), dtype=torch.float32, device=dev).index_fill_(0, real, float(self.mbrThreshold))
+        pairs, offsets_s, _, _, _ = _nsci._mbr_decode_raw(score.contiguous(), noise.contiguous(), tau, float(self.mbrThreshold), tol, start,
+                                                       retry=tol != (0, 0))
+        if pitch != P:
+            return pairs, torch.cat([offsets_s.index_select(0, real), offsets_s[-1:]])
+        return pairs, offsets_s
 
     @torch.no_grad()
     def decode_step(self, ctxBatch: torch.Tensor, start: Optional[torch.Tensor], beginTime: torch.Tensor, lastFrameIdx: int,
@@ -268,7 +311,7 @@ class SegmentTranscriber(nn.Module):
             K = int(offsets[-1])                                                         # the step's one host sync
             if K < 0:
                 _lib.async_error()               # consumed here: the next library call must not report this time-out again
-                raise RuntimeError("semicrf_viterbi: a bounded hand-off wait timed out on the device; the decode result is invalid")
+                raise RuntimeError(self._invalid_decode_message())
         lastP = torch.empty(B, dtype=torch.int32, device=dev)
         nextStart = torch.empty(B, dtype=torch.int32, device=dev)
         if K == 0:                                                                       # :570-572: nothing detected
@@ -470,7 +513,17 @@ class SegmentTranscriber(nn.Module):
         the largest interval count seen so far per recording in the batch), the real count travels to the host with the step's rows
         and is checked one step late, when the rows are merged.  A count above the cap (the heads saw a truncated list) restarts
         the whole call with `synchronous=True`: every step then waits for its count, as in round 3.  Same Notes either way.
-        `ctx_fns[f](s, T)` must therefore be RE-CALLABLE (a pure function of the step): a restart asks for step 0 again."""
+        `ctx_fns[f](s, T)` must therefore be RE-CALLABLE (a pure function of the step): a restart asks for step 0 again.
+
+        decoder = "mbr" decodes every segment by decode_mbr(mbrThreshold, mbrTolerance) from the carried start instead of Viterbi;
+        everything behind the decode (onset filter, heads, events, the next start, the merger) is the same.  Without a tolerance
+        its lattice bound is exact, nothing is truncated and the capped route above works as it does for Viterbi; with
+        mbrTolerance set the lattice may need a retry that reads a count from the device, so the call runs its
+        `synchronous=True` route from the start."""
+        if self.decoder not in ("viterbi", "mbr"):
+            raise ValueError(f"decoder must be 'viterbi' or 'mbr', not {self.decoder!r}")
+        if self.decoder == "mbr" and _nsci._tolerance(self.mbrTolerance, "decoder 'mbr'") != (0, 0):
+            synchronous = True
         plans = [self.segment_plan(n, stepInSecond, segmentSizeInSecond) for n in nSamples]
         P = len(self.targetMIDIPitch)
         dev = next(self.parameters()).device
@@ -521,7 +574,7 @@ class SegmentTranscriber(nn.Module):
                 K = int(kpin[s & 1])
                 if K < 0:
                     _lib.async_error()           # consumed here: the next library call must not report this time-out again
-                    raise RuntimeError("semicrf_viterbi: a bounded hand-off wait timed out on the device; the decode result is invalid")
+                    raise RuntimeError(self._invalid_decode_message())
                 if K > cap:
                     raise _Overflow()
             kmax_per_file[0] = max(kmax_per_file[0], K / max(len(active), 1))
