@@ -712,6 +712,33 @@ int interval_features_gather_bwd(const float* gout, const float* ctx, int C, int
                                  int64_t K, const int32_t* offsets, float* dctx, int64_t lddc, semicrf_stream_t stream);
 
 /*
+ * Attribute-head training loss.  Replaces: the part of TransKun.log_prob behind the two heads (ModelTransformer.py:284-328) --
+ * the velocity log_softmax + gather, ContinuousBernoulli(logits).log_prob of the refined onset/offset, Bernoulli(logits).log_prob
+ * of their presence and the scatter_add into the per-chain logProb -- on the heads' raw outputs.  Rows are the K target intervals
+ * in chain order (offsets [C+1]); per row: logitsVelocity [K][128], ofLogits [K][4] (columns 0-1 the value logits, 2-3 the
+ * presence logits), velocity int32 [K] in 0..127 (anything else gives NaN, never an access out of bounds), ofRefined [K][2] in
+ * [-0.5, 0.5] (shifted to x = r * 0.99 + 0.5 in fp32 here), ofPresence [K][2] in {0, 1}:
+ *   lpVel  = logitsVelocity[v] - logsumexp(logitsVelocity)
+ *   lpOF   = sum_j x_j l_j - softplus(l_j) + logC(l_j)
+ *   lpPres = sum_j p_j l'_j - softplus(l'_j)
+ *   rowLogProb[i] = (lpVel + lpOF) + lpPres;   out[c] = (rows of chain c summed in ascending order, fp32) + base[c]
+ * logC is torch's ContinuousBernoulli log-normaliser INCLUDING its fp32 probability clamp: log(l / tanh(l / 2)) for
+ * |l| < log((1 - 2^-23) / 2^-23) = 15.942..., that value's constant beyond (derivative 0), log 2 at 0 -- evaluated from the logit
+ * without the cancellation of torch's probability-space formula (csrc/attr_loss_math.h).
+ * No atomics: out[c] depends on the rows of chain c only and is bit-identical from run to run.  base (or NULL: zeros) is the
+ * CRF term; out may not alias rowLogProb.  K == 0 launches nothing and leaves out untouched (the result is base itself).
+ * Backward, for the upstream gradient g[c] = gout[c * gstride] (gstride 0: one value for every chain, as -logp.sum(-1).mean() gives):
+ *   dLogitsVelocity [K][128] = g (onehot(v) - softmax),  dOfLogits [K][4] = g (x_j - sigmoid(l_j) + logC'(l_j)) | g (p_j - sigmoid(l'_j))
+ * (d out / d base = 1 is the caller's).  Both calls only enqueue kernels on `stream`: no synchronisation, allocation or workspace.
+ */
+int semicrf_attribute_loss_fwd(const float* logitsVelocity, const float* ofLogits, const int32_t* velocity, const float* ofRefined,
+                               const float* ofPresence, int64_t K, const int32_t* offsets, int C, const float* base, float* rowLogProb,
+                               float* out, semicrf_stream_t stream);
+int semicrf_attribute_loss_bwd(const float* gout, int gstride, const float* logitsVelocity, const float* ofLogits, const int32_t* velocity,
+                               const float* ofRefined, const float* ofPresence, int64_t K, const int32_t* offsets, int C,
+                               float* dLogitsVelocity, float* dOfLogits, semicrf_stream_t stream);
+
+/*
  * Transcription segment loop, on the packed decode output in HBM.
  *
  * segment_onset_filter.  Replaces: the onsetBound filter of TransKun.transcribeFrames (ModelTransformer.py:554-555),

@@ -76,3 +76,140 @@ def fetchIntervalFeaturesBatch(ctxBatch: torch.Tensor, intervalsBatch: Sequence[
         raise RuntimeError("fetchIntervalFeaturesBatch: no intervals (the reference fails in torch.cat of an empty list)")
     out, sym, sc = attribute_input_packed(ctxBatch, pairs, offsets, K)
     return out[:, :D], out[:, D:2 * D], sym, sc
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# the attribute-head training loss (TransKun.log_prob, ModelTransformer.py:284-330)
+# ----------------------------------------------------------------------------------------------------------------------
+def _f32c(t: torch.Tensor) -> torch.Tensor:
+    t = t.detach()
+    if t.dtype != torch.float32:
+        t = t.float()
+    return t if t.is_contiguous() else t.contiguous()
+
+
+class _AttributeLogProb(torch.autograd.Function):
+    """out [C] = base + the per-chain sums of (lpVel + lpOF) + lpPres over the chain's rows (semicrf_attribute_loss_fwd / _bwd;
+    the CPU dispatch key runs the same formulas on the host).  Once differentiable, w.r.t. logitsVelocity, ofLogits and base."""
+
+    @staticmethod
+    def forward(ctx, logitsVelocity, ofLogits, base, velocity, ofRefined, ofPresence, offsets):
+        K, C = logitsVelocity.shape[0], offsets.shape[0] - 1
+        dev = logitsVelocity.device
+        lv, of = _f32c(logitsVelocity), _f32c(ofLogits)
+        b = None if base is None else _f32c(base).reshape(C)
+        ctx.in_dtypes = (logitsVelocity.dtype, ofLogits.dtype, None if base is None else base.dtype)
+        ctx.base_shape = None if base is None else base.shape
+        ctx.K, ctx.C = K, C
+        if K == 0:                                       # ModelTransformer.py:273: the whole block is skipped
+            return b.clone() if b is not None else torch.zeros(C, dtype=torch.float32, device=dev)
+        rows = torch.empty(K, dtype=torch.float32, device=dev)
+        out = torch.empty(C, dtype=torch.float32, device=dev)
+        _lib.ops().attribute_loss_fwd(lv, of, velocity, ofRefined, ofPresence, K, offsets, C, b if b is not None else out, b is not None,
+                                      rows, out)
+        ctx.save_for_backward(lv, of, velocity, ofRefined, ofPresence, offsets)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        K, C = ctx.K, ctx.C
+        dt_lv, dt_of, dt_base = ctx.in_dtypes
+        need = ctx.needs_input_grad
+        dbase = grad_output.reshape(ctx.base_shape).to(dt_base) if need[2] else None
+        if K == 0:
+            dev = grad_output.device
+            return (torch.zeros(0, 128, dtype=dt_lv, device=dev) if need[0] else None,
+                    torch.zeros(0, 4, dtype=dt_of, device=dev) if need[1] else None, dbase, None, None, None, None)
+        lv, of, velocity, ofRefined, ofPresence, offsets = ctx.saved_tensors
+        g, gstride = _nsci._gout_strided(grad_output, C)
+        dlv, dof = torch.empty_like(lv), torch.empty_like(of)
+        _lib.ops().attribute_loss_bwd(g, gstride, lv, of, velocity, ofRefined, ofPresence, K, offsets, C, dlv, dof)
+        return dlv.to(dt_lv) if need[0] else None, dof.to(dt_of) if need[1] else None, dbase, None, None, None, None
+
+
+def attribute_log_prob(logitsVelocity: torch.Tensor, ofLogits: torch.Tensor, velocity: torch.Tensor, ofRefined: torch.Tensor,
+                       ofPresence: torch.Tensor, offsets: torch.Tensor, base: torch.Tensor = None) -> torch.Tensor:
+    """The attribute-head part of TransKun.log_prob (ModelTransformer.py:284-330) on the heads' RAW outputs, as one node: per chain c
+    (rows offsets[c] .. offsets[c+1] of the K target intervals, chain order)
+
+        out[c] = base[c] + sum_rows  log_softmax(logitsVelocity)[v]
+                                   + ContinuousBernoulli(logits=ofLogits[:, :2]).log_prob(ofRefined * 0.99 + 0.5).sum(-1)
+                                   + Bernoulli(logits=ofLogits[:, 2:]).log_prob(ofPresence).sum(-1)
+
+    logitsVelocity [K, 128]; ofLogits [K, 4], the onset/offset head's output before .chunk(2, -1); velocity [K] integers 0..127;
+    ofRefined [K, 2] in [-0.5, 0.5] (NOT shifted: the shift of :304 happens inside, in fp32); ofPresence [K, 2] in {0, 1}; offsets int32
+    [C+1]; base [C] (any shape with C elements; the CRF's logProb) or None.  Returns fp32 [C].  Gradients flow to logitsVelocity,
+    ofLogits and base (once differentiable).  All tensors on one device, a GPU (HIP kernels) or the CPU (host kernels).
+
+    The ContinuousBernoulli normaliser follows torch's fp32 definition, clamp at eps = 2^-23 included, but is evaluated from the
+    logit without torch's cancellation.  The sum has a fixed order ((vel + of) + presence per row, rows ascending, base last) and
+    uses no atomics: results are bit-identical between runs and a chain's value does not depend on the rest of the batch.
+    Nothing here synchronises with the host; velocities outside 0..127 give NaN (pack_attribute_targets checks them on the host)."""
+    K = logitsVelocity.shape[0]
+    C = offsets.shape[0] - 1
+    assert logitsVelocity.shape == (K, 128) and ofLogits.shape == (K, 4), "logitsVelocity [K, 128] and ofLogits [K, 4] expected"
+    assert velocity.shape == (K,) and ofRefined.shape == (K, 2) and ofPresence.shape == (K, 2), "targets: velocity [K], ofRefined [K, 2], ofPresence [K, 2]"
+    assert offsets.dtype == torch.int32 and offsets.dim() == 1 and C >= 1, "offsets: int32 [C+1]"
+    assert base is None or base.numel() == C, "base must hold one value per chain"
+    _lib.require_device(logitsVelocity, "logitsVelocity")
+    vel = velocity if velocity.dtype == torch.int32 else velocity.to(torch.int32)
+    return _AttributeLogProb.apply(logitsVelocity, ofLogits, base, vel.contiguous(), _f32c(ofRefined), _f32c(ofPresence), offsets.contiguous())
+
+
+def attribute_log_prob_torch(logitsVelocity, ofLogits, velocity, ofRefined, ofPresence, offsets, base=None) -> torch.Tensor:
+    """attribute_log_prob's arguments and result by the reference's OWN formulation (ModelTransformer.py:291-328), torch call for
+    torch call: what a caller had to run before the fused op existed.  For comparisons (tools/bench_attr_loss.py, the tests); the
+    package itself never takes this route on its own."""
+    C = offsets.shape[0] - 1
+    logProb = torch.zeros(C, dtype=logitsVelocity.dtype, device=logitsVelocity.device) if base is None else base.reshape(C)
+    if logitsVelocity.shape[0] == 0:                                                                     # :273
+        return logProb
+    counts = (offsets[1:] - offsets[:-1]).long()
+    scatterIdx = torch.repeat_interleave(torch.arange(C, device=offsets.device), counts, output_size=logitsVelocity.shape[0])
+    logits = torch.nn.functional.log_softmax(logitsVelocity, dim=-1)                                     # :291
+    logProbVelocity = torch.gather(logits, dim=-1, index=velocity.long().unsqueeze(-1)).squeeze(-1)      # :295
+    refined = ofRefined.to(logitsVelocity.dtype) * 0.99 + 0.5                                            # :304
+    ofValue, ofPres = ofLogits.chunk(2, dim=-1)                                                          # :306
+    logProbOF = torch.distributions.ContinuousBernoulli(logits=ofValue).log_prob(refined).sum(-1)        # :311-313
+    logProbOFPresence = torch.distributions.Bernoulli(logits=ofPres).log_prob(ofPresence.to(logitsVelocity.dtype)).sum(-1)   # :315-317
+    return logProb.scatter_add(-1, scatterIdx, logProbVelocity + logProbOF + logProbOFPresence)         # :328
+
+
+def _flatten_target(x):
+    """The nested per-segment / per-symbol lists of prepareIntervals (data["velocity"] etc.), a flat sequence or a tensor -> a CPU
+    tensor or a flat list (the forms SegmentTranscriber._target_tensor takes)."""
+    if isinstance(x, torch.Tensor):
+        return x.detach().cpu()
+    x = list(x)
+    if x and isinstance(x[0], (list, tuple)) and (len(x[0]) == 0 or isinstance(x[0][0], (list, tuple))):
+        x = [v for seg in x for sym in seg for v in sym]                                 # sum(sum(..., []), []), :251-253, :286-288
+    return x
+
+
+def pack_attribute_targets(velocityBatch, ofRefinedGTBatch, ofPresenceGTBatch, K: int, device):
+    """The three targets of the attribute heads as device tensors for attribute_log_prob: (velocity int32 [K], ofRefined fp32 [K, 2],
+    ofPresence fp32 [K, 2]).  Each argument: nested per segment and symbol as prepareIntervals yields it, flat in chain order, or a
+    tensor.  Checked on the host (ValueError): velocities are integers in 0..127 and every target has K entries.  Everything
+    travels in ONE pinned, non-blocking copy (the reference uploads three tensors, :293-298)."""
+    K = int(K)
+    vel = torch.as_tensor(_flatten_target(velocityBatch))
+    if vel.numel() != K:
+        raise ValueError(f"velocityBatch: {vel.numel()} values for {K} target intervals")
+    velf = vel.to(torch.float64).reshape(K)
+    if K and (bool((velf != velf.round()).any()) or float(velf.min()) < 0 or float(velf.max()) > 127):
+        raise ValueError("velocityBatch: velocities must be integers in 0..127")
+    refined = torch.as_tensor(_flatten_target(ofRefinedGTBatch), dtype=torch.float32)
+    presence = torch.as_tensor(_flatten_target(ofPresenceGTBatch), dtype=torch.float32)
+    if refined.numel() != 2 * K:
+        raise ValueError(f"ofRefinedGTBatch: {refined.numel()} values for {K} target intervals (2 each)")
+    if presence.numel() != 2 * K:
+        raise ValueError(f"ofPresenceGTBatch: {presence.numel()} values for {K} target intervals (2 each)")
+    dev = torch.device(device)
+    # one buffer of 5 K 32-bit words: [velocity as int32 bits | refined | presence]
+    host = torch.empty(5 * K, dtype=torch.float32, pin_memory=dev.type == "cuda")
+    host[:K].view(torch.int32).copy_(velf)
+    host[K:3 * K].copy_(refined.reshape(2 * K))
+    host[3 * K:].copy_(presence.reshape(2 * K))
+    d = host.to(dev, non_blocking=True)
+    return d[:K].view(torch.int32), d[K:3 * K].view(K, 2), d[3 * K:].view(K, 2)

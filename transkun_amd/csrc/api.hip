@@ -58,6 +58,12 @@ void launch_interval_features(const float* ctx, int C, int T, int D, long long l
                               hipStream_t stream);
 void launch_interval_features_bwd(const float* gout, const float* ctx, int C, int T, int D, long long ldc, const int* pairs,
                                   int K, const int* offsets, float* dctx, long long lddc, hipStream_t stream);
+void launch_attr_loss_fwd(const float* logitsVelocity, const float* ofLogits, const int* velocity, const float* ofRefined,
+                          const float* ofPresence, int K, const int* offsets, int C, const float* base, float* rowLogProb, float* out,
+                          hipStream_t stream);
+void launch_attr_loss_bwd(const float* gout, int gstride, const float* logitsVelocity, const float* ofLogits, const int* velocity,
+                          const float* ofRefined, const float* ofPresence, int K, const int* offsets, int C, float* dLogitsVelocity,
+                          float* dOfLogits, hipStream_t stream);
 void launch_interval_score_path_bwd(const float* gout, const int* pairs, int K, const int* offsets, const float* q,
                                     const float* k, int C, int T, int D, long long ldq, long long ldk, float qscale, int mode,
                                     float* dq, float* dk, float* ddiag, long long lddq, long long lddk, long long lddd,
@@ -1094,6 +1100,39 @@ int interval_features_gather_bwd(const float* gout, const float* ctx, int C, int
     SEMICRF_CHECK_ARG(K >= 0 && K < (1ll << 31) && (K == 0 || (pairs && gout)), "bad interval count / buffers");
     launch_interval_features_bwd(gout, ctx, C, T, D, ldc, pairs, (int)K, offsets, dctx, lddc, (hipStream_t)stream);
     SEMICRF_CHECK_LAUNCH("interval_features_gather_bwd");
+    return SEMICRF_OK;
+}
+
+int semicrf_attribute_loss_fwd(const float* logitsVelocity, const float* ofLogits, const int32_t* velocity, const float* ofRefined,
+                               const float* ofPresence, int64_t K, const int32_t* offsets, int C, const float* base, float* rowLogProb,
+                               float* out, semicrf_stream_t stream)
+{
+    SEMICRF_CHECK_ARG(C >= 1, "C=%d must be >= 1", C);
+    SEMICRF_CHECK_ARG(K >= 0 && K < (1ll << 31), "bad interval count");
+    if (K == 0) return SEMICRF_OK;                         // nothing to add: the caller's base IS the result (ModelTransformer.py:273)
+    SEMICRF_CHECK_ARG(logitsVelocity && ofLogits && velocity && ofRefined && ofPresence && offsets && rowLogProb && out,
+                      "logitsVelocity/ofLogits/velocity/ofRefined/ofPresence/offsets/rowLogProb/out must be non-NULL");
+    SEMICRF_CHECK_ARG(((uintptr_t)logitsVelocity & 7) == 0, "logitsVelocity must be 8-byte aligned");
+    launch_attr_loss_fwd(logitsVelocity, ofLogits, velocity, ofRefined, ofPresence, (int)K, offsets, C, base, rowLogProb, out,
+                         (hipStream_t)stream);
+    SEMICRF_CHECK_LAUNCH("semicrf_attribute_loss_fwd");
+    return SEMICRF_OK;
+}
+
+int semicrf_attribute_loss_bwd(const float* gout, int gstride, const float* logitsVelocity, const float* ofLogits, const int32_t* velocity,
+                               const float* ofRefined, const float* ofPresence, int64_t K, const int32_t* offsets, int C,
+                               float* dLogitsVelocity, float* dOfLogits, semicrf_stream_t stream)
+{
+    SEMICRF_CHECK_ARG(C >= 1, "C=%d must be >= 1", C);
+    SEMICRF_CHECK_ARG(K >= 0 && K < (1ll << 31), "bad interval count");
+    SEMICRF_CHECK_ARG(gstride == 0 || gstride == 1, "gout stride must be 0 (one value for all chains) or 1");
+    if (K == 0) return SEMICRF_OK;
+    SEMICRF_CHECK_ARG(gout && logitsVelocity && ofLogits && velocity && ofRefined && ofPresence && offsets && dLogitsVelocity && dOfLogits,
+                      "gout/logitsVelocity/ofLogits/velocity/ofRefined/ofPresence/offsets/dLogitsVelocity/dOfLogits must be non-NULL");
+    SEMICRF_CHECK_ARG((((uintptr_t)logitsVelocity | (uintptr_t)dLogitsVelocity) & 7) == 0, "logitsVelocity/dLogitsVelocity must be 8-byte aligned");
+    launch_attr_loss_bwd(gout, gstride, logitsVelocity, ofLogits, velocity, ofRefined, ofPresence, (int)K, offsets, C, dLogitsVelocity,
+                         dOfLogits, (hipStream_t)stream);
+    SEMICRF_CHECK_LAUNCH("semicrf_attribute_loss_bwd");
     return SEMICRF_OK;
 }
 

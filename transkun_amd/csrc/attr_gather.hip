@@ -9,18 +9,9 @@
 //   symIdx[i] = c % nSym,   scatterIdx[i] = c      (the reference's symIdx_all / scatterIdx_all, int64)
 // One wave per interval, 16-byte accesses; HBM-bound (reads 2 D floats, writes 3 D per interval).
 #include "common.h"
+#include "chain_search.h"
 
 namespace semicrf {
-
-__device__ __forceinline__ int chain_of_interval(const int* __restrict__ offsets, int C, int i)
-{
-    int lo = 0, hi = C;                       // largest c with offsets[c] <= i
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (offsets[mid] <= i) lo = mid; else hi = mid;
-    }
-    return lo;
-}
 
 __global__ __launch_bounds__(256) void interval_features_kernel(const float* __restrict__ ctx, int C, int T, int D,
                                                                 long long ldc, const int* __restrict__ pairs, int K,

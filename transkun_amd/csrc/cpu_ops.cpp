@@ -15,6 +15,7 @@
 #include <cstring>
 #include <vector>
 
+#include "attr_loss_math.h"
 #include "cpu_ops.h"
 
 namespace semicrf_cpu {
@@ -979,6 +980,66 @@ void eval_path_bwd(const float* gout, int T, int B, const int32_t* pairs, const 
             if (dScore) dScore[((size_t)e * T + b) * Bs + c] += gout[c];
             if (dNoise)
                 for (int t = b; t < e; ++t) dNoise[(size_t)t * Bs + c] -= gout[c];
+        }
+    }
+}
+
+// ---- attribute-head training loss (ModelTransformer.py:284-328) -------------------------------------------------------------
+namespace {
+// max and log(sum exp(x - max)) of a row's velocity logits, in double
+inline void row_logsumexp(const float* x, double& m, double& logs)
+{
+    using semicrf::attr_loss::NVEL;
+    m = x[0];
+    for (int k = 1; k < NVEL; ++k) m = std::max(m, (double)x[k]);
+    double sum = 0.0;
+    for (int k = 0; k < NVEL; ++k) sum += exp((double)x[k] - m);
+    logs = log(sum);
+}
+}  // namespace
+
+void attribute_loss_fwd(const float* logitsVelocity, const float* ofLogits, const int32_t* velocity, const float* ofRefined,
+                        const float* ofPresence, int64_t K, const int32_t* offsets, int C, const float* base, float* rowLogProb, float* out)
+{
+    using namespace semicrf::attr_loss;
+#pragma omp parallel for schedule(static)
+    for (int64_t i = 0; i < K; ++i) {
+        const float* x = logitsVelocity + (size_t)i * NVEL;
+        double m, logs, lpOF, lpPres;
+        row_logsumexp(x, m, logs);
+        const int v = velocity[i];
+        const float lpVel = v >= 0 && v < NVEL ? (float)(((double)x[v] - m) - logs) : NAN;
+        of_terms<double>(ofLogits + 4 * (size_t)i, ofRefined + 2 * (size_t)i, ofPresence + 2 * (size_t)i, lpOF, lpPres);
+        rowLogProb[i] = (lpVel + (float)lpOF) + (float)lpPres;
+    }
+#pragma omp parallel for schedule(static)
+    for (int c = 0; c < C; ++c) {
+        const int64_t b = std::max<int64_t>(offsets[c], 0), e = std::min<int64_t>(offsets[c + 1], K);
+        if (e <= b) { out[c] = base ? base[c] : 0.0f; continue; }
+        float acc = rowLogProb[b];
+        for (int64_t i = b + 1; i < e; ++i) acc += rowLogProb[i];
+        out[c] = base ? acc + base[c] : acc;
+    }
+}
+
+void attribute_loss_bwd(const float* gout, int gstride, const float* logitsVelocity, const float* ofLogits, const int32_t* velocity,
+                        const float* ofRefined, const float* ofPresence, int64_t K, const int32_t* offsets, int C, float* dLogitsVelocity,
+                        float* dOfLogits)
+{
+    using namespace semicrf::attr_loss;
+#pragma omp parallel for schedule(dynamic, 8)
+    for (int c = 0; c < C; ++c) {
+        const double g = gout[(size_t)c * gstride];
+        const int64_t b = std::max<int64_t>(offsets[c], 0), e = std::min<int64_t>(offsets[c + 1], K);
+        for (int64_t i = b; i < e; ++i) {
+            const float* x = logitsVelocity + (size_t)i * NVEL;
+            float* d = dLogitsVelocity + (size_t)i * NVEL;
+            double m, logs, dd[4];
+            row_logsumexp(x, m, logs);
+            const int v = velocity[i];
+            for (int k = 0; k < NVEL; ++k) d[k] = (float)(g * ((k == v ? 1.0 : 0.0) - exp(((double)x[k] - m) - logs)));
+            of_grads<double>(ofLogits + 4 * (size_t)i, ofRefined + 2 * (size_t)i, ofPresence + 2 * (size_t)i, dd);
+            for (int j = 0; j < 4; ++j) dOfLogits[4 * (size_t)i + j] = (float)(g * dd[j]);
         }
     }
 }

@@ -36,4 +36,12 @@ void covariance(const float* score, const float* noise, const float* weight, con
                 const double* state, float* C, float* Cn /* or null when T = 1 */);
 void eval_path(const float* score, const float* noise, int T, int B, const int32_t* pairs, const int32_t* offsets, float* out);
 void eval_path_bwd(const float* gout, int T, int B, const int32_t* pairs, const int32_t* offsets, float* dScore, float* dNoise);
+// the attribute-head training loss (semicrf_attribute_loss_fwd / _bwd): the formulas of attr_loss_math.h per row in double, each
+// row term rounded to fp32, then the pinned fp32 order -- (lpVel + lpOF) + lpPres, rows ascending per chain, base last
+void attribute_loss_fwd(const float* logitsVelocity, const float* ofLogits, const int32_t* velocity, const float* ofRefined,
+                        const float* ofPresence, int64_t K, const int32_t* offsets, int C, const float* base /* or null */,
+                        float* rowLogProb, float* out);
+void attribute_loss_bwd(const float* gout, int gstride, const float* logitsVelocity, const float* ofLogits, const int32_t* velocity,
+                        const float* ofRefined, const float* ofPresence, int64_t K, const int32_t* offsets, int C,
+                        float* dLogitsVelocity, float* dOfLogits);
 }  // namespace semicrf_cpu

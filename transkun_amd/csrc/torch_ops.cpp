@@ -799,6 +799,68 @@ void interval_features_gather_bwd_op(Tensor gout, Tensor ctx, int64_t C, int64_t
           "interval_features_gather_bwd");
 }
 
+// ---- attribute-head training loss (semicrf_attribute_loss_fwd / _bwd) ---------------------------------------------------
+struct AttrLossArgs { const float *lv, *of, *r, *p; const int32_t *vel, *off; };
+inline AttrLossArgs attr_loss_args(const Tensor& logitsVelocity, const Tensor& ofLogits, const Tensor& velocity, const Tensor& ofRefined,
+                                   const Tensor& ofPresence, int64_t K, const Tensor& offsets, int64_t C)
+{
+    STD_TORCH_CHECK(K >= 0 && K < (1ll << 31) && C >= 1 && C < (1ll << 31), "semicrf: bad interval / chain count");
+    return AttrLossArgs{f32(logitsVelocity, K * 128, "logitsVelocity"), f32(ofLogits, K * 4, "ofLogits"), f32(ofRefined, K * 2, "ofRefined"),
+                        f32(ofPresence, K * 2, "ofPresence"), i32(velocity, K, "velocity"), i32(offsets, C + 1, "offsets")};
+}
+void attribute_loss_fwd_op(Tensor logitsVelocity, Tensor ofLogits, Tensor velocity, Tensor ofRefined, Tensor ofPresence, int64_t K,
+                           Tensor offsets, int64_t C, Tensor base, bool has_base, Tensor rowLogProb, Tensor out)
+{
+    Ctx c(out); c.same(out, logitsVelocity, ofLogits, velocity, ofRefined, ofPresence, offsets, rowLogProb);
+    if (has_base) c.same(out, base);
+    const AttrLossArgs a = attr_loss_args(logitsVelocity, ofLogits, velocity, ofRefined, ofPresence, K, offsets, C);
+    check(semicrf_attribute_loss_fwd(a.lv, a.of, a.vel, a.r, a.p, K, a.off, (int)C, has_base ? f32(base, C, "base") : nullptr,
+                                     f32w(rowLogProb, K, "rowLogProb"), f32w(out, C, "out"), c.stream),
+          "semicrf_attribute_loss_fwd");
+}
+void attribute_loss_bwd_op(Tensor gout, int64_t gstride, Tensor logitsVelocity, Tensor ofLogits, Tensor velocity, Tensor ofRefined,
+                           Tensor ofPresence, int64_t K, Tensor offsets, int64_t C, Tensor dLogitsVelocity, Tensor dOfLogits)
+{
+    Ctx c(gout); c.same(gout, logitsVelocity, ofLogits, velocity, ofRefined, ofPresence, offsets, dLogitsVelocity, dOfLogits);
+    STD_TORCH_CHECK(gstride == 0 || gstride == 1, "semicrf: bad gout stride");
+    const AttrLossArgs a = attr_loss_args(logitsVelocity, ofLogits, velocity, ofRefined, ofPresence, K, offsets, C);
+    check(semicrf_attribute_loss_bwd(f32(gout, gstride ? C : 1, "gout"), (int)gstride, a.lv, a.of, a.vel, a.r, a.p, K, a.off, (int)C,
+                                     f32w(dLogitsVelocity, K * 128, "dLogitsVelocity"), f32w(dOfLogits, K * 4, "dOfLogits"), c.stream),
+          "semicrf_attribute_loss_bwd");
+}
+// the same two on CPU tensors (cpu_ops.cpp); the offsets are checked here: the host kernels index with them
+inline void check_offsets(const int32_t* off, int64_t K, int64_t C)
+{
+    STD_TORCH_CHECK(off[0] == 0 && off[C] == K, "semicrf: offsets must run from 0 to K");
+    for (int64_t c = 0; c < C; ++c) STD_TORCH_CHECK(off[c] <= off[c + 1], "semicrf: offsets must not decrease");
+}
+void attribute_loss_fwd_cpu(Tensor logitsVelocity, Tensor ofLogits, Tensor velocity, Tensor ofRefined, Tensor ofPresence, int64_t K,
+                            Tensor offsets, int64_t C, Tensor base, bool has_base, Tensor rowLogProb, Tensor out)
+{
+    all_cpu(logitsVelocity, ofLogits, velocity, ofRefined, ofPresence, offsets, rowLogProb, out);
+    if (has_base) all_cpu(base);
+    const AttrLossArgs a = attr_loss_args(logitsVelocity, ofLogits, velocity, ofRefined, ofPresence, K, offsets, C);
+    const float* b = has_base ? f32(base, C, "base") : nullptr;
+    float* rows = f32w(rowLogProb, K, "rowLogProb");
+    float* o = f32w(out, C, "out");
+    if (K == 0) return;
+    check_offsets(a.off, K, C);
+    semicrf_cpu::attribute_loss_fwd(a.lv, a.of, a.vel, a.r, a.p, K, a.off, (int)C, b, rows, o);
+}
+void attribute_loss_bwd_cpu(Tensor gout, int64_t gstride, Tensor logitsVelocity, Tensor ofLogits, Tensor velocity, Tensor ofRefined,
+                            Tensor ofPresence, int64_t K, Tensor offsets, int64_t C, Tensor dLogitsVelocity, Tensor dOfLogits)
+{
+    all_cpu(gout, logitsVelocity, ofLogits, velocity, ofRefined, ofPresence, offsets, dLogitsVelocity, dOfLogits);
+    STD_TORCH_CHECK(gstride == 0 || gstride == 1, "semicrf: bad gout stride");
+    const AttrLossArgs a = attr_loss_args(logitsVelocity, ofLogits, velocity, ofRefined, ofPresence, K, offsets, C);
+    const float* g = f32(gout, gstride ? C : 1, "gout");
+    float* dlv = f32w(dLogitsVelocity, K * 128, "dLogitsVelocity");
+    float* dof = f32w(dOfLogits, K * 4, "dOfLogits");
+    if (K == 0) return;
+    check_offsets(a.off, K, C);
+    semicrf_cpu::attribute_loss_bwd(g, (int)gstride, a.lv, a.of, a.vel, a.r, a.p, K, a.off, (int)C, dlv, dof);
+}
+
 // ---- transcription segment loop ----------------------------------------------------------------------------------------
 void segment_onset_filter_op(Tensor pairs, Tensor offsets, int64_t B, int64_t bound, Tensor pairs_out, Tensor offsets_out, Tensor counts_ws)
 {
@@ -888,6 +950,10 @@ STABLE_TORCH_LIBRARY(semicrf, m)
           "Tensor(b!) symIdx, Tensor(c!) scatterIdx) -> ()");
     m.def("interval_features_gather_bwd(Tensor gout, Tensor ctx, int C, int T, int D, int ldc, Tensor pairs, int K, Tensor offsets, "
           "Tensor(a!) dctx, int lddc) -> ()");
+    m.def("attribute_loss_fwd(Tensor logitsVelocity, Tensor ofLogits, Tensor velocity, Tensor ofRefined, Tensor ofPresence, int K, "
+          "Tensor offsets, int C, Tensor base, bool has_base, Tensor(a!) rowLogProb, Tensor(b!) out) -> ()");
+    m.def("attribute_loss_bwd(Tensor gout, int gstride, Tensor logitsVelocity, Tensor ofLogits, Tensor velocity, Tensor ofRefined, "
+          "Tensor ofPresence, int K, Tensor offsets, int C, Tensor(a!) dLogitsVelocity, Tensor(b!) dOfLogits) -> ()");
     m.def("segment_onset_filter(Tensor pairs, Tensor offsets, int B, int bound, Tensor(a!) pairs_out, Tensor(b!) offsets_out, "
           "Tensor(c!) counts_ws) -> ()");
     m.def("segment_events(Tensor pairs, int K, Tensor offsets, int B, int nSym, Tensor ofValue, Tensor ofPresence, int lastFrameIdx, "
@@ -916,6 +982,8 @@ STABLE_TORCH_LIBRARY_IMPL(semicrf, CPU, m)
     m.impl("eval_path_bwd", TORCH_BOX(&eval_path_bwd_cpu));
     m.impl("logprob_fwd", TORCH_BOX(&logprob_fwd_cpu));
     m.impl("logprob_bwd", TORCH_BOX(&logprob_bwd_cpu));
+    m.impl("attribute_loss_fwd", TORCH_BOX(&attribute_loss_fwd_cpu));
+    m.impl("attribute_loss_bwd", TORCH_BOX(&attribute_loss_bwd_cpu));
 }
 
 STABLE_TORCH_LIBRARY_IMPL(semicrf, CUDA, m)
@@ -952,6 +1020,8 @@ STABLE_TORCH_LIBRARY_IMPL(semicrf, CUDA, m)
     m.impl("merge_weights_bwd", TORCH_BOX(&merge_weights_bwd_op));
     m.impl("interval_features_gather", TORCH_BOX(&interval_features_gather_op));
     m.impl("interval_features_gather_bwd", TORCH_BOX(&interval_features_gather_bwd_op));
+    m.impl("attribute_loss_fwd", TORCH_BOX(&attribute_loss_fwd_op));
+    m.impl("attribute_loss_bwd", TORCH_BOX(&attribute_loss_bwd_op));
     m.impl("segment_onset_filter", TORCH_BOX(&segment_onset_filter_op));
     m.impl("segment_events", TORCH_BOX(&segment_events_op));
 }

@@ -253,14 +253,17 @@ class _ScorerCRFLogProb(torch.autograd.Function):
         return (dqd.view(N, P, T, D + QPAD), dk.view(N, P, T, D), None, None, None, None, None, None, None, None)
 
 
-def scorer_crf_logprob(scorer: ScaledInnerProductIntervalScorer, ctx: torch.Tensor, intervals, projection: str = "merged") -> torch.Tensor:
+def scorer_crf_logprob(scorer: ScaledInnerProductIntervalScorer, ctx: torch.Tensor, intervals, projection: str = "merged",
+                       packed=None) -> torch.Tensor:
     """log p(intervals | ctx) per chain, [N*P], differentiable w.r.t. ctx and the scorer's parameters.
 
     ctx: [N, P, T, size] on the GPU; intervals: List (len N*P, chain index n*P + p) of Lists of (begin, end).
     Equivalent to NeuralSemiCRFInterval(*[x.flatten(-2) for x in scorer(ctx)]).logProb(intervals).
     projection: "merged" (default; shapes merged_eligible takes, else "separate") -- ONE size -> size GEMM instead of the reference's
     size -> 2 D + 1 (merged_weights): the same scores up to fp32 reassociation, half the Linear's flops; "separate": q and k
-    projected as the reference does, bit-identical scores to ScaledInnerProductIntervalScorer.forward."""
+    projected as the reference does, bit-identical scores to ScaledInnerProductIntervalScorer.forward.
+    packed: (pairs, offsets) as pack_intervals(intervals, T, N*P, ctx.device) returns them, for a caller that has packed the
+    intervals already (SegmentTranscriber.log_prob shares them with the attribute gather); None: packed here."""
     assert ctx.dim() == 4
     N, P, T, _ = ctx.shape
     D = scorer.size * scorer.expansionFactor
@@ -271,7 +274,7 @@ def scorer_crf_logprob(scorer: ScaledInnerProductIntervalScorer, ctx: torch.Tens
     lin = scorer.map[0]
     W, bias = lin.weight, lin.bias
     x = ctx.float()
-    pairs, offsets = _nsci.pack_intervals(intervals, T, N * P, ctx.device)
+    pairs, offsets = packed if packed is not None else _nsci.pack_intervals(intervals, T, N * P, ctx.device)
     fs = 2 | contraction_bits(getattr(scorer, "contraction", "fp32"))
     if fs & (BF16X3 | BWD_BF16X3 | PROJ_BF16X3):
         _bf16x3_selfcheck(x.device)

@@ -52,7 +52,17 @@ def train_step(model: SegmentModel, ctx: torch.Tensor, intervals, seconds_per_se
     bucket: a FlatGradBucket over model.parameters() (make it once, pass it every step): gradients live in its persistent
     flat buffer, the exchange is a reduce-scatter + all-gather that the backward pass starts itself on a side stream and
     that overlaps the loss bookkeeping; without it the gradients are concatenated and all-reduced after the backward
-    (allreduce_gradients_flat, the round-1 exchange)."""
+    (allreduce_gradients_flat, the round-1 exchange).
+
+    log_prob: a callable (scorer, ctx, intervals) -> log-probabilities with N*P elements, default default_log_prob (the CRF term
+    alone).  The reference's whole training loss, attribute heads included (ModelTransformer.py:240-332), is
+    SegmentTranscriber.log_prob; it owns its scorer and heads and needs the attribute targets, so close over them --
+
+        st = SegmentTranscriber(...)                 # its parameters are the ones to hand to the optimiser / bucket
+        batch = [intervals[n * P:(n + 1) * P] for n in range(N)]
+        train_step(model, ctx, intervals, log_prob=lambda scorer, ctx, iv: st.log_prob(ctx, batch, velocity, ofRefined, ofPresence))
+
+    (the `scorer` argument, model.scorer, is then unused: share the module, st.scorer = model.scorer, to train one scorer)."""
     N = ctx.shape[0]
     fn = log_prob or default_log_prob
     if bucket is not None:

@@ -335,6 +335,49 @@ class SegmentTranscriber(nn.Module):
                     velocity=velocity, times=times, flags=flags, lastP=lastP, nextStart=nextStart, ofValue=ofValue, ofPresence=ofPresence)
 
     # ------------------------------------------------------------------------------------------------------------------
+    # the training loss
+    # ------------------------------------------------------------------------------------------------------------------
+    def log_prob(self, ctxBatch: torch.Tensor, intervalsBatch, velocityBatch, ofRefinedGTBatch, ofPresenceGTBatch,
+                 projection: str = "merged", attributeRoute: str = "fused") -> torch.Tensor:
+        """TransKun.log_prob (ModelTransformer.py:240-332) from `ctx` on: log p(intervals, velocities, refinements, presence | ctx) per
+        segment and symbol, [N, P], differentiable w.r.t. ctxBatch and every parameter of this module.
+
+        ctxBatch [N, P, T, D] on the GPU (the backbone's output); the targets as prepareIntervals yields them, per segment and symbol:
+        intervalsBatch[n][p] a list of (begin, end), velocityBatch / ofRefinedGTBatch / ofPresenceGTBatch the reference's
+        data["velocity"], data["endPointRefine"], data["endPointPresence"] of those intervals -- nested like the intervals, or flat in
+        chain order (sequences or tensors: attributes.pack_attribute_targets).
+
+        scorer -> CRF logProb (fused.scorer_crf_logprob, `projection` as there) -> the heads' inputs gathered at the TARGET intervals
+        (:275-281) -> the two heads as the torch modules they are (dropout active in training mode, as in the reference) ->
+        attributes.attribute_log_prob with the CRF term as its base (:284-330).  The target intervals are packed once, for the CRF
+        term and the gather; the attribute targets travel in one pinned copy; nothing synchronises with the host.  Without a single
+        target interval the result is the CRF term (:273).
+
+        attributeRoute "torch" evaluates :290-328 by the reference's own torch calls instead (attributes.attribute_log_prob_torch:
+        some 25 small kernels, an atomic scatter_add and ContinuousBernoulli's synchronising argument check) -- for comparisons only."""
+        assert ctxBatch.dim() == 4
+        N, P, T, D = ctxBatch.shape
+        assert P == len(self.targetMIDIPitch)
+        assert len(intervalsBatch) == N
+        if attributeRoute not in ("fused", "torch"):
+            raise ValueError(f"attributeRoute must be 'fused' or 'torch', not {attributeRoute!r}")
+        flat = [sym for seg in intervalsBatch for sym in seg]                            # :256
+        assert len(flat) == N * P                                                        # :257
+        dev = ctxBatch.device
+        pairs, offsets = _nsci.pack_intervals(flat, T, N * P, dev)
+        K = pairs._semicrf_K
+        if K > 0:
+            velocity, ofRefined, ofPresence = attributes.pack_attribute_targets(velocityBatch, ofRefinedGTBatch, ofPresenceGTBatch, K, dev)
+        logProb = fused.scorer_crf_logprob(self.scorer, ctxBatch, flat, projection=projection, packed=(pairs, offsets))     # :263-265
+        if K == 0:                                                                       # :273
+            return logProb.view(N, P)
+        attributeInput, _, _ = attributes.attribute_input_packed(ctxBatch, pairs, offsets, K)                               # :275-281
+        logitsVelocity = self.velocityPredictor(attributeInput)                          # :290
+        ofLogits = self.refinedOFPredictor(attributeInput)                               # :306
+        fn = attributes.attribute_log_prob if attributeRoute == "fused" else attributes.attribute_log_prob_torch
+        return fn(logitsVelocity, ofLogits, velocity, ofRefined, ofPresence, offsets, base=logProb).view(N, P)            # :291-330
+
+    # ------------------------------------------------------------------------------------------------------------------
     # the validation statistic
     # ------------------------------------------------------------------------------------------------------------------
     @torch.no_grad()
