@@ -739,6 +739,34 @@ int semicrf_attribute_loss_bwd(const float* gout, int gstride, const float* logi
                                float* dLogitsVelocity, float* dOfLogits, semicrf_stream_t stream);
 
 /*
+ * Attribute-head readout of transcription.  Replaces: the torch lines behind the two heads in TransKun.transcribeFrames
+ * (ModelTransformer.py:590-651) -- softmax and the velocity criterion, ContinuousBernoulli(logits).mean shifted back and clamped,
+ * the sign of the presence logits -- on the heads' raw outputs, row-wise (no offsets: the per-chain part stays segment_events).
+ * Per row i of K: logitsVelocity [K][128], ofLogits [K][4] (columns 0-1 the value logits, 2-3 the presence logits), p = softmax:
+ *   SEMICRF_VEL_HAMMING  velocityClass[i] = the smallest index of the largest logit (= argmax p, exactly)
+ *   SEMICRF_VEL_MSE      velocityMean[i]  = sum_w p[w] w
+ *   SEMICRF_VEL_MATCH    velocityClass[i] = the smallest v with the largest r[v] = sum of p[w] over |w - v| <= 12 (each r[v] summed
+ *                        directly in ascending w: a row with one dominant logit at m gives max(0, m - 12) every time)
+ *   SEMICRF_VEL_MAE      velocityClass[i] = the smallest v with p[0] + ... + p[v] > 0.5
+ *   ofValue[i][j]    = clamp((mean(l_j) - 0.5) / 0.99, -0.5, 0.5), mean = the ContinuousBernoulli mean INCLUDING torch's fp32
+ *                      probability clamp: mean - 0.5 = sign(l) h(min(|l|, l*)), h(a) = 0.5 coth(a / 2) - 1 / a, l* = 15.942...
+ *                      (beyond it the constant 0.4416912), evaluated from the logit without the cancellation of torch's
+ *                      probability-space formula (csrc/attr_decode_math.h); NaN gives NaN
+ *   ofPresence[i][j] = l'_j > 0 (bytes 0 / 1; NaN gives 0)
+ * A row whose softmax is not finite (a NaN, a +inf, or all -inf) gives class 0 (torch.argmax of an all-NaN row) and mean NaN.
+ * velocityClass (int64 [K]) is required for the three class criteria, velocityMean (float [K]) for SEMICRF_VEL_MSE; the other may be
+ * NULL and is not written.  ofValue: float [K][2], ofPresence: bytes [K][2].  SEMICRF_EINVAL for an unknown criterion or a missing
+ * output; K == 0 launches nothing.  One launch on `stream`: no synchronisation, allocation, workspace or atomics; a row's result
+ * depends on that row alone and is bit-identical from run to run.
+ */
+#define SEMICRF_VEL_HAMMING 0
+#define SEMICRF_VEL_MSE 1
+#define SEMICRF_VEL_MATCH 2
+#define SEMICRF_VEL_MAE 3
+int semicrf_attribute_decode(const float* logitsVelocity, const float* ofLogits, int64_t K, int criterion, int64_t* velocityClass,
+                             float* velocityMean, float* ofValue, unsigned char* ofPresence, semicrf_stream_t stream);
+
+/*
  * Transcription segment loop, on the packed decode output in HBM.
  *
  * segment_onset_filter.  Replaces: the onsetBound filter of TransKun.transcribeFrames (ModelTransformer.py:554-555),

@@ -96,6 +96,7 @@ _SIGS = {
     "interval_features_gather_bwd": (_i, [_vp, _vp, _i, _i, _i, _i64, _vp, _i64, _vp, _vp, _i64, _vp]),
     "semicrf_attribute_loss_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _i, _vp, _vp, _vp, _vp]),
     "semicrf_attribute_loss_bwd": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i, _vp, _vp, _vp]),
+    "semicrf_attribute_decode": (_i, [_vp, _vp, _i64, _i, _vp, _vp, _vp, _vp, _vp]),
     "interval_score_bwd_ws": (_i, [_vp, _vp, _vp, _i, _i, _i, _i64, _i64, ctypes.c_float, _i, _vp, _vp, _vp, _i64, _i64, _i64, _vp, ctypes.c_size_t, _vp]),
     "interval_score_bwd_workspace_bytes": (ctypes.c_size_t, [_i, _i, _i]),
     "segment_onset_filter": (_i, [_vp, _vp, _i, _i, _vp, _i64, _vp, _vp, _vp]),

@@ -176,6 +176,71 @@ def attribute_log_prob_torch(logitsVelocity, ofLogits, velocity, ofRefined, ofPr
     return logProb.scatter_add(-1, scatterIdx, logProbVelocity + logProbOF + logProbOFPresence)         # :328
 
 
+# ----------------------------------------------------------------------------------------------------------------------
+# the attribute-head readout of transcription (TransKun.transcribeFrames, ModelTransformer.py:590-651)
+# ----------------------------------------------------------------------------------------------------------------------
+VELOCITY_CRITERIA = {"hamming": 0, "mse": 1, "match": 2, "mae": 3}          # SEMICRF_VEL_*
+
+
+def attribute_decode(logitsVelocity: torch.Tensor, ofLogits: torch.Tensor, criterion: str = "hamming"):
+    """What transcribeFrames reads out of the two heads' RAW outputs (ModelTransformer.py:590-651), as one op (one launch on a GPU):
+    logitsVelocity [K, 128] and ofLogits [K, 4] (the onset/offset head's output before .chunk(2, -1)) -> (velocity, ofValue, ofPresence).
+
+    velocity [K], with p = softmax(logitsVelocity): "hamming" the mode (int64; the smallest index of the largest logit), "mse" the
+    mean sum_w p[w] w (float32), "match" the smallest v with the largest sum of p[w] over |w - v| <= 12 (int64), "mae" the median,
+    the smallest v with p[0] + ... + p[v] > 0.5 (int64).  A row whose softmax is not finite gives class 0 / mean NaN.
+    ofValue float32 [K, 2] = clamp((ContinuousBernoulli(logits).mean - 0.5) / 0.99, -0.5, 0.5) with torch's fp32 probability clamp,
+    evaluated from the logit (below 1e-6 of the definition where the torch calls in fp32 lose 3e-3); ofPresence bool [K, 2] = logit > 0.
+
+    Both tensors on one device, a GPU (csrc/attr_decode.hip) or the CPU (the host kernel: the same formulas in double).  Row-wise,
+    without atomics: a row's result depends on that row alone and is bit-identical from run to run; nothing synchronises with the
+    host.  An unknown criterion raises with the reference's message."""
+    if criterion not in VELOCITY_CRITERIA:
+        raise Exception("Unrecognized criterion: {}".format(criterion))
+    K = logitsVelocity.shape[0]
+    assert logitsVelocity.shape == (K, 128) and ofLogits.shape == (K, 4), "logitsVelocity [K, 128] and ofLogits [K, 4] expected"
+    _lib.require_device(logitsVelocity, "logitsVelocity")
+    dev = logitsVelocity.device
+    mse = criterion == "mse"
+    cls = torch.empty(0 if mse else K, dtype=torch.int64, device=dev)
+    mean = torch.empty(K if mse else 0, dtype=torch.float32, device=dev)
+    ofValue = torch.empty(K, 2, dtype=torch.float32, device=dev)
+    ofPresence = torch.empty(K, 2, dtype=torch.uint8, device=dev)
+    if K > 0:
+        _lib.ops().attribute_decode(_f32c(logitsVelocity), _f32c(ofLogits), K, VELOCITY_CRITERIA[criterion], cls, mean, ofValue, ofPresence)
+    return (mean if mse else cls), ofValue, ofPresence.view(torch.bool)
+
+
+def velocity_torch(logitsVelocity: torch.Tensor, criterion: str) -> torch.Tensor:
+    """The velocity criteria of ModelTransformer.py:590-632 as the reference's torch calls."""
+    pVelocity = torch.nn.functional.softmax(logitsVelocity, dim=-1)                  # :590-637
+    dev = pVelocity.device
+    if criterion == "hamming":
+        return torch.argmax(pVelocity, dim=-1)
+    if criterion == "mse":
+        return (pVelocity * torch.arange(128, device=dev)).sum(-1)
+    if criterion == "match":
+        w = torch.arange(128, device=dev)
+        utility = ((w.unsqueeze(1) - w.unsqueeze(0)).abs() < 0.1 * 128).float()
+        return torch.argmax(pVelocity @ utility, dim=-1)
+    if criterion == "mae":
+        tmp = (pVelocity.cumsum(-1) - 0.5) > 0
+        return torch.argmax(tmp * torch.arange(128, 0., -1, device=dev), dim=-1)
+    raise Exception("Unrecognized criterion: {}".format(criterion))
+
+
+def attribute_decode_torch(logitsVelocity: torch.Tensor, ofLogits: torch.Tensor, criterion: str = "hamming"):
+    """attribute_decode's arguments and result by the reference's OWN formulation (ModelTransformer.py:590-651), torch call for torch
+    call, in the dtype of its inputs: SegmentTranscriber.decode_step's default route (attributeDecode = "torch"), and the comparison
+    route of the tests and tools/bench_attr_decode.py."""
+    velocity = velocity_torch(logitsVelocity, criterion)
+    ofValue, ofPresence = ofLogits.chunk(2, dim=-1)                                  # :646-655
+    ofDist = torch.distributions.ContinuousBernoulli(logits=ofValue, validate_args=False)   # (the argument check is a host sync)
+    ofValue = torch.clamp((ofDist.mean - 0.5) / 0.99, -0.5, 0.5).float().contiguous()
+    ofPresence = (ofPresence > 0).contiguous()
+    return velocity, ofValue, ofPresence
+
+
 def _flatten_target(x):
     """The nested per-segment / per-symbol lists of prepareIntervals (data["velocity"] etc.), a flat sequence or a tensor -> a CPU
     tensor or a flat list (the forms SegmentTranscriber._target_tensor takes)."""

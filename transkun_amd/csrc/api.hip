@@ -61,6 +61,8 @@ void launch_interval_features_bwd(const float* gout, const float* ctx, int C, in
 void launch_attr_loss_fwd(const float* logitsVelocity, const float* ofLogits, const int* velocity, const float* ofRefined,
                           const float* ofPresence, int K, const int* offsets, int C, const float* base, float* rowLogProb, float* out,
                           hipStream_t stream);
+void launch_attr_decode(const float* logitsVelocity, const float* ofLogits, int K, int criterion, long long* velocityClass,
+                        float* velocityMean, float* ofValue, unsigned char* ofPresence, hipStream_t stream);
 void launch_attr_loss_bwd(const float* gout, int gstride, const float* logitsVelocity, const float* ofLogits, const int* velocity,
                           const float* ofRefined, const float* ofPresence, int K, const int* offsets, int C, float* dLogitsVelocity,
                           float* dOfLogits, hipStream_t stream);
@@ -1133,6 +1135,22 @@ int semicrf_attribute_loss_bwd(const float* gout, int gstride, const float* logi
     launch_attr_loss_bwd(gout, gstride, logitsVelocity, ofLogits, velocity, ofRefined, ofPresence, (int)K, offsets, C, dLogitsVelocity,
                          dOfLogits, (hipStream_t)stream);
     SEMICRF_CHECK_LAUNCH("semicrf_attribute_loss_bwd");
+    return SEMICRF_OK;
+}
+
+int semicrf_attribute_decode(const float* logitsVelocity, const float* ofLogits, int64_t K, int criterion, int64_t* velocityClass,
+                             float* velocityMean, float* ofValue, unsigned char* ofPresence, semicrf_stream_t stream)
+{
+    SEMICRF_CHECK_ARG(criterion >= SEMICRF_VEL_HAMMING && criterion <= SEMICRF_VEL_MAE, "criterion=%d is none of SEMICRF_VEL_*", criterion);
+    SEMICRF_CHECK_ARG(K >= 0 && K < (1ll << 31), "bad row count");
+    SEMICRF_CHECK_ARG(criterion == SEMICRF_VEL_MSE ? velocityMean != nullptr : velocityClass != nullptr,
+                      "velocityClass (class criteria) / velocityMean (SEMICRF_VEL_MSE) must be non-NULL");
+    if (K == 0) return SEMICRF_OK;
+    SEMICRF_CHECK_ARG(logitsVelocity && ofLogits && ofValue && ofPresence, "logitsVelocity/ofLogits/ofValue/ofPresence must be non-NULL");
+    SEMICRF_CHECK_ARG(((uintptr_t)logitsVelocity & 7) == 0, "logitsVelocity must be 8-byte aligned");
+    launch_attr_decode(logitsVelocity, ofLogits, (int)K, criterion, (long long*)velocityClass, velocityMean, ofValue, ofPresence,
+                       (hipStream_t)stream);
+    SEMICRF_CHECK_LAUNCH("semicrf_attribute_decode");
     return SEMICRF_OK;
 }
 

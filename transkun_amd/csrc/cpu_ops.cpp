@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "attr_loss_math.h"
+#include "attr_decode_math.h"
 #include "cpu_ops.h"
 
 namespace semicrf_cpu {
@@ -1041,6 +1042,57 @@ void attribute_loss_bwd(const float* gout, int gstride, const float* logitsVeloc
             of_grads<double>(ofLogits + 4 * (size_t)i, ofRefined + 2 * (size_t)i, ofPresence + 2 * (size_t)i, dd);
             for (int j = 0; j < 4; ++j) dOfLogits[4 * (size_t)i + j] = (float)(g * dd[j]);
         }
+    }
+}
+
+// ---- attribute-head readout of transcription (ModelTransformer.py:590-651) ----------------------------------------------------
+void attribute_decode(const float* logitsVelocity, const float* ofLogits, int64_t K, int criterion, int64_t* velocityClass,
+                      float* velocityMean, float* ofValue, unsigned char* ofPresence)
+{
+    using namespace semicrf::attr_decode;
+#pragma omp parallel for schedule(static)
+    for (int64_t i = 0; i < K; ++i) {
+        const float* x = logitsVelocity + (size_t)i * NVEL;
+        double p[NVEL];
+        double m = x[0];
+        int first = 0;                                                        // the smallest index of the largest logit
+        bool nan = x[0] != x[0];
+        for (int w = 1; w < NVEL; ++w) {
+            nan = nan || x[w] != x[w];
+            if ((double)x[w] > m) { m = x[w]; first = w; }
+        }
+        double sum = 0.0;
+        for (int w = 0; w < NVEL; ++w) { p[w] = exp((double)x[w] - m); sum += p[w]; }
+        const bool finite = !nan && sum < INFINITY;                           // (a +inf or all -inf: inf - inf = NaN in the sum)
+        for (int w = 0; w < NVEL; ++w) p[w] /= sum;
+        int cls = 0;
+        if (criterion == CRIT_HAMMING) {
+            cls = first;
+        } else if (criterion == CRIT_MSE) {
+            double t = 0.0;
+            for (int w = 0; w < NVEL; ++w) t += p[w] * w;
+            velocityMean[i] = finite ? (float)t : NAN;
+        } else if (criterion == CRIT_MATCH) {
+            double best = -1.0;
+            for (int v = 0; v < NVEL; ++v) {
+                double r = 0.0;                                               // summed directly, ascending w: equal windows tie exactly
+                for (int w = std::max(v - MATCH_RADIUS, 0); w <= std::min(v + MATCH_RADIUS, NVEL - 1); ++w) r += p[w];
+                if (r > best) { best = r; cls = v; }
+            }
+        } else {
+            double c = 0.0;
+            cls = 0;
+            for (int v = 0; v < NVEL; ++v) {
+                c += p[v];
+                if (c > 0.5) { cls = v; break; }
+            }
+        }
+        if (criterion != CRIT_MSE) velocityClass[i] = finite ? cls : 0;
+        const float* of = ofLogits + 4 * (size_t)i;
+        ofValue[2 * (size_t)i] = (float)of_value<double>((double)of[0]);
+        ofValue[2 * (size_t)i + 1] = (float)of_value<double>((double)of[1]);
+        ofPresence[2 * (size_t)i] = of_presence(of[2]);
+        ofPresence[2 * (size_t)i + 1] = of_presence(of[3]);
     }
 }
 

@@ -44,4 +44,8 @@ void attribute_loss_fwd(const float* logitsVelocity, const float* ofLogits, cons
 void attribute_loss_bwd(const float* gout, int gstride, const float* logitsVelocity, const float* ofLogits, const int32_t* velocity,
                         const float* ofRefined, const float* ofPresence, int64_t K, const int32_t* offsets, int C,
                         float* dLogitsVelocity, float* dOfLogits);
+// the attribute-head readout (semicrf_attribute_decode): the formulas of attr_decode_math.h per row in double, each result rounded
+// to fp32; velocityClass or velocityMean by criterion (the other may be null)
+void attribute_decode(const float* logitsVelocity, const float* ofLogits, int64_t K, int criterion, int64_t* velocityClass,
+                      float* velocityMean, float* ofValue, unsigned char* ofPresence);
 }  // namespace semicrf_cpu

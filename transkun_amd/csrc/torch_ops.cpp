@@ -861,6 +861,38 @@ void attribute_loss_bwd_cpu(Tensor gout, int64_t gstride, Tensor logitsVelocity,
     semicrf_cpu::attribute_loss_bwd(g, (int)gstride, a.lv, a.of, a.vel, a.r, a.p, K, a.off, (int)C, dlv, dof);
 }
 
+// ---- attribute-head readout of transcription (semicrf_attribute_decode) ---------------------------------------------------
+// velocityClass (int64 [K]) for the class criteria, velocityMean (fp32 [K]) for mse; the other is passed empty and not written
+struct AttrDecodeArgs { const float *lv, *of; int64_t* cls; float *mean, *val; unsigned char* pres; };
+inline AttrDecodeArgs attr_decode_args(const Tensor& logitsVelocity, const Tensor& ofLogits, int64_t K, int64_t criterion, const Tensor& velocityClass,
+                                       const Tensor& velocityMean, const Tensor& ofValue, const Tensor& ofPresence)
+{
+    STD_TORCH_CHECK(K >= 0 && K < (1ll << 31), "semicrf: bad row count");
+    STD_TORCH_CHECK(criterion >= SEMICRF_VEL_HAMMING && criterion <= SEMICRF_VEL_MAE, "semicrf: unknown velocity criterion");
+    const bool mse = criterion == SEMICRF_VEL_MSE;
+    want(velocityClass, ScalarType::Long, mse ? 0 : K, "velocityClass");
+    want(ofPresence, ScalarType::Byte, 2 * K, "ofPresence");
+    return AttrDecodeArgs{f32(logitsVelocity, K * 128, "logitsVelocity"), f32(ofLogits, K * 4, "ofLogits"),
+                          mse ? nullptr : (int64_t*)velocityClass.data_ptr(), mse ? f32w(velocityMean, K, "velocityMean") : nullptr,
+                          f32w(ofValue, 2 * K, "ofValue"), (unsigned char*)ofPresence.data_ptr()};
+}
+void attribute_decode_op(Tensor logitsVelocity, Tensor ofLogits, int64_t K, int64_t criterion, Tensor velocityClass, Tensor velocityMean,
+                         Tensor ofValue, Tensor ofPresence)
+{
+    Ctx c(ofValue); c.same(ofValue, logitsVelocity, ofLogits, ofPresence);
+    const AttrDecodeArgs a = attr_decode_args(logitsVelocity, ofLogits, K, criterion, velocityClass, velocityMean, ofValue, ofPresence);
+    if (K == 0) return;
+    check(semicrf_attribute_decode(a.lv, a.of, K, (int)criterion, a.cls, a.mean, a.val, a.pres, c.stream), "semicrf_attribute_decode");
+}
+void attribute_decode_cpu(Tensor logitsVelocity, Tensor ofLogits, int64_t K, int64_t criterion, Tensor velocityClass, Tensor velocityMean,
+                          Tensor ofValue, Tensor ofPresence)
+{
+    all_cpu(logitsVelocity, ofLogits, velocityClass, velocityMean, ofValue, ofPresence);
+    const AttrDecodeArgs a = attr_decode_args(logitsVelocity, ofLogits, K, criterion, velocityClass, velocityMean, ofValue, ofPresence);
+    if (K == 0) return;
+    semicrf_cpu::attribute_decode(a.lv, a.of, K, (int)criterion, a.cls, a.mean, a.val, a.pres);
+}
+
 // ---- transcription segment loop ----------------------------------------------------------------------------------------
 void segment_onset_filter_op(Tensor pairs, Tensor offsets, int64_t B, int64_t bound, Tensor pairs_out, Tensor offsets_out, Tensor counts_ws)
 {
@@ -954,6 +986,8 @@ STABLE_TORCH_LIBRARY(semicrf, m)
           "Tensor offsets, int C, Tensor base, bool has_base, Tensor(a!) rowLogProb, Tensor(b!) out) -> ()");
     m.def("attribute_loss_bwd(Tensor gout, int gstride, Tensor logitsVelocity, Tensor ofLogits, Tensor velocity, Tensor ofRefined, "
           "Tensor ofPresence, int K, Tensor offsets, int C, Tensor(a!) dLogitsVelocity, Tensor(b!) dOfLogits) -> ()");
+    m.def("attribute_decode(Tensor logitsVelocity, Tensor ofLogits, int K, int criterion, Tensor(a!) velocityClass, Tensor(b!) velocityMean, "
+          "Tensor(c!) ofValue, Tensor(d!) ofPresence) -> ()");
     m.def("segment_onset_filter(Tensor pairs, Tensor offsets, int B, int bound, Tensor(a!) pairs_out, Tensor(b!) offsets_out, "
           "Tensor(c!) counts_ws) -> ()");
     m.def("segment_events(Tensor pairs, int K, Tensor offsets, int B, int nSym, Tensor ofValue, Tensor ofPresence, int lastFrameIdx, "
@@ -984,6 +1018,7 @@ STABLE_TORCH_LIBRARY_IMPL(semicrf, CPU, m)
     m.impl("logprob_bwd", TORCH_BOX(&logprob_bwd_cpu));
     m.impl("attribute_loss_fwd", TORCH_BOX(&attribute_loss_fwd_cpu));
     m.impl("attribute_loss_bwd", TORCH_BOX(&attribute_loss_bwd_cpu));
+    m.impl("attribute_decode", TORCH_BOX(&attribute_decode_cpu));
 }
 
 STABLE_TORCH_LIBRARY_IMPL(semicrf, CUDA, m)
@@ -1022,6 +1057,7 @@ STABLE_TORCH_LIBRARY_IMPL(semicrf, CUDA, m)
     m.impl("interval_features_gather_bwd", TORCH_BOX(&interval_features_gather_bwd_op));
     m.impl("attribute_loss_fwd", TORCH_BOX(&attribute_loss_fwd_op));
     m.impl("attribute_loss_bwd", TORCH_BOX(&attribute_loss_bwd_op));
+    m.impl("attribute_decode", TORCH_BOX(&attribute_decode_op));
     m.impl("segment_onset_filter", TORCH_BOX(&segment_onset_filter_op));
     m.impl("segment_events", TORCH_BOX(&segment_events_op));
 }

@@ -182,6 +182,9 @@ class SegmentTranscriber(nn.Module):
                                         # model restricted to the frames from the start on) instead of the MAP path
         self.mbrThreshold = 0.5         # decoder == "mbr": the threshold of decode_mbr, a float in (0, 1]
         self.mbrTolerance = None        # decoder == "mbr": decode_mbr's tolerance (None, an int or (onset, offset) in frames)
+        self.attributeDecode = "torch"  # "fused": what decode_step reads out of the two heads (velocity, refined onset/offset, presence)
+                                        # by attributes.attribute_decode, one launch, instead of the reference's torch calls; the
+                                        # refined times then no longer carry those calls' fp32 cancellation (3e-3 of a frame)
         self._merged = None
         self.velocityPredictor = _head(size * 3, velocityPredictorHiddenSize, 128, velocityDropoutProb)           # :109-115
         self.refinedOFPredictor = _head(size * 3, refinedOFPredictorHiddenSize, 4, refinedOFDropoutProb)          # :119-125
@@ -289,6 +292,8 @@ class SegmentTranscriber(nn.Module):
         assert ctxBatch.dim() == 4
         Fn, P, T, D = ctxBatch.shape
         assert P == len(self.targetMIDIPitch)
+        if self.attributeDecode not in ("torch", "fused"):
+            raise ValueError(f"attributeDecode must be 'torch' or 'fused', not {self.attributeDecode!r}")
         B = Fn * P
         dev = ctxBatch.device
         ops = _lib.ops()
@@ -322,11 +327,12 @@ class SegmentTranscriber(nn.Module):
                         lastP=lastP, nextStart=nextStart)
         attributeInput, sym, sc = attributes.attribute_input_packed(ctxBatch, pairs, offsets, K)       # :578-586
         logitsVelocity = self.velocityPredictor(attributeInput)
-        velocity = self._velocity(logitsVelocity, velocityCriteron)
-        ofValue, ofPresence = self.refinedOFPredictor(attributeInput).chunk(2, dim=-1)               # :646-655
-        ofDist = torch.distributions.ContinuousBernoulli(logits=ofValue, validate_args=False)   # (the argument check is a host sync)
-        ofValue = torch.clamp((ofDist.mean - 0.5) / 0.99, -0.5, 0.5).float().contiguous()
-        ofPresence = (ofPresence > 0).contiguous()
+        ofLogits = self.refinedOFPredictor(attributeInput)
+        # :590-655.  "torch": the reference's torch calls (some twenty small launches); "fused": one launch on the same head outputs
+        # (with k_cap the rows behind the real count hold whatever the heads make of frame pairs clamped into the segment: the op
+        # takes any row, as the torch calls do)
+        readout = attributes.attribute_decode if self.attributeDecode == "fused" else attributes.attribute_decode_torch
+        velocity, ofValue, ofPresence = readout(logitsVelocity, ofLogits, velocityCriteron)
         times = torch.empty(K, 2, dtype=torch.float64, device=dev)
         flags = torch.empty(K, 2, dtype=torch.uint8, device=dev)
         ops.segment_events(pairs, K, offsets, B, P, ofValue, ofPresence.view(torch.uint8), int(lastFrameIdx), self.hopSize / self.fs,
@@ -381,7 +387,8 @@ class SegmentTranscriber(nn.Module):
     # the validation statistic
     # ------------------------------------------------------------------------------------------------------------------
     @torch.no_grad()
-    def computeStats(self, ctxBatch: torch.Tensor, intervalsBatch, velocityBatch, ofRefinedGTBatch, tolerance=None) -> dict:
+    def computeStats(self, ctxBatch: torch.Tensor, intervalsBatch, velocityBatch, ofRefinedGTBatch, tolerance=None,
+                     attributeRoute: str = "torch") -> dict:
         """ModelTransformer.py:388-495 from `ctx` on (the backbone's output in the place of the audio, as in decode_step): decode
         without a forced start, compare the decoded paths with the target intervals (compareBracket and compareFramewise, :426-438)
         and evaluate the two attribute heads on the TARGET intervals (:445-481).  The decoded paths never leave the device: the
@@ -395,7 +402,11 @@ class SegmentTranscriber(nn.Module):
         Returns the reference's dict: nGT, nEst, nCorrect, nGTFramewise, nEstFramewise, nCorrectFramewise (ints), seVelocityForced,
         seOFForced (floats: the squared error of the softmax-weighted mean velocity, and of the ContinuousBernoulli mean shifted
         back and clamped to +-0.5; evaluated in float64 from the heads' fp32 logits).  With tolerance (None, an int or
-        (onset, offset) in frames, 0..8) also nCorrectTolerant: the matches within that window.  Without a single target interval the heads are not run and both errors are 0."""
+        (onset, offset) in frames, 0..8) also nCorrectTolerant: the matches within that window.  Without a single target interval the heads are not run and both errors are 0.
+
+        attributeRoute "fused" takes the mean velocity and the clamped ContinuousBernoulli mean from attributes.attribute_decode
+        (criterion "mse": fp32, one launch, each row within 8 eps32 of the float64 value) instead of the float64 torch calls; the
+        differences and the two sums are formed in float64 either way."""
         assert ctxBatch.dim() == 4
         Fn, P, T, D = ctxBatch.shape
         assert P == len(self.targetMIDIPitch)
@@ -403,6 +414,8 @@ class SegmentTranscriber(nn.Module):
         B = Fn * P
         dev = ctxBatch.device
         tol = _nsci._tolerance(tolerance, "computeStats")
+        if attributeRoute not in ("torch", "fused"):
+            raise ValueError(f"attributeRoute must be 'torch' or 'fused', not {attributeRoute!r}")
         flat = [sym for seg in intervalsBatch for sym in seg]                            # :415-416
         assert len(flat) == B
         # everything the host has to say goes first: the copies need nothing from the GPU and nothing below waits for them
@@ -421,12 +434,17 @@ class SegmentTranscriber(nn.Module):
             # The heads run in fp32 as in the reference; what follows their logits runs in float64 (K x 128 values).  The closed form
             # of the ContinuousBernoulli mean, p / (2p - 1) + 1 / (log(1 - p) - log p), is the difference of two terms that grow like
             # 1 / |logit| towards logit 0: in fp32 it loses up to 1e-5 absolute there, 1e-4 of seOFForced on heads with small logits.
-            logitsVelocity = self.velocityPredictor(attributeInput).double()             # :454
-            pVelocity = F.softmax(logitsVelocity, dim=-1)                                # :455
-            velocity = (pVelocity * torch.arange(128, device=dev, dtype=torch.float64)).sum(-1)   # :459-460
-            ofValue, _ = self.refinedOFPredictor(attributeInput).double().chunk(2, dim=-1)        # :463
-            ofDist = torch.distributions.ContinuousBernoulli(logits=ofValue, validate_args=False)   # (the argument check is a host sync)
-            ofValue = torch.clamp((ofDist.mean - 0.5) / 0.99, -0.5, 0.5)                 # :467-468
+            if attributeRoute == "fused":
+                # the op evaluates the mean from the logit: its fp32 is good enough (no cancellation left), in one launch
+                velocity, ofValue, _ = attributes.attribute_decode(self.velocityPredictor(attributeInput), self.refinedOFPredictor(attributeInput), "mse")
+                velocity, ofValue = velocity.double(), ofValue.double()
+            else:
+                logitsVelocity = self.velocityPredictor(attributeInput).double()             # :454
+                pVelocity = F.softmax(logitsVelocity, dim=-1)                                # :455
+                velocity = (pVelocity * torch.arange(128, device=dev, dtype=torch.float64)).sum(-1)   # :459-460
+                ofValue, _ = self.refinedOFPredictor(attributeInput).double().chunk(2, dim=-1)        # :463
+                ofDist = torch.distributions.ContinuousBernoulli(logits=ofValue, validate_args=False)   # (the argument check is a host sync)
+                ofValue = torch.clamp((ofDist.mean - 0.5) / 0.99, -0.5, 0.5)                 # :467-468
             out[8] = (velocity - vel_gt).pow(2).sum()                                    # :481
             out[9] = (ofValue - of_gt).pow(2).sum()                                      # :480
         h = out.cpu().tolist()                                                           # the one host sync
@@ -456,23 +474,6 @@ class SegmentTranscriber(nn.Module):
         if x.device.type == "cpu" and torch.device(dev).type == "cuda":
             x = x.pin_memory()
         return x.to(dev, non_blocking=True)
-
-    @staticmethod
-    def _velocity(logitsVelocity: torch.Tensor, criterion: str) -> torch.Tensor:
-        pVelocity = F.softmax(logitsVelocity, dim=-1)                                    # :590-637
-        dev = pVelocity.device
-        if criterion == "hamming":
-            return torch.argmax(pVelocity, dim=-1)
-        if criterion == "mse":
-            return (pVelocity * torch.arange(128, device=dev)).sum(-1)
-        if criterion == "match":
-            w = torch.arange(128, device=dev)
-            utility = ((w.unsqueeze(1) - w.unsqueeze(0)).abs() < 0.1 * 128).float()
-            return torch.argmax(pVelocity @ utility, dim=-1)
-        if criterion == "mae":
-            tmp = (pVelocity.cumsum(-1) - 0.5) > 0
-            return torch.argmax(tmp * torch.arange(128, 0., -1, device=dev), dim=-1)
-        raise Exception("Unrecognized criterion: {}".format(criterion))
 
     @staticmethod
     def _packed_rows(step: dict) -> torch.Tensor:
