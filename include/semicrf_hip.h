@@ -56,6 +56,7 @@ extern "C" {
 #define SEMICRF_OP_EXPECTATION 9       /* semicrf_expectation / semicrf_covariance (one workspace for the pair) */
 #define SEMICRF_OP_MBR_SELECT 10       /* semicrf_mbr_select */
 #define SEMICRF_OP_MARGINAL_DECODE_TOL 11   /* semicrf_marginal_decode_tol */
+#define SEMICRF_OP_ATTRIBUTE_HEADS 12       /* semicrf_attribute_heads: T = rows K, B = Hv + Ho (see there) */
 
 #define SEMICRF_TOL_MAX 8              /* largest onset / offset tolerance (frames) of the *_tol entry points */
 
@@ -765,6 +766,37 @@ int semicrf_attribute_loss_bwd(const float* gout, int gstride, const float* logi
 #define SEMICRF_VEL_MAE 3
 int semicrf_attribute_decode(const float* logitsVelocity, const float* ofLogits, int64_t K, int criterion, int64_t* velocityClass,
                              float* velocityMean, float* ofValue, unsigned char* ofPresence, semicrf_stream_t stream);
+
+/*
+ * The two attribute heads of transcription, from the packed decode output to their raw outputs (inference only).  Replaces: the
+ * gather interval_features_gather, the materialised [K][3D] input and the two nn.Sequential heads (Linear, GELU, Dropout, Linear) of
+ * TransKun.transcribeFrames (ModelTransformer.py:578-590, :638; the modules of :112-128) in eval mode.  For interval i of chain c
+ * (found from offsets as the gather does), (b, e) = pairs[i]:
+ *   x_i               = [ ctx[c][b][:] | ctx[c][e][:] | ctx[c][b][:] * ctx[c][e][:] ]    (3 D values, never written to memory)
+ *   logitsVelocity[i] = W2v gelu(W1v x_i + b1v) + b2v        [Nv]
+ *   ofLogits[i]       = W2o gelu(W1o x_i + b1o) + b2o        [No]
+ * gelu is the exact erf form (csrc/attr_heads_math.h).  ctx: [C][T] rows of ldc >= D floats.  The weights are PACKED, fp32, dense:
+ *   W1 [3D][Hv + Ho]   column j < Hv: row j of the velocity head's first Linear weight; column Hv + j: the onset/offset head's
+ *   b1 [Hv + Ho]       the two first biases, in the same order
+ *   W2 [Hv][Nv] followed by [Ho][No]: the second Linear weights, TRANSPOSED (hidden-major)
+ *   b2 [Nv + No]
+ * Exact fp32 on the matrix pipe (v_mfma_f32_32x32x2_f32).  Every output element is ONE fixed chain of operations: the contraction
+ * over k = 0 .. 3D-1 ascending, + b1, gelu; per slice of SEMICRF_HEADS_SLICE hidden columns of its head the contraction over the
+ * slice's columns ascending; the slices' partial sums added in ascending order, b2 last.  No atomics: a row's outputs are
+ * bit-identical whatever K is, wherever the row sits and whatever the other rows hold.  pairs outside [0, T-1] are clamped into it.
+ * symIdx[i] = c % nSym and scatterIdx[i] = c (int64 [K]) as the gather writes them; either may be NULL.
+ * Workspace: semicrf_attribute_heads_workspace_bytes(K, Hv, Ho, Nv, No), the slices' partial sums (about K * (Nv * ceil(Hv / 64) +
+ * No * ceil(Ho / 64)) floats); semicrf_workspace_bytes(SEMICRF_OP_ATTRIBUTE_HEADS, K, Hv + Ho) is an upper bound of it for heads of at
+ * most 128 outputs each.  Two launches on `stream` (the tiles; the sum over slices), none for K == 0; no synchronisation or allocation.
+ * SEMICRF_EINVAL: a NULL pointer, a size below 1, K < 0, ldc < D; SEMICRF_EWORKSPACE: a workspace that is too small.
+ */
+#define SEMICRF_HEADS_ROW_TILE 64
+#define SEMICRF_HEADS_SLICE 64
+size_t semicrf_attribute_heads_workspace_bytes(int64_t K, int Hv, int Ho, int Nv, int No);
+int semicrf_attribute_heads(const float* ctx, int C, int T, int D, int64_t ldc, const int32_t* pairs, int64_t K, const int32_t* offsets,
+                            int nSym, const float* W1, const float* b1, const float* W2, const float* b2, int Hv, int Ho, int Nv, int No,
+                            float* logitsVelocity, float* ofLogits, int64_t* symIdx, int64_t* scatterIdx, void* ws, size_t ws_bytes,
+                            semicrf_stream_t stream);
 
 /*
  * Transcription segment loop, on the packed decode output in HBM.

@@ -10,6 +10,7 @@ keeps the reference's signature (Python lists in, four tensors out) for callers 
 from __future__ import annotations
 
 import importlib
+import weakref
 from typing import List, Sequence, Tuple
 
 import torch
@@ -239,6 +240,129 @@ def attribute_decode_torch(logitsVelocity: torch.Tensor, ofLogits: torch.Tensor,
     ofValue = torch.clamp((ofDist.mean - 0.5) / 0.99, -0.5, 0.5).float().contiguous()
     ofPresence = (ofPresence > 0).contiguous()
     return velocity, ofValue, ofPresence
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# the two attribute heads themselves (TransKun.transcribeFrames, ModelTransformer.py:578-590, :638), inference only
+# ----------------------------------------------------------------------------------------------------------------------
+HEADS_ROW_TILE = _lib.HEADS_ROW_TILE            # intervals per workgroup of the kernel (SEMICRF_HEADS_ROW_TILE)
+_HEADS_PACKED = weakref.WeakKeyDictionary()     # velocityPredictor -> (key, packed weights)
+
+
+def _head_linears(head: torch.nn.Module, name: str):
+    """(first Linear, second Linear) of a head built as the reference builds it (ModelTransformer.py:112-128): Linear, GELU (the exact erf
+    form), Dropout, Linear.  A training-mode Dropout with p > 0 raises ValueError: the op evaluates the heads in eval mode only."""
+    mods = list(head.children()) if isinstance(head, torch.nn.Sequential) else []
+    if len(mods) < 3 or not isinstance(mods[0], torch.nn.Linear) or not isinstance(mods[-1], torch.nn.Linear):
+        raise TypeError(f"{name}: expected nn.Sequential(Linear, GELU, [Dropout,] Linear)")
+    ngelu = 0
+    for m in mods[1:-1]:
+        if isinstance(m, torch.nn.GELU) and getattr(m, "approximate", "none") == "none":
+            ngelu += 1
+        elif isinstance(m, torch.nn.Dropout):
+            if m.training and m.p > 0:
+                raise ValueError(f"{name} is in training mode with dropout p = {m.p}: attribute_heads is the eval-mode forward only "
+                                 "(call .eval(), or use attribute_heads_torch)")
+        else:
+            raise TypeError(f"{name}: unsupported layer {type(m).__name__} between the two Linear layers")
+    if ngelu != 1 or mods[0].out_features != mods[-1].in_features:
+        raise TypeError(f"{name}: expected exactly one exact-erf GELU between two matching Linear layers")
+    return mods[0], mods[-1]
+
+
+def _packed_heads(velocityPredictor, refinedOFPredictor):
+    """The two heads' parameters in the layout of semicrf_attribute_heads (include/semicrf_hip.h), fp32: W1 [3D, Hv + Ho], b1 [Hv + Ho],
+    W2 = W2v^T [Hv, Nv] followed by W2o^T [Ho, No] (flat), b2 [Nv + No].  Packed by torch calls once and kept until a parameter's
+    `_version` (an optimizer step, load_state_dict: both write in place) or storage changes."""
+    v1, v2 = _head_linears(velocityPredictor, "velocityPredictor")
+    o1, o2 = _head_linears(refinedOFPredictor, "refinedOFPredictor")
+    if v1.in_features != o1.in_features:
+        raise ValueError("the two heads must take the same input")
+    lins = (v1, v2, o1, o2)
+    params = [p for l in lins for p in (l.weight, l.bias) if p is not None]
+    key = (id(refinedOFPredictor),) + tuple((p._version, p.data_ptr(), p.dtype, p.device) for p in params)
+    hit = _HEADS_PACKED.get(velocityPredictor)
+    if hit is not None and hit[0] == key:
+        return hit[1]
+    with torch.no_grad():
+        def bias(l):
+            return l.bias.float() if l.bias is not None else torch.zeros(l.out_features, dtype=torch.float32, device=l.weight.device)
+        W1 = torch.cat([v1.weight.float().t(), o1.weight.float().t()], dim=1).contiguous()
+        b1 = torch.cat([bias(v1), bias(o1)]).contiguous()
+        W2 = torch.cat([v2.weight.float().t().reshape(-1), o2.weight.float().t().reshape(-1)]).contiguous()
+        b2 = torch.cat([bias(v2), bias(o2)]).contiguous()
+    packed = dict(W1=W1, b1=b1, W2=W2, b2=b2, Hv=v1.out_features, Ho=o1.out_features, Nv=v2.out_features, No=o2.out_features,
+                  nIn=v1.in_features)
+    _HEADS_PACKED[velocityPredictor] = (key, packed)
+    return packed
+
+
+def attribute_heads(ctxBatch: torch.Tensor, pairs: torch.Tensor, offsets: torch.Tensor, velocityPredictor, refinedOFPredictor, K: int = None):
+    """The gather and both attribute heads as ONE op (semicrf_attribute_heads; two launches on a GPU): attribute_input_packed's
+    arguments plus the two head modules (nn.Sequential(Linear, GELU, Dropout, Linear), as SegmentTranscriber holds them) ->
+    (logitsVelocity [K, Nv], ofLogits [K, No], symIdx [K], scatterIdx [K]), what
+
+        x, symIdx, scatterIdx = attribute_input_packed(ctxBatch, pairs, offsets, K)
+        velocityPredictor(x), refinedOFPredictor(x)
+
+    gives in eval mode (attribute_heads_torch), without the [K, 3D] input ever reaching memory.  Exact fp32 on the matrix pipe; every
+    output element is one fixed chain of operations (include/semicrf_hip.h), so a row's outputs are bit-identical whatever K is,
+    wherever the row sits, whatever the other rows hold and from run to run.  Rows past offsets[-1] (the k_cap route of decode_step)
+    are legal: any pair of frames inside [0, T-1] is.  ctxBatch [N, SYM, T, D] on a GPU (HIP kernels) or the CPU (the host mirror:
+    the same order of operations); any float dtype (converted to fp32 first); a view with a row stride above D is read in place.
+    The output sizes Nv, No and the hidden sizes come from the modules.  K = offsets[-1] if not given (one host sync); otherwise
+    nothing waits for the host, and the call can be captured in a HIP graph.
+
+    Forward only: RuntimeError if grad mode is on and ctxBatch or a parameter requires grad.  ValueError if a head is in training
+    mode with a dropout probability above 0.  The packed weights are cached (see _packed_heads)."""
+    assert ctxBatch.dim() == 4
+    N, SYM, T, D = ctxBatch.shape
+    _lib.require_device(ctxBatch, "ctxBatch")
+    w = _packed_heads(velocityPredictor, refinedOFPredictor)
+    if torch.is_grad_enabled() and (ctxBatch.requires_grad or any(p.requires_grad for m in (velocityPredictor, refinedOFPredictor)
+                                                                  for p in m.parameters())):
+        raise RuntimeError("attribute_heads is forward-only: call it under torch.no_grad() (training keeps the torch modules, "
+                           "attribute_heads_torch)")
+    if w["nIn"] != 3 * D:
+        raise ValueError(f"the heads take {w['nIn']} inputs, ctxBatch gives 3 * {D}")
+    dev = ctxBatch.device
+    if w["W1"].device != dev:
+        raise RuntimeError(f"the heads' parameters are on {w['W1'].device}, ctxBatch on {dev}")
+    if K is None:
+        K = int(offsets[-1])
+    K = int(K)
+    assert pairs.dtype == torch.int32 and offsets.dtype == torch.int32 and offsets.numel() == N * SYM + 1
+    x = ctxBatch.detach()
+    if x.dtype != torch.float32:
+        x = x.float()
+    ldc = x.stride(2)
+    if not ((D == 1 or x.stride(3) == 1) and ldc >= D and x.stride(1) == T * ldc and x.stride(0) == SYM * T * ldc):
+        x = x.contiguous()
+        ldc = D
+    C = N * SYM
+    x3 = x.as_strided((C, T, D), (T * ldc, ldc, 1), x.storage_offset())
+    Hv, Ho, Nv, No = w["Hv"], w["Ho"], w["Nv"], w["No"]
+    logitsVelocity = torch.empty(K, Nv, dtype=torch.float32, device=dev)
+    ofLogits = torch.empty(K, No, dtype=torch.float32, device=dev)
+    sym = torch.empty(K, dtype=torch.int64, device=dev)
+    sc = torch.empty(K, dtype=torch.int64, device=dev)
+    if K > 0:
+        if dev.type == "cpu":
+            ws = torch.empty(0, dtype=torch.uint8)
+        else:
+            ws = torch.empty(int(_lib.load().semicrf_attribute_heads_workspace_bytes(K, Hv, Ho, Nv, No)), dtype=torch.uint8, device=dev)
+        _lib.ops().attribute_heads(x3, C, T, D, ldc, pairs.contiguous(), K, offsets.contiguous(), SYM, w["W1"], w["b1"], w["W2"], w["b2"],
+                                   Hv, Ho, Nv, No, logitsVelocity, ofLogits, sym, sc, ws)
+    return logitsVelocity, ofLogits, sym, sc
+
+
+def attribute_heads_torch(ctxBatch: torch.Tensor, pairs: torch.Tensor, offsets: torch.Tensor, velocityPredictor, refinedOFPredictor,
+                          K: int = None):
+    """attribute_heads' arguments and result by the gather kernel and the two torch modules (ModelTransformer.py:578-590, :638): the
+    [K, 3D] input in memory, six stock launches and two BLAS calls.  SegmentTranscriber's default route (attributeHeads = "torch"),
+    the route of training, and the comparison route of the tests and tools/bench_attr_heads.py."""
+    attributeInput, sym, sc = attribute_input_packed(ctxBatch, pairs, offsets, K)
+    return velocityPredictor(attributeInput), refinedOFPredictor(attributeInput), sym, sc
 
 
 def _flatten_target(x):

@@ -61,6 +61,10 @@ void launch_interval_features_bwd(const float* gout, const float* ctx, int C, in
 void launch_attr_loss_fwd(const float* logitsVelocity, const float* ofLogits, const int* velocity, const float* ofRefined,
                           const float* ofPresence, int K, const int* offsets, int C, const float* base, float* rowLogProb, float* out,
                           hipStream_t stream);
+size_t attr_heads_workspace_bytes(long long K, int Hv, int Ho, int Nv, int No);
+void launch_attr_heads(const float* ctx, int C, int T, int D, long long ldc, const int* pairs, int K, const int* offsets, int nSym,
+                       const float* W1, const float* b1, const float* W2, const float* b2, int Hv, int Ho, int Nv, int No,
+                       float* logitsVelocity, float* ofLogits, long long* symIdx, long long* scatterIdx, float* ws, hipStream_t stream);
 void launch_attr_decode(const float* logitsVelocity, const float* ofLogits, int K, int criterion, long long* velocityClass,
                         float* velocityMean, float* ofValue, unsigned char* ofPresence, hipStream_t stream);
 void launch_attr_loss_bwd(const float* gout, int gstride, const float* logitsVelocity, const float* ofLogits, const int* velocity,
@@ -321,6 +325,8 @@ size_t semicrf_workspace_bytes(int op, int T, int B)
         case SEMICRF_OP_EXPECTATION: return expectation_workspace_bytes(T, B);
         case SEMICRF_OP_MBR_SELECT: return mbr_select_workspace_bytes(T, B);
         case SEMICRF_OP_MARGINAL_DECODE_TOL: return marginal_decode_tol_workspace_bytes(T, B);
+        // T = rows, B = Hv + Ho: the two heads have at most (B + 63) / 64 + 1 slices between them, 128 outputs a plane at the most
+        case SEMICRF_OP_ATTRIBUTE_HEADS: return attr_heads_workspace_bytes(T, 64 * ((B + 63) / 64 + 1), 1, 128, 1);
         default: return 0;
     }
 }
@@ -1151,6 +1157,39 @@ int semicrf_attribute_decode(const float* logitsVelocity, const float* ofLogits,
     launch_attr_decode(logitsVelocity, ofLogits, (int)K, criterion, (long long*)velocityClass, velocityMean, ofValue, ofPresence,
                        (hipStream_t)stream);
     SEMICRF_CHECK_LAUNCH("semicrf_attribute_decode");
+    return SEMICRF_OK;
+}
+
+size_t semicrf_attribute_heads_workspace_bytes(int64_t K, int Hv, int Ho, int Nv, int No)
+{
+    if (K < 0 || Hv < 1 || Ho < 1 || Nv < 1 || No < 1) return 0;
+    return attr_heads_workspace_bytes(K, Hv, Ho, Nv, No);
+}
+
+int semicrf_attribute_heads(const float* ctx, int C, int T, int D, int64_t ldc, const int32_t* pairs, int64_t K, const int32_t* offsets,
+                            int nSym, const float* W1, const float* b1, const float* W2, const float* b2, int Hv, int Ho, int Nv, int No,
+                            float* logitsVelocity, float* ofLogits, int64_t* symIdx, int64_t* scatterIdx, void* ws, size_t ws_bytes,
+                            semicrf_stream_t stream)
+{
+    SEMICRF_CHECK_ARG(C >= 1 && T >= 1 && D >= 1 && nSym >= 1, "C=%d T=%d D=%d nSym=%d must be >= 1", C, T, D, nSym);
+    SEMICRF_CHECK_ARG(Hv >= 1 && Ho >= 1 && Nv >= 1 && No >= 1, "Hv=%d Ho=%d Nv=%d No=%d must be >= 1", Hv, Ho, Nv, No);
+    SEMICRF_CHECK_ARG(D < (1 << 20) && Hv < (1 << 21) && Ho < (1 << 21) && Nv < (1 << 20) && No < (1 << 20), "D / hidden / output sizes too large");
+    SEMICRF_CHECK_ARG(K >= 0 && K < (1ll << 31), "bad interval count K=%lld", (long long)K);
+    SEMICRF_CHECK_ARG(ldc >= D, "bad row stride ldc=%lld < D=%d", (long long)ldc, D);
+    SEMICRF_CHECK_ARG(ctx && offsets, "ctx/offsets must be non-NULL");
+    SEMICRF_CHECK_ARG(W1 && b1 && W2 && b2, "W1/b1/W2/b2 must be non-NULL");
+    if (K == 0) return SEMICRF_OK;
+    SEMICRF_CHECK_ARG(pairs && logitsVelocity && ofLogits, "pairs/logitsVelocity/ofLogits must be non-NULL");
+    SEMICRF_CHECK_ARG((long long)K * ((long long)Nv + No) < (1ll << 38), "K * (Nv + No) too large");
+    const size_t need = attr_heads_workspace_bytes(K, Hv, Ho, Nv, No);
+    SEMICRF_CHECK_ARG(ws && ((uintptr_t)ws & 3) == 0, "ws must be non-NULL and 4-byte aligned");
+    if (ws_bytes < need) {
+        set_error("workspace too small for attribute_heads: %zu bytes given, semicrf_attribute_heads_workspace_bytes says %zu", ws_bytes, need);
+        return SEMICRF_EWORKSPACE;
+    }
+    launch_attr_heads(ctx, C, T, D, ldc, pairs, (int)K, offsets, nSym, W1, b1, W2, b2, Hv, Ho, Nv, No, logitsVelocity, ofLogits,
+                      (long long*)symIdx, (long long*)scatterIdx, (float*)ws, (hipStream_t)stream);
+    SEMICRF_CHECK_LAUNCH("semicrf_attribute_heads");
     return SEMICRF_OK;
 }
 

@@ -17,6 +17,7 @@
 
 #include "attr_loss_math.h"
 #include "attr_decode_math.h"
+#include "attr_heads_math.h"
 #include "cpu_ops.h"
 
 namespace semicrf_cpu {
@@ -1093,6 +1094,59 @@ void attribute_decode(const float* logitsVelocity, const float* ofLogits, int64_
         ofValue[2 * (size_t)i + 1] = (float)of_value<double>((double)of[1]);
         ofPresence[2 * (size_t)i] = of_presence(of[2]);
         ofPresence[2 * (size_t)i + 1] = of_presence(of[3]);
+    }
+}
+
+// ---- the two attribute heads (semicrf_attribute_heads; ModelTransformer.py:578-590, :638) ---------------------------------------
+// The order of operations of attr_heads.hip per output element, in fp32: the k chain of layer 1 ascending from +0 (fmaf), + b1, gelu,
+// per slice of HEADS_SLICE hidden columns the chain of layer 2 ascending from +0, the slices' sums added in ascending order, b2 last.
+void attribute_heads(const float* ctx, int C, int T, int D, int64_t ldc, const int32_t* pairs, int64_t K, const int32_t* offsets, int nSym,
+                     const float* W1, const float* b1, const float* W2, const float* b2, int Hv, int Ho, int Nv, int No,
+                     float* logitsVelocity, float* ofLogits, int64_t* symIdx, int64_t* scatterIdx)
+{
+    using namespace semicrf::attr_heads;
+    const int nk = 3 * D, H = Hv + Ho;
+#pragma omp parallel
+    {
+        std::vector<float> x((size_t)nk), h((size_t)H);
+#pragma omp for schedule(dynamic, 4)
+        for (int64_t i = 0; i < K; ++i) {
+            int lo = 0, hi = C;                                               // chain_of_interval (chain_search.h)
+            while (hi - lo > 1) {
+                const int mid = (lo + hi) >> 1;
+                if (offsets[mid] <= i) lo = mid; else hi = mid;
+            }
+            const int c = lo;
+            const int b = std::min(std::max(pairs[2 * i], 0), T - 1), e = std::min(std::max(pairs[2 * i + 1], 0), T - 1);
+            const float* pa = ctx + ((size_t)c * T + b) * ldc;
+            const float* pb = ctx + ((size_t)c * T + e) * ldc;
+            for (int d = 0; d < D; ++d) { x[d] = pa[d]; x[D + d] = pb[d]; x[2 * D + d] = pa[d] * pb[d]; }
+            std::fill(h.begin(), h.end(), 0.0f);
+            for (int k = 0; k < nk; ++k) {
+                const float xv = x[k];
+                const float* w = W1 + (size_t)k * H;
+                for (int j = 0; j < H; ++j) h[j] = fmaf(xv, w[j], h[j]);
+            }
+            for (int j = 0; j < H; ++j) h[j] = gelu<float>(h[j] + b1[j]);
+            for (int head = 0; head < 2; ++head) {
+                const int Hh = head ? Ho : Hv, N = head ? No : Nv;
+                const float* g = h.data() + (head ? Hv : 0);
+                const float* w2 = head ? W2 + (size_t)Hv * Nv : W2;
+                const float* bias = head ? b2 + Nv : b2;
+                float* out = head ? ofLogits + (size_t)i * No : logitsVelocity + (size_t)i * Nv;
+                for (int n = 0; n < N; ++n) {
+                    float t = 0.0f;
+                    for (int j0 = 0; j0 < Hh; j0 += HEADS_SLICE) {
+                        float p = 0.0f;
+                        for (int j = j0; j < std::min(j0 + HEADS_SLICE, Hh); ++j) p = fmaf(g[j], w2[(size_t)j * N + n], p);
+                        t = j0 == 0 ? p : t + p;
+                    }
+                    out[n] = t + bias[n];
+                }
+            }
+            if (symIdx) symIdx[i] = c % nSym;
+            if (scatterIdx) scatterIdx[i] = c;
+        }
     }
 }
 

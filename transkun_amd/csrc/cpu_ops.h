@@ -48,4 +48,9 @@ void attribute_loss_bwd(const float* gout, int gstride, const float* logitsVeloc
 // to fp32; velocityClass or velocityMean by criterion (the other may be null)
 void attribute_decode(const float* logitsVelocity, const float* ofLogits, int64_t K, int criterion, int64_t* velocityClass,
                       float* velocityMean, float* ofValue, unsigned char* ofPresence);
+// the two attribute heads (semicrf_attribute_heads): the device kernel's order of operations per output element, in fp32
+// (attr_heads_math.h); the weights packed as the C ABI takes them; symIdx / scatterIdx may be null
+void attribute_heads(const float* ctx, int C, int T, int D, int64_t ldc, const int32_t* pairs, int64_t K, const int32_t* offsets, int nSym,
+                     const float* W1, const float* b1, const float* W2, const float* b2, int Hv, int Ho, int Nv, int No,
+                     float* logitsVelocity, float* ofLogits, int64_t* symIdx, int64_t* scatterIdx);
 }  // namespace semicrf_cpu

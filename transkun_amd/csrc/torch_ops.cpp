@@ -893,6 +893,55 @@ void attribute_decode_cpu(Tensor logitsVelocity, Tensor ofLogits, int64_t K, int
     semicrf_cpu::attribute_decode(a.lv, a.of, K, (int)criterion, a.cls, a.mean, a.val, a.pres);
 }
 
+// ---- the two attribute heads (semicrf_attribute_heads) --------------------------------------------------------------------------
+// ctx is a [C, T, D] tensor, possibly a view with rows of ldc >= D floats (its strides are checked against ldc); the packed
+// weights and every output are dense and checked for their element counts.  symIdx / scatterIdx: int64 [K], or empty (not written).
+struct AttrHeadsArgs { const float *ctx, *W1, *b1, *W2, *b2; const int32_t *pairs, *off; float *lv, *of; int64_t *sym, *sc; };
+inline AttrHeadsArgs attr_heads_args(const Tensor& ctx, int64_t C, int64_t T, int64_t D, int64_t ldc, const Tensor& pairs, int64_t K,
+                                     const Tensor& offsets, int64_t nSym, const Tensor& W1, const Tensor& b1, const Tensor& W2, const Tensor& b2,
+                                     int64_t Hv, int64_t Ho, int64_t Nv, int64_t No, const Tensor& logitsVelocity, const Tensor& ofLogits,
+                                     const Tensor& symIdx, const Tensor& scatterIdx)
+{
+    score_dims(C, T, D);
+    STD_TORCH_CHECK(K >= 0 && K < (1ll << 31), "semicrf: bad interval count");
+    STD_TORCH_CHECK(nSym >= 1 && ldc >= D, "semicrf: bad nSym / row stride");
+    STD_TORCH_CHECK(Hv >= 1 && Ho >= 1 && Nv >= 1 && No >= 1 && Hv < (1 << 21) && Ho < (1 << 21) && Nv < (1 << 20) && No < (1 << 20),
+                    "semicrf: bad head sizes");
+    STD_TORCH_CHECK(ctx.dim() == 3 && ctx.size(0) == C && ctx.size(1) == T && ctx.size(2) == D, "semicrf: `ctx` must be [C, T, D]");
+    STD_TORCH_CHECK((D == 1 || ctx.stride(2) == 1) && (T == 1 || ctx.stride(1) == ldc) && (C == 1 || ctx.stride(0) == T * ldc),
+                    "semicrf: `ctx` must be [C][T] rows of ldc floats with unit stride inside a row");
+    if (symIdx.numel() > 0) want(symIdx, ScalarType::Long, K, "symIdx");
+    if (scatterIdx.numel() > 0) want(scatterIdx, ScalarType::Long, K, "scatterIdx");
+    return AttrHeadsArgs{f32s(ctx, "ctx"), f32(W1, 3 * D * (Hv + Ho), "W1"), f32(b1, Hv + Ho, "b1"), f32(W2, Hv * Nv + Ho * No, "W2"),
+                         f32(b2, Nv + No, "b2"), i32(pairs, 2 * K, "pairs"), i32(offsets, C + 1, "offsets"),
+                         f32w(logitsVelocity, K * Nv, "logitsVelocity"), f32w(ofLogits, K * No, "ofLogits"),
+                         symIdx.numel() > 0 ? (int64_t*)symIdx.data_ptr() : nullptr,
+                         scatterIdx.numel() > 0 ? (int64_t*)scatterIdx.data_ptr() : nullptr};
+}
+void attribute_heads_op(Tensor ctx, int64_t C, int64_t T, int64_t D, int64_t ldc, Tensor pairs, int64_t K, Tensor offsets, int64_t nSym,
+                        Tensor W1, Tensor b1, Tensor W2, Tensor b2, int64_t Hv, int64_t Ho, int64_t Nv, int64_t No, Tensor logitsVelocity,
+                        Tensor ofLogits, Tensor symIdx, Tensor scatterIdx, Tensor ws)
+{
+    Ctx c(ctx); c.same(ctx, pairs, offsets, W1, b1, W2, b2, logitsVelocity, ofLogits, symIdx, scatterIdx, ws);
+    const AttrHeadsArgs a = attr_heads_args(ctx, C, T, D, ldc, pairs, K, offsets, nSym, W1, b1, W2, b2, Hv, Ho, Nv, No, logitsVelocity, ofLogits,
+                                            symIdx, scatterIdx);
+    if (K == 0) return;
+    check(semicrf_attribute_heads(a.ctx, (int)C, (int)T, (int)D, ldc, a.pairs, K, a.off, (int)nSym, a.W1, a.b1, a.W2, a.b2, (int)Hv, (int)Ho,
+                                  (int)Nv, (int)No, a.lv, a.of, a.sym, a.sc, bytes(ws, "ws"), (size_t)ws.numel(), c.stream),
+          "semicrf_attribute_heads");
+}
+void attribute_heads_cpu(Tensor ctx, int64_t C, int64_t T, int64_t D, int64_t ldc, Tensor pairs, int64_t K, Tensor offsets, int64_t nSym,
+                         Tensor W1, Tensor b1, Tensor W2, Tensor b2, int64_t Hv, int64_t Ho, int64_t Nv, int64_t No, Tensor logitsVelocity,
+                         Tensor ofLogits, Tensor symIdx, Tensor scatterIdx, Tensor ws)
+{
+    all_cpu(ctx, pairs, offsets, W1, b1, W2, b2, logitsVelocity, ofLogits, symIdx, scatterIdx, ws);
+    const AttrHeadsArgs a = attr_heads_args(ctx, C, T, D, ldc, pairs, K, offsets, nSym, W1, b1, W2, b2, Hv, Ho, Nv, No, logitsVelocity, ofLogits,
+                                            symIdx, scatterIdx);
+    if (K == 0) return;
+    semicrf_cpu::attribute_heads(a.ctx, (int)C, (int)T, (int)D, ldc, a.pairs, K, a.off, (int)nSym, a.W1, a.b1, a.W2, a.b2, (int)Hv, (int)Ho,
+                                 (int)Nv, (int)No, a.lv, a.of, a.sym, a.sc);
+}
+
 // ---- transcription segment loop ----------------------------------------------------------------------------------------
 void segment_onset_filter_op(Tensor pairs, Tensor offsets, int64_t B, int64_t bound, Tensor pairs_out, Tensor offsets_out, Tensor counts_ws)
 {
@@ -988,6 +1037,9 @@ STABLE_TORCH_LIBRARY(semicrf, m)
           "Tensor ofPresence, int K, Tensor offsets, int C, Tensor(a!) dLogitsVelocity, Tensor(b!) dOfLogits) -> ()");
     m.def("attribute_decode(Tensor logitsVelocity, Tensor ofLogits, int K, int criterion, Tensor(a!) velocityClass, Tensor(b!) velocityMean, "
           "Tensor(c!) ofValue, Tensor(d!) ofPresence) -> ()");
+    m.def("attribute_heads(Tensor ctx, int C, int T, int D, int ldc, Tensor pairs, int K, Tensor offsets, int nSym, Tensor W1, Tensor b1, "
+          "Tensor W2, Tensor b2, int Hv, int Ho, int Nv, int No, Tensor(a!) logitsVelocity, Tensor(b!) ofLogits, Tensor(c!) symIdx, "
+          "Tensor(d!) scatterIdx, Tensor(e!) ws) -> ()");
     m.def("segment_onset_filter(Tensor pairs, Tensor offsets, int B, int bound, Tensor(a!) pairs_out, Tensor(b!) offsets_out, "
           "Tensor(c!) counts_ws) -> ()");
     m.def("segment_events(Tensor pairs, int K, Tensor offsets, int B, int nSym, Tensor ofValue, Tensor ofPresence, int lastFrameIdx, "
@@ -1019,6 +1071,7 @@ STABLE_TORCH_LIBRARY_IMPL(semicrf, CPU, m)
     m.impl("attribute_loss_fwd", TORCH_BOX(&attribute_loss_fwd_cpu));
     m.impl("attribute_loss_bwd", TORCH_BOX(&attribute_loss_bwd_cpu));
     m.impl("attribute_decode", TORCH_BOX(&attribute_decode_cpu));
+    m.impl("attribute_heads", TORCH_BOX(&attribute_heads_cpu));
 }
 
 STABLE_TORCH_LIBRARY_IMPL(semicrf, CUDA, m)
@@ -1058,6 +1111,7 @@ STABLE_TORCH_LIBRARY_IMPL(semicrf, CUDA, m)
     m.impl("attribute_loss_fwd", TORCH_BOX(&attribute_loss_fwd_op));
     m.impl("attribute_loss_bwd", TORCH_BOX(&attribute_loss_bwd_op));
     m.impl("attribute_decode", TORCH_BOX(&attribute_decode_op));
+    m.impl("attribute_heads", TORCH_BOX(&attribute_heads_op));
     m.impl("segment_onset_filter", TORCH_BOX(&segment_onset_filter_op));
     m.impl("segment_events", TORCH_BOX(&segment_events_op));
 }

@@ -185,6 +185,9 @@ class SegmentTranscriber(nn.Module):
         self.attributeDecode = "torch"  # "fused": what decode_step reads out of the two heads (velocity, refined onset/offset, presence)
                                         # by attributes.attribute_decode, one launch, instead of the reference's torch calls; the
                                         # refined times then no longer carry those calls' fp32 cancellation (3e-3 of a frame)
+        self.attributeHeads = "torch"   # "fused": the gather and both heads of decode_step / computeStats by attributes.attribute_heads
+                                        # (exact fp32 on the matrix pipe, two launches, the [K, 3D] input never in memory) instead of
+                                        # the gather kernel + the two torch modules; eval mode only; log_prob keeps the modules
         self._merged = None
         self.velocityPredictor = _head(size * 3, velocityPredictorHiddenSize, 128, velocityDropoutProb)           # :109-115
         self.refinedOFPredictor = _head(size * 3, refinedOFPredictorHiddenSize, 4, refinedOFDropoutProb)          # :119-125
@@ -249,6 +252,12 @@ class SegmentTranscriber(nn.Module):
             pairs, offsets = _nsci._viterbi_raw(score, noise, start, False)              # transcribeFrames :549
         return pairs, offsets
 
+    def _attribute_heads_fn(self):
+        """The route of the gather + the two heads, by attributeHeads."""
+        if self.attributeHeads not in ("torch", "fused"):
+            raise ValueError(f"attributeHeads must be 'torch' or 'fused', not {self.attributeHeads!r}")
+        return attributes.attribute_heads if self.attributeHeads == "fused" else attributes.attribute_heads_torch
+
     def _invalid_decode_message(self) -> str:
         """What offsets[-1] = -1 behind _decode_packed means, by decoder."""
         if self.decoder == "mbr":
@@ -294,6 +303,7 @@ class SegmentTranscriber(nn.Module):
         assert P == len(self.targetMIDIPitch)
         if self.attributeDecode not in ("torch", "fused"):
             raise ValueError(f"attributeDecode must be 'torch' or 'fused', not {self.attributeDecode!r}")
+        heads = self._attribute_heads_fn()
         B = Fn * P
         dev = ctxBatch.device
         ops = _lib.ops()
@@ -325,9 +335,7 @@ class SegmentTranscriber(nn.Module):
             return dict(K=0, pairs=pairs[:0], offsets=offsets, symIdx=e.long(), scatterIdx=e.long(), velocity=e.long(),
                         times=torch.empty(0, 2, dtype=torch.float64, device=dev), flags=torch.empty(0, 2, dtype=torch.uint8, device=dev),
                         lastP=lastP, nextStart=nextStart)
-        attributeInput, sym, sc = attributes.attribute_input_packed(ctxBatch, pairs, offsets, K)       # :578-586
-        logitsVelocity = self.velocityPredictor(attributeInput)
-        ofLogits = self.refinedOFPredictor(attributeInput)
+        logitsVelocity, ofLogits, sym, sc = heads(ctxBatch, pairs, offsets, self.velocityPredictor, self.refinedOFPredictor, K)   # :578-590, :638
         # :590-655.  "torch": the reference's torch calls (some twenty small launches); "fused": one launch on the same head outputs
         # (with k_cap the rows behind the real count hold whatever the heads make of frame pairs clamped into the segment: the op
         # takes any row, as the torch calls do)
@@ -416,6 +424,7 @@ class SegmentTranscriber(nn.Module):
         tol = _nsci._tolerance(tolerance, "computeStats")
         if attributeRoute not in ("torch", "fused"):
             raise ValueError(f"attributeRoute must be 'torch' or 'fused', not {attributeRoute!r}")
+        heads = self._attribute_heads_fn()
         flat = [sym for seg in intervalsBatch for sym in seg]                            # :415-416
         assert len(flat) == B
         # everything the host has to say goes first: the copies need nothing from the GPU and nothing below waits for them
@@ -430,19 +439,19 @@ class SegmentTranscriber(nn.Module):
         out[:7] = stats.sum(0, dtype=torch.int64)                                        # :428-438
         out[7] = stats.min()                                                             # -1: a chain the kernel rejected
         if K > 0:
-            attributeInput, _, _ = attributes.attribute_input_packed(ctxBatch, ref_pairs, ref_offsets, K)   # :445-450
+            logitsVelocity32, ofLogits32, _, _ = heads(ctxBatch, ref_pairs, ref_offsets, self.velocityPredictor, self.refinedOFPredictor, K)   # :445-454, :463
             # The heads run in fp32 as in the reference; what follows their logits runs in float64 (K x 128 values).  The closed form
             # of the ContinuousBernoulli mean, p / (2p - 1) + 1 / (log(1 - p) - log p), is the difference of two terms that grow like
             # 1 / |logit| towards logit 0: in fp32 it loses up to 1e-5 absolute there, 1e-4 of seOFForced on heads with small logits.
             if attributeRoute == "fused":
                 # the op evaluates the mean from the logit: its fp32 is good enough (no cancellation left), in one launch
-                velocity, ofValue, _ = attributes.attribute_decode(self.velocityPredictor(attributeInput), self.refinedOFPredictor(attributeInput), "mse")
+                velocity, ofValue, _ = attributes.attribute_decode(logitsVelocity32, ofLogits32, "mse")
                 velocity, ofValue = velocity.double(), ofValue.double()
             else:
-                logitsVelocity = self.velocityPredictor(attributeInput).double()             # :454
+                logitsVelocity = logitsVelocity32.double()                                   # :454
                 pVelocity = F.softmax(logitsVelocity, dim=-1)                                # :455
                 velocity = (pVelocity * torch.arange(128, device=dev, dtype=torch.float64)).sum(-1)   # :459-460
-                ofValue, _ = self.refinedOFPredictor(attributeInput).double().chunk(2, dim=-1)        # :463
+                ofValue, _ = ofLogits32.double().chunk(2, dim=-1)                            # :463
                 ofDist = torch.distributions.ContinuousBernoulli(logits=ofValue, validate_args=False)   # (the argument check is a host sync)
                 ofValue = torch.clamp((ofDist.mean - 0.5) / 0.99, -0.5, 0.5)                 # :467-468
             out[8] = (velocity - vel_gt).pow(2).sum()                                    # :481
