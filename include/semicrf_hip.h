@@ -57,6 +57,7 @@ extern "C" {
 #define SEMICRF_OP_MBR_SELECT 10       /* semicrf_mbr_select */
 #define SEMICRF_OP_MARGINAL_DECODE_TOL 11   /* semicrf_marginal_decode_tol */
 #define SEMICRF_OP_ATTRIBUTE_HEADS 12       /* semicrf_attribute_heads: T = rows K, B = Hv + Ho (see there) */
+#define SEMICRF_OP_ATTRIBUTE_HEADS_BWD 13   /* semicrf_attribute_heads_bwd: T = rows K, B = Hv + Ho (see there) */
 
 #define SEMICRF_TOL_MAX 8              /* largest onset / offset tolerance (frames) of the *_tol entry points */
 
@@ -797,6 +798,63 @@ int semicrf_attribute_heads(const float* ctx, int C, int T, int D, int64_t ldc, 
                             int nSym, const float* W1, const float* b1, const float* W2, const float* b2, int Hv, int Ho, int Nv, int No,
                             float* logitsVelocity, float* ofLogits, int64_t* symIdx, int64_t* scatterIdx, void* ws, size_t ws_bytes,
                             semicrf_stream_t stream);
+
+/*
+ * The attribute heads in TRAINING: the forward with dropout, and the backward of the gather + both heads.  Replaces: the gather, the
+ * [K][3D] input and the two nn.Sequential forwards of TransKun.log_prob (ModelTransformer.py:275-281, :290, :306) with their autograd
+ * (per Linear two GEMMs, the GELU and dropout backwards, cat / mul backwards and the gather's atomic scatter).  Arguments and packed
+ * weights as semicrf_attribute_heads.
+ *
+ * semicrf_attribute_heads_train_fwd: the arithmetic of semicrf_attribute_heads (the same kernel) with, per row i and packed hidden
+ *   column j (0 .. Hv + Ho - 1; the velocity head's columns first),
+ *     z[i][j] = (W1 x_i)[j] + b1[j]                       saved to `z` [K][Hv + Ho] for the backward
+ *     A[i][j] = keep(seed, i, j) ? gelu(z[i][j]) * scale_head : 0          scale_head = (float)(1 / (1 - p_head))
+ *   in gelu's place in layer 2.  A head with p = 0 (pv, po: the heads' dropout probabilities, 0 <= p < 1; pass 0 for a head in eval
+ *   mode) is neither masked nor scaled: with pv = po = 0 the outputs are bit-identical to semicrf_attribute_heads'.  Workspace as
+ *   semicrf_attribute_heads (semicrf_attribute_heads_train_fwd_workspace_bytes is the same number).
+ *
+ * The mask is a stateless function of (seed, i, j): Philox-4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as
+ *   1, 2, 3", SC 2011; multipliers 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 / 0xBB67AE85, ten rounds) with
+ *     counter = (i >> 2, j, 0, 0) and key = (seed & 0xffffffff, seed >> 32);
+ *   element (i, j) takes output word i & 3 and is kept iff word >= floor(p_head * 2^32) (as an unsigned 32-bit number).  i is the
+ *   GLOBAL row index, so a row's outputs are bit-identical whatever K is and whatever the other rows hold, in training too.
+ *   semicrf_attribute_heads_dropout_mask writes it as bytes (1 = kept) [K][Hv + Ho]; a head with p = 0 is all ones.
+ *
+ * semicrf_attribute_heads_bwd: given dLogitsVelocity [K][Nv], dOfLogits [K][No] and the forward's z, seed, pv, po; per head, with
+ *   M = keep / (1 - p) (1 where p = 0), every contraction a fmaf chain from +0 in the stated order:
+ *     dA[i][j]  = sum over n ascending of dOut[i][n] W2[j][n];   dz[i][j] = (dA[i][j] * M) * gelu'(z[i][j])
+ *                 gelu'(z) = Phi(z) + z phi(z), the exact erf form (csrc/attr_heads_math.h)
+ *     dW2[j][n] = sum_i A[i][j] dOut[i][n]     (A recomputed from z and the mask)         db2[n] = sum_i dOut[i][n]
+ *     dW1[k][j] = sum_i x_i[k] dz[i][j]        (x gathered again; matrix pipe)             db1[j] = sum_i dz[i][j]
+ *     dx[i][k]  = sum over j ascending of dz[i][j] W1[k][j]      (matrix pipe; never stored)
+ *     ga_i = fmaf(dx_ab, ctx[c][e], dx_a),  gb_i = fmaf(dx_ab, ctx[c][b], dx_b)            (the three thirds of dx_i)
+ *     dctx[c][b][:] += ga_i, then dctx[c][e][:] += gb_i, rows i in ascending order, on dctx zeroed by the call
+ *   Sums over rows: per chunk of SEMICRF_HEADS_BWD_ROW_CHUNK rows one partial (rows ascending; the two bias gradients as 8 sums over
+ *   the rows r = q (mod 8) of the chunk added in ascending q, in double, rounded to fp32 once per chunk), the chunks' partials added in ascending order.  No atomics: one wave
+ *   per chain (and 256 columns) walks the chain's rows offsets[c] .. offsets[c+1] (the last chain: to K), so every result is
+ *   bit-identical from run to run.  Outputs: dctx [C][T][D] dense, dW1 [3D][Hv + Ho], db1 [Hv + Ho], dW2 and db2 in the layout of W2
+ *   and b2.  Workspace: semicrf_attribute_heads_bwd_workspace_bytes(K, D, Hv, Ho, Nv, No): dz [K][Hv + Ho], (ga, gb) [K][2][D], the
+ *   rows' frames, and ceil(K / chunk) planes of all parameter gradients; semicrf_workspace_bytes(SEMICRF_OP_ATTRIBUTE_HEADS_BWD, K,
+ *   Hv + Ho) is an upper bound of it for 3 D <= Hv + Ho and heads of at most 128 outputs each.
+ *
+ * All three: launches on `stream` only (the backward also one hipMemsetAsync of dctx), no synchronisation, no allocation; K == 0
+ * launches nothing and writes nothing.  SEMICRF_EINVAL: a NULL pointer, a size below 1, K < 0, ldc < D, p outside [0, 1), more than
+ * 65535 row chunks; SEMICRF_EWORKSPACE: a workspace that is too small.  The seed is a host value: a captured call replays ONE mask.
+ */
+#define SEMICRF_HEADS_BWD_ROW_CHUNK 512
+size_t semicrf_attribute_heads_train_fwd_workspace_bytes(int64_t K, int Hv, int Ho, int Nv, int No);
+int semicrf_attribute_heads_train_fwd(const float* ctx, int C, int T, int D, int64_t ldc, const int32_t* pairs, int64_t K,
+                                      const int32_t* offsets, int nSym, const float* W1, const float* b1, const float* W2, const float* b2,
+                                      int Hv, int Ho, int Nv, int No, uint64_t seed, double pv, double po, float* logitsVelocity,
+                                      float* ofLogits, float* z, int64_t* symIdx, int64_t* scatterIdx, void* ws, size_t ws_bytes,
+                                      semicrf_stream_t stream);
+size_t semicrf_attribute_heads_bwd_workspace_bytes(int64_t K, int D, int Hv, int Ho, int Nv, int No);
+int semicrf_attribute_heads_bwd(const float* dLogitsVelocity, const float* dOfLogits, const float* z, const float* ctx, int C, int T, int D,
+                                int64_t ldc, const int32_t* pairs, int64_t K, const int32_t* offsets, const float* W1, const float* W2,
+                                int Hv, int Ho, int Nv, int No, uint64_t seed, double pv, double po, float* dctx, float* dW1, float* db1,
+                                float* dW2, float* db2, void* ws, size_t ws_bytes, semicrf_stream_t stream);
+int semicrf_attribute_heads_dropout_mask(uint64_t seed, int64_t K, int Hv, int Ho, double pv, double po, unsigned char* mask,
+                                         semicrf_stream_t stream);
 
 /*
  * Transcription segment loop, on the packed decode output in HBM.

@@ -29,8 +29,10 @@ OP_EXPECTATION = 9
 OP_MBR_SELECT = 10
 OP_MARGINAL_DECODE_TOL = 11
 OP_ATTRIBUTE_HEADS = 12
+OP_ATTRIBUTE_HEADS_BWD = 13
 HEADS_ROW_TILE = 64                             # SEMICRF_HEADS_ROW_TILE: intervals per workgroup of semicrf_attribute_heads
 HEADS_SLICE = 64                                # SEMICRF_HEADS_SLICE: hidden columns per workgroup
+HEADS_BWD_ROW_CHUNK = 512                       # SEMICRF_HEADS_BWD_ROW_CHUNK: rows per partial plane of semicrf_attribute_heads_bwd's row sums
 TOL_MAX = 8                                     # SEMICRF_TOL_MAX
 LEN_MODES = {"linear": 0, "sqrt": 1, "none": 2}
 
@@ -102,6 +104,13 @@ _SIGS = {
     "semicrf_attribute_decode": (_i, [_vp, _vp, _i64, _i, _vp, _vp, _vp, _vp, _vp]),
     "semicrf_attribute_heads_workspace_bytes": (_sz, [_i64, _i, _i, _i, _i]),
     "semicrf_attribute_heads": (_i, [_vp, _i, _i, _i, _i64, _vp, _i64, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "semicrf_attribute_heads_train_fwd_workspace_bytes": (_sz, [_i64, _i, _i, _i, _i]),
+    "semicrf_attribute_heads_train_fwd": (_i, [_vp, _i, _i, _i, _i64, _vp, _i64, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, ctypes.c_uint64,
+                                               ctypes.c_double, ctypes.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "semicrf_attribute_heads_bwd_workspace_bytes": (_sz, [_i64, _i, _i, _i, _i, _i]),
+    "semicrf_attribute_heads_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i64, _vp, _i64, _vp, _vp, _vp, _i, _i, _i, _i, ctypes.c_uint64,
+                                         ctypes.c_double, ctypes.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "semicrf_attribute_heads_dropout_mask": (_i, [ctypes.c_uint64, _i64, _i, _i, ctypes.c_double, ctypes.c_double, _vp, _vp]),
     "interval_score_bwd_ws": (_i, [_vp, _vp, _vp, _i, _i, _i, _i64, _i64, ctypes.c_float, _i, _vp, _vp, _vp, _i64, _i64, _i64, _vp, ctypes.c_size_t, _vp]),
     "interval_score_bwd_workspace_bytes": (ctypes.c_size_t, [_i, _i, _i]),
     "segment_onset_filter": (_i, [_vp, _vp, _i, _i, _vp, _i64, _vp, _vp, _vp]),

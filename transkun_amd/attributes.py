@@ -249,33 +249,45 @@ HEADS_ROW_TILE = _lib.HEADS_ROW_TILE            # intervals per workgroup of the
 _HEADS_PACKED = weakref.WeakKeyDictionary()     # velocityPredictor -> (key, packed weights)
 
 
-def _head_linears(head: torch.nn.Module, name: str):
-    """(first Linear, second Linear) of a head built as the reference builds it (ModelTransformer.py:112-128): Linear, GELU (the exact erf
-    form), Dropout, Linear.  A training-mode Dropout with p > 0 raises ValueError: the op evaluates the heads in eval mode only."""
+def _head_layers(head: torch.nn.Module, name: str):
+    """(first Linear, second Linear, p) of a head built as the reference builds it (ModelTransformer.py:112-128): Linear, GELU (the exact
+    erf form), Dropout, Linear.  p: the probability of the head's Dropout if it is in training mode (it must follow the GELU), else 0."""
     mods = list(head.children()) if isinstance(head, torch.nn.Sequential) else []
     if len(mods) < 3 or not isinstance(mods[0], torch.nn.Linear) or not isinstance(mods[-1], torch.nn.Linear):
         raise TypeError(f"{name}: expected nn.Sequential(Linear, GELU, [Dropout,] Linear)")
-    ngelu = 0
+    ngelu, p = 0, 0.0
     for m in mods[1:-1]:
         if isinstance(m, torch.nn.GELU) and getattr(m, "approximate", "none") == "none":
             ngelu += 1
         elif isinstance(m, torch.nn.Dropout):
             if m.training and m.p > 0:
-                raise ValueError(f"{name} is in training mode with dropout p = {m.p}: attribute_heads is the eval-mode forward only "
-                                 "(call .eval(), or use attribute_heads_torch)")
+                if p > 0 or ngelu != 1:
+                    raise TypeError(f"{name}: one Dropout, between the GELU and the second Linear, is supported in training mode")
+                p = float(m.p)
         else:
             raise TypeError(f"{name}: unsupported layer {type(m).__name__} between the two Linear layers")
     if ngelu != 1 or mods[0].out_features != mods[-1].in_features:
         raise TypeError(f"{name}: expected exactly one exact-erf GELU between two matching Linear layers")
-    return mods[0], mods[-1]
+    return mods[0], mods[-1], p
 
 
-def _packed_heads(velocityPredictor, refinedOFPredictor):
+def _head_linears(head: torch.nn.Module, name: str):
+    """(first Linear, second Linear) of a head in eval mode.  A training-mode Dropout with p > 0 raises ValueError: attribute_heads
+    evaluates the heads in eval mode only (attribute_heads_train takes both modes)."""
+    l1, l2, p = _head_layers(head, name)
+    if p > 0:
+        raise ValueError(f"{name} is in training mode with dropout p = {p}: attribute_heads is the eval-mode forward only "
+                         "(call .eval(), or use attribute_heads_train / attribute_heads_torch)")
+    return l1, l2
+
+
+def _packed_heads(velocityPredictor, refinedOFPredictor, train: bool = False):
     """The two heads' parameters in the layout of semicrf_attribute_heads (include/semicrf_hip.h), fp32: W1 [3D, Hv + Ho], b1 [Hv + Ho],
     W2 = W2v^T [Hv, Nv] followed by W2o^T [Ho, No] (flat), b2 [Nv + No].  Packed by torch calls once and kept until a parameter's
-    `_version` (an optimizer step, load_state_dict: both write in place) or storage changes."""
-    v1, v2 = _head_linears(velocityPredictor, "velocityPredictor")
-    o1, o2 = _head_linears(refinedOFPredictor, "refinedOFPredictor")
+    `_version` (an optimizer step, load_state_dict: both write in place) or storage changes.  train: a head may be in training mode
+    (attribute_heads_train; the dict is the same)."""
+    v1, v2 = (_head_layers if train else _head_linears)(velocityPredictor, "velocityPredictor")[:2]
+    o1, o2 = (_head_layers if train else _head_linears)(refinedOFPredictor, "refinedOFPredictor")[:2]
     if v1.in_features != o1.in_features:
         raise ValueError("the two heads must take the same input")
     lins = (v1, v2, o1, o2)
@@ -354,6 +366,148 @@ def attribute_heads(ctxBatch: torch.Tensor, pairs: torch.Tensor, offsets: torch.
         _lib.ops().attribute_heads(x3, C, T, D, ldc, pairs.contiguous(), K, offsets.contiguous(), SYM, w["W1"], w["b1"], w["W2"], w["b2"],
                                    Hv, Ho, Nv, No, logitsVelocity, ofLogits, sym, sc, ws)
     return logitsVelocity, ofLogits, sym, sc
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# the heads in training: dropout in the forward, and the backward (semicrf_attribute_heads_train_fwd / _bwd)
+# ----------------------------------------------------------------------------------------------------------------------
+HEADS_BWD_ROW_CHUNK = _lib.HEADS_BWD_ROW_CHUNK  # rows per partial plane of the backward's sums over rows (SEMICRF_HEADS_BWD_ROW_CHUNK)
+
+
+def _seed_arg(seed) -> int:
+    """A seed (any int; its low 64 bits count) as the signed 64-bit value the torch ops carry."""
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    return seed - (1 << 64) if seed >= (1 << 63) else seed
+
+
+def attribute_heads_dropout_mask(seed: int, K: int, Hv: int, Ho: int, pv: float, po: float, device="cpu") -> torch.Tensor:
+    """The dropout mask of attribute_heads_train as a tensor: bool [K, Hv + Ho], True = kept; column j < Hv belongs to the velocity head
+    (probability pv), column Hv + j to the onset/offset head (po); a head with p = 0 keeps everything.  A stateless function of
+    (seed, row, column) (Philox-4x32-10, include/semicrf_hip.h): the first rows of a larger K are the same rows.  On a GPU by
+    semicrf_attribute_heads_dropout_mask, on the CPU by the host mirror: the same bits."""
+    dev = torch.device(device)
+    mask = torch.empty(int(K), int(Hv) + int(Ho), dtype=torch.uint8, device=dev)
+    _lib.ops().attribute_heads_dropout_mask(mask, _seed_arg(seed), int(K), int(Hv), int(Ho), float(pv), float(po))
+    return mask.view(torch.bool)
+
+
+class _AttributeHeadsTrain(torch.autograd.Function):
+    """The op behind attribute_heads_train.  Inputs that take a gradient: ctxBatch and the eight parameters (a missing bias is None)."""
+
+    @staticmethod
+    def forward(ctx, ctxBatch, pairs, offsets, K, seed, pv, po, w, v1w, v1b, v2w, v2b, o1w, o1b, o2w, o2b):
+        N, SYM, T, D = ctxBatch.shape
+        dev = ctxBatch.device
+        x = ctxBatch.detach()
+        if x.dtype != torch.float32:
+            x = x.float()
+        ldc = x.stride(2)
+        if not ((D == 1 or x.stride(3) == 1) and ldc >= D and x.stride(1) == T * ldc and x.stride(0) == SYM * T * ldc):
+            x = x.contiguous()
+            ldc = D
+        C = N * SYM
+        x3 = x.as_strided((C, T, D), (T * ldc, ldc, 1), x.storage_offset())
+        Hv, Ho, Nv, No = w["Hv"], w["Ho"], w["Nv"], w["No"]
+        logitsVelocity = torch.empty(K, Nv, dtype=torch.float32, device=dev)
+        ofLogits = torch.empty(K, No, dtype=torch.float32, device=dev)
+        z = torch.empty(K, Hv + Ho, dtype=torch.float32, device=dev)
+        sym = torch.empty(K, dtype=torch.int64, device=dev)
+        sc = torch.empty(K, dtype=torch.int64, device=dev)
+        pairs, offsets = pairs.contiguous(), offsets.contiguous()
+        if K > 0:
+            if dev.type == "cpu":
+                ws = torch.empty(0, dtype=torch.uint8)
+            else:
+                ws = torch.empty(int(_lib.load().semicrf_attribute_heads_train_fwd_workspace_bytes(K, Hv, Ho, Nv, No)), dtype=torch.uint8,
+                                 device=dev)
+            _lib.ops().attribute_heads_train_fwd(x3, C, T, D, ldc, pairs, K, offsets, SYM, w["W1"], w["b1"], w["W2"], w["b2"], Hv, Ho, Nv, No,
+                                                 seed, pv, po, logitsVelocity, ofLogits, z, sym, sc, ws)
+        ctx.save_for_backward(x3, pairs, offsets, z, w["W1"], w["W2"])
+        ctx.geom = (C, T, D, ldc, K, Hv, Ho, Nv, No, seed, pv, po, tuple(ctxBatch.shape), ctxBatch.dtype)
+        ctx.has_bias = tuple(b is not None for b in (v1b, v2b, o1b, o2b))
+        ctx.mark_non_differentiable(sym, sc)
+        return logitsVelocity, ofLogits, sym, sc
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dLv, dOf, _dsym, _dsc):
+        x3, pairs, offsets, z, W1, W2 = ctx.saved_tensors
+        C, T, D, ldc, K, Hv, Ho, Nv, No, seed, pv, po, shape, dtype = ctx.geom
+        dev = x3.device
+        H = Hv + Ho
+        dctx = torch.empty(C, T, D, dtype=torch.float32, device=dev)
+        # all parameter gradients in one buffer, in the layout of a partial plane: dW1 [3D, H] | db1 [H] | dW2 (as W2) | db2 [Nv + No]
+        n1, n2 = 3 * D * H, Hv * Nv + Ho * No
+        flat = torch.empty(n1 + H + n2 + Nv + No, dtype=torch.float32, device=dev)
+        dW1, db1, dW2, db2 = flat[:n1], flat[n1:n1 + H], flat[n1 + H:n1 + H + n2], flat[n1 + H + n2:]
+        if K > 0:
+            dLv = torch.zeros(K, Nv, dtype=torch.float32, device=dev) if dLv is None else dLv.float().contiguous()
+            dOf = torch.zeros(K, No, dtype=torch.float32, device=dev) if dOf is None else dOf.float().contiguous()
+            if dev.type == "cpu":
+                ws = torch.empty(0, dtype=torch.uint8)
+            else:
+                ws = torch.empty(int(_lib.load().semicrf_attribute_heads_bwd_workspace_bytes(K, D, Hv, Ho, Nv, No)), dtype=torch.uint8,
+                                 device=dev)
+            _lib.ops().attribute_heads_bwd(dLv, dOf, z, x3, C, T, D, ldc, pairs, K, offsets, W1, W2, Hv, Ho, Nv, No, seed, pv, po, dctx, dW1, db1,
+                                           dW2, db2, ws)
+        else:
+            dctx.zero_(); flat.zero_()
+        dW1 = dW1.view(3 * D, H)
+        gv2, go2 = dW2[:Hv * Nv].view(Hv, Nv), dW2[Hv * Nv:].view(Ho, No)
+        # the packed gradients go back to the parameters as transposed slices (nn.Linear keeps [out, in])
+        grads = [dW1[:, :Hv].t(), db1[:Hv], gv2.t(), db2[:Nv], dW1[:, Hv:].t(), db1[Hv:], go2.t(), db2[Nv:]]
+        for at, has in zip((1, 3, 5, 7), ctx.has_bias):
+            if not has:
+                grads[at] = None
+        need = ctx.needs_input_grad
+        gctx = dctx.view(shape).to(dtype) if need[0] else None
+        return (gctx, None, None, None, None, None, None, None) + tuple(g if need[8 + i] else None for i, g in enumerate(grads))
+
+
+def attribute_heads_train(ctxBatch: torch.Tensor, pairs: torch.Tensor, offsets: torch.Tensor, velocityPredictor, refinedOFPredictor,
+                          K: int = None, seed: int = None):
+    """attribute_heads for TRAINING: the same arguments and the same four results, differentiable (once; a second differentiation
+    raises) w.r.t. ctxBatch and the weight and bias of the four Linear layers, with each head's Dropout applied when the head is in
+    training mode (its own p; the two may differ).  The forward is attribute_heads' kernel in its training mode
+    (semicrf_attribute_heads_train_fwd: it also saves z = W1 x + b1, [K, Hv + Ho] fp32); the backward is semicrf_attribute_heads_bwd
+    (csrc/attr_heads_bwd.hip): exact fp32 on the matrix pipe for dW1 and dx, the [K, 3D] input gathered again instead of stored, no
+    atomics -- every gradient is bit-identical from run to run.  With both heads in eval mode (or p = 0) the outputs are
+    bit-identical to attribute_heads'.
+
+    Dropout: element (row i, packed hidden column j) is kept iff attribute_heads_dropout_mask(seed, ...)[i, j]: a stateless function
+    of (seed, i, j), so a row's outputs do not depend on K or on the other rows in training either.  seed = None draws one value per
+    call from torch's CPU default generator (torch.manual_seed makes runs reproducible; nothing waits for the device); an explicit
+    seed makes the call reproducible.  The seed is a HOST value: a call captured in a HIP graph replays one and the same mask.
+
+    The parameters must be fp32 (TypeError otherwise); ctxBatch may be any float dtype and a view with a row stride above D, its
+    gradient comes back in its dtype and shape.  A Linear without a bias gets no bias gradient.  CPU tensors run the host mirror."""
+    assert ctxBatch.dim() == 4
+    N, SYM, T, D = ctxBatch.shape
+    _lib.require_device(ctxBatch, "ctxBatch")
+    v1, v2, pv = _head_layers(velocityPredictor, "velocityPredictor")
+    o1, o2, po = _head_layers(refinedOFPredictor, "refinedOFPredictor")
+    params = (v1.weight, v1.bias, v2.weight, v2.bias, o1.weight, o1.bias, o2.weight, o2.bias)
+    for p in params:
+        if p is not None and p.dtype != torch.float32:
+            raise TypeError(f"attribute_heads_train: the heads' parameters must be float32, not {p.dtype}")
+    if not (pv < 1.0 and po < 1.0):
+        raise ValueError("attribute_heads_train: a dropout probability of 1 leaves nothing to train")
+    w = _packed_heads(velocityPredictor, refinedOFPredictor, train=True)
+    if w["nIn"] != 3 * D:
+        raise ValueError(f"the heads take {w['nIn']} inputs, ctxBatch gives 3 * {D}")
+    if w["W1"].device != ctxBatch.device:
+        raise RuntimeError(f"the heads' parameters are on {w['W1'].device}, ctxBatch on {ctxBatch.device}")
+    if K is None:
+        K = int(offsets[-1])
+    K = int(K)
+    assert pairs.dtype == torch.int32 and offsets.dtype == torch.int32 and offsets.numel() == N * SYM + 1
+    if seed is None:
+        if pv > 0 or po > 0:
+            lo, hi = torch.randint(0, 1 << 32, (2,), dtype=torch.int64).tolist()       # the CPU default generator: no device sync
+            seed = (hi << 32) | lo
+        else:
+            seed = 0
+    return _AttributeHeadsTrain.apply(ctxBatch, pairs, offsets, K, _seed_arg(seed), float(pv), float(po), w, *params)
 
 
 def attribute_heads_torch(ctxBatch: torch.Tensor, pairs: torch.Tensor, offsets: torch.Tensor, velocityPredictor, refinedOFPredictor,

@@ -64,7 +64,14 @@ void launch_attr_loss_fwd(const float* logitsVelocity, const float* ofLogits, co
 size_t attr_heads_workspace_bytes(long long K, int Hv, int Ho, int Nv, int No);
 void launch_attr_heads(const float* ctx, int C, int T, int D, long long ldc, const int* pairs, int K, const int* offsets, int nSym,
                        const float* W1, const float* b1, const float* W2, const float* b2, int Hv, int Ho, int Nv, int No,
-                       float* logitsVelocity, float* ofLogits, long long* symIdx, long long* scatterIdx, float* ws, hipStream_t stream);
+                       float* logitsVelocity, float* ofLogits, long long* symIdx, long long* scatterIdx, float* ws, hipStream_t stream,
+                       float* zsave = nullptr, unsigned long long seed = 0, double pv = 0.0, double po = 0.0);
+size_t attr_heads_bwd_workspace_bytes(long long K, int D, int Hv, int Ho, int Nv, int No);
+hipError_t launch_attr_heads_bwd(const float* dLv, const float* dOf, const float* z, const float* ctx, int C, int T, int D, long long ldc,
+                                 const int* pairs, int K, const int* offsets, const float* W1, const float* W2, int Hv, int Ho, int Nv, int No,
+                                 unsigned long long seed, double pv, double po, float* dctx, float* dW1, float* db1, float* dW2, float* db2,
+                                 float* ws, hipStream_t stream);
+void launch_attr_heads_mask(unsigned long long seed, long long K, int Hv, int Ho, double pv, double po, unsigned char* mask, hipStream_t stream);
 void launch_attr_decode(const float* logitsVelocity, const float* ofLogits, int K, int criterion, long long* velocityClass,
                         float* velocityMean, float* ofValue, unsigned char* ofPresence, hipStream_t stream);
 void launch_attr_loss_bwd(const float* gout, int gstride, const float* logitsVelocity, const float* ofLogits, const int* velocity,
@@ -327,6 +334,8 @@ size_t semicrf_workspace_bytes(int op, int T, int B)
         case SEMICRF_OP_MARGINAL_DECODE_TOL: return marginal_decode_tol_workspace_bytes(T, B);
         // T = rows, B = Hv + Ho: the two heads have at most (B + 63) / 64 + 1 slices between them, 128 outputs a plane at the most
         case SEMICRF_OP_ATTRIBUTE_HEADS: return attr_heads_workspace_bytes(T, 64 * ((B + 63) / 64 + 1), 1, 128, 1);
+        // T = rows, B = Hv + Ho: a bound for 3 D <= B and at most 128 outputs a head (every term grows with D, the hidden sizes, the outputs)
+        case SEMICRF_OP_ATTRIBUTE_HEADS_BWD: return attr_heads_bwd_workspace_bytes(T, (B + 2) / 3, B, 1, 128, 128);
         default: return 0;
     }
 }
@@ -1190,6 +1199,99 @@ int semicrf_attribute_heads(const float* ctx, int C, int T, int D, int64_t ldc, 
     launch_attr_heads(ctx, C, T, D, ldc, pairs, (int)K, offsets, nSym, W1, b1, W2, b2, Hv, Ho, Nv, No, logitsVelocity, ofLogits,
                       (long long*)symIdx, (long long*)scatterIdx, (float*)ws, (hipStream_t)stream);
     SEMICRF_CHECK_LAUNCH("semicrf_attribute_heads");
+    return SEMICRF_OK;
+}
+
+size_t semicrf_attribute_heads_train_fwd_workspace_bytes(int64_t K, int Hv, int Ho, int Nv, int No)
+{
+    return semicrf_attribute_heads_workspace_bytes(K, Hv, Ho, Nv, No);
+}
+
+// the checks the three training entry points share with semicrf_attribute_heads
+static int check_heads_sizes(int Hv, int Ho, int Nv, int No, int64_t K, double pv, double po)
+{
+    SEMICRF_CHECK_ARG(Hv >= 1 && Ho >= 1 && Nv >= 1 && No >= 1, "Hv=%d Ho=%d Nv=%d No=%d must be >= 1", Hv, Ho, Nv, No);
+    SEMICRF_CHECK_ARG(Hv < (1 << 21) && Ho < (1 << 21) && Nv < (1 << 20) && No < (1 << 20), "hidden / output sizes too large");
+    SEMICRF_CHECK_ARG(K >= 0 && K < (1ll << 31), "bad interval count K=%lld", (long long)K);
+    SEMICRF_CHECK_ARG(pv >= 0.0 && pv < 1.0 && po >= 0.0 && po < 1.0, "dropout probabilities pv=%g po=%g must lie in [0, 1)", pv, po);
+    return SEMICRF_OK;
+}
+
+int semicrf_attribute_heads_train_fwd(const float* ctx, int C, int T, int D, int64_t ldc, const int32_t* pairs, int64_t K,
+                                      const int32_t* offsets, int nSym, const float* W1, const float* b1, const float* W2, const float* b2,
+                                      int Hv, int Ho, int Nv, int No, uint64_t seed, double pv, double po, float* logitsVelocity,
+                                      float* ofLogits, float* z, int64_t* symIdx, int64_t* scatterIdx, void* ws, size_t ws_bytes,
+                                      semicrf_stream_t stream)
+{
+    SEMICRF_CHECK_ARG(C >= 1 && T >= 1 && D >= 1 && nSym >= 1, "C=%d T=%d D=%d nSym=%d must be >= 1", C, T, D, nSym);
+    if (const int rc = check_heads_sizes(Hv, Ho, Nv, No, K, pv, po)) return rc;
+    SEMICRF_CHECK_ARG(D < (1 << 20), "D too large");
+    SEMICRF_CHECK_ARG(ldc >= D, "bad row stride ldc=%lld < D=%d", (long long)ldc, D);
+    SEMICRF_CHECK_ARG(ctx && offsets, "ctx/offsets must be non-NULL");
+    SEMICRF_CHECK_ARG(W1 && b1 && W2 && b2, "W1/b1/W2/b2 must be non-NULL");
+    if (K == 0) return SEMICRF_OK;
+    SEMICRF_CHECK_ARG(pairs && logitsVelocity && ofLogits && z, "pairs/logitsVelocity/ofLogits/z must be non-NULL");
+    SEMICRF_CHECK_ARG((long long)K * ((long long)Nv + No) < (1ll << 38), "K * (Nv + No) too large");
+    const size_t need = attr_heads_workspace_bytes(K, Hv, Ho, Nv, No);
+    SEMICRF_CHECK_ARG(ws && ((uintptr_t)ws & 3) == 0, "ws must be non-NULL and 4-byte aligned");
+    if (ws_bytes < need) {
+        set_error("workspace too small for attribute_heads_train_fwd: %zu bytes given, semicrf_attribute_heads_train_fwd_workspace_bytes says %zu",
+                  ws_bytes, need);
+        return SEMICRF_EWORKSPACE;
+    }
+    launch_attr_heads(ctx, C, T, D, ldc, pairs, (int)K, offsets, nSym, W1, b1, W2, b2, Hv, Ho, Nv, No, logitsVelocity, ofLogits,
+                      (long long*)symIdx, (long long*)scatterIdx, (float*)ws, (hipStream_t)stream, z, seed, pv, po);
+    SEMICRF_CHECK_LAUNCH("semicrf_attribute_heads_train_fwd");
+    return SEMICRF_OK;
+}
+
+size_t semicrf_attribute_heads_bwd_workspace_bytes(int64_t K, int D, int Hv, int Ho, int Nv, int No)
+{
+    if (K < 0 || D < 1 || Hv < 1 || Ho < 1 || Nv < 1 || No < 1) return 0;
+    return attr_heads_bwd_workspace_bytes(K, D, Hv, Ho, Nv, No);
+}
+
+int semicrf_attribute_heads_bwd(const float* dLogitsVelocity, const float* dOfLogits, const float* z, const float* ctx, int C, int T, int D,
+                                int64_t ldc, const int32_t* pairs, int64_t K, const int32_t* offsets, const float* W1, const float* W2,
+                                int Hv, int Ho, int Nv, int No, uint64_t seed, double pv, double po, float* dctx, float* dW1, float* db1,
+                                float* dW2, float* db2, void* ws, size_t ws_bytes, semicrf_stream_t stream)
+{
+    SEMICRF_CHECK_ARG(C >= 1 && T >= 1 && D >= 1, "C=%d T=%d D=%d must be >= 1", C, T, D);
+    if (const int rc = check_heads_sizes(Hv, Ho, Nv, No, K, pv, po)) return rc;
+    SEMICRF_CHECK_ARG(D < (1 << 20) && (long long)C * T < (1ll << 31), "D or C * T too large");
+    SEMICRF_CHECK_ARG(3ll * D * ((long long)Hv + Ho) < (1ll << 36), "3 D (Hv + Ho) too large");
+    SEMICRF_CHECK_ARG(ldc >= D, "bad row stride ldc=%lld < D=%d", (long long)ldc, D);
+    SEMICRF_CHECK_ARG(K <= 65535ll * SEMICRF_HEADS_BWD_ROW_CHUNK, "K=%lld: more than 65535 row chunks", (long long)K);
+    SEMICRF_CHECK_ARG(ctx && offsets, "ctx/offsets must be non-NULL");
+    SEMICRF_CHECK_ARG(W1 && W2, "W1/W2 must be non-NULL");
+    if (K == 0) return SEMICRF_OK;
+    SEMICRF_CHECK_ARG(pairs && dLogitsVelocity && dOfLogits && z, "pairs/dLogitsVelocity/dOfLogits/z must be non-NULL");
+    SEMICRF_CHECK_ARG(dctx && dW1 && db1 && dW2 && db2, "dctx/dW1/db1/dW2/db2 must be non-NULL");
+    const size_t need = attr_heads_bwd_workspace_bytes(K, D, Hv, Ho, Nv, No);
+    SEMICRF_CHECK_ARG(ws && ((uintptr_t)ws & 3) == 0, "ws must be non-NULL and 4-byte aligned");
+    if (ws_bytes < need) {
+        set_error("workspace too small for attribute_heads_bwd: %zu bytes given, semicrf_attribute_heads_bwd_workspace_bytes says %zu", ws_bytes,
+                  need);
+        return SEMICRF_EWORKSPACE;
+    }
+    const hipError_t e = launch_attr_heads_bwd(dLogitsVelocity, dOfLogits, z, ctx, C, T, D, ldc, pairs, (int)K, offsets, W1, W2, Hv, Ho, Nv, No,
+                                               seed, pv, po, dctx, dW1, db1, dW2, db2, (float*)ws, (hipStream_t)stream);
+    if (e != hipSuccess) {
+        set_error("semicrf_attribute_heads_bwd: %s", hipGetErrorString(e));
+        return SEMICRF_ELAUNCH;
+    }
+    SEMICRF_CHECK_LAUNCH("semicrf_attribute_heads_bwd");
+    return SEMICRF_OK;
+}
+
+int semicrf_attribute_heads_dropout_mask(uint64_t seed, int64_t K, int Hv, int Ho, double pv, double po, unsigned char* mask,
+                                         semicrf_stream_t stream)
+{
+    if (const int rc = check_heads_sizes(Hv, Ho, 1, 1, K, pv, po)) return rc;
+    if (K == 0) return SEMICRF_OK;
+    SEMICRF_CHECK_ARG(mask, "mask must be non-NULL");
+    launch_attr_heads_mask(seed, K, Hv, Ho, pv, po, mask, (hipStream_t)stream);
+    SEMICRF_CHECK_LAUNCH("semicrf_attribute_heads_dropout_mask");
     return SEMICRF_OK;
 }
 

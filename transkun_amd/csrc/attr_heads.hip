@@ -3,7 +3,9 @@
 //   x_i               = [ ctx[c,b,:] | ctx[c,e,:] | ctx[c,b,:] * ctx[c,e,:] ]            3 D values, never written to HBM
 //   logitsVelocity[i] = W2v gelu(W1v x_i + b1v) + b2v                                     [Nv]
 //   ofLogits[i]       = W2o gelu(W1o x_i + b1o) + b2o                                     [No]
-// in exact fp32 on the matrix pipe (v_mfma_f32_32x32x2_f32: a k-ordered fmaf chain), inference only (dropout is the identity).
+// in exact fp32 on the matrix pipe (v_mfma_f32_32x32x2_f32: a k-ordered fmaf chain).  TRAIN = false: inference (dropout is the
+// identity).  TRAIN = true (semicrf_attribute_heads_train_fwd): the same chain per output element, with z = W1 x + b1 saved for the
+// backward (attr_heads_bwd.hip) and, for a head with p > 0, the dropout mask of attr_heads_math.h between gelu and layer 2.
 //
 // Grid = (row tiles of 64 intervals) x (slices of 64 hidden columns, the velocity head's first): at the model's K = 1400 rows the
 // row tiles alone are 22 workgroups, with the 16 slices of Hv = Ho = 512 they are 352.  The slice count depends on Hv and Ho only.
@@ -39,13 +41,13 @@ constexpr int HEADS_SMEM = 2 * HEADS_STAGE > HEADS_SLICE * HEADS_LDH ? 2 * HEADS
 // row of a 32 x 32 result block held in accumulator register r of a lane in half wave hh (the column is lane & 31)
 __device__ __forceinline__ int heads_acc_row(int r, int hh) { return (r & 3) + 8 * (r >> 2) + 4 * hh; }
 
-template <bool VEC>
+template <bool VEC, bool TRAIN>
 __global__ __launch_bounds__(256, 2) void attr_heads_kernel(const float* __restrict__ ctx, int C, int T, int D, long long ldc,
                                                          const int* __restrict__ pairs, int K, const int* __restrict__ offsets, int nSym,
                                                          const float* __restrict__ W1, const float* __restrict__ b1,
                                                          const float* __restrict__ W2, int Hv, int Ho, int Nv, int No,
                                                          float* __restrict__ ws, long long* __restrict__ symIdx,
-                                                         long long* __restrict__ scatterIdx)
+                                                         long long* __restrict__ scatterIdx, float* __restrict__ zsave, DropoutParams drop)
 {
     __shared__ __attribute__((aligned(16))) float smem[HEADS_SMEM];
     // two stages of {x chunk [32 k][96], W1 chunk [32 k][96]}, k-major; after layer 1 the gelu tile [64 hidden][97] takes their place
@@ -179,10 +181,32 @@ __global__ __launch_bounds__(256, 2) void attr_heads_kernel(const float* __restr
         const int col = ct * 32 + l31;
         const bool real = col < wv;
         const float bias = real ? b1[pcol0 + col] : 0.0f;
+        if (!TRAIN) {
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int row = rt * 32 + heads_acc_row(r, hh);
-            Hs[col * HEADS_LDH + row] = real ? gelu<float>(acc[r] + bias) : 0.0f;
+            for (int r = 0; r < 16; ++r) {
+                const int row = rt * 32 + heads_acc_row(r, hh);
+                Hs[col * HEADS_LDH + row] = real ? gelu<float>(acc[r] + bias) : 0.0f;
+            }
+        } else {
+            const int head = vel ? 0 : 1;
+            const bool masked = drop.on[head] != 0;
+            const unsigned thr = drop.thr[head];
+            const float scale = drop.scale[head];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {                     // registers 4 q .. 4 q + 3: four consecutive rows from a multiple of 4
+                const int rowq = rt * 32 + heads_acc_row(4 * q, hh);
+                uint32_t draw[4] = {0u, 0u, 0u, 0u};
+                if (masked) dropout_draws(drop.seed, (uint32_t)((row0 + rowq) >> 2), (uint32_t)(pcol0 + col), draw);
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const int row = rowq + u;
+                    const float zz = acc[4 * q + u] + bias;
+                    float g = gelu<float>(zz);
+                    if (masked) g = draw[u] >= thr ? g * scale : 0.0f;
+                    Hs[col * HEADS_LDH + row] = real ? g : 0.0f;
+                    if (real && row0 + row < K) zsave[(size_t)(row0 + row) * (size_t)ldw + pcol0 + col] = zz;
+                }
+            }
         }
     }
     __syncthreads();
@@ -242,18 +266,24 @@ size_t attr_heads_workspace_bytes(long long K, int Hv, int Ho, int Nv, int No)
 
 void launch_attr_heads(const float* ctx, int C, int T, int D, long long ldc, const int* pairs, int K, const int* offsets, int nSym,
                        const float* W1, const float* b1, const float* W2, const float* b2, int Hv, int Ho, int Nv, int No,
-                       float* logitsVelocity, float* ofLogits, long long* symIdx, long long* scatterIdx, float* ws, hipStream_t stream)
+                       float* logitsVelocity, float* ofLogits, long long* symIdx, long long* scatterIdx, float* ws, hipStream_t stream,
+                       float* zsave, unsigned long long seed, double pv, double po)
 {
     if (K <= 0) return;
+    const DropoutParams drop = dropout_params(seed, zsave ? pv : 0.0, zsave ? po : 0.0);
     const int Sv = slices_of(Hv), So = slices_of(Ho);
     const dim3 grid((K + HEADS_ROWS - 1) / HEADS_ROWS, Sv + So), block(256);
     const bool vec = (D & 3) == 0 && (ldc & 3) == 0 && (Hv & 3) == 0 && (Ho & 3) == 0 && (((uintptr_t)ctx | (uintptr_t)W1) & 15) == 0;
-    if (vec)
-        hipLaunchKernelGGL(attr_heads_kernel<true>, grid, block, 0, stream, ctx, C, T, D, ldc, pairs, K, offsets, nSym, W1, b1, W2, Hv, Ho, Nv,
-                           No, ws, symIdx, scatterIdx);
-    else
-        hipLaunchKernelGGL(attr_heads_kernel<false>, grid, block, 0, stream, ctx, C, T, D, ldc, pairs, K, offsets, nSym, W1, b1, W2, Hv, Ho, Nv,
-                           No, ws, symIdx, scatterIdx);
+    // zsave != nullptr: the training forward (z saved, dropout by pv / po)
+#define SEMICRF_HEADS_LAUNCH(VEC, TRAIN)                                                                                                  \
+    hipLaunchKernelGGL((attr_heads_kernel<VEC, TRAIN>), grid, block, 0, stream, ctx, C, T, D, ldc, pairs, K, offsets, nSym, W1, b1, W2, Hv, \
+                       Ho, Nv, No, ws, symIdx, scatterIdx, zsave, drop)
+    if (zsave) {
+        if (vec) SEMICRF_HEADS_LAUNCH(true, true); else SEMICRF_HEADS_LAUNCH(false, true);
+    } else {
+        if (vec) SEMICRF_HEADS_LAUNCH(true, false); else SEMICRF_HEADS_LAUNCH(false, false);
+    }
+#undef SEMICRF_HEADS_LAUNCH
     const long long total = (long long)K * ((long long)Nv + No);
     hipLaunchKernelGGL(attr_heads_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, ws, b2, K, Sv, So, Nv, No,
                        logitsVelocity, ofLogits);

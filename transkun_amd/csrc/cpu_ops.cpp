@@ -1097,12 +1097,28 @@ void attribute_decode(const float* logitsVelocity, const float* ofLogits, int64_
     }
 }
 
+// the dropout mask of the training heads (attr_heads_math.h): element (row i, packed column j) of `head`
+static inline bool dropout_keep(const semicrf::attr_heads::DropoutParams& drop, int64_t i, int j, int head)
+{
+    if (!drop.on[head]) return true;
+    uint32_t draw[4];
+    semicrf::attr_heads::dropout_draws(drop.seed, (uint32_t)(i >> 2), (uint32_t)j, draw);
+    return draw[i & 3] >= drop.thr[head];
+}
+static inline float dropout_apply(const semicrf::attr_heads::DropoutParams& drop, int64_t i, int j, int head, float g)
+{
+    if (!drop.on[head]) return g;
+    return dropout_keep(drop, i, j, head) ? g * drop.scale[head] : 0.0f;
+}
+
 // ---- the two attribute heads (semicrf_attribute_heads; ModelTransformer.py:578-590, :638) ---------------------------------------
 // The order of operations of attr_heads.hip per output element, in fp32: the k chain of layer 1 ascending from +0 (fmaf), + b1, gelu,
 // per slice of HEADS_SLICE hidden columns the chain of layer 2 ascending from +0, the slices' sums added in ascending order, b2 last.
-void attribute_heads(const float* ctx, int C, int T, int D, int64_t ldc, const int32_t* pairs, int64_t K, const int32_t* offsets, int nSym,
-                     const float* W1, const float* b1, const float* W2, const float* b2, int Hv, int Ho, int Nv, int No,
-                     float* logitsVelocity, float* ofLogits, int64_t* symIdx, int64_t* scatterIdx)
+// zsave != nullptr: the training forward (z saved; a head with drop.on masked and scaled between gelu and layer 2)
+static void attribute_heads_impl(const float* ctx, int C, int T, int D, int64_t ldc, const int32_t* pairs, int64_t K, const int32_t* offsets,
+                                 int nSym, const float* W1, const float* b1, const float* W2, const float* b2, int Hv, int Ho, int Nv, int No,
+                                 float* logitsVelocity, float* ofLogits, int64_t* symIdx, int64_t* scatterIdx, float* zsave,
+                                 const semicrf::attr_heads::DropoutParams& drop)
 {
     using namespace semicrf::attr_heads;
     const int nk = 3 * D, H = Hv + Ho;
@@ -1127,7 +1143,15 @@ void attribute_heads(const float* ctx, int C, int T, int D, int64_t ldc, const i
                 const float* w = W1 + (size_t)k * H;
                 for (int j = 0; j < H; ++j) h[j] = fmaf(xv, w[j], h[j]);
             }
-            for (int j = 0; j < H; ++j) h[j] = gelu<float>(h[j] + b1[j]);
+            if (!zsave) {
+                for (int j = 0; j < H; ++j) h[j] = gelu<float>(h[j] + b1[j]);
+            } else {
+                for (int j = 0; j < H; ++j) {
+                    const float zz = h[j] + b1[j];
+                    zsave[(size_t)i * H + j] = zz;
+                    h[j] = dropout_apply(drop, i, j, j < Hv ? 0 : 1, gelu<float>(zz));
+                }
+            }
             for (int head = 0; head < 2; ++head) {
                 const int Hh = head ? Ho : Hv, N = head ? No : Nv;
                 const float* g = h.data() + (head ? Hv : 0);
@@ -1146,6 +1170,157 @@ void attribute_heads(const float* ctx, int C, int T, int D, int64_t ldc, const i
             }
             if (symIdx) symIdx[i] = c % nSym;
             if (scatterIdx) scatterIdx[i] = c;
+        }
+    }
+}
+
+void attribute_heads(const float* ctx, int C, int T, int D, int64_t ldc, const int32_t* pairs, int64_t K, const int32_t* offsets, int nSym,
+                     const float* W1, const float* b1, const float* W2, const float* b2, int Hv, int Ho, int Nv, int No,
+                     float* logitsVelocity, float* ofLogits, int64_t* symIdx, int64_t* scatterIdx)
+{
+    attribute_heads_impl(ctx, C, T, D, ldc, pairs, K, offsets, nSym, W1, b1, W2, b2, Hv, Ho, Nv, No, logitsVelocity, ofLogits, symIdx, scatterIdx,
+                         nullptr, semicrf::attr_heads::dropout_params(0, 0.0, 0.0));
+}
+
+void attribute_heads_train_fwd(const float* ctx, int C, int T, int D, int64_t ldc, const int32_t* pairs, int64_t K, const int32_t* offsets,
+                               int nSym, const float* W1, const float* b1, const float* W2, const float* b2, int Hv, int Ho, int Nv, int No,
+                               uint64_t seed, double pv, double po, float* logitsVelocity, float* ofLogits, float* z, int64_t* symIdx,
+                               int64_t* scatterIdx)
+{
+    attribute_heads_impl(ctx, C, T, D, ldc, pairs, K, offsets, nSym, W1, b1, W2, b2, Hv, Ho, Nv, No, logitsVelocity, ofLogits, symIdx, scatterIdx,
+                         z, semicrf::attr_heads::dropout_params(seed, pv, po));
+}
+
+void attribute_heads_dropout_mask(uint64_t seed, int64_t K, int Hv, int Ho, double pv, double po, unsigned char* mask)
+{
+    using namespace semicrf::attr_heads;
+    const DropoutParams drop = dropout_params(seed, pv, po);
+    const int H = Hv + Ho;
+#pragma omp parallel for
+    for (int64_t i = 0; i < K; ++i)
+        for (int j = 0; j < H; ++j) mask[(size_t)i * H + j] = dropout_keep(drop, i, j, j < Hv ? 0 : 1) ? 1 : 0;
+}
+
+// The backward of the heads in the order of operations of attr_heads_bwd.hip (include/semicrf_hip.h), in fp32.
+void attribute_heads_bwd(const float* dLv, const float* dOf, const float* z, const float* ctx, int C, int T, int D, int64_t ldc,
+                         const int32_t* pairs, int64_t K, const int32_t* offsets, const float* W1, const float* W2, int Hv, int Ho, int Nv,
+                         int No, uint64_t seed, double pv, double po, float* dctx, float* dW1, float* db1, float* dW2, float* db2)
+{
+    using namespace semicrf::attr_heads;
+    const DropoutParams drop = dropout_params(seed, pv, po);
+    const int H = Hv + Ho, nk = 3 * D;
+    const int64_t nch = (K + HEADS_BWD_ROWS - 1) / HEADS_BWD_ROWS;
+    std::fill(dctx, dctx + (size_t)C * T * D, 0.0f);
+    if (K <= 0) return;
+    std::vector<int64_t> fa((size_t)K), fb((size_t)K);       // the rows' two frames c T + b, c T + e
+    std::vector<float> dz((size_t)K * H), g((size_t)K * 2 * D);
+    auto head_of = [&](int j) { return j < Hv ? 0 : 1; };
+    // dz = (dOut W2 * M) * gelu'(z), the contraction over n ascending
+#pragma omp parallel for schedule(dynamic, 4)
+    for (int64_t i = 0; i < K; ++i) {
+        int lo = 0, hi = C;
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (offsets[mid] <= i) lo = mid; else hi = mid;
+        }
+        const int b = std::min(std::max(pairs[2 * i], 0), T - 1), e = std::min(std::max(pairs[2 * i + 1], 0), T - 1);
+        fa[i] = (int64_t)lo * T + b;
+        fb[i] = (int64_t)lo * T + e;
+        for (int j = 0; j < H; ++j) {
+            const int head = head_of(j), N = head ? No : Nv;
+            const float* w = head ? W2 + (size_t)Hv * Nv + (size_t)(j - Hv) * No : W2 + (size_t)j * Nv;
+            const float* d = head ? dOf + (size_t)i * No : dLv + (size_t)i * Nv;
+            float t = 0.0f;
+            for (int n = 0; n < N; ++n) t = fmaf(d[n], w[n], t);
+            if (drop.on[head]) t = dropout_keep(drop, i, j, head) ? t * drop.scale[head] : 0.0f;
+            dz[(size_t)i * H + j] = t * gelu_grad<float>(z[(size_t)i * H + j]);
+        }
+    }
+    // sums over rows: one partial per chunk (rows ascending), the chunks' partials added in ascending order
+    auto chunk_end = [&](int64_t ch) { return std::min<int64_t>(K, (ch + 1) * HEADS_BWD_ROWS); };
+    // the bias gradients: per chunk 8 sums over r = q (mod 8) added in ascending q, all in double, rounded to fp32 once
+    auto column_sum = [&](const float* src, size_t ld) {
+        float total = 0.0f;
+        for (int64_t ch = 0; ch < nch; ++ch) {
+            double sub[HEADS_BWD_SUBSUMS];
+            for (int q = 0; q < HEADS_BWD_SUBSUMS; ++q) {
+                double t = 0.0;
+                for (int64_t i = ch * HEADS_BWD_ROWS + q; i < chunk_end(ch); i += HEADS_BWD_SUBSUMS) t += (double)src[(size_t)i * ld];
+                sub[q] = t;
+            }
+            double s = sub[0];
+            for (int q = 1; q < HEADS_BWD_SUBSUMS; ++q) s += sub[q];
+            total = ch == 0 ? (float)s : total + (float)s;
+        }
+        return total;
+    };
+#pragma omp parallel
+    {
+        std::vector<float> acc((size_t)std::max(std::max(Nv, No), H)), tot(acc.size());
+#pragma omp for schedule(dynamic, 4) nowait
+        for (int j = 0; j < H; ++j) {                         // dW2 row j, db1[j]
+            const int head = head_of(j), N = head ? No : Nv;
+            const float* dOut = head ? dOf : dLv;
+            float* out = head ? dW2 + (size_t)Hv * Nv + (size_t)(j - Hv) * No : dW2 + (size_t)j * Nv;
+            for (int64_t ch = 0; ch < nch; ++ch) {
+                std::fill(acc.begin(), acc.begin() + N, 0.0f);
+                for (int64_t i = ch * HEADS_BWD_ROWS; i < chunk_end(ch); ++i) {
+                    const float a = dropout_apply(drop, i, j, head, gelu<float>(z[(size_t)i * H + j]));
+                    const float* d = dOut + (size_t)i * N;
+                    for (int n = 0; n < N; ++n) acc[n] = fmaf(a, d[n], acc[n]);
+                }
+                for (int n = 0; n < N; ++n) tot[n] = ch == 0 ? acc[n] : tot[n] + acc[n];
+            }
+            std::copy(tot.begin(), tot.begin() + N, out);
+            db1[j] = column_sum(dz.data() + j, (size_t)H);
+        }
+#pragma omp for schedule(static) nowait
+        for (int n = 0; n < Nv + No; ++n) db2[n] = n < Nv ? column_sum(dLv + n, (size_t)Nv) : column_sum(dOf + (n - Nv), (size_t)No);
+#pragma omp for schedule(dynamic, 4)
+        for (int k = 0; k < nk; ++k) {                        // dW1 row k = x[:, k]^T dz
+            for (int64_t ch = 0; ch < nch; ++ch) {
+                std::fill(acc.begin(), acc.begin() + H, 0.0f);
+                for (int64_t i = ch * HEADS_BWD_ROWS; i < chunk_end(ch); ++i) {
+                    const float* pa = ctx + (size_t)fa[i] * ldc;
+                    const float* pb = ctx + (size_t)fb[i] * ldc;
+                    const float xv = k < D ? pa[k] : k < 2 * D ? pb[k - D] : pa[k - 2 * D] * pb[k - 2 * D];
+                    const float* d = dz.data() + (size_t)i * H;
+                    for (int j = 0; j < H; ++j) acc[j] = fmaf(xv, d[j], acc[j]);
+                }
+                for (int j = 0; j < H; ++j) tot[j] = ch == 0 ? acc[j] : tot[j] + acc[j];
+            }
+            std::copy(tot.begin(), tot.begin() + H, dW1 + (size_t)k * H);
+        }
+        // dx = dz W1^T (j ascending), folded into (ga, gb) per row
+#pragma omp for schedule(dynamic, 4)
+        for (int64_t i = 0; i < K; ++i) {
+            const float* pa = ctx + (size_t)fa[i] * ldc;
+            const float* pb = ctx + (size_t)fb[i] * ldc;
+            const float* d = dz.data() + (size_t)i * H;
+            for (int dd = 0; dd < D; ++dd) {
+                float dx[3];
+                for (int t = 0; t < 3; ++t) {
+                    const float* w = W1 + ((size_t)t * D + dd) * H;
+                    float s = 0.0f;
+                    for (int j = 0; j < H; ++j) s = fmaf(d[j], w[j], s);
+                    dx[t] = s;
+                }
+                g[(2 * (size_t)i) * D + dd] = fmaf(dx[2], pb[dd], dx[0]);
+                g[(2 * (size_t)i + 1) * D + dd] = fmaf(dx[2], pa[dd], dx[1]);
+            }
+        }
+        // dctx: per chain its rows in ascending order, ga before gb
+#pragma omp for schedule(dynamic, 1)
+        for (int c = 0; c < C; ++c) {
+            const int64_t lo = std::min<int64_t>(std::max<int64_t>(offsets[c], 0), K);
+            const int64_t hi = c == C - 1 ? K : std::min<int64_t>(std::max<int64_t>(offsets[c + 1], 0), K);
+            for (int64_t i = lo; i < hi; ++i) {
+                const int b = std::min(std::max(pairs[2 * i], 0), T - 1), e = std::min(std::max(pairs[2 * i + 1], 0), T - 1);
+                float* qb = dctx + ((size_t)c * T + b) * D;
+                float* qe = dctx + ((size_t)c * T + e) * D;
+                const float* gi = g.data() + 2 * (size_t)i * D;
+                for (int dd = 0; dd < D; ++dd) { qb[dd] += gi[dd]; qe[dd] += gi[D + dd]; }
+            }
         }
     }
 }

@@ -53,4 +53,13 @@ void attribute_decode(const float* logitsVelocity, const float* ofLogits, int64_
 void attribute_heads(const float* ctx, int C, int T, int D, int64_t ldc, const int32_t* pairs, int64_t K, const int32_t* offsets, int nSym,
                      const float* W1, const float* b1, const float* W2, const float* b2, int Hv, int Ho, int Nv, int No,
                      float* logitsVelocity, float* ofLogits, int64_t* symIdx, int64_t* scatterIdx);
+// the heads in training (semicrf_attribute_heads_train_fwd / _bwd / _dropout_mask): the same order of operations, in fp32
+void attribute_heads_train_fwd(const float* ctx, int C, int T, int D, int64_t ldc, const int32_t* pairs, int64_t K, const int32_t* offsets,
+                               int nSym, const float* W1, const float* b1, const float* W2, const float* b2, int Hv, int Ho, int Nv, int No,
+                               uint64_t seed, double pv, double po, float* logitsVelocity, float* ofLogits, float* z, int64_t* symIdx,
+                               int64_t* scatterIdx);
+void attribute_heads_bwd(const float* dLv, const float* dOf, const float* z, const float* ctx, int C, int T, int D, int64_t ldc,
+                         const int32_t* pairs, int64_t K, const int32_t* offsets, const float* W1, const float* W2, int Hv, int Ho, int Nv,
+                         int No, uint64_t seed, double pv, double po, float* dctx, float* dW1, float* db1, float* dW2, float* db2);
+void attribute_heads_dropout_mask(uint64_t seed, int64_t K, int Hv, int Ho, double pv, double po, unsigned char* mask);
 }  // namespace semicrf_cpu

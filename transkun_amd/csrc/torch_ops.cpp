@@ -942,6 +942,105 @@ void attribute_heads_cpu(Tensor ctx, int64_t C, int64_t T, int64_t D, int64_t ld
                                  (int)Nv, (int)No, a.lv, a.of, a.sym, a.sc);
 }
 
+// ---- the attribute heads in training (semicrf_attribute_heads_train_fwd / _bwd / _dropout_mask) -------------------------------------
+// seed: the 64 bits of an int; z [K, Hv + Ho] and the gradients are dense and checked for their element counts
+void attribute_heads_train_fwd_op(Tensor ctx, int64_t C, int64_t T, int64_t D, int64_t ldc, Tensor pairs, int64_t K, Tensor offsets, int64_t nSym,
+                                  Tensor W1, Tensor b1, Tensor W2, Tensor b2, int64_t Hv, int64_t Ho, int64_t Nv, int64_t No, int64_t seed,
+                                  double pv, double po, Tensor logitsVelocity, Tensor ofLogits, Tensor z, Tensor symIdx, Tensor scatterIdx,
+                                  Tensor ws)
+{
+    Ctx c(ctx); c.same(ctx, pairs, offsets, W1, b1, W2, b2, logitsVelocity, ofLogits, z, symIdx, scatterIdx, ws);
+    const AttrHeadsArgs a = attr_heads_args(ctx, C, T, D, ldc, pairs, K, offsets, nSym, W1, b1, W2, b2, Hv, Ho, Nv, No, logitsVelocity, ofLogits,
+                                            symIdx, scatterIdx);
+    float* zp = f32w(z, K * (Hv + Ho), "z");
+    if (K == 0) return;
+    check(semicrf_attribute_heads_train_fwd(a.ctx, (int)C, (int)T, (int)D, ldc, a.pairs, K, a.off, (int)nSym, a.W1, a.b1, a.W2, a.b2, (int)Hv,
+                                            (int)Ho, (int)Nv, (int)No, (uint64_t)seed, pv, po, a.lv, a.of, zp, a.sym, a.sc, bytes(ws, "ws"),
+                                            (size_t)ws.numel(), c.stream),
+          "semicrf_attribute_heads_train_fwd");
+}
+void attribute_heads_train_fwd_cpu(Tensor ctx, int64_t C, int64_t T, int64_t D, int64_t ldc, Tensor pairs, int64_t K, Tensor offsets, int64_t nSym,
+                                   Tensor W1, Tensor b1, Tensor W2, Tensor b2, int64_t Hv, int64_t Ho, int64_t Nv, int64_t No, int64_t seed,
+                                   double pv, double po, Tensor logitsVelocity, Tensor ofLogits, Tensor z, Tensor symIdx, Tensor scatterIdx,
+                                   Tensor ws)
+{
+    all_cpu(ctx, pairs, offsets, W1, b1, W2, b2, logitsVelocity, ofLogits, z, symIdx, scatterIdx, ws);
+    const AttrHeadsArgs a = attr_heads_args(ctx, C, T, D, ldc, pairs, K, offsets, nSym, W1, b1, W2, b2, Hv, Ho, Nv, No, logitsVelocity, ofLogits,
+                                            symIdx, scatterIdx);
+    float* zp = f32w(z, K * (Hv + Ho), "z");
+    STD_TORCH_CHECK(pv >= 0.0 && pv < 1.0 && po >= 0.0 && po < 1.0, "semicrf: dropout probabilities must lie in [0, 1)");
+    if (K == 0) return;
+    semicrf_cpu::attribute_heads_train_fwd(a.ctx, (int)C, (int)T, (int)D, ldc, a.pairs, K, a.off, (int)nSym, a.W1, a.b1, a.W2, a.b2, (int)Hv,
+                                           (int)Ho, (int)Nv, (int)No, (uint64_t)seed, pv, po, a.lv, a.of, zp, a.sym, a.sc);
+}
+
+struct AttrHeadsBwdArgs { const float *dlv, *dof, *z, *ctx, *W1, *W2; const int32_t *pairs, *off; float *dctx, *dW1, *db1, *dW2, *db2; };
+inline AttrHeadsBwdArgs attr_heads_bwd_args(const Tensor& dLv, const Tensor& dOf, const Tensor& z, const Tensor& ctx, int64_t C, int64_t T,
+                                            int64_t D, int64_t ldc, const Tensor& pairs, int64_t K, const Tensor& offsets, const Tensor& W1,
+                                            const Tensor& W2, int64_t Hv, int64_t Ho, int64_t Nv, int64_t No, double pv, double po,
+                                            const Tensor& dctx, const Tensor& dW1, const Tensor& db1, const Tensor& dW2, const Tensor& db2)
+{
+    score_dims(C, T, D);
+    STD_TORCH_CHECK(K >= 0 && K < (1ll << 31) && ldc >= D && C * T < (1ll << 31), "semicrf: bad interval count / row stride / C * T");
+    STD_TORCH_CHECK(Hv >= 1 && Ho >= 1 && Nv >= 1 && No >= 1 && Hv < (1 << 21) && Ho < (1 << 21) && Nv < (1 << 20) && No < (1 << 20),
+                    "semicrf: bad head sizes");
+    STD_TORCH_CHECK(pv >= 0.0 && pv < 1.0 && po >= 0.0 && po < 1.0, "semicrf: dropout probabilities must lie in [0, 1)");
+    STD_TORCH_CHECK(ctx.dim() == 3 && ctx.size(0) == C && ctx.size(1) == T && ctx.size(2) == D, "semicrf: `ctx` must be [C, T, D]");
+    STD_TORCH_CHECK((D == 1 || ctx.stride(2) == 1) && (T == 1 || ctx.stride(1) == ldc) && (C == 1 || ctx.stride(0) == T * ldc),
+                    "semicrf: `ctx` must be [C][T] rows of ldc floats with unit stride inside a row");
+    const int64_t H = Hv + Ho;
+    return AttrHeadsBwdArgs{f32(dLv, K * Nv, "dLogitsVelocity"), f32(dOf, K * No, "dOfLogits"), f32(z, K * H, "z"), f32s(ctx, "ctx"),
+                            f32(W1, 3 * D * H, "W1"), f32(W2, Hv * Nv + Ho * No, "W2"), i32(pairs, 2 * K, "pairs"),
+                            i32(offsets, C + 1, "offsets"), f32w(dctx, C * T * D, "dctx"), f32w(dW1, 3 * D * H, "dW1"), f32w(db1, H, "db1"),
+                            f32w(dW2, Hv * Nv + Ho * No, "dW2"), f32w(db2, Nv + No, "db2")};
+}
+void attribute_heads_bwd_op(Tensor dLv, Tensor dOf, Tensor z, Tensor ctx, int64_t C, int64_t T, int64_t D, int64_t ldc, Tensor pairs, int64_t K,
+                            Tensor offsets, Tensor W1, Tensor W2, int64_t Hv, int64_t Ho, int64_t Nv, int64_t No, int64_t seed, double pv,
+                            double po, Tensor dctx, Tensor dW1, Tensor db1, Tensor dW2, Tensor db2, Tensor ws)
+{
+    Ctx c(ctx); c.same(ctx, dLv, dOf, z, pairs, offsets, W1, W2, dctx, dW1, db1, dW2, db2, ws);
+    const AttrHeadsBwdArgs a = attr_heads_bwd_args(dLv, dOf, z, ctx, C, T, D, ldc, pairs, K, offsets, W1, W2, Hv, Ho, Nv, No, pv, po, dctx, dW1,
+                                                   db1, dW2, db2);
+    if (K == 0) return;
+    check(semicrf_attribute_heads_bwd(a.dlv, a.dof, a.z, a.ctx, (int)C, (int)T, (int)D, ldc, a.pairs, K, a.off, a.W1, a.W2, (int)Hv, (int)Ho,
+                                      (int)Nv, (int)No, (uint64_t)seed, pv, po, a.dctx, a.dW1, a.db1, a.dW2, a.db2, bytes(ws, "ws"),
+                                      (size_t)ws.numel(), c.stream),
+          "semicrf_attribute_heads_bwd");
+}
+void attribute_heads_bwd_cpu(Tensor dLv, Tensor dOf, Tensor z, Tensor ctx, int64_t C, int64_t T, int64_t D, int64_t ldc, Tensor pairs, int64_t K,
+                             Tensor offsets, Tensor W1, Tensor W2, int64_t Hv, int64_t Ho, int64_t Nv, int64_t No, int64_t seed, double pv,
+                             double po, Tensor dctx, Tensor dW1, Tensor db1, Tensor dW2, Tensor db2, Tensor ws)
+{
+    all_cpu(ctx, dLv, dOf, z, pairs, offsets, W1, W2, dctx, dW1, db1, dW2, db2, ws);
+    const AttrHeadsBwdArgs a = attr_heads_bwd_args(dLv, dOf, z, ctx, C, T, D, ldc, pairs, K, offsets, W1, W2, Hv, Ho, Nv, No, pv, po, dctx, dW1,
+                                                   db1, dW2, db2);
+    if (K == 0) return;
+    semicrf_cpu::attribute_heads_bwd(a.dlv, a.dof, a.z, a.ctx, (int)C, (int)T, (int)D, ldc, a.pairs, K, a.off, a.W1, a.W2, (int)Hv, (int)Ho,
+                                     (int)Nv, (int)No, (uint64_t)seed, pv, po, a.dctx, a.dW1, a.db1, a.dW2, a.db2);
+}
+
+inline unsigned char* mask_args(const Tensor& mask, int64_t K, int64_t Hv, int64_t Ho, double pv, double po)
+{
+    STD_TORCH_CHECK(K >= 0 && K < (1ll << 31) && Hv >= 1 && Ho >= 1 && Hv < (1 << 21) && Ho < (1 << 21), "semicrf: bad mask shape");
+    STD_TORCH_CHECK(pv >= 0.0 && pv < 1.0 && po >= 0.0 && po < 1.0, "semicrf: dropout probabilities must lie in [0, 1)");
+    want(mask, ScalarType::Byte, K * (Hv + Ho), "mask");
+    return K > 0 ? (unsigned char*)mask.data_ptr() : nullptr;
+}
+void attribute_heads_dropout_mask_op(Tensor mask, int64_t seed, int64_t K, int64_t Hv, int64_t Ho, double pv, double po)
+{
+    Ctx c(mask);
+    unsigned char* m = mask_args(mask, K, Hv, Ho, pv, po);
+    if (K == 0) return;
+    check(semicrf_attribute_heads_dropout_mask((uint64_t)seed, K, (int)Hv, (int)Ho, pv, po, m, c.stream), "semicrf_attribute_heads_dropout_mask");
+}
+void attribute_heads_dropout_mask_cpu(Tensor mask, int64_t seed, int64_t K, int64_t Hv, int64_t Ho, double pv, double po)
+{
+    all_cpu(mask);
+    unsigned char* m = mask_args(mask, K, Hv, Ho, pv, po);
+    if (K == 0) return;
+    semicrf_cpu::attribute_heads_dropout_mask((uint64_t)seed, K, (int)Hv, (int)Ho, pv, po, m);
+}
+
 // ---- transcription segment loop ----------------------------------------------------------------------------------------
 void segment_onset_filter_op(Tensor pairs, Tensor offsets, int64_t B, int64_t bound, Tensor pairs_out, Tensor offsets_out, Tensor counts_ws)
 {
@@ -1040,6 +1139,13 @@ STABLE_TORCH_LIBRARY(semicrf, m)
     m.def("attribute_heads(Tensor ctx, int C, int T, int D, int ldc, Tensor pairs, int K, Tensor offsets, int nSym, Tensor W1, Tensor b1, "
           "Tensor W2, Tensor b2, int Hv, int Ho, int Nv, int No, Tensor(a!) logitsVelocity, Tensor(b!) ofLogits, Tensor(c!) symIdx, "
           "Tensor(d!) scatterIdx, Tensor(e!) ws) -> ()");
+    m.def("attribute_heads_train_fwd(Tensor ctx, int C, int T, int D, int ldc, Tensor pairs, int K, Tensor offsets, int nSym, Tensor W1, "
+          "Tensor b1, Tensor W2, Tensor b2, int Hv, int Ho, int Nv, int No, int seed, float pv, float po, Tensor(a!) logitsVelocity, "
+          "Tensor(b!) ofLogits, Tensor(c!) z, Tensor(d!) symIdx, Tensor(e!) scatterIdx, Tensor(f!) ws) -> ()");
+    m.def("attribute_heads_bwd(Tensor dLogitsVelocity, Tensor dOfLogits, Tensor z, Tensor ctx, int C, int T, int D, int ldc, Tensor pairs, "
+          "int K, Tensor offsets, Tensor W1, Tensor W2, int Hv, int Ho, int Nv, int No, int seed, float pv, float po, Tensor(a!) dctx, "
+          "Tensor(b!) dW1, Tensor(c!) db1, Tensor(d!) dW2, Tensor(e!) db2, Tensor(f!) ws) -> ()");
+    m.def("attribute_heads_dropout_mask(Tensor(a!) mask, int seed, int K, int Hv, int Ho, float pv, float po) -> ()");
     m.def("segment_onset_filter(Tensor pairs, Tensor offsets, int B, int bound, Tensor(a!) pairs_out, Tensor(b!) offsets_out, "
           "Tensor(c!) counts_ws) -> ()");
     m.def("segment_events(Tensor pairs, int K, Tensor offsets, int B, int nSym, Tensor ofValue, Tensor ofPresence, int lastFrameIdx, "
@@ -1072,6 +1178,9 @@ STABLE_TORCH_LIBRARY_IMPL(semicrf, CPU, m)
     m.impl("attribute_loss_bwd", TORCH_BOX(&attribute_loss_bwd_cpu));
     m.impl("attribute_decode", TORCH_BOX(&attribute_decode_cpu));
     m.impl("attribute_heads", TORCH_BOX(&attribute_heads_cpu));
+    m.impl("attribute_heads_train_fwd", TORCH_BOX(&attribute_heads_train_fwd_cpu));
+    m.impl("attribute_heads_bwd", TORCH_BOX(&attribute_heads_bwd_cpu));
+    m.impl("attribute_heads_dropout_mask", TORCH_BOX(&attribute_heads_dropout_mask_cpu));
 }
 
 STABLE_TORCH_LIBRARY_IMPL(semicrf, CUDA, m)
@@ -1112,6 +1221,9 @@ STABLE_TORCH_LIBRARY_IMPL(semicrf, CUDA, m)
     m.impl("attribute_loss_bwd", TORCH_BOX(&attribute_loss_bwd_op));
     m.impl("attribute_decode", TORCH_BOX(&attribute_decode_op));
     m.impl("attribute_heads", TORCH_BOX(&attribute_heads_op));
+    m.impl("attribute_heads_train_fwd", TORCH_BOX(&attribute_heads_train_fwd_op));
+    m.impl("attribute_heads_bwd", TORCH_BOX(&attribute_heads_bwd_op));
+    m.impl("attribute_heads_dropout_mask", TORCH_BOX(&attribute_heads_dropout_mask_op));
     m.impl("segment_onset_filter", TORCH_BOX(&segment_onset_filter_op));
     m.impl("segment_events", TORCH_BOX(&segment_events_op));
 }

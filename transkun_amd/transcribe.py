@@ -187,7 +187,8 @@ class SegmentTranscriber(nn.Module):
                                         # refined times then no longer carry those calls' fp32 cancellation (3e-3 of a frame)
         self.attributeHeads = "torch"   # "fused": the gather and both heads of decode_step / computeStats by attributes.attribute_heads
                                         # (exact fp32 on the matrix pipe, two launches, the [K, 3D] input never in memory) instead of
-                                        # the gather kernel + the two torch modules; eval mode only; log_prob keeps the modules
+                                        # the gather kernel + the two torch modules; eval mode only; log_prob has its own keyword
+                                        # (attributeHeads = "fused": attributes.attribute_heads_train, forward and backward)
         self._merged = None
         self.velocityPredictor = _head(size * 3, velocityPredictorHiddenSize, 128, velocityDropoutProb)           # :109-115
         self.refinedOFPredictor = _head(size * 3, refinedOFPredictorHiddenSize, 4, refinedOFDropoutProb)          # :119-125
@@ -352,7 +353,8 @@ class SegmentTranscriber(nn.Module):
     # the training loss
     # ------------------------------------------------------------------------------------------------------------------
     def log_prob(self, ctxBatch: torch.Tensor, intervalsBatch, velocityBatch, ofRefinedGTBatch, ofPresenceGTBatch,
-                 projection: str = "merged", attributeRoute: str = "fused") -> torch.Tensor:
+                 projection: str = "merged", attributeRoute: str = "fused", attributeHeads: str = "torch",
+                 seed: Optional[int] = None) -> torch.Tensor:
         """TransKun.log_prob (ModelTransformer.py:240-332) from `ctx` on: log p(intervals, velocities, refinements, presence | ctx) per
         segment and symbol, [N, P], differentiable w.r.t. ctxBatch and every parameter of this module.
 
@@ -368,13 +370,20 @@ class SegmentTranscriber(nn.Module):
         target interval the result is the CRF term (:273).
 
         attributeRoute "torch" evaluates :290-328 by the reference's own torch calls instead (attributes.attribute_log_prob_torch:
-        some 25 small kernels, an atomic scatter_add and ContinuousBernoulli's synchronising argument check) -- for comparisons only."""
+        some 25 small kernels, an atomic scatter_add and ContinuousBernoulli's synchronising argument check) -- for comparisons only.
+
+        attributeHeads "fused" evaluates the gather and both heads, forward and backward, by attributes.attribute_heads_train (HIP:
+        dropout by the modules' own p when they are in training mode, the [K, 3D] input never in memory, no atomics) instead of the
+        gather kernel and the torch modules; `seed` is that op's (None: drawn from torch's default generator).  The default "torch"
+        keeps the modules; self.attributeHeads (the transcription-side switch) is not consulted here."""
         assert ctxBatch.dim() == 4
         N, P, T, D = ctxBatch.shape
         assert P == len(self.targetMIDIPitch)
         assert len(intervalsBatch) == N
         if attributeRoute not in ("fused", "torch"):
             raise ValueError(f"attributeRoute must be 'fused' or 'torch', not {attributeRoute!r}")
+        if attributeHeads not in ("torch", "fused"):
+            raise ValueError(f"attributeHeads must be 'torch' or 'fused', not {attributeHeads!r}")
         flat = [sym for seg in intervalsBatch for sym in seg]                            # :256
         assert len(flat) == N * P                                                        # :257
         dev = ctxBatch.device
@@ -385,9 +394,13 @@ class SegmentTranscriber(nn.Module):
         logProb = fused.scorer_crf_logprob(self.scorer, ctxBatch, flat, projection=projection, packed=(pairs, offsets))     # :263-265
         if K == 0:                                                                       # :273
             return logProb.view(N, P)
-        attributeInput, _, _ = attributes.attribute_input_packed(ctxBatch, pairs, offsets, K)                               # :275-281
-        logitsVelocity = self.velocityPredictor(attributeInput)                          # :290
-        ofLogits = self.refinedOFPredictor(attributeInput)                               # :306
+        if attributeHeads == "fused":                                                    # :275-281, :290, :306 as one differentiable op
+            logitsVelocity, ofLogits, _, _ = attributes.attribute_heads_train(ctxBatch, pairs, offsets, self.velocityPredictor,
+                                                                              self.refinedOFPredictor, K, seed=seed)
+        else:
+            attributeInput, _, _ = attributes.attribute_input_packed(ctxBatch, pairs, offsets, K)                           # :275-281
+            logitsVelocity = self.velocityPredictor(attributeInput)                      # :290
+            ofLogits = self.refinedOFPredictor(attributeInput)                           # :306
         fn = attributes.attribute_log_prob if attributeRoute == "fused" else attributes.attribute_log_prob_torch
         return fn(logitsVelocity, ofLogits, velocity, ofRefined, ofPresence, offsets, base=logProb).view(N, P)            # :291-330
 
