@@ -117,11 +117,9 @@ def truth_and_bound(ctx, pairs, offsets, K, vp, op):
     return out[0], out[1], bound[0], bound[1], chain
 
 
-@functools.lru_cache(maxsize=None)
-def gate_case(D, Hv, Ho, scale):
-    """One case of the gate, computed once and shared by the CPU and GPU forms: inputs, yardstick, bounds, torch's fp32 error."""
-    seed = 1000 + 7 * D + Hv + int(scale)
-    vp, op = make_heads(D, Hv, Ho, seed)
+def make_gate_case(D, Hv, Ho, scale, seed, Nv=128, No=4):
+    """One case of the gate at K_GATE rows: inputs, yardstick, bounds, torch's fp32 error."""
+    vp, op = make_heads(D, Hv, Ho, seed, Nv, No)
     ctx = make_ctx(D, scale, seed + 1)
     pairs, offsets = pack_rows(make_rows(K_GATE, seed + 2))
     tv, to, bv, bo, chain = truth_and_bound(ctx, pairs, offsets, K_GATE, vp, op)
@@ -130,6 +128,12 @@ def gate_case(D, Hv, Ho, scale):
     use32 = (float(((fv.double() - tv).abs() / bv).max()), float(((fo.double() - to).abs() / bo).max()))
     return dict(vp=vp, op=op, ctx=ctx, pairs=pairs, offsets=offsets, K=K_GATE, truth=(tv, to), bound=(bv, bo), e32=e32, use32=use32,
                 chain=chain)
+
+
+@functools.lru_cache(maxsize=None)
+def gate_case(D, Hv, Ho, scale):
+    """make_gate_case with the head sizes of the model, computed once and shared by the CPU and GPU forms."""
+    return make_gate_case(D, Hv, Ho, scale, 1000 + 7 * D + Hv + int(scale))
 
 
 def to_device(dev, vp, op, *tensors):

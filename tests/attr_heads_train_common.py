@@ -21,9 +21,9 @@ def params_of(vp, op):
     return [vp[0].weight, vp[0].bias, vp[-1].weight, vp[-1].bias, op[0].weight, op[0].bias, op[-1].weight, op[-1].bias]
 
 
-def make_train_heads(D, Hv, Ho, seed, pv=0.1, po=0.1):
+def make_train_heads(D, Hv, Ho, seed, pv=0.1, po=0.1, Nv=128, No=4):
     """attr_heads_common.make_heads in TRAINING mode, with the two dropout probabilities."""
-    vp, op = common.make_heads(D, Hv, Ho, seed)
+    vp, op = common.make_heads(D, Hv, Ho, seed, Nv, No)
     vp, op = copy.deepcopy(vp), copy.deepcopy(op)
     vp[2].p, op[2].p = pv, po
     return vp.train(), op.train()
@@ -52,12 +52,14 @@ def modules_with_mask(ctx, pairs, offsets, K, vp, op, mask, pv, po, dlv, dof, dt
     return outs[0].detach(), outs[1].detach(), [g.detach() for g in grads]
 
 
-def make_case(D, Hv, Ho, scale, pv, po, K, seed):
-    vp, op = make_train_heads(D, Hv, Ho, seed, pv, po)
+def make_case(D, Hv, Ho, scale, pv, po, K, seed, Nv=128, No=4, layout=None):
+    """layout: (pairs int32 [K, 2] inside [0, T - 1], offsets int32 [C + 1]) in place of the seeded rows of make_rows (rows past
+    offsets[-1] belong to the last chain).  The case keeps torch's fp32 results ("f32") next to their errors ("e32")."""
+    vp, op = make_train_heads(D, Hv, Ho, seed, pv, po, Nv, No)
     ctx = common.make_ctx(D, scale, seed + 1)
-    pairs, offsets = common.pack_rows(common.make_rows(K, seed + 2))
+    pairs, offsets = common.pack_rows(common.make_rows(K, seed + 2)) if layout is None else layout
     g = torch.Generator().manual_seed(seed + 3)
-    dlv, dof = torch.randn(K, 128, generator=g), torch.randn(K, 4, generator=g)
+    dlv, dof = torch.randn(K, Nv, generator=g), torch.randn(K, No, generator=g)
     mseed = 0x9E3779B97F4A7C15 ^ (seed * 1000003)            # (above 2^63: the whole 64 bits travel)
     mask = mask_of(mseed, K, Hv, Ho, pv, po)
     tv, to, tg = modules_with_mask(ctx, pairs, offsets, K, vp, op, mask, pv, po, dlv, dof, torch.float64)
@@ -65,7 +67,7 @@ def make_case(D, Hv, Ho, scale, pv, po, K, seed):
     truth = [tv, to] + tg
     e32 = [float((f.double() - t).abs().max()) for f, t in zip([fv, fo] + fg, truth)]
     return dict(vp=vp, op=op, ctx=ctx, pairs=pairs, offsets=offsets, K=K, dlv=dlv, dof=dof, seed=mseed, mask=mask, truth=truth, e32=e32,
-                pv=pv, po=po)
+                pv=pv, po=po, f32=[fv, fo] + fg)
 
 
 @functools.lru_cache(maxsize=None)
