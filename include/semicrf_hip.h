@@ -879,6 +879,56 @@ int segment_events(const int32_t* pairs, int64_t K, const int32_t* offsets, int 
                    const unsigned char* ofPresence, int lastFrameIdx, double frameDur, const double* beginTime, int stepFrames,
                    double* times, unsigned char* flags, int32_t* lastP, int32_t* nextStart, semicrf_stream_t stream);
 
+/*
+ * The optimizer step on flat fp32 buffers.  Replaces: train.py:239-246 -- the clip value as a quantile of the past gradient norms
+ * (TrainUtil.py:12-25, a host deque), clip_grad_norm_, the host read of the norm, and torch_optimizer.AdaBelief(weight_decouple=True,
+ * rectify=True) looping over every parameter -- by three launches and no host synchronisation.  csrc/optim_math.h holds the arithmetic.
+ *
+ * semicrf_grad_sqnorm.  partials[i] = the sum of squares of workgroup i's share of flat[0:numel], squares and sums in double (1e30 does
+ *   not overflow).  The number of partials and every order of addition depend on numel (and the alignment of flat) only: no atomics,
+ *   the same bits every run.  partials: SEMICRF_SQNORM_MAX_PARTIALS doubles.
+ *
+ * semicrf_clip_from_history (one workgroup).  The adaptive clip value and the norm history, MovingBuffer(initValue, maxLen) on the device:
+ *   ring [capacity] fp32 (capacity <= SEMICRF_HISTORY_MAX), state = {count, head} (int32; a fresh history is ring[0] = 40, state = {1, 0}).
+ *     norm  = fp32(sqrt(partials summed in index order, double))   when partials != NULL (numel: what semicrf_grad_sqnorm was given),
+ *             *norm_in                                             when partials == NULL and norm_in != NULL, else there is no norm
+ *     clip  = the q-quantile of the count values in the ring BEFORE this call: np.quantile's linear interpolation at q (count - 1),
+ *             in double, rounded to fp32; NaN if the ring holds a NaN; skipped when q < 0
+ *     coef  = min(1, clip / (norm + 1e-6)) in fp32 (clip_grad_norm_); NaN if either is NaN -- a non-finite norm propagates
+ *     stats = {norm, clip, coef}; an entry that was not computed is left alone
+ *     append != 0 (and there is a norm): the norm goes into the ring, replacing the oldest value once count == capacity
+ *
+ * semicrf_adabelief_step.  The update of optim_math.h over p, g, m, s [numel]; g is read only.  groups: up to SEMICRF_OPTIM_MAX_GROUPS
+ *   contiguous element ranges [g[i-1].end, g[i].end) with g[n-1].end == numel, each with its own factors, passed by value; ranges may
+ *   begin anywhere: an access of four elements that crosses a boundary gives each element its own group's factors.  coef: a device
+ *   fp32 (stats + 2 above) or NULL for 1.  16-byte accesses when the four buffers are 16-byte aligned, 4-byte accesses otherwise.
+ */
+#define SEMICRF_OPTIM_MAX_GROUPS 8
+#define SEMICRF_SQNORM_MAX_PARTIALS 256
+#define SEMICRF_HISTORY_MAX 16384
+typedef struct semicrf_adabelief_group {
+    int64_t end;       /* one past the group's last element */
+    float decay;       /* 1 - lr*wd */
+    float b1, omb1;    /* beta1, 1 - beta1 */
+    float b2, omb2;    /* beta2, 1 - beta2 */
+    float eps;
+    float sqrt_bc2;    /* sqrt(1 - beta2^t) */
+    float step;        /* rectified: rt*lr/(1 - beta1^t); otherwise lr */
+    int32_t rectified; /* rho_t > 4 */
+    int32_t pad_;
+} semicrf_adabelief_group;
+typedef struct semicrf_adabelief_groups {
+    int32_t n;
+    int32_t pad_;
+    semicrf_adabelief_group g[SEMICRF_OPTIM_MAX_GROUPS];
+} semicrf_adabelief_groups;
+
+int semicrf_grad_sqnorm(const float* flat, int64_t numel, double* partials, semicrf_stream_t stream);
+int semicrf_clip_from_history(const double* partials, int64_t numel, const float* norm_in, double q, float* ring, int capacity,
+                              int32_t* state, int append, float* stats, semicrf_stream_t stream);
+int semicrf_adabelief_step(float* p, const float* g, float* m, float* s, int64_t numel, const float* coef,
+                           semicrf_adabelief_groups groups, semicrf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,5 +7,7 @@ without a GPU raises.
 """
 from . import CRF  # noqa: F401
 from .CRF import NeuralSemiCRFInterval  # noqa: F401
+from .optim import FusedAdaBelief, GradNormHistory, optimizer_groups  # noqa: F401
 
-__all__ = ["CRF", "NeuralSemiCRFInterval"]
+__all__ = ["CRF", "NeuralSemiCRFInterval", "FusedAdaBelief", "GradNormHistory", "optimizer_groups"]
+

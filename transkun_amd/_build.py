@@ -98,7 +98,7 @@ def build_torch_shim(force: bool = False, verbose: bool = False) -> str:
     troot = os.path.dirname(torch.__file__)
     cxx = os.environ.get("CXX") or shutil.which("g++") or "c++"
     tmp = TORCH_LIB + ".tmp"
-    cmd = [cxx, "-O2", "-std=c++17", "-fPIC", "-shared", "-fopenmp", "-fno-fast-math", "-I" + os.path.join(troot, "include"), src, cpu_src,
+    cmd = [cxx, "-O2", "-std=c++17", "-fPIC", "-shared", "-fopenmp", "-fno-fast-math", "-ffp-contract=off", "-I" + os.path.join(troot, "include"), src, cpu_src,
            "-o", tmp,
            "-L" + HERE, "-l:libsemicrf_hip.so", "-L" + os.path.join(troot, "lib"), "-ltorch_cpu", "-ltorch_hip", "-lc10",
            "-Wl,-rpath,$ORIGIN", "-Wl,-rpath," + os.path.join(troot, "lib")]

@@ -41,6 +41,23 @@ _i = ctypes.c_int
 _i64 = ctypes.c_int64
 _sz = ctypes.c_size_t
 
+OPTIM_MAX_GROUPS = 8                            # SEMICRF_OPTIM_MAX_GROUPS: parameter groups of semicrf_adabelief_step
+SQNORM_MAX_PARTIALS = 256                       # SEMICRF_SQNORM_MAX_PARTIALS: doubles in the workspace of semicrf_grad_sqnorm
+HISTORY_MAX = 16384                             # SEMICRF_HISTORY_MAX: largest norm history of semicrf_clip_from_history
+
+
+class AdaBeliefGroup(ctypes.Structure):
+    """semicrf_adabelief_group (include/semicrf_hip.h)."""
+    _fields_ = [("end", ctypes.c_int64), ("decay", ctypes.c_float), ("b1", ctypes.c_float), ("omb1", ctypes.c_float),
+                ("b2", ctypes.c_float), ("omb2", ctypes.c_float), ("eps", ctypes.c_float), ("sqrt_bc2", ctypes.c_float),
+                ("step", ctypes.c_float), ("rectified", ctypes.c_int32), ("pad_", ctypes.c_int32)]
+
+
+class AdaBeliefGroups(ctypes.Structure):
+    """semicrf_adabelief_groups: passed BY VALUE to semicrf_adabelief_step."""
+    _fields_ = [("n", ctypes.c_int32), ("pad_", ctypes.c_int32), ("g", AdaBeliefGroup * OPTIM_MAX_GROUPS)]
+
+
 _SIGS = {
     "semicrf_abi_version": (ctypes.c_int, []),
     "semicrf_last_error": (ctypes.c_char_p, []),
@@ -111,6 +128,9 @@ _SIGS = {
     "semicrf_attribute_heads_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i64, _vp, _i64, _vp, _vp, _vp, _i, _i, _i, _i, ctypes.c_uint64,
                                          ctypes.c_double, ctypes.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "semicrf_attribute_heads_dropout_mask": (_i, [ctypes.c_uint64, _i64, _i, _i, ctypes.c_double, ctypes.c_double, _vp, _vp]),
+    "semicrf_grad_sqnorm": (_i, [_vp, _i64, _vp, _vp]),
+    "semicrf_clip_from_history": (_i, [_vp, _i64, _vp, ctypes.c_double, _vp, _i, _vp, _i, _vp, _vp]),
+    "semicrf_adabelief_step": (_i, [_vp, _vp, _vp, _vp, _i64, _vp, AdaBeliefGroups, _vp]),
     "interval_score_bwd_ws": (_i, [_vp, _vp, _vp, _i, _i, _i, _i64, _i64, ctypes.c_float, _i, _vp, _vp, _vp, _i64, _i64, _i64, _vp, ctypes.c_size_t, _vp]),
     "interval_score_bwd_workspace_bytes": (ctypes.c_size_t, [_i, _i, _i]),
     "segment_onset_filter": (_i, [_vp, _vp, _i, _i, _vp, _i64, _vp, _vp, _vp]),

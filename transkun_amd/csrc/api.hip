@@ -77,6 +77,11 @@ void launch_attr_decode(const float* logitsVelocity, const float* ofLogits, int 
 void launch_attr_loss_bwd(const float* gout, int gstride, const float* logitsVelocity, const float* ofLogits, const int* velocity,
                           const float* ofRefined, const float* ofPresence, int K, const int* offsets, int C, float* dLogitsVelocity,
                           float* dOfLogits, hipStream_t stream);
+void launch_grad_sqnorm(const float* flat, long long numel, double* partials, hipStream_t stream);
+void launch_clip_from_history(const double* partials, long long numel, const float* norm_in, double q, float* ring, int capacity,
+                              int* state, int append, float* stats, hipStream_t stream);
+void launch_adabelief_step(float* p, const float* g, float* m, float* s, long long numel, const float* coef,
+                           const semicrf_adabelief_groups& groups, hipStream_t stream);
 void launch_interval_score_path_bwd(const float* gout, const int* pairs, int K, const int* offsets, const float* q,
                                     const float* k, int C, int T, int D, long long ldq, long long ldk, float qscale, int mode,
                                     float* dq, float* dk, float* ddiag, long long lddq, long long lddk, long long lddd,
@@ -1315,6 +1320,47 @@ int segment_events(const int32_t* pairs, int64_t K, const int32_t* offsets, int 
     launch_segment_events(pairs, offsets, B, nSym, ofValue, ofPresence, lastFrameIdx, frameDur, beginTime, stepFrames, times, flags,
                           lastP, nextStart, (hipStream_t)stream);
     SEMICRF_CHECK_LAUNCH("segment_events");
+    return SEMICRF_OK;
+}
+
+int semicrf_grad_sqnorm(const float* flat, int64_t numel, double* partials, semicrf_stream_t stream)
+{
+    SEMICRF_CHECK_ARG(numel >= 1 && numel < (1ll << 40), "numel=%lld must be in [1, 2^40)", (long long)numel);
+    SEMICRF_CHECK_ARG(flat && partials, "flat/partials must be non-NULL");
+    SEMICRF_CHECK_ARG(((uintptr_t)flat & 3) == 0 && ((uintptr_t)partials & 7) == 0, "flat must be 4-byte, partials 8-byte aligned");
+    launch_grad_sqnorm(flat, numel, partials, (hipStream_t)stream);
+    SEMICRF_CHECK_LAUNCH("semicrf_grad_sqnorm");
+    return SEMICRF_OK;
+}
+
+int semicrf_clip_from_history(const double* partials, int64_t numel, const float* norm_in, double q, float* ring, int capacity,
+                              int32_t* state, int append, float* stats, semicrf_stream_t stream)
+{
+    SEMICRF_CHECK_ARG(capacity >= 1 && capacity <= SEMICRF_HISTORY_MAX, "capacity=%d must be in [1, %d]", capacity, SEMICRF_HISTORY_MAX);
+    SEMICRF_CHECK_ARG(ring && state && stats, "ring/state/stats must be non-NULL");
+    SEMICRF_CHECK_ARG(!partials || (numel >= 1 && numel < (1ll << 40)), "numel=%lld must be in [1, 2^40) when partials are given", (long long)numel);
+    SEMICRF_CHECK_ARG(q < 0.0 || q <= 1.0, "the quantile q=%g must lie in [0, 1] (negative: none)", q);
+    SEMICRF_CHECK_ARG(((uintptr_t)partials & 7) == 0, "partials must be 8-byte aligned");
+    launch_clip_from_history(partials, numel, norm_in, q, ring, capacity, state, append, stats, (hipStream_t)stream);
+    SEMICRF_CHECK_LAUNCH("semicrf_clip_from_history");
+    return SEMICRF_OK;
+}
+
+int semicrf_adabelief_step(float* p, const float* g, float* m, float* s, int64_t numel, const float* coef,
+                           semicrf_adabelief_groups groups, semicrf_stream_t stream)
+{
+    SEMICRF_CHECK_ARG(numel >= 1 && numel < (1ll << 40), "numel=%lld must be in [1, 2^40)", (long long)numel);
+    SEMICRF_CHECK_ARG(p && g && m && s, "p/g/m/s must be non-NULL");
+    SEMICRF_CHECK_ARG((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)s) & 3) == 0, "p/g/m/s must be 4-byte aligned");
+    SEMICRF_CHECK_ARG(groups.n >= 1 && groups.n <= SEMICRF_OPTIM_MAX_GROUPS, "groups.n=%d must be in [1, %d]", groups.n, SEMICRF_OPTIM_MAX_GROUPS);
+    int64_t last = 0;
+    for (int i = 0; i < groups.n; ++i) {
+        SEMICRF_CHECK_ARG(groups.g[i].end > last, "group %d is empty or out of order (end=%lld)", i, (long long)groups.g[i].end);
+        last = groups.g[i].end;
+    }
+    SEMICRF_CHECK_ARG(last == numel, "the last group ends at %lld, not at numel=%lld", (long long)last, (long long)numel);
+    launch_adabelief_step(p, g, m, s, numel, coef, groups, (hipStream_t)stream);
+    SEMICRF_CHECK_LAUNCH("semicrf_adabelief_step");
     return SEMICRF_OK;
 }
 

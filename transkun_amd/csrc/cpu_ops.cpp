@@ -13,9 +13,11 @@
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <vector>
 
 #include "attr_loss_math.h"
+#include "optim_math.h"
 #include "attr_decode_math.h"
 #include "attr_heads_math.h"
 #include "cpu_ops.h"
@@ -1322,6 +1324,84 @@ void attribute_heads_bwd(const float* dLv, const float* dOf, const float* z, con
                 for (int dd = 0; dd < D; ++dd) { qb[dd] += gi[dd]; qe[dd] += gi[D + dd]; }
             }
         }
+    }
+}
+
+// ---- the optimizer step (semicrf_grad_sqnorm / semicrf_clip_from_history / semicrf_adabelief_step; optim_math.h) ---------------------
+// The norm's partial sums: blocks of SQNORM_PER_BLOCK consecutive elements, each summed in ascending order in double, block b into
+// partial b % n (ascending b): a fixed order for a given numel.
+void grad_sqnorm(const float* flat, int64_t numel, double* partials)
+{
+    using namespace semicrf::optim;
+    const int n = sqnorm_partials(numel);
+    const int64_t nblk = (numel + SQNORM_PER_BLOCK - 1) / SQNORM_PER_BLOCK;
+    std::vector<double> blk((size_t)nblk);
+#pragma omp parallel for schedule(static)
+    for (int64_t b = 0; b < nblk; ++b) {
+        const int64_t lo = b * SQNORM_PER_BLOCK, hi = std::min<int64_t>(lo + SQNORM_PER_BLOCK, numel);
+        double acc = 0.0;
+        for (int64_t i = lo; i < hi; ++i) acc += (double)flat[i] * (double)flat[i];
+        blk[(size_t)b] = acc;
+    }
+    for (int i = 0; i < n; ++i) partials[i] = 0.0;
+    for (int64_t b = 0; b < nblk; ++b) partials[b % n] += blk[(size_t)b];
+}
+
+void clip_from_history(const double* partials, int64_t numel, const float* norm_in, double q, float* ring, int capacity, int32_t* state,
+                       int append, float* stats)
+{
+    using namespace semicrf::optim;
+    bool has_norm = false;
+    float norm = 0.0f;
+    if (partials) {
+        const int n = sqnorm_partials(numel);
+        double t = partials[0];
+        for (int i = 1; i < n; ++i) t += partials[i];
+        norm = (float)std::sqrt(t);
+        has_norm = true;
+    } else if (norm_in) {
+        norm = *norm_in;
+        has_norm = true;
+    }
+    const int count = std::min(std::max((int)state[0], 0), capacity), head = std::min(std::max((int)state[1], 0), capacity - 1);
+    const bool want_clip = q >= 0.0;
+    float clip = 0.0f;
+    if (want_clip) {
+        std::vector<float> v((size_t)count);
+        bool nan = false;
+        for (int i = 0; i < count; ++i) { v[(size_t)i] = ring[(head + i) % capacity]; nan = nan || v[(size_t)i] != v[(size_t)i]; }
+        if (nan || count < 1) {
+            clip = std::numeric_limits<float>::quiet_NaN();
+        } else {
+            std::sort(v.begin(), v.end());
+            const double pos = q * (double)(count - 1);
+            const int lo = std::min(std::max((int)std::floor(pos), 0), count - 1), hi = std::min(lo + 1, count - 1);
+            clip = (float)quantile_lerp((double)v[(size_t)lo], (double)v[(size_t)hi], pos - (double)lo);
+        }
+    }
+    if (has_norm) stats[0] = norm;
+    if (want_clip) stats[1] = clip;
+    if (has_norm && want_clip) stats[2] = clip_coef(clip, norm);
+    if (append && has_norm) {
+        if (count < capacity) {
+            ring[(head + count) % capacity] = norm;
+            state[0] = count + 1;
+        } else {
+            ring[head] = norm;
+            state[1] = (head + 1) % capacity;
+        }
+    }
+}
+
+void adabelief_step(float* p, const float* g, float* m, float* s, int64_t numel, const float* coef_ptr,
+                    const semicrf_adabelief_groups& groups)
+{
+    const float coef = coef_ptr ? *coef_ptr : 1.0f;
+    for (int gi = 0; gi < groups.n; ++gi) {
+        const int64_t lo = gi ? groups.g[gi - 1].end : 0, hi = std::min<int64_t>(groups.g[gi].end, numel);
+        const semicrf_adabelief_group k = groups.g[gi];
+#pragma omp parallel for schedule(static) if (hi - lo > 65536)
+        for (int64_t i = lo; i < hi; ++i) semicrf::optim::adabelief_update(p[i], g[i], m[i], s[i], coef, k);
     }
 }
 

@@ -2,6 +2,7 @@
 // entry points of the same name in include/semicrf_hip.h, with host pointers and no stream / workspace.
 #pragma once
 #include <cstdint>
+#include "../../include/semicrf_hip.h"
 
 namespace semicrf_cpu {
 void logz_fwd(const float* score, const float* noise, int T, int B, float* logZ, float* v /* [T][B], required */);
@@ -62,4 +63,11 @@ void attribute_heads_bwd(const float* dLv, const float* dOf, const float* z, con
                          const int32_t* pairs, int64_t K, const int32_t* offsets, const float* W1, const float* W2, int Hv, int Ho, int Nv,
                          int No, uint64_t seed, double pv, double po, float* dctx, float* dW1, float* db1, float* dW2, float* db2);
 void attribute_heads_dropout_mask(uint64_t seed, int64_t K, int Hv, int Ho, double pv, double po, unsigned char* mask);
+// the optimizer step (semicrf_grad_sqnorm / semicrf_clip_from_history / semicrf_adabelief_step): the arithmetic of optim_math.h, the
+// update in fp32 in the device kernel's order of operations (the same bits); partials: as many as the device writes for this numel
+void grad_sqnorm(const float* flat, int64_t numel, double* partials);
+void clip_from_history(const double* partials /* or null */, int64_t numel, const float* norm_in /* or null */, double q, float* ring,
+                       int capacity, int32_t* state, int append, float* stats);
+void adabelief_step(float* p, const float* g, float* m, float* s, int64_t numel, const float* coef /* or null: 1 */,
+                    const semicrf_adabelief_groups& groups);
 }  // namespace semicrf_cpu

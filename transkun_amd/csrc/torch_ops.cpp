@@ -861,6 +861,94 @@ void attribute_loss_bwd_cpu(Tensor gout, int64_t gstride, Tensor logitsVelocity,
     semicrf_cpu::attribute_loss_bwd(g, (int)gstride, a.lv, a.of, a.vel, a.r, a.p, K, a.off, (int)C, dlv, dof);
 }
 
+// ---- the optimizer step (semicrf_grad_sqnorm / semicrf_clip_from_history / semicrf_adabelief_step) ---------------------------------
+// table: a HOST tensor, float64 [n_groups][10] = {end, decay, b1, 1-b1, b2, 1-b2, eps, sqrt_bc2, step, rectified}, the factors already
+// rounded to fp32 by the caller (a double holds an fp32 and an element count exactly): it becomes the by-value struct of the C ABI
+inline semicrf_adabelief_groups optim_groups(const Tensor& table, int64_t numel)
+{
+    STD_TORCH_CHECK(table.defined() && table.is_cpu() && table.scalar_type() == ScalarType::Double && table.is_contiguous() &&
+                    table.dim() == 2 && table.size(1) == 10, "semicrf: the group table must be a contiguous host float64 [n][10] tensor");
+    const int64_t n = table.size(0);
+    STD_TORCH_CHECK(n >= 1 && n <= SEMICRF_OPTIM_MAX_GROUPS, "semicrf: ", n, " parameter groups, at most ", SEMICRF_OPTIM_MAX_GROUPS, " fit");
+    semicrf_adabelief_groups G{};
+    G.n = (int32_t)n;
+    const double* t = (const double*)table.data_ptr();
+    int64_t last = 0;
+    for (int64_t i = 0; i < n; ++i, t += 10) {
+        semicrf_adabelief_group& k = G.g[i];
+        k.end = (int64_t)t[0];
+        STD_TORCH_CHECK(k.end > last, "semicrf: parameter group ", i, " is empty or out of order");
+        last = k.end;
+        k.decay = (float)t[1]; k.b1 = (float)t[2]; k.omb1 = (float)t[3]; k.b2 = (float)t[4]; k.omb2 = (float)t[5]; k.eps = (float)t[6];
+        k.sqrt_bc2 = (float)t[7]; k.step = (float)t[8]; k.rectified = t[9] != 0.0;
+    }
+    STD_TORCH_CHECK(last == numel, "semicrf: the groups cover ", last, " elements, the buffers hold ", numel);
+    return G;
+}
+inline double* f64w(const Tensor& t, int64_t n, const char* name) { want(t, ScalarType::Double, n, name); return (double*)t.data_ptr(); }
+inline void numel_ok(int64_t numel) { STD_TORCH_CHECK(numel >= 1 && numel < (1ll << 40), "semicrf: bad element count"); }
+inline void history_ok(const Tensor& ring, int64_t capacity, const Tensor& state, const Tensor& stats)
+{
+    STD_TORCH_CHECK(capacity >= 1 && capacity <= SEMICRF_HISTORY_MAX, "semicrf: the history holds 1 to ", SEMICRF_HISTORY_MAX, " values");
+    want(ring, ScalarType::Float, capacity, "ring"); want(state, ScalarType::Int, 2, "state"); want(stats, ScalarType::Float, 3, "stats");
+}
+void grad_sqnorm_op(Tensor flat, int64_t numel, Tensor partials)
+{
+    Ctx c(flat); c.same(flat, partials);
+    numel_ok(numel);
+    check(semicrf_grad_sqnorm(f32(flat, numel, "flat"), numel, f64w(partials, SEMICRF_SQNORM_MAX_PARTIALS, "partials"), c.stream),
+          "semicrf_grad_sqnorm");
+}
+void clip_from_history_op(Tensor partials, bool has_partials, int64_t numel, Tensor norm_in, bool has_norm, double q, Tensor ring,
+                          int64_t capacity, Tensor state, bool append, Tensor stats)
+{
+    Ctx c(ring); c.same(ring, state, stats);
+    if (has_partials) { c.same(ring, partials); numel_ok(numel); }
+    if (has_norm) c.same(ring, norm_in);
+    history_ok(ring, capacity, state, stats);
+    check(semicrf_clip_from_history(has_partials ? f64w(partials, SEMICRF_SQNORM_MAX_PARTIALS, "partials") : nullptr, numel,
+                                    has_norm ? f32(norm_in, 1, "norm_in") : nullptr, q, f32w(ring, capacity, "ring"), (int)capacity,
+                                    i32(state, 2, "state"), append ? 1 : 0, f32w(stats, 3, "stats"), c.stream),
+          "semicrf_clip_from_history");
+}
+void adabelief_step_op(Tensor p, Tensor g, Tensor m, Tensor s, int64_t numel, Tensor coef, bool has_coef, Tensor table)
+{
+    Ctx c(p); c.same(p, g, m, s);
+    if (has_coef) c.same(p, coef);
+    numel_ok(numel);
+    const semicrf_adabelief_groups G = optim_groups(table, numel);
+    check(semicrf_adabelief_step(f32w(p, numel, "p"), f32(g, numel, "g"), f32w(m, numel, "m"), f32w(s, numel, "s"), numel,
+                                 has_coef ? f32(coef, 1, "coef") : nullptr, G, c.stream),
+          "semicrf_adabelief_step");
+}
+void grad_sqnorm_cpu(Tensor flat, int64_t numel, Tensor partials)
+{
+    all_cpu(flat, partials);
+    numel_ok(numel);
+    semicrf_cpu::grad_sqnorm(f32(flat, numel, "flat"), numel, f64w(partials, SEMICRF_SQNORM_MAX_PARTIALS, "partials"));
+}
+void clip_from_history_cpu(Tensor partials, bool has_partials, int64_t numel, Tensor norm_in, bool has_norm, double q, Tensor ring,
+                           int64_t capacity, Tensor state, bool append, Tensor stats)
+{
+    all_cpu(ring, state, stats);
+    if (has_partials) { all_cpu(partials); numel_ok(numel); }
+    if (has_norm) all_cpu(norm_in);
+    history_ok(ring, capacity, state, stats);
+    STD_TORCH_CHECK(q < 0.0 || q <= 1.0, "semicrf: the quantile must lie in [0, 1]");
+    semicrf_cpu::clip_from_history(has_partials ? f64w(partials, SEMICRF_SQNORM_MAX_PARTIALS, "partials") : nullptr, numel,
+                                   has_norm ? f32(norm_in, 1, "norm_in") : nullptr, q, f32w(ring, capacity, "ring"), (int)capacity,
+                                   i32(state, 2, "state"), append ? 1 : 0, f32w(stats, 3, "stats"));
+}
+void adabelief_step_cpu(Tensor p, Tensor g, Tensor m, Tensor s, int64_t numel, Tensor coef, bool has_coef, Tensor table)
+{
+    all_cpu(p, g, m, s);
+    if (has_coef) all_cpu(coef);
+    numel_ok(numel);
+    const semicrf_adabelief_groups G = optim_groups(table, numel);
+    semicrf_cpu::adabelief_step(f32w(p, numel, "p"), f32(g, numel, "g"), f32w(m, numel, "m"), f32w(s, numel, "s"), numel,
+                                has_coef ? f32(coef, 1, "coef") : nullptr, G);
+}
+
 // ---- attribute-head readout of transcription (semicrf_attribute_decode) ---------------------------------------------------
 // velocityClass (int64 [K]) for the class criteria, velocityMean (fp32 [K]) for mse; the other is passed empty and not written
 struct AttrDecodeArgs { const float *lv, *of; int64_t* cls; float *mean, *val; unsigned char* pres; };
@@ -1146,6 +1234,10 @@ STABLE_TORCH_LIBRARY(semicrf, m)
           "int K, Tensor offsets, Tensor W1, Tensor W2, int Hv, int Ho, int Nv, int No, int seed, float pv, float po, Tensor(a!) dctx, "
           "Tensor(b!) dW1, Tensor(c!) db1, Tensor(d!) dW2, Tensor(e!) db2, Tensor(f!) ws) -> ()");
     m.def("attribute_heads_dropout_mask(Tensor(a!) mask, int seed, int K, int Hv, int Ho, float pv, float po) -> ()");
+    m.def("grad_sqnorm(Tensor flat, int numel, Tensor(a!) partials) -> ()");
+    m.def("clip_from_history(Tensor partials, bool has_partials, int numel, Tensor norm_in, bool has_norm, float q, Tensor(a!) ring, "
+          "int capacity, Tensor(b!) state, bool append, Tensor(c!) stats) -> ()");
+    m.def("adabelief_step(Tensor(a!) p, Tensor g, Tensor(b!) m, Tensor(c!) s, int numel, Tensor coef, bool has_coef, Tensor table) -> ()");
     m.def("segment_onset_filter(Tensor pairs, Tensor offsets, int B, int bound, Tensor(a!) pairs_out, Tensor(b!) offsets_out, "
           "Tensor(c!) counts_ws) -> ()");
     m.def("segment_events(Tensor pairs, int K, Tensor offsets, int B, int nSym, Tensor ofValue, Tensor ofPresence, int lastFrameIdx, "
@@ -1181,6 +1273,9 @@ STABLE_TORCH_LIBRARY_IMPL(semicrf, CPU, m)
     m.impl("attribute_heads_train_fwd", TORCH_BOX(&attribute_heads_train_fwd_cpu));
     m.impl("attribute_heads_bwd", TORCH_BOX(&attribute_heads_bwd_cpu));
     m.impl("attribute_heads_dropout_mask", TORCH_BOX(&attribute_heads_dropout_mask_cpu));
+    m.impl("grad_sqnorm", TORCH_BOX(&grad_sqnorm_cpu));
+    m.impl("clip_from_history", TORCH_BOX(&clip_from_history_cpu));
+    m.impl("adabelief_step", TORCH_BOX(&adabelief_step_cpu));
 }
 
 STABLE_TORCH_LIBRARY_IMPL(semicrf, CUDA, m)
@@ -1224,6 +1319,9 @@ STABLE_TORCH_LIBRARY_IMPL(semicrf, CUDA, m)
     m.impl("attribute_heads_train_fwd", TORCH_BOX(&attribute_heads_train_fwd_op));
     m.impl("attribute_heads_bwd", TORCH_BOX(&attribute_heads_bwd_op));
     m.impl("attribute_heads_dropout_mask", TORCH_BOX(&attribute_heads_dropout_mask_op));
+    m.impl("grad_sqnorm", TORCH_BOX(&grad_sqnorm_op));
+    m.impl("clip_from_history", TORCH_BOX(&clip_from_history_op));
+    m.impl("adabelief_step", TORCH_BOX(&adabelief_step_op));
     m.impl("segment_onset_filter", TORCH_BOX(&segment_onset_filter_op));
     m.impl("segment_events", TORCH_BOX(&segment_events_op));
 }

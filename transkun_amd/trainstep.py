@@ -45,7 +45,8 @@ def default_log_prob(scorer, ctx, intervals):
 
 
 def train_step(model: SegmentModel, ctx: torch.Tensor, intervals, seconds_per_segment: float = 16.0, group=None,
-               log_prob: Optional[Callable] = None, bucket_bytes: int = 64 << 20, bucket: Optional[FlatGradBucket] = None):
+               log_prob: Optional[Callable] = None, bucket_bytes: int = 64 << 20, bucket: Optional[FlatGradBucket] = None,
+               optimizer=None):
     """One train.py-shaped step on this rank's segments.  ctx: [N, P, T, size]; intervals: N*P lists (chain n*P + p).
     Returns (stats [3] = summed loss / seconds / batch count over ranks, number of gradient collectives issued).
 
@@ -62,9 +63,18 @@ def train_step(model: SegmentModel, ctx: torch.Tensor, intervals, seconds_per_se
         batch = [intervals[n * P:(n + 1) * P] for n in range(N)]
         train_step(model, ctx, intervals, log_prob=lambda scorer, ctx, iv: st.log_prob(ctx, batch, velocity, ofRefined, ofPresence))
 
-    (the `scorer` argument, model.scorer, is then unused: share the module, st.scorer = model.scorer, to train one scorer)."""
+    (the `scorer` argument, model.scorer, is then unused: share the module, st.scorer = model.scorer, to train one scorer).
+
+    optimizer: a transkun_amd.optim.FusedAdaBelief over the model's parameters (make it once).  Its own bucket (optimizer.bucket:
+    gradients and parameters share one flat layout) is the bucket of the step, and optimizer.step() -- the adaptive clip value,
+    clip_grad_norm_ and AdaBelief of train.py:239-246 as three launches, no host synchronisation -- follows the exchange.  None: the
+    step ends with the exchange, as before."""
     N = ctx.shape[0]
     fn = log_prob or default_log_prob
+    if optimizer is not None:
+        if bucket is not None and bucket is not optimizer.bucket:
+            raise ValueError("train_step: with optimizer= the bucket of the step is optimizer.bucket")
+        bucket = optimizer.bucket
     if bucket is not None:
         bucket.zero()
         bucket.arm()
@@ -88,4 +98,6 @@ def train_step(model: SegmentModel, ctx: torch.Tensor, intervals, seconds_per_se
         ncoll = bucket.wait()                                                           # train.py:229
     else:
         ncoll = allreduce_gradients_flat(model.parameters(), group=group, bucket_bytes=bucket_bytes)
+    if optimizer is not None:
+        optimizer.step()                                                                # train.py:239-246
     return stats, ncoll
