@@ -490,6 +490,37 @@ int semicrf_logprob_bwd_f(const float* score, const float* noise, const float* v
                           float* dScore, float* dNoise, int flags, void* ws, size_t ws_bytes, semicrf_stream_t stream);
 
 /*
+ * logProb's backward as ONE launch: the path table.  semicrf_logprob_bwd[_f] runs the gradient sweep and then a second kernel that
+ * scatters +g onto the path's cells and -g onto its covered gaps.  With a table of the path, every writer of the sweep adds those
+ * terms to what it stores (the same roundings in the same order: the results are bit-identical) and the second kernel is not
+ * launched.
+ *   ptab int32 [T][B], index f * B + c, one word per (frame, chain):
+ *     bits 0..29  the END frame of the path interval that BEGINS at frame f, SEMICRF_PTAB_NONE if none does;
+ *     bit 30      SEMICRF_PTAB_COVERED: the gap between frames f and f + 1 lies inside an interval (begin <= f < end).
+ *   semicrf_logprob_fwd_t: semicrf_logprob_fwd, and when ptab is non-NULL the launch also writes every word of ptab (no fill
+ *     needed, no extra launch).  ptab belongs to the call: keep it with v / logZ for the backward, not in the workspace.  Non-NULL
+ *     only where semicrf_logprob_path_table_supported(T, B) returns 1 (SEMICRF_EINVAL otherwise).
+ *   semicrf_logprob_bwd_t: semicrf_logprob_bwd_f with the table of the forward call of the SAME pairs (or NULL: exactly
+ *     semicrf_logprob_bwd_f).  Launches that cannot use it -- short sequences, whose band is stored by the ring itself; the
+ *     row-sequential implementation; more chains than one launch takes -- ignore it and scatter as before.
+ * PRECONDITION for a non-NULL ptab, on top of 0 <= begin <= end < T: within a chain the pairs are sorted by begin, begins ascend
+ * strictly and end_k <= begin_k+1 -- every frame begins at most one interval and every gap is covered at most once (what the
+ * reference's targets are).  The device code does not check it; the host that packs the pairs does (transkun_amd asks its marshal
+ * module) and passes NULL for any other path.  A table that breaks it gives wrong gradients, never an access outside dScore.
+ * Adds nothing to the ABI's existing entry points (version 2).
+ */
+#define SEMICRF_PTAB_COVERED (1 << 30)
+#define SEMICRF_PTAB_NONE ((1 << 30) - 1)
+int semicrf_logprob_path_table_supported(int T, int B);
+int semicrf_logprob_fwd_t(const float* score, const float* noise, int T, int B, const int32_t* pairs, int64_t K,
+                          const int32_t* offsets, float* logProb, float* logZ, float* v, int32_t* ptab, void* ws, size_t ws_bytes,
+                          semicrf_stream_t stream);
+int semicrf_logprob_bwd_t(const float* score, const float* noise, const float* v, const float* logZ, const float* gout,
+                          int gout_stride, int T, int B, const int32_t* pairs, int64_t K, const int32_t* offsets,
+                          float* dScore, float* dNoise, int flags, const int32_t* ptab, void* ws, size_t ws_bytes,
+                          semicrf_stream_t stream);
+
+/*
  * Interval-score construction.  Replaces: ScaledInnerProductIntervalScorer.forward after the
  * Linear map (LayersTransformer.py:406-441).
  *   q,k: [C][T][D] with row strides ldq/ldk (in floats; >= D); diag: [C][T] with stride ldd between

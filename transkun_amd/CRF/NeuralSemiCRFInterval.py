@@ -116,6 +116,8 @@ def pack_intervals(intervals: Sequence[Sequence[Tuple[int, int]]], T: int, B: in
         pairs_d = pairs_h.to(device, non_blocking=True)
         offsets_d = offsets_h.to(device, non_blocking=True)
     pairs_d._semicrf_K = K          # number of real intervals (the tensor holds one dummy row when K == 0)
+    # can logProb's backward take the path as a table (begins ascend strictly, no interval starts inside the previous one)?
+    pairs_d._semicrf_simple = bool(ordered) and bool(mm.path_is_simple(pairs_h.data_ptr(), offsets_h.data_ptr(), B))
     return pairs_d, offsets_d
 
 
@@ -338,10 +340,25 @@ def _logz_bwd_raw(score, noise, v, logz, gout, want_q: bool = False):
     return dscore, dnoise, (q if want_q else None)
 
 
-def _logprob_fwd_raw(score, noise, pairs, offsets, want_v: bool):
+# logProb's backward in ONE launch: the forward's path wave leaves the path as a table [T, B] and the gradient sweep's writers add
+# the path's own +-gout to what they store (semicrf_logprob_fwd_t / _bwd_t), instead of a scatter kernel behind the sweep.
+# PATH_FOLD = False forces the two-launch route (same bits); PATH_ROUTES counts the routes _LogProb.backward has taken.
+PATH_FOLD = True
+PATH_ROUTES = {"folded": 0, "scatter": 0}
+
+
+def _path_table_ok(score, pairs) -> bool:
+    """Does this call get a path table?  The path must be one the table can hold (pack_intervals checked it on the host), the
+    gradient sweep of this shape one whose every cell has a writer that can look its row up (semicrf_logprob_path_table_supported)."""
+    if not (PATH_FOLD and score.is_cuda and getattr(pairs, "_semicrf_simple", False)) or _odd_pad(score):
+        return False
+    return _lib.load().semicrf_logprob_path_table_supported(int(score.shape[0]), int(score.shape[2])) == 1
+
+
+def _logprob_fwd_raw(score, noise, pairs, offsets, want_v: bool, ptab=None):
     """(logProb [B], logZ [B], alpha [T,B] or None) from ONE launch: spare waves of the forward sweep compute the path scores, the
     ring wave that finalises logZ subtracts (semicrf_logprob_fwd; bit-identical to _eval_path_raw(...) - logZ).  `pairs` must be
-    ready on the current stream (_ready)."""
+    ready on the current stream (_ready).  ptab: an int32 [T, B] tensor the launch fills with the path table, or None."""
     K = getattr(pairs, "_semicrf_K", pairs.shape[0])
     if _odd_pad(score):
         logz, v = _logz_fwd_raw(score, noise, want_v)
@@ -352,7 +369,8 @@ def _logprob_fwd_raw(score, noise, pairs, offsets, want_v: bool):
     logz = torch.empty(B, dtype=torch.float32, device=dev)
     v = torch.empty((T, B) if want_v else (0,), dtype=torch.float32, device=dev)
     ws = _lib.leased_workspace(_lib.OP_LOGZ_FWD, T, B, dev)
-    _lib.ops().logprob_fwd(score, noise, pairs, int(K), offsets, lp, logz, v, want_v, ws)
+    _lib.ops().logprob_fwd(score, noise, pairs, int(K), offsets, lp, logz, v, want_v, ws, ptab if ptab is not None else offsets,
+                           ptab is not None)
     return lp, logz, (v if want_v else None)
 
 
@@ -589,17 +607,23 @@ class _LogProb(torch.autograd.Function):
         T, B = score_c.shape[0], score_c.shape[2]
         K = getattr(pairs, "_semicrf_K", pairs.shape[0])
         _ready(pairs)                                   # the intervals' copy ran on a side stream
-        lp, logz, v = _logprob_fwd_raw(score_c, noise_c, pairs, offsets, need)
+        # (the table is this call's own tensor, saved for backward -- not workspace: other calls may run in between)
+        ptab = torch.empty((T, B), dtype=torch.int32, device=score_c.device) if need and _path_table_ok(score_c, pairs) else None
+        lp, logz, v = _logprob_fwd_raw(score_c, noise_c, pairs, offsets, need, ptab)
         if need:
-            ctx.save_for_backward(score_c, noise_c, v, logz, pairs, offsets)
+            ctx.save_for_backward(score_c, noise_c, v, logz, pairs, offsets, *([ptab] if ptab is not None else []))
             ctx.K = K
         ctx.in_dtypes = (score.dtype, noiseScore.dtype)
         return lp.to(score.dtype)
 
     @staticmethod
     def backward(ctx, grad_output):
-        score, noise, v, logz, pairs, offsets = ctx.saved_tensors
+        score, noise, v, logz, pairs, offsets = ctx.saved_tensors[:6]
+        ptab = ctx.saved_tensors[6] if len(ctx.saved_tensors) > 6 else None
         T, B = score.shape[0], score.shape[2]
+        # (the library ignores the table where the launch cannot use it -- the implementation switch may have moved since forward)
+        folded = ptab is not None and PATH_FOLD and _lib.load().semicrf_logprob_path_table_supported(int(T), int(B)) == 1
+        PATH_ROUTES["folded" if folded else "scatter"] += 1
         if _odd_pad(score):
             g = _gout(grad_output, B)
             dscore, dnoise, _ = _logz_bwd_raw(score, noise, v, logz, -g)
@@ -609,7 +633,8 @@ class _LogProb(torch.autograd.Function):
             dscore, flags, pkey = _GRAD_POOL.take(T, B, score.device)
             dnoise = torch.empty_like(noise)
             ws = _lib.leased_workspace(_lib.OP_LOGZ_BWD, T, B, score.device)
-            _lib.ops().logprob_bwd(score, noise, v, logz, g, gstride, pairs, int(ctx.K), offsets, dscore, dnoise, flags, ws)
+            _lib.ops().logprob_bwd(score, noise, v, logz, g, gstride, pairs, int(ctx.K), offsets, dscore, dnoise, flags, ws,
+                                   ptab if folded else offsets, folded)
             _GRAD_POOL.give(pkey, dscore)
         return dscore.to(ctx.in_dtypes[0]), dnoise.to(ctx.in_dtypes[1]), None, None
 

@@ -70,6 +70,9 @@ _SIGS = {
     "semicrf_async_error": (ctypes.c_int, []),
     "semicrf_logz_bwd_f": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
     "semicrf_logprob_bwd_f": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i64, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
+    "semicrf_logprob_path_table_supported": (_i, [_i, _i]),
+    "semicrf_logprob_fwd_t": (_i, [_vp, _vp, _i, _i, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "semicrf_logprob_bwd_t": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i64, _vp, _vp, _vp, _i, _vp, _vp, _sz, _vp]),
     "semicrf_debug_wg_ticket": (_i, [_i, _i, _i]),
     "semicrf_debug_score_variant": (None, [_i]),
     "semicrf_logz_fwd": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),

@@ -162,9 +162,11 @@ int read_and_clear_device_status();
 int launch_persist_logz_bwd(const float* score, const float* noise, const float* v, const float* logZ,
                             const float* gout, int T, int B, float* dScore, float* dNoise, float* q_out, void* ws,
                             hipStream_t stream, int lease, unsigned lease_tag, int gstride = 1, float gscale = 1.0f, int keep_upper = 0,
-                            float noise_add = 0.0f);
+                            float noise_add = 0.0f, const int* ptab = nullptr, int* path_folded = nullptr);
 int launch_persist_logprob_fwd(const float* score, const float* noise, int T, int B, float* u_out, float* logZ, const int* pairs,
-                               int K, const int* offsets, float* logProb, void* ws, hipStream_t stream, int lease, unsigned lease_tag);
+                               int K, const int* offsets, float* logProb, void* ws, hipStream_t stream, int lease, unsigned lease_tag,
+                               int* ptab = nullptr);
+int persist_path_fold_possible(int T, int B);
 
 static bool use_persist(int T, int B) { return g_impl.load() == 0 && persist_supported(T, B); }
 
@@ -356,7 +358,7 @@ static int check_common(const float* score, const float* noise, int T, int B)
 }
 
 // the intervals of semicrf_logprob_fwd, when the sweep's launch can compute the path scores on the side (*folded = 1)
-struct PathFold { const int32_t* pairs; int64_t K; const int32_t* offsets; float* logProb; int folded; };
+struct PathFold { const int32_t* pairs; int64_t K; const int32_t* offsets; float* logProb; int folded; int32_t* ptab; };
 
 static int logz_fwd_impl(const float* score, const float* noise, int T, int B, float* logZ, float* v, void* ws,
                          size_t ws_bytes, semicrf_stream_t stream, PathFold* pf)
@@ -376,7 +378,7 @@ static int logz_fwd_impl(const float* score, const float* noise, int T, int B, f
     if (fast) {
         unsigned ltag = 0;
         const int lease = lease_acquire(ws, SEMICRF_OP_LOGZ_FWD, T, B, &ltag, st);
-        const int rc = pf ? launch_persist_logprob_fwd(score, noise, T, B, vv, logZ, pf->pairs, (int)pf->K, pf->offsets, pf->logProb, pws, st, lease, ltag)
+        const int rc = pf ? launch_persist_logprob_fwd(score, noise, T, B, vv, logZ, pf->pairs, (int)pf->K, pf->offsets, pf->logProb, pws, st, lease, ltag, pf->ptab)
                           : launch_persist_sweep(0, 0, score, noise, T, B, vv, logZ, nullptr, pws, st, lease, ltag);
         if (rc) {
             lease_failed(ws);
@@ -399,7 +401,8 @@ int semicrf_logz_fwd(const float* score, const float* noise, int T, int B, float
 
 static int logz_bwd_impl(const float* score, const float* noise, const float* v, const float* logZ,
                          const float* gout, int gstride, float gscale, int T, int B, float* dScore, float* dNoise, float* q_out,
-                         int flags, void* ws, size_t ws_bytes, semicrf_stream_t stream, float noise_add = 0.0f, int* noise_folded = nullptr)
+                         int flags, void* ws, size_t ws_bytes, semicrf_stream_t stream, float noise_add = 0.0f, int* noise_folded = nullptr,
+                         const int32_t* ptab = nullptr, int* path_folded = nullptr)
 {
     if (int rc = check_common(score, noise, T, B)) return rc;
     SEMICRF_CHECK_ARG((flags & ~SEMICRF_GRAD_UPPER_IS_ZERO) == 0, "unknown flags %d", flags);
@@ -418,7 +421,7 @@ static int logz_bwd_impl(const float* score, const float* noise, const float* v,
         // beta sweep fused with the marginals: score is read once, dScore written once
         unsigned ltag = 0;
         const int lease = lease_acquire(ws, SEMICRF_OP_LOGZ_BWD, T, B, &ltag, st);
-        if (launch_persist_logz_bwd(score, noise, v, logZ, gout, T, B, dScore, dNoise, q, pws, st, lease, ltag, gstride, gscale, keep_upper, noise_add)) {
+        if (launch_persist_logz_bwd(score, noise, v, logZ, gout, T, B, dScore, dNoise, q, pws, st, lease, ltag, gstride, gscale, keep_upper, noise_add, ptab, path_folded)) {
             lease_failed(ws);
             set_error("persistent sweep could not be enqueued (too many chain chunks for this device)"); return SEMICRF_ELAUNCH;
         }
@@ -451,11 +454,25 @@ int semicrf_logprob_fwd(const float* score, const float* noise, int T, int B, co
                         const int32_t* offsets, float* logProb, float* logZ, float* v, void* ws, size_t ws_bytes,
                         semicrf_stream_t stream)
 {
+    return semicrf_logprob_fwd_t(score, noise, T, B, pairs, K, offsets, logProb, logZ, v, nullptr, ws, ws_bytes, stream);
+}
+
+int semicrf_logprob_path_table_supported(int T, int B)
+{
+    return (T >= 1 && B >= 1 && use_persist(T, B) && persist_path_fold_possible(T, B)) ? 1 : 0;
+}
+
+int semicrf_logprob_fwd_t(const float* score, const float* noise, int T, int B, const int32_t* pairs, int64_t K,
+                          const int32_t* offsets, float* logProb, float* logZ, float* v, int32_t* ptab, void* ws, size_t ws_bytes,
+                          semicrf_stream_t stream)
+{
     SEMICRF_CHECK_ARG(offsets && logProb && logZ, "offsets/logProb/logZ must be non-NULL");
     SEMICRF_CHECK_ARG(K >= 0 && K < (1ll << 31) && (K == 0 || pairs), "bad interval count");
+    // the table is written by the sweep's path role: no sweep launch, no table (the caller asks semicrf_logprob_path_table_supported)
+    SEMICRF_CHECK_ARG(ptab == nullptr || (T >= 1 && B >= 1 && use_persist(T, B)), "a path table needs the persistent sweep (T=%d, B=%d)", T, B);
     // ONE launch where the persistent sweep runs (round 5): spare waves of the sweep's launch compute the path scores while it runs,
     // the ring wave that finalises logZ subtracts (persist.hip: path_role); the row-sequential fallback keeps the path kernel
-    PathFold pf{pairs, K, offsets, logProb, 0};
+    PathFold pf{pairs, K, offsets, logProb, 0, ptab};
     if (int rc = logz_fwd_impl(score, noise, T, B, logZ, v, ws, ws_bytes, stream, &pf)) return rc;
     if (!pf.folded) launch_eval_path(score, noise, T, B, (int)K, pairs, offsets, logProb, (hipStream_t)stream, logZ);
     SEMICRF_CHECK_LAUNCH("semicrf_logprob_fwd");
@@ -473,15 +490,26 @@ int semicrf_logprob_bwd_f(const float* score, const float* noise, const float* v
                           int gout_stride, int T, int B, const int32_t* pairs, int64_t K, const int32_t* offsets, float* dScore,
                           float* dNoise, int flags, void* ws, size_t ws_bytes, semicrf_stream_t stream)
 {
+    return semicrf_logprob_bwd_t(score, noise, v, logZ, gout, gout_stride, T, B, pairs, K, offsets, dScore, dNoise, flags, nullptr, ws, ws_bytes,
+                                 stream);
+}
+
+int semicrf_logprob_bwd_t(const float* score, const float* noise, const float* v, const float* logZ, const float* gout,
+                          int gout_stride, int T, int B, const int32_t* pairs, int64_t K, const int32_t* offsets, float* dScore,
+                          float* dNoise, int flags, const int32_t* ptab, void* ws, size_t ws_bytes, semicrf_stream_t stream)
+{
     SEMICRF_CHECK_ARG(offsets, "offsets must be non-NULL");
     SEMICRF_CHECK_ARG(K >= 0 && K < (1ll << 31) && (K == 0 || pairs), "bad interval count");
     // d logProb = d evalPath - d logZ: the marginals with -gout, then +gout on the path's cells and uncovered gaps
     // (round 5: the path score's `+ gout on every gap` is added by the gradient sweep's ring waves as they store the noise marginals;
-    // what is left for a second launch is the scatter onto the path's own cells and covered gaps)
-    int noise_folded = 0;
+    // what is left for a second launch is the scatter onto the path's own cells and covered gaps -- and with the forward call's path
+    // table, in a launch whose band has writers of its own, not even that: every writer of the sweep adds the path's term to what it
+    // stores.  The scatter stays for short sequences, the row-sequential implementation, chain chunks and callers without a table.)
+    int noise_folded = 0, path_folded = 0;
     if (int rc = logz_bwd_impl(score, noise, v, logZ, gout, gout_stride, -1.0f, T, B, dScore, dNoise, nullptr, flags, ws, ws_bytes, stream,
-                               1.0f, &noise_folded)) return rc;
-    launch_eval_path_bwd(gout, T, B, (int)K, pairs, offsets, dScore, dNoise, (hipStream_t)stream, gout_stride, 1.0f, noise_folded);
+                               1.0f, &noise_folded, ptab, &path_folded)) return rc;
+    if (!path_folded)
+        launch_eval_path_bwd(gout, T, B, (int)K, pairs, offsets, dScore, dNoise, (hipStream_t)stream, gout_stride, 1.0f, noise_folded);
     SEMICRF_CHECK_LAUNCH("semicrf_logprob_bwd");
     return SEMICRF_OK;
 }

@@ -194,6 +194,12 @@ struct SweepParams {
     float* pathOut;        // [B] logProb
     u64* pathg;            // [B] granules (workspace)
     float noiseAdd;        // GRAD: dNoise gets noiseAdd * gout[c] on top of the marginal (d cum[T-1] / d noise of the path score), 0: nothing
+    // logProb's backward as ONE launch: the forward's path role also leaves the path as a table (pathscore.h: path_table_wave), and
+    // every writer of the gradient sweep applies the path's own terms to what it stores -- + noiseAdd * gout[c] (the path score's
+    // weight) on the cell of a path interval, the same with a minus on a covered gap -- as the scatter kernel's atomics did
+    // afterwards (evalpath.hip), rounding for rounding
+    int* ptabOut;          // forward: [T][B] table to fill, or nullptr
+    const int* ptab;       // GRAD: [T][B] table of the forward call, or nullptr: the caller scatters
     float* band;           // SEMICRF_BANDX: [K][bandSpines][NBT][16 columns][16 rows][4 chains]: the band, spine-major (workspace), or nullptr
     unsigned* bandFlags;   // ... [32-chain groups][K + 2][8]: {launch tag, row block} once tile t of (row block, group) has been copied
     int bandSpines;        // ... spines of the whole batch (the copy is indexed by the batch's spine number)
@@ -226,6 +232,17 @@ __device__ __forceinline__ void store_granule(u64* p, u64 g)
 __device__ __forceinline__ u64 load_granule(const u64* p)
 {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// A field of the kernel's argument, read again where it is needed instead of being carried in registers from the kernel's start
+// (the panels have neither a vector nor a scalar register to spare across their tile loop; the empty asm keeps the load in place)
+template <typename Tp>
+__device__ __forceinline__ Tp kernarg_again(size_t off)
+{
+    typedef __attribute__((address_space(4))) const char ka_t;
+    ka_t* ka = (ka_t*)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(ka));
+    return *(__attribute__((address_space(4))) const Tp*)(ka + off);
 }
 
 template <int DIR>
@@ -335,7 +352,7 @@ constexpr int NLOADER = SEMICRF_NLOADER;              // loader waves per ring (
 #endif
 constexpr int NRBUF = SEMICRF_NRBUF;                  // row-block buffers between the loader and the ring
 constexpr int TILE_BYTES = PB * PB * RS * 4;          // 4096: [column u][row r][chain] floats
-constexpr int NCONST = 3;                             // per-row constants: diagonal cell, noise, alpha (GRAD)
+constexpr int NCONST = 4;                             // per-row constants: diagonal cell, noise, alpha (GRAD), path table word (GRAD)
 constexpr int LDS_TILES = 0;
 constexpr int LDS_CONST = LDS_TILES + NRBUF * RING * TILE_BYTES;       // [NRBUF][NCONST][64] floats
 constexpr int LDS_FAR = LDS_CONST + NRBUF * NCONST * 256;              // [8][64] x {value, key, seq, pad}
@@ -448,6 +465,7 @@ __device__ __forceinline__ void loader_role(const SweepParams& P, int sg, char* 
     const float* const score = P.score;
     const float* const noise = P.noise;
     const float* const vfwd = P.vfwd;
+    const float* const tabw = P.ptab ? (const float*)P.ptab : P.vfwd;
     const int lane = threadIdx.x & 63;
     const int cbase = P.c0 + sg * GS;
     const size_t last4 = (size_t)T * T * Bs - 4;                 // last element offset a 16-byte load may start at
@@ -460,7 +478,7 @@ __device__ __forceinline__ void loader_role(const SweepParams& P, int sg, char* 
     int* const cons = ready + NRBUF;
     int* const nready = cons + RING;
     const int* const fcons = nready + NNSLOT;
-    constexpr int NL = RING * 4 + 2 + (GRAD ? 1 : 0) + NNEAR * 4 + ((GRAD && NNEAR > 0) ? 1 : 0);   // loads per row block (exactly, the waits count them)
+    constexpr int NL = RING * 4 + 2 + (GRAD ? 2 : 0) + NNEAR * 4 + ((GRAD && NNEAR > 0) ? 1 : 0);   // loads per row block (exactly, the waits count them)
     constexpr int LDEPTH = 3 * NL <= 63 ? 3 : 2;
     static_assert(2 * NL <= 63, "loader pipeline");
 
@@ -524,8 +542,11 @@ __device__ __forceinline__ void loader_role(const SweepParams& P, int sg, char* 
         __builtin_amdgcn_global_load_lds((gbl_void_t*)(score + ((size_t)frow * T + frow) * Bs + cc), (lds_void_t*)cb, 4, 0, 0);
         __builtin_amdgcn_global_load_lds((gbl_void_t*)(noise + (size_t)gap_of<DIR>(prow_c >= 1 ? prow_c : 1, T) * Bs + cc),
                                          (lds_void_t*)(cb + 256), 4, 0, 0);
-        if (GRAD)
+        if (GRAD) {
             __builtin_amdgcn_global_load_lds((gbl_void_t*)(vfwd + (size_t)frow * Bs + cc), (lds_void_t*)(cb + 512), 4, 0, 0);
+            // the path table's word of (frame, chain), indexed like alpha (no table: alpha once more -- the load count is fixed, the ring ignores it)
+            __builtin_amdgcn_global_load_lds((gbl_void_t*)(tabw + (size_t)frow * Bs + cc), (lds_void_t*)(cb + 768), 4, 0, 0);
+        }
         if (NNEAR > 0) {
             // the near tiles of row block kr: column blocks kr - RING - n (clamped: the first blocks have none, nobody reads them)
             char* const nb = lds + LDS_NEAR + (kr % NNSLOT) * NEAR_SLOT_BYTES;
@@ -838,6 +859,9 @@ __device__ __forceinline__ void spine_role(const SweepParams& P, int sg, int rin
     float gz = 0.f, lzc = 0.f;
     float nadd = 0.f;     // logProb's backward: + gout on every gap (the path score's cum[T-1] term; the product, then the sum: two
                           // roundings, exactly what a separate `dNoise += gout` pass over the stored marginal gave)
+                          // With the path table the same weight goes onto the path's own terms: + on the diagonal cell of a one-frame
+                          // interval, - on a covered gap.
+    const bool fold = GRAD && P.ptab != nullptr;
     if (GRAD && cvalid) {                                                                                 // the only global loads of a ring wave
         const float go = P.gout[(size_t)c * P.gstride];
         gz = go * P.gscale; lzc = P.logZ[c]; nadd = P.noiseAdd * go;
@@ -878,6 +902,10 @@ __device__ __forceinline__ void spine_role(const SweepParams& P, int sg, int rin
         for (int i = 0; i < RING; ++i) X[i] = read_tile(i);
         const float* cst = (const float*)(lds + LDS_CONST + slot * NCONST * 256) + lane;
         const float dcell = cst[0], nzl = cst[64], vfl = cst[128];
+        // the path table's word of this lane's frame (pathscore.h): does a one-frame interval sit on the diagonal cell, is the gap
+        // behind the frame -- the gap this lane stores in DIR 1 -- covered?
+        const int pte = fold ? __float_as_int(cst[192]) : PTAB_NONE;
+        const bool pdiag = (pte & PTAB_NONE) == frow, pgap = (pte & PTAB_COVERED) != 0;
         // first sub-diagonal cell of this lane's row: column r-1 of the own tile (last column of the previous tile for row 0)
         const float s1own = *(const float*)(lds + LDS_TILES + (slot * RING + RING - 1) * TILE_BYTES +
                                             ((((r > 0 ? r - 1 : 0) * PB) + r) * RS + ch) * 4);
@@ -979,8 +1007,11 @@ __device__ __forceinline__ void spine_role(const SweepParams& P, int sg, int rin
                         float p = fmaf(X.v[u], LOG2E, uq[q]);
                         if (GRAD && ringBand && rvalid && j < prow) grad_store(j, gz * fexp2(p + arow));
                         if (last && u == PB - 1 && r == 0) {
-                            if (GRAD && rvalid)       // noise marginal of the gap between prow-1 and prow
-                                dNoise[(size_t)gap_of<DIR>(prow, T) * Bs + c] = gz * fexp2(uq[q] + nz * LOG2E + arow) + nadd;
+                            if (GRAD && rvalid) {     // noise marginal of the gap between prow-1 and prow
+                                float nv = gz * fexp2(uq[q] + nz * LOG2E + arow) + nadd;
+                                if (pgap) nv = nv - nadd;           // a covered gap: the scatter's atomicAdd(-gout), after the sum above
+                                dNoise[(size_t)gap_of<DIR>(prow, T) * Bs + c] = nv;
+                            }
                             p = uq[q] + wl;
                         }
                         t[u] = p;
@@ -1075,7 +1106,11 @@ __device__ __forceinline__ void spine_role(const SweepParams& P, int sg, int rin
                     });
                 }
                 const float um1 = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(mine), 0x111, 0xf, 0xf, false));   // row_shr:1
-                if (rvalid && r >= 1) dNoise[(size_t)gap_of<DIR>(prow, T) * Bs + c] = gz * fexp2(um1 + nz * LOG2E + arow) + nadd;
+                if (rvalid && r >= 1) {
+                    float nv = gz * fexp2(um1 + nz * LOG2E + arow) + nadd;
+                    if (pgap) nv = nv - nadd;
+                    dNoise[(size_t)gap_of<DIR>(prow, T) * Bs + c] = nv;
+                }
             }
         } else {
             // (max,+): the same walk over the block's triangle on DPP row broadcasts.  Row j's value is final after step j-1 (the
@@ -1134,8 +1169,11 @@ __device__ __forceinline__ void spine_role(const SweepParams& P, int sg, int rin
                 }
                 pathOut[c] = ok ? __uint_as_float((unsigned)gr) - mine * sc : __uint_as_float(0x7fc00000u);
             }
-            if (GRAD)      // diagonal: gout * exp(alpha + beta - logZ + s - 2 softplus(s))
-                dScore[((size_t)frow * T + frow) * Bs + c] = gz * fexp2(arow + mine + draw - 2.0f * sp);
+            if (GRAD) {    // diagonal: gout * exp(alpha + beta - logZ + s - 2 softplus(s))
+                float dv = gz * fexp2(arow + mine + draw - 2.0f * sp);
+                if (pdiag) dv = dv + nadd;                  // a one-frame interval of the path: the scatter's atomicAdd(+gout)
+                dScore[((size_t)frow * T + frow) * Bs + c] = dv;
+            }
             if (MODE == 1) code[(size_t)c * T + frow] = (mykey + 1) | (sp > 0.0f ? 0x40000000 : 0);
         }
         if (SEMICRF_PANEL_PROBES && trace) ts[k] = __builtin_amdgcn_s_memrealtime();                 // chain probe: u published
@@ -1340,6 +1378,7 @@ __device__ __forceinline__ void panel_role(const SweepParams& P, char* lds, int 
     const float* const logZp = P.logZ;
     const float* const goutp = P.gout;
     float* const dScore = P.dScore;
+    constexpr bool PFOLD = GRAD && DIR == 1;                           // the path table (a row is a begin frame in DIR 1 only)
     const int lane = threadIdx.x & 63;
     const int slot = lane >> 3, q8 = lane & 7;
     const size_t Bs = (size_t)B;
@@ -1423,6 +1462,15 @@ __device__ __forceinline__ void panel_role(const SweepParams& P, char* lds, int 
                 }
             }
         }
+        int ptab_words[4] = {PTAB_NONE, PTAB_NONE, PTAB_NONE, PTAB_NONE};
+        const int* const ptab = PFOLD ? kernarg_again<const int*>(offsetof(SweepParams, ptab)) : nullptr;
+        if (PFOLD && ptab != nullptr) {
+            // (row and chains clamped into the task's own: a word looked at twice can only raise the flag for a cell that IS the task's)
+            const int prow = pbase + (slot & 3) < T ? pbase + (slot & 3) : T - 1;
+            const int* const pr = ptab + (size_t)frame_of<DIR>(prow, T) * Bs;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) ptab_words[i] = pr[c + i < c1 ? c + i : c1 - 1];
+        }
         // ---- addressing -----------------------------------------------------------------------------------
         // Buffer addressing: one VGPR byte offset per lane (constant over the task), everything that depends
         // on (tile, rr, h) is wave-uniform and lives in the SGPR base / soffset -- no per-load 64-bit VALU math.
@@ -1452,6 +1500,21 @@ __device__ __forceinline__ void panel_role(const SweepParams& P, char* lds, int 
                 issued += 10;
                 if (i == 0) mark0 = issued; else if (i == 1) mark1 = issued; else mark2 = issued;
             }
+
+        // The path table: does a path interval that begins in one of the task's rows end in one of its columns?  One wave-uniform
+        // flag, found while the first tiles are on their way (slot s looks at row s & 3 of its four chains; the words were
+        // requested in front of the tiles, so the wait for them is part of the wait for the first stage); the words themselves are
+        // dropped -- the tile loop knows nothing of the path.
+        bool pathfix = false;
+        if (PFOLD && ptab != nullptr) {
+            bool hit = false;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int pj = T - 1 - (ptab_words[i] & PTAB_NONE);      // none: far below zero
+                hit = hit | ((unsigned)(pj - m0 * PB) < (unsigned)((m1 - m0) * PB));
+            }
+            pathfix = __any(hit);
+        }
 
         for (int m = m0, s = 0; m < m1; ++m, s = (s + 1 == PNS ? 0 : s + 1)) {
             char* const stage = stage0 + s * PSTAGE_BYTES;
@@ -1710,6 +1773,36 @@ __device__ __forceinline__ void panel_role(const SweepParams& P, char* lds, int 
         }
         if (SEMICRF_PANEL_PROBES && (dbg & 16u) && g == 0 && m1 == q + 1 && lane == 0 && k < 64)
             P.ts[256 + 64 * q4 + k] = __builtin_amdgcn_s_memrealtime();     // chain probe: partial stored (per row quarter)
+        // ---- the path's cells among this task's (rare: a few thousand cells per call against ~10^5 tasks) --------------------------
+        // Behind the hand-off, with the accumulators dead.  The cell (row rr, column pj) was stored by THIS wave -- by the lane whose
+        // slot is pj & 7, for its chain quad -- so once the wave's stores are acknowledged that lane reads the marginal back (device
+        // scope: past this CU's vector cache) and stores marginal + gout with the policy of the first store: no other wave, no atomics,
+        // one rounding as in the scatter kernel.
+        if (PFOLD && pathfix) {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            const int* const ptab2 = kernarg_again<const int*>(offsetof(SweepParams, ptab));
+            const float* const gout2 = kernarg_again<const float*>(offsetof(SweepParams, gout));
+            float* const dScore2 = kernarg_again<float*>(offsetof(SweepParams, dScore));
+            const int gstride2 = kernarg_again<int>(offsetof(SweepParams, gstride));
+            const float wpath = kernarg_again<float>(offsetof(SweepParams, noiseAdd));
+            int f0, f1;
+            part_tiles(k - FAR0, part, f0, f1);
+#pragma nounroll
+            for (int n = 0; n < 16; ++n) {                               // (row n >> 2, chain n & 3 of the quad): a plain loop, it runs rarely
+                const int prow = pbase + (n >> 2), ci = c + (n & 3);
+                if (prow >= T) break;
+                const int fb = frame_of<DIR>(prow, T);
+                const int pend = ptab2[(size_t)fb * Bs + (ci < c1 ? ci : c1 - 1)] & PTAB_NONE;
+                const int pj = T - 1 - pend;
+                if (ci < c1 && (unsigned)(pj - f0 * PB) < (unsigned)((f1 - f0) * PB) && (pj & 7) == (lane >> 3)) {
+                    float* const cell = dScore2 + ((size_t)pend * T + fb) * Bs + ci;
+                    const float mv = __hip_atomic_load(cell, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    const float nv = mv + wpath * gout2[(size_t)ci * gstride2];
+                    if (grad_nt) __builtin_nontemporal_store(nv, cell);
+                    else *cell = nv;
+                }
+            }
+        }
         if (tr) tsp[3] = __builtin_amdgcn_s_memrealtime();
         ++tn;
     }
@@ -1776,6 +1869,7 @@ __device__ __forceinline__ void band_role(const SweepParams& P)
     unsigned* const ctrl = P.ctrl;
     const float* __restrict__ score = P.score;
     float* const dScore = P.dScore;
+    const int* __restrict__ ptab = P.ptab;
     const int lane = threadIdx.x & 63;
     const int q8 = lane & 7, pjsub = (lane >> 3) & 1, pisub = lane >> 4;
     const int nG = P.nPanelGroups;
@@ -1803,14 +1897,22 @@ __device__ __forceinline__ void band_role(const SweepParams& P)
         const int cl = c < c1 ? c : c0;
         const bool v0 = c < c1, v1 = c + 1 < c1, v2 = c + 2 < c1, v3 = c + 3 < c1;
         float gz[4], ar[4];
+        // the path table (DIR 1: a row is a begin frame): the column position of the path interval that begins in this lane's row, per
+        // chain (-1: none, or no table), and what its cell gets on top of the marginal
+        float gp[4];
+        int pjp[4];
         {
             const int fr = frame_of<DIR>(pic, T);
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const bool ok = c + i < c1;
                 const float lz = ok ? P.logZ[c + i] : 0.f;
-                gz[i] = ok ? P.gout[(size_t)(c + i) * P.gstride] * P.gscale : 0.f;
+                const float go = ok ? P.gout[(size_t)(c + i) * P.gstride] : 0.f;
+                gz[i] = ok ? go * P.gscale : 0.f;
                 ar[i] = ok ? (P.vfwd[(size_t)fr * Bs + c + i] - lz) * LOG2E : 0.f;
+                const int pend = (DIR == 1 && ok && rowok && ptab) ? (ptab[(size_t)fr * Bs + c + i] & PTAB_NONE) : PTAB_NONE;
+                pjp[i] = pend != PTAB_NONE ? T - 1 - pend : -1;
+                gp[i] = P.noiseAdd * go;
             }
         }
         v4u x[8], uu[8];
@@ -1851,6 +1953,14 @@ __device__ __forceinline__ void band_role(const SweepParams& P)
             gv.y = __float_as_uint(gz[1] * fexp2(fmaf(__uint_as_float(x[e].y), LOG2E, __uint_as_float(uu[e].y)) + ar[1]));
             gv.z = __float_as_uint(gz[2] * fexp2(fmaf(__uint_as_float(x[e].z), LOG2E, __uint_as_float(uu[e].z)) + ar[2]));
             gv.w = __float_as_uint(gz[3] * fexp2(fmaf(__uint_as_float(x[e].w), LOG2E, __uint_as_float(uu[e].w)) + ar[3]));
+            {
+                // the cell of a path interval: marginal + noiseAdd * gout, rounded once -- what the scatter's atomicAdd left
+                const int pj = m * PB + 2 * e + pjsub;
+                if (pj == pjp[0]) gv.x = __float_as_uint(__uint_as_float(gv.x) + gp[0]);
+                if (pj == pjp[1]) gv.y = __float_as_uint(__uint_as_float(gv.y) + gp[1]);
+                if (pj == pjp[2]) gv.z = __float_as_uint(__uint_as_float(gv.z) + gp[2]);
+                if (pj == pjp[3]) gv.w = __float_as_uint(__uint_as_float(gv.w) + gp[3]);
+            }
             float* const dst = dScore + off[e];
 #if defined(SEMICRF_BAND_ABL) && SEMICRF_BAND_ABL == 1
             asm volatile("" ::"v"(gv));                              // timing ablation: computed, not stored
@@ -1888,6 +1998,8 @@ __device__ __forceinline__ void path_role(const SweepParams& P)
         // lane 0 masked off: an endless loop on chain c0 (gfx950, ROCm 7.2; found as a hang of the whole launch).
         __builtin_amdgcn_wave_barrier();
         store_granule(P.pathg + c, make_granule(P.tag, (float)r));
+        // the same walk leaves the path as a table for the backward call (every word of the chain's column, every call)
+        if (P.ptabOut) path_table_wave(P.ptabOut, P.T, P.B, P.pathK, P.pathPairs, P.pathOffsets, c);
     }
 }
 
@@ -2296,8 +2408,10 @@ struct GradArgs {
     const float* vfwd; const float* logZ; const float* gout; float* dScore; float* dNoise; int gstride; float gscale;
     int keep_upper;       // the cells begin > end of dScore hold zeros already (SEMICRF_GRAD_UPPER_IS_ZERO): not written
     float noise_add;      // dNoise += noise_add * gout on every gap (logProb's backward), 0: nothing
+    const int* ptab;      // the forward call's path table (logProb's backward), or nullptr
+    int* path_folded;     // ... set to 1 when the launch applied the path's own terms (the caller then skips its scatter)
 };
-struct PathArgs { const int* pairs; const int* offsets; int K; float* out; };
+struct PathArgs { const int* pairs; const int* offsets; int K; float* out; int* ptab; };
 
 template <int MODE, int DIR, bool GRAD>
 static void launch_one(const SweepParams& P, int grid, hipStream_t stream)
@@ -2322,6 +2436,7 @@ static int launch_persist_sweep_impl(int mode, int dir, const float* score, cons
 {
     SweepParams P;
     P.pathPairs = nullptr; P.pathOffsets = nullptr; P.pathK = 0; P.pathOut = nullptr; P.pathg = nullptr; P.pathSpine = 0; P.noiseAdd = 0.0f;
+    P.ptabOut = nullptr; P.ptab = nullptr;
     P.vfwd = nullptr; P.logZ = nullptr; P.gout = nullptr; P.dScore = nullptr; P.dNoise = nullptr; P.gstride = 1; P.gscale = 1.0f;
     if (grad) {
         P.vfwd = grad->vfwd; P.logZ = grad->logZ; P.gout = grad->gout; P.dScore = grad->dScore; P.dNoise = grad->dNoise;
@@ -2352,6 +2467,7 @@ static int launch_persist_sweep_impl(int mode, int dir, const float* score, cons
     if (path && mode == 0 && dir == 0 && !grad) {
         // (offsets is never null here; pairs may be when K == 0 -- the role only looks at pairs[k] for k < K)
         P.pathPairs = path->pairs ? path->pairs : path->offsets; P.pathOffsets = path->offsets; P.pathK = path->K; P.pathOut = path->out;
+        P.ptabOut = path->ptab;
         P.pathg = (u64*)(w + ug_off + 2 * ug_bytes);
     }
     P.u_out = u_out; P.last_out = last_out; P.code = code;
@@ -2449,6 +2565,11 @@ static int launch_persist_sweep_impl(int mode, int dir, const float* score, cons
             if (bw > NT / 64 - pw - zw) bw = NT / 64 - pw - zw;
         }
         P.bandWaves = bw;
+        // The path's own terms inside this launch: where every cell has ONE writer that knows its row -- band waves for the band (a
+        // ring that stores the band itself does so in the middle of its dependent chain: short sequences keep the scatter), panels
+        // for the far field -- and the whole batch is one launch.
+        P.ptab = (grad && grad->ptab && bw > 0 && nchunks == 1 && NNEAR == 0) ? grad->ptab : nullptr;
+        if (grad && grad->path_folded) *grad->path_folded = P.ptab != nullptr ? 1 : 0;
         P.gradLazyShort = nb < 256 ? 1 : 0;
         // Two far waves taking turns halve the far wave's share of a block's period (one device-scope round trip per block and wave):
         // worth 3 - 4 % where the forward / decode sweeps are hand-off-bound, i.e. with few chains; with many chains, and in the gradient
@@ -2490,19 +2611,31 @@ int launch_persist_sweep(int mode, int dir, const float* score, const float* noi
 
 // logZ and logProb = path - logZ in one launch (the path scores by spare waves while the sweep runs)
 int launch_persist_logprob_fwd(const float* score, const float* noise, int T, int B, float* u_out, float* logZ, const int* pairs,
-                               int K, const int* offsets, float* logProb, void* ws, hipStream_t stream, int lease, unsigned lease_tag)
+                               int K, const int* offsets, float* logProb, void* ws, hipStream_t stream, int lease, unsigned lease_tag, int* ptab)
 {
-    const PathArgs pa{pairs, offsets, K, logProb};
+    const PathArgs pa{pairs, offsets, K, logProb, ptab};
     return launch_persist_sweep_impl(0, 0, score, noise, T, B, u_out, logZ, nullptr, ws, stream, nullptr, lease, lease_tag, &pa);
 }
 
 // Fused backward: beta sweep + marginals (dScore fully written incl. the zero upper triangle, dNoise).
 int launch_persist_logz_bwd(const float* score, const float* noise, const float* v, const float* logZ,
                             const float* gout, int T, int B, float* dScore, float* dNoise, float* q_out, void* ws,
-                            hipStream_t stream, int lease, unsigned lease_tag, int gstride, float gscale, int keep_upper, float noise_add)
+                            hipStream_t stream, int lease, unsigned lease_tag, int gstride, float gscale, int keep_upper, float noise_add,
+                            const int* ptab, int* path_folded)
 {
-    GradArgs ga{v, logZ, gout, dScore, dNoise, gstride, gscale, keep_upper, noise_add};
+    if (path_folded) *path_folded = 0;
+    GradArgs ga{v, logZ, gout, dScore, dNoise, gstride, gscale, keep_upper, noise_add, ptab, path_folded};
     return launch_persist_sweep_impl(0, 1, score, noise, T, B, q_out, nullptr, nullptr, ws, stream, &ga, lease, lease_tag);
+}
+
+// Can a gradient sweep of this shape apply the path's own terms (SweepParams::ptab)?  The conditions launch_persist_sweep_impl checks
+// per launch, for the callers that decide up front whether to ask the forward call for a table.
+int persist_path_fold_possible(int T, int B)
+{
+    const int ncu = device_cus();
+    const int nSpine = (B + GS - 1) / GS, maxSpine = ncu / 2 > 0 ? ncu / 2 : 1;
+    // (an odd batch keeps the scatter: its 16-byte pieces straddle lines and it is a rare shape -- nothing here is tuned for it)
+    return NNEAR == 0 && B % 2 == 0 && (T + PB - 1) / PB > FAR0 && nSpine <= maxSpine && ncu - (nSpine + SPH - 1) / SPH > 0;
 }
 
 // host-side view of the workgroup -> role map (tests/test_abi.py checks that it is a permutation for every launch shape)

@@ -141,6 +141,24 @@ static PyObject* m_pack_into(PyObject* self, PyObject* args)
     return PyLong_FromLongLong(k);
 }
 
+/* path_is_simple(pairs_addr, offsets_addr, B) -> bool: can the packed path be written as a path table (include/semicrf_hip.h:
+ * semicrf_logprob_fwd_t)?  Within every chain begin <= end, the begins ascend strictly and no interval starts before the previous
+ * one has ended: every frame begins at most one interval, every gap is covered at most once. */
+static PyObject* m_path_is_simple(PyObject* self, PyObject* args)
+{
+    unsigned long long pa, oa;
+    long long B;
+    if (!PyArg_ParseTuple(args, "KKL", &pa, &oa, &B)) return NULL;
+    const int32_t* pairs = (const int32_t*)(uintptr_t)pa;
+    const int32_t* off = (const int32_t*)(uintptr_t)oa;
+    for (long long c = 0; c < B; ++c)
+        for (long long k = off[c]; k < off[c + 1]; ++k) {
+            if (pairs[2 * k] > pairs[2 * k + 1]) Py_RETURN_FALSE;
+            if (k > off[c] && (pairs[2 * k] <= pairs[2 * k - 2] || pairs[2 * k] < pairs[2 * k - 1])) Py_RETURN_FALSE;
+        }
+    Py_RETURN_TRUE;
+}
+
 
 /* ------------------------------------------------------------------------------------------------------------------------
  * The cross-segment event merge of TransKun.transcribe (ModelTransformer.py:803-843) and Data.resolveOverlapping (Data.py:170-214)
@@ -586,6 +604,7 @@ static PyMethodDef methods[] = {
     {"unpack", m_unpack, METH_VARARGS, "packed int32 pairs/offsets (host addresses) -> list of lists of (begin, end)"},
     {"pack_into", m_pack_into, METH_VARARGS, "list of lists of (begin, end) -> packed int32 buffers; returns K (ordered: begin <= end required)"},
     {"count", m_count, METH_O, "total number of intervals"},
+    {"path_is_simple", m_path_is_simple, METH_VARARGS, "packed int32 pairs/offsets (host addresses), B -> can the path be a path table"},
     {"tm_new", m_tm_new, METH_VARARGS, "event merger for n_files recordings of P symbols"},
     {"tm_add", m_tm_add, METH_VARARGS, "merge the packed events of one step (rows of 7 doubles at a host address)"},
     {"tm_finish", m_tm_finish, METH_VARARGS, "the final Note list of one recording"},

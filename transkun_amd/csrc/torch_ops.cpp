@@ -356,28 +356,31 @@ void eval_path_bwd(Tensor gout, int64_t T, int64_t B, Tensor pairs, int64_t K, T
 }
 
 // logProb as one call each way (semicrf_logprob_fwd / _bwd): gout holds B values (gstride 1) or ONE (gstride 0)
+// ptab / has_ptab: the path table of semicrf_logprob_fwd_t / _bwd_t (int32 [T][B]; has_ptab false: none, pass any int32 tensor)
 void logprob_fwd(Tensor score, Tensor noise, Tensor pairs, int64_t K, Tensor offsets, Tensor logProb, Tensor logZ, Tensor v, bool want_v,
-                 Tensor ws)
+                 Tensor ws, Tensor ptab, bool has_ptab)
 {
     Ctx c(score); c.same(score, noise, pairs, offsets, logProb, logZ, v, ws);
+    if (has_ptab) c.same(score, ptab);
     const Dims d = crf_dims(score, noise);
     STD_TORCH_CHECK(K >= 0, "semicrf: negative interval count");
-    check(semicrf_logprob_fwd(cfp(score), cfp(noise), d.T, d.B, i32(pairs, 2 * K, "pairs"), K, i32(offsets, d.B + 1, "offsets"),
-                              f32w(logProb, d.B, "logProb"), f32w(logZ, d.B, "logZ"), want_v ? f32w(v, (int64_t)d.T * d.B, "v") : nullptr,
-                              bytes(ws, "ws"), (size_t)ws.numel(), c.stream),
+    check(semicrf_logprob_fwd_t(cfp(score), cfp(noise), d.T, d.B, i32(pairs, 2 * K, "pairs"), K, i32(offsets, d.B + 1, "offsets"),
+                                f32w(logProb, d.B, "logProb"), f32w(logZ, d.B, "logZ"), want_v ? f32w(v, (int64_t)d.T * d.B, "v") : nullptr,
+                                has_ptab ? i32(ptab, (int64_t)d.T * d.B, "ptab") : nullptr, bytes(ws, "ws"), (size_t)ws.numel(), c.stream),
           "semicrf_logprob_fwd");
 }
 void logprob_bwd(Tensor score, Tensor noise, Tensor v, Tensor logZ, Tensor gout, int64_t gstride, Tensor pairs, int64_t K, Tensor offsets,
-                 Tensor dScore, Tensor dNoise, int64_t flags, Tensor ws)
+                 Tensor dScore, Tensor dNoise, int64_t flags, Tensor ws, Tensor ptab, bool has_ptab)
 {
     Ctx c(score); c.same(score, noise, v, logZ, gout, pairs, offsets, dScore, dNoise, ws);
+    if (has_ptab) c.same(score, ptab);
     const Dims d = crf_dims(score, noise);
     const int64_t TB = (int64_t)d.T * d.B;
     STD_TORCH_CHECK(K >= 0 && (gstride == 0 || gstride == 1), "semicrf: bad interval count / gout stride");
-    check(semicrf_logprob_bwd_f(cfp(score), cfp(noise), f32(v, TB, "v"), f32(logZ, d.B, "logZ"), f32(gout, gstride ? d.B : 1, "gout"),
+    check(semicrf_logprob_bwd_t(cfp(score), cfp(noise), f32(v, TB, "v"), f32(logZ, d.B, "logZ"), f32(gout, gstride ? d.B : 1, "gout"),
                                 (int)gstride, d.T, d.B, i32(pairs, 2 * K, "pairs"), K, i32(offsets, d.B + 1, "offsets"),
-                                f32w(dScore, TB * d.T, "dScore"), f32w(dNoise, TB - d.B, "dNoise"), (int)flags, bytes(ws, "ws"),
-                                (size_t)ws.numel(), c.stream),
+                                f32w(dScore, TB * d.T, "dScore"), f32w(dNoise, TB - d.B, "dNoise"), (int)flags,
+                                has_ptab ? i32(ptab, TB, "ptab") : nullptr, bytes(ws, "ws"), (size_t)ws.numel(), c.stream),
           "semicrf_logprob_bwd");
 }
 
@@ -606,9 +609,11 @@ void eval_path_bwd_cpu(Tensor gout, int64_t T, int64_t B, Tensor pairs, int64_t 
                                has_dn ? f32w(dNoise, (T - 1) * B, "dNoise") : nullptr);
 }
 
+// (the CPU kernels scatter the path's terms themselves: a path table is refused, not ignored)
 void logprob_fwd_cpu(Tensor score, Tensor noise, Tensor pairs, int64_t K, Tensor offsets, Tensor logProb, Tensor logZ, Tensor v, bool want_v,
-                     Tensor ws)
+                     Tensor ws, Tensor ptab, bool has_ptab)
 {
+    STD_TORCH_CHECK(!has_ptab, "semicrf: the path table belongs to the GPU sweeps");
     logz_fwd_cpu(score, noise, logZ, v, want_v, ws);
     eval_path_cpu(score, noise, pairs, K, offsets, logProb, ws);
     float* lp = (float*)logProb.data_ptr();
@@ -616,8 +621,9 @@ void logprob_fwd_cpu(Tensor score, Tensor noise, Tensor pairs, int64_t K, Tensor
     for (int64_t c = 0; c < score.size(2); ++c) lp[c] -= lz[c];
 }
 void logprob_bwd_cpu(Tensor score, Tensor noise, Tensor v, Tensor logZ, Tensor gout, int64_t gstride, Tensor pairs, int64_t K, Tensor offsets,
-                     Tensor dScore, Tensor dNoise, int64_t flags, Tensor ws)
+                     Tensor dScore, Tensor dNoise, int64_t flags, Tensor ws, Tensor ptab, bool has_ptab)
 {
+    STD_TORCH_CHECK(!has_ptab, "semicrf: the path table belongs to the GPU sweeps");
     all_cpu(score, noise, v, logZ, gout, pairs, offsets, dScore, dNoise);
     const Dims d = crf_dims(score, noise);
     const int64_t TB = (int64_t)d.T * d.B;
@@ -1189,9 +1195,9 @@ STABLE_TORCH_LIBRARY(semicrf, m)
     m.def("eval_path_bwd(Tensor gout, int T, int B, Tensor pairs, int K, Tensor offsets, Tensor(a!) dScore, bool has_ds, Tensor(b!) dNoise, "
           "bool has_dn) -> ()");
     m.def("logprob_fwd(Tensor score, Tensor noise, Tensor pairs, int K, Tensor offsets, Tensor(a!) logProb, Tensor(b!) logZ, Tensor(c!) v, "
-          "bool want_v, Tensor(d!) ws) -> ()");
+          "bool want_v, Tensor(d!) ws, Tensor(e!) ptab, bool has_ptab) -> ()");
     m.def("logprob_bwd(Tensor score, Tensor noise, Tensor v, Tensor logZ, Tensor gout, int gstride, Tensor pairs, int K, Tensor offsets, "
-          "Tensor(a!) dScore, Tensor(b!) dNoise, int flags, Tensor(c!) ws) -> ()");
+          "Tensor(a!) dScore, Tensor(b!) dNoise, int flags, Tensor(c!) ws, Tensor ptab, bool has_ptab) -> ()");
     // (group, pitch): the slot layout of the chain axis (include/semicrf_hip.h, *_p entry points); group == pitch: contiguous
     // rowc / drowc, ldrc / lddrc: the merged projection's per-(chain, end) constant (*_pc entry points); stride 0: none (pass any tensor)
     m.def("interval_score_fwd(Tensor q, Tensor k, Tensor diag, Tensor rowc, int C, int T, int D, int ldq, int ldk, int ldd, int ldrc, "
