@@ -960,6 +960,42 @@ int semicrf_clip_from_history(const double* partials, int64_t numel, const float
 int semicrf_adabelief_step(float* p, const float* g, float* m, float* s, int64_t numel, const float* coef,
                            semicrf_adabelief_groups groups, semicrf_stream_t stream);
 
+/*
+ * The attention of the backbone's transformer layers for many short, independent sequences (forward only).  Replaces: the head
+ * split `unflatten / transpose`, F.scaled_dot_product_attention and the merge `transpose / flatten` of MultiHeadAttentionKernel.forward
+ * with kernel = None (LayersTransformer.py:173-186), and with them the transposed copies of BasicBlock's time-axis half (:327-337).
+ * For every sequence s = (s0, s1), s0 < n0, s1 < n1, head h < H, query i < Lq:
+ *   out[s][i][h][:] = sum over j < Lk of softmax_j(q[s][i][h][:] . k[s][j][h][:] / sqrt(d)) v[s][j][h][:]
+ * fp32, no mask, no dropout, no bias.  The layout is TOKEN-MAJOR: a token's H d values are contiguous, head h the slice
+ * [h d, (h + 1) d).  Each of q, k, v, out has its own three ELEMENT strides: token (s0, s1, l) starts at
+ * base + s0 stride_s0 + s1 stride_s1 + l stride_l.  One [N][T'][F'][H d] buffer serves the frequency axis as n0 = N, n1 = T', L = F'
+ * (strides T' F' H d, F' H d, H d) and the time axis as n0 = N, n1 = F', L = T' (strides T' F' H d, H d, F' H d): no transposed copy.
+ * q has Lq tokens per sequence, k and v have Lk (cross attention: Lq != Lk).  Strides are >= 0; a 0 repeats a tensor over that dimension
+ * (not for out); a token stride stays below 2^28 elements.  All offsets are 64-bit.
+ *
+ * Supported (semicrf_axial_attention_supported returns 1): 1 <= Lq, Lk <= SEMICRF_ATTENTION_MAX_L; d a multiple of 8 in
+ * [8, SEMICRF_ATTENTION_MAX_D]; H >= 1.  n0 n1 H < 2^31 (2^20 sequences and more).  n0 n1 == 0 launches nothing.
+ *
+ * Exact fp32 on the matrix pipe (v_mfma_f32_32x32x2_f32), one fixed chain of operations per output element (csrc/attention_math.h):
+ * q . k a fmaf chain over the head dimension ascending from +0, times (float)(1 / sqrt(d)); the maximum over the keys j < Lk; exp of
+ * the difference; the sum of the exponentials as S0 + S1, S_b over the keys with ((j >> 2) & 1) == b ascending; P V a fmaf chain over
+ * the keys ascending from +0; one division by the sum.  Keys from Lk to the tile edge are masked before the maximum and contribute
+ * exact zeros; K and V rows past Lk and query rows past Lq are never read (zeros are formed in registers), rows past Lq never stored;
+ * the head dimension is padded with zeros in LDS and registers only.  No atomics; tile sizes depend on Lk and d alone: a sequence's
+ * result is bit-identical from run to run, whatever n0, n1, its position in the batch and the strides are.
+ * One launch on `stream`; no workspace, no synchronisation, no allocation.  16-byte loads of the Q and K rows when q, k are 16-byte
+ * aligned and their strides multiples of 4, 4-byte loads otherwise (the same numbers).
+ * SEMICRF_EINVAL, with nothing launched and `out` untouched: a shape outside the supported set, a NULL or misaligned pointer, a
+ * negative count or stride, n0 n1 H >= 2^31.
+ */
+#define SEMICRF_ATTENTION_MAX_L 256
+#define SEMICRF_ATTENTION_MAX_D 64
+int semicrf_axial_attention_supported(int Lq, int Lk, int H, int d);
+int semicrf_axial_attention(const float* q, const float* k, const float* v, float* out, int64_t n0, int64_t n1, int Lq, int Lk, int H, int d,
+                            int64_t q_stride_s0, int64_t q_stride_s1, int64_t q_stride_l, int64_t k_stride_s0, int64_t k_stride_s1,
+                            int64_t k_stride_l, int64_t v_stride_s0, int64_t v_stride_s1, int64_t v_stride_l, int64_t out_stride_s0,
+                            int64_t out_stride_s1, int64_t out_stride_l, semicrf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -33,6 +33,8 @@ OP_ATTRIBUTE_HEADS_BWD = 13
 HEADS_ROW_TILE = 64                             # SEMICRF_HEADS_ROW_TILE: intervals per workgroup of semicrf_attribute_heads
 HEADS_SLICE = 64                                # SEMICRF_HEADS_SLICE: hidden columns per workgroup
 HEADS_BWD_ROW_CHUNK = 512                       # SEMICRF_HEADS_BWD_ROW_CHUNK: rows per partial plane of semicrf_attribute_heads_bwd's row sums
+ATTENTION_MAX_L = 256                           # SEMICRF_ATTENTION_MAX_L: the longest sequence of semicrf_axial_attention
+ATTENTION_MAX_D = 64                            # SEMICRF_ATTENTION_MAX_D: its largest head dimension (a multiple of 8)
 TOL_MAX = 8                                     # SEMICRF_TOL_MAX
 LEN_MODES = {"linear": 0, "sqrt": 1, "none": 2}
 
@@ -134,6 +136,8 @@ _SIGS = {
     "semicrf_grad_sqnorm": (_i, [_vp, _i64, _vp, _vp]),
     "semicrf_clip_from_history": (_i, [_vp, _i64, _vp, ctypes.c_double, _vp, _i, _vp, _i, _vp, _vp]),
     "semicrf_adabelief_step": (_i, [_vp, _vp, _vp, _vp, _i64, _vp, AdaBeliefGroups, _vp]),
+    "semicrf_axial_attention_supported": (_i, [_i, _i, _i, _i]),
+    "semicrf_axial_attention": (_i, [_vp, _vp, _vp, _vp, _i64, _i64, _i, _i, _i, _i] + [_i64] * 12 + [_vp]),
     "interval_score_bwd_ws": (_i, [_vp, _vp, _vp, _i, _i, _i, _i64, _i64, ctypes.c_float, _i, _vp, _vp, _vp, _i64, _i64, _i64, _vp, ctypes.c_size_t, _vp]),
     "interval_score_bwd_workspace_bytes": (ctypes.c_size_t, [_i, _i, _i]),
     "segment_onset_filter": (_i, [_vp, _vp, _i, _i, _vp, _i64, _vp, _vp, _vp]),

@@ -1,0 +1,405 @@
+"""The backbone of the transcriber: the module that turns the spectrogram features of a segment into `ctx`, with its attention as a
+fused HIP op.
+
+Mirrors the reference's `Backbone` and the modules it is built from (LayersTransformer.py:12-372, :444-660) under the reference's
+constructor arguments and parameter names, so `load_state_dict(reference_state_dict, strict=True)` works:
+
+    RMSNorm, TiedDropout, LearnableSpatialPositionEmbedding, ResBlock, MultiHeadAttentionKernel (kernel = None only), BasicBlock, Backbone
+
+What is native here is the attention.  Every layer attends along the frequency axis and along the time axis of one [N, T', F', D]
+hidden state: hundreds of independent sequences of at most a few hundred tokens, head dimension 40 at the model's size.
+`axial_attention` runs them through `torch.ops.semicrf.axial_attention` (csrc/attention.hip on a GPU, the host mirror in
+csrc/cpu_ops.cpp on the CPU), whose contract is token-major with three strides per tensor: both axes read the SAME buffer, so
+`BasicBlock` keeps the hidden state [N, T', F', D] and contiguous from its input to its output -- no `transpose(-3, -2)` around the
+time-axis half, and none of the copies eager PyTorch makes for the projections and the attention of a transposed tensor.
+
+Forward only: under autograd (gradients enabled and an input requiring grad), for dtypes other than float32, for shapes outside the
+op's supported set and for broadcasting keys, `axial_attention` takes the stock route -- `F.scaled_dot_product_attention` on head-split
+views, exactly the reference's call -- so training works as before.  `attention = "fused" | "torch"` on every attention module, and on
+`Backbone` for all of its layers, picks the route.
+
+Hidden size and head dimension come from the constructor as in the reference: head_dim = ceil(ceil(hiddenFactor * embed_dim) /
+num_heads), hidden size = head_dim * num_heads (the model: embed_dim 160, 4 heads, hiddenFactorAttn 1 -> d = 40).
+"""
+from __future__ import annotations
+
+import math
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+import torch.utils.checkpoint
+
+from . import _lib
+
+ROUTES = ("fused", "torch")
+DEFAULT_ATTENTION = "fused"
+
+
+# ---- the attention ------------------------------------------------------------------------------------------------------------------
+def attention_supported(Lq: int, Lk: int, num_heads: int, head_dim: int) -> bool:
+    """semicrf_axial_attention_supported: 1 <= Lq, Lk <= 256, head_dim a multiple of 8 in [8, 64], num_heads >= 1."""
+    return bool(_lib.load().semicrf_axial_attention_supported(int(Lq), int(Lk), int(num_heads), int(head_dim)))
+
+
+def attention_torch(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, num_heads: int) -> torch.Tensor:
+    """The stock route: the reference's call (LayersTransformer.py:173-186) -- heads split off the last dimension and moved in front of
+    the sequence as views, F.scaled_dot_product_attention, heads merged back."""
+    d = q.shape[-1] // num_heads
+    qh, kh, vh = (t.unflatten(-1, (num_heads, d)).transpose(-2, -3) for t in (q, k, v))
+    return F.scaled_dot_product_attention(qh, kh, vh).transpose(-2, -3).flatten(-2, -1)
+
+
+def _merge(sizes, strides):
+    """(size, stride) of the dimensions merged into one, or None when they do not lie evenly spaced in memory."""
+    dims = [(n, s) for n, s in zip(sizes, strides) if n != 1]
+    if not dims:
+        return 1, 0
+    n, s = dims[-1]
+    for m, t in reversed(dims[:-1]):
+        if t != s * n:
+            return None
+        n *= m
+    return n, s
+
+
+def _as_sequences(t: torch.Tensor, split: int):
+    """t [..., L, HD] as the op's 4-d view [n0, n1, L, HD] with the leading dimensions cut at `split`, or None (no copy is made)."""
+    if t.shape[-1] != 1 and t.stride(-1) != 1:
+        return None
+    lead, lst = t.shape[:-2], t.stride()[:-2]
+    a, b = _merge(lead[:split], lst[:split]), _merge(lead[split:], lst[split:])
+    if a is None or b is None:
+        return None
+    return torch.as_strided(t, (a[0], b[0], t.shape[-2], t.shape[-1]), (a[1], b[1], t.stride(-2), 1), t.storage_offset())
+
+
+def _fused_applies(q, k, v, num_heads) -> bool:
+    if not (q.dtype == k.dtype == v.dtype == torch.float32) or not (q.device == k.device == v.device):
+        return False
+    if q.device.type not in ("cuda", "cpu") or q.dim() < 2 or k.shape != v.shape or q.numel() == 0 or k.numel() == 0:
+        return False
+    if k.shape[:-2] != q.shape[:-2] or k.shape[-1] != q.shape[-1] or q.shape[-1] % num_heads != 0:
+        return False                                            # broadcasting batch dimensions: the stock route
+    if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad):
+        return False                                            # forward only
+    return attention_supported(q.shape[-2], k.shape[-2], num_heads, q.shape[-1] // num_heads)
+
+
+def axial_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, num_heads: int, route: str = "fused") -> torch.Tensor:
+    """softmax(q k^T / sqrt(d)) v per head and sequence.  q [..., Lq, H d], k and v [..., Lk, H d], arbitrary strided views whose last
+    dimension is contiguous: the leading dimensions are handed to the op as its two sequence dimensions by strides alone (a tensor
+    whose leading dimensions cannot be expressed that way is made contiguous first, that tensor only).  Returns [..., Lq, H d], laid
+    out in memory like q (so the result of a transposed view transposes back into a contiguous tensor).
+
+    route = "fused": the HIP op (the host kernel for CPU tensors) whenever it applies; the stock route (attention_torch) when the
+    shape is outside the supported set, the dtype is not float32, k / v broadcast against q, or gradients are enabled and an input
+    requires grad.  route = "torch": always the stock route.  Always usable, always differentiable."""
+    if route not in ROUTES:
+        raise ValueError(f"route must be one of {ROUTES}, not {route!r}")
+    if route == "torch" or not _fused_applies(q, k, v, num_heads):
+        return attention_torch(q, k, v, num_heads)
+    nlead = q.dim() - 2
+    best = None
+    for split in range(nlead + 1):
+        views = [_as_sequences(t, split) for t in (q, k, v)]
+        copies = sum(x is None for x in views)
+        if best is None or copies < best[0]:
+            best = (copies, split, views)
+        if copies == 0:
+            break
+    _, split, views = best
+    q4, k4, v4 = (x if x is not None else _as_sequences(t.contiguous(), split) for x, t in zip(views, (q, k, v)))
+    out = torch.empty_like(q)                                   # q's own layout when q is dense
+    o4 = _as_sequences(out, split) if views[0] is not None else None
+    if o4 is None:
+        out = torch.empty(q.shape, dtype=q.dtype, device=q.device)
+        o4 = _as_sequences(out, split)
+    _lib.ops().axial_attention(q4, k4, v4, o4, num_heads)
+    return out
+
+
+# ---- the modules --------------------------------------------------------------------------------------------------------------------
+class RMSNorm(nn.Module):
+    """x / sqrt(mean(x^2) + eps) over the last dimension; no parameters."""
+
+    def __init__(self, eps=1e-6):
+        super().__init__()
+        self.eps = eps
+
+    def forward(self, x):
+        return x * torch.rsqrt(x.pow(2).mean(dim=-1, keepdim=True) + self.eps)
+
+
+class TiedDropout(nn.Module):
+    """Dropout whose mask is shared along `axis` (training only)."""
+
+    def __init__(self, dropoutProb, axis):
+        super().__init__()
+        self.dropout = nn.Dropout(dropoutProb)
+        self.axis = axis
+
+    def forward(self, x):
+        if not self.training:
+            return x
+        shape = list(x.shape)
+        shape[self.axis] = 1
+        return self.dropout(torch.ones(*shape, device=x.device)) * x
+
+
+class LearnableSpatialPositionEmbedding(nn.Module):
+    """Random-Fourier-feature position embedding with a learnable projection: mlp(cos(proj(coord)) / sqrt(embedSize / 2))."""
+
+    def __init__(self, embedSize, coordDim, gamma=10.0, dropoutProb=0.0):
+        super().__init__()
+        self.gamma = gamma
+        self.proj = nn.Linear(coordDim, embedSize)
+        self.mlp = nn.Sequential(nn.Linear(embedSize, 4 * embedSize), nn.GELU(), nn.Dropout(dropoutProb),
+                                 nn.Linear(4 * embedSize, embedSize))
+        self.dropout = nn.Dropout(dropoutProb)
+        self._reset_parameters()
+
+    def _reset_parameters(self):
+        nn.init.normal_(self.proj.weight, std=1 / self.gamma)
+        nn.init.uniform_(self.proj.bias, a=-math.pi, b=math.pi)
+
+    def forwardWithCoordVec(self, coord):
+        """coord [..., coordDim] -> [..., embedSize] (coordinates are taken in the projection's dtype)."""
+        phi = self.proj(coord.to(self.proj.weight.dtype))
+        return self.mlp(torch.cos(phi) / math.sqrt(phi.shape[-1] / 2))
+
+    def forward(self, *coords):
+        """One 1-d coordinate vector per dimension -> the embedding of their grid [len(c0), len(c1), .., embedSize]."""
+        return self.forwardWithCoordVec(torch.stack(torch.meshgrid(coords, indexing="ij"), dim=-1))
+
+
+class ResBlock(nn.Module):
+    """x + dropout(module(norm(x), *args)) * scale: pre-norm residual with LayerScale (initialised to 1e-2).  Only x is normalised."""
+
+    def __init__(self, module, size, prenorm=True, dropoutProb=0.0):
+        super().__init__()
+        self.module = module
+        self.norm = RMSNorm()
+        self.scale = nn.Parameter(torch.ones(size) * 1e-2)
+        self.dropout = nn.Dropout(dropoutProb)
+
+    def forward(self, x, *args):
+        return x + self.dropout(self.module(self.norm(x), *args)) * self.scale
+
+
+class MultiHeadAttentionKernel(nn.Module):
+    """Multi-head attention with bias-free q / k / v projections stored [in, hidden] and a Linear output projection.  Only
+    kernel = None (exact softmax attention) is implemented, as in the reference: with any other kernel the parameters exist (a
+    checkpoint loads) and forward raises NotImplementedError.
+
+    attention: "fused" (axial_attention's HIP op where it applies) or "torch" (the stock route)."""
+
+    def __init__(self, embed_dim, num_heads, dropout=0., k_dim=None, v_dim=None, fourierSize=32, kernel="fourier", hiddenFactor=1):
+        super().__init__()
+        self.embed_dim = embed_dim
+        self.num_heads = num_heads
+        self.kernel = kernel
+        self.fourierSize = fourierSize
+        self.head_dim = int(math.ceil(math.ceil(hiddenFactor * embed_dim) / num_heads))
+        hiddenSize = self.head_dim * num_heads
+        self.q_proj_weight = nn.Parameter(torch.empty((embed_dim, hiddenSize)))
+        self.k_proj_weight = nn.Parameter(torch.empty((embed_dim if k_dim is None else k_dim, hiddenSize)))
+        self.v_proj_weight = nn.Parameter(torch.empty((embed_dim if v_dim is None else v_dim, hiddenSize)))
+        self.out_proj = nn.Linear(hiddenSize, embed_dim)
+        if kernel is not None:
+            self.gamma = nn.Parameter(torch.tensor(1.0))
+            self.norm = RMSNorm()
+        self.attention = DEFAULT_ATTENTION
+        self._reset_parameters()
+
+    def _reset_parameters(self):
+        for w in (self.k_proj_weight, self.q_proj_weight, self.v_proj_weight):
+            nn.init.xavier_uniform_(w)
+
+    def forward(self, query, key=None, value=None, seq_dim=-2):
+        """query [..., Lq, embed_dim], key / value [..., Lk, .] (key defaults to query, value to key) -> [..., Lq, embed_dim].
+        seq_dim = -3: the SEQUENCE is dimension -3 of the inputs and dimension -2 counts independent sequences -- the attention along
+        the other axis of the same buffers, without transposing them (the projections are per token)."""
+        if key is None:
+            key = query
+        if value is None:
+            value = key
+        if self.kernel is not None:
+            raise NotImplementedError("MultiHeadAttentionKernel: only kernel = None is implemented")
+        if seq_dim not in (-2, -3):
+            raise ValueError("seq_dim must be -2 or -3")
+        q, k, v = query @ self.q_proj_weight, key @ self.k_proj_weight, value @ self.v_proj_weight
+        if seq_dim == -3:
+            q, k, v = q.transpose(-3, -2), k.transpose(-3, -2), v.transpose(-3, -2)
+        fetched = axial_attention(q, k, v, self.num_heads, route=self.attention)
+        if seq_dim == -3:
+            fetched = fetched.transpose(-3, -2)
+        return self.out_proj(fetched)
+
+
+def _feed_forward(inputSize, hiddenSize, dropoutProb):
+    return nn.Sequential(nn.Linear(inputSize, hiddenSize), nn.GELU(), nn.Dropout(dropoutProb), nn.Linear(hiddenSize, inputSize))
+
+
+class BasicBlock(nn.Module):
+    """One transformer layer over x [N, T, F, D]: per enabled axis an attention ResBlock and a feed-forward ResBlock.
+    "F": along the frequency axis; "T": along the time axis; "All0" / "0All": between the rest and the first frequency track;
+    "FT": over all tokens (kernel "positive": not implemented, as in the reference).
+
+    With attention = "fused" the "F" and "T" halves run on the [N, T, F, D] buffer as it is: everything but the attention is per
+    token, and the two halves differ only in which dimension the attention is told is the sequence.  With "torch" the block follows
+    the reference's order of operations, `transpose(-3, -2)` around the time-axis half included."""
+
+    def __init__(self, inputSize, num_heads, fourierSize, hiddenFactor=2, hiddenFactorAttn=1, approxKernels=[None, None, None, None],
+                 enabled=["F", "T", "All0", "0All"], dropoutProb=0.0):
+        super().__init__()
+        fnnHiddenSize = int(math.ceil(inputSize * hiddenFactor))
+        self.enabled = enabled
+
+        def attn(kernel, fourier):
+            return ResBlock(MultiHeadAttentionKernel(inputSize, num_heads=num_heads, fourierSize=fourier, kernel=kernel,
+                                                     hiddenFactor=hiddenFactorAttn), size=inputSize, dropoutProb=dropoutProb)
+
+        def fnn():
+            return ResBlock(_feed_forward(inputSize, fnnHiddenSize, dropoutProb), size=inputSize, dropoutProb=dropoutProb)
+
+        if "F" in enabled:
+            self.mhaBlockF, self.fnnBlockF = attn(approxKernels[0], fourierSize), fnn()
+        if "T" in enabled:
+            self.mhaBlockT, self.fnnBlockT = attn(approxKernels[1], fourierSize), fnn()
+        if "All0" in enabled or "0All" in enabled:
+            self.mhaBlockAll0, self.fnnBlockAll0 = attn(approxKernels[2], fourierSize), fnn()
+        if "FT" in enabled:
+            self.mhaBlockFT, self.fnnBlockFT = attn("positive", 64), fnn()
+
+    def attention_modules(self):
+        return [m for m in self.modules() if isinstance(m, MultiHeadAttentionKernel)]
+
+    @property
+    def attention(self):
+        routes = {m.attention for m in self.attention_modules()}
+        return routes.pop() if len(routes) == 1 else "mixed"
+
+    @attention.setter
+    def attention(self, route):
+        if route not in ROUTES:
+            raise ValueError(f"attention must be one of {ROUTES}, not {route!r}")
+        for m in self.attention_modules():
+            m.attention = route
+
+    def forward(self, x, mem=None, crossAttn=False):
+        nT, nF = x.shape[-3], x.shape[-2]
+        if mem is None:
+            mem = x
+        h = x
+        if "F" in self.enabled:
+            h = self.fnnBlockF(self.mhaBlockF(h, mem))
+        rest = [e for e in self.enabled if e not in ("F", "T")]
+        if self.attention == "fused":
+            if "T" in self.enabled:                              # the same buffers, the other axis: nothing is transposed
+                h = self.fnnBlockT(self.mhaBlockT(h, mem, None, -3))
+            if not rest:
+                return h
+            h, mem = h.transpose(-3, -2), mem.transpose(-3, -2)
+        else:
+            h, mem = h.transpose(-3, -2), mem.transpose(-3, -2)  # [N, F, T, D]
+            if "T" in self.enabled:
+                h = self.fnnBlockT(self.mhaBlockT(h, mem))
+        if "All0" in self.enabled or "0All" in self.enabled:
+            h0, h1 = h.split([1, h.shape[-3] - 1], dim=-3)
+            if "All0" in self.enabled:
+                h1 = self.mhaBlockAll0(h1, mem[..., 0:1, :, :])
+            if "0All" in self.enabled:
+                h0 = self.mhaBlockAll0(h0, mem.flatten(-3, -2).unsqueeze(-3))
+            h = self.fnnBlockAll0(torch.cat([h0, h1], dim=-3))
+        if "FT" in self.enabled:
+            h = self.fnnBlockFT(self.mhaBlockFT(h.flatten(-3, -2), mem.flatten(-3, -2))).unflatten(-2, (nF, nT))
+        h = h.transpose(-3, -2)
+        assert h.shape == x.shape
+        return h
+
+
+def _down_stage(cin, cout, stride, dropoutProb):
+    return [nn.Conv2d(cin, cout, 3, padding=1, stride=stride), nn.GroupNorm(4, cout), nn.GELU(), nn.Dropout2d(dropoutProb)]
+
+
+class Backbone(nn.Module):
+    """x [N, T, F, inputSize] (the frontend's features), outputIndices [P] -> ctx [N, P, T, baseSize * expansionFactor].
+
+    A convolution stem (3 x 3 input convolution plus a frequency position embedding, then three strided stages: patches of 8 frames
+    x 4 bins with downsampleF, 8 x 1 without) gives tokens of width 4 baseSize on a [T / 8, F / 4] grid; one aggregation track is
+    prepended on each axis; P target tokens per frame row (position embeddings of (time, output index)) are appended along the
+    frequency axis; nLayers BasicBlocks; the target tokens are upsampled 8x in time by a transposed convolution and cut to T.
+
+    attention: "fused" | "torch" for all layers (the property reads "mixed" when they differ)."""
+
+    def __init__(self, inputSize, baseSize, posEmbedInitGamma, nHead, fourierSize=16, hiddenFactor=2, hiddenFactorAttn=1,
+                 expansionFactor=1, dropoutProb=0.0, nLayers=4, enabledAttn=["F", "T"], useGradientCheckpoint=True, downsampleF=True,
+                 upsampleProjOnly=True):
+        super().__init__()
+        b = baseSize
+        self.posEmbedBuilder = LearnableSpatialPositionEmbedding(b, coordDim=1, gamma=posEmbedInitGamma, dropoutProb=dropoutProb)
+        self.inputConv = nn.Conv2d(inputSize, b, kernel_size=3, padding=1)
+        self.dropoutTied = TiedDropout(dropoutProb, axis=-3)
+        fs = 2 if downsampleF else 1                              # the frequency stride of stages 2 and 3
+        self.downConv = nn.Sequential(
+            nn.ConstantPad2d((2, 1, 4, 3) if downsampleF else (0, 0, 4, 3), value=0.0),
+            *_down_stage(b, 2 * b, (2, 1), dropoutProb),
+            *_down_stage(2 * b, 4 * b, (2, fs), dropoutProb),
+            *_down_stage(4 * b, 4 * b, (2, fs), dropoutProb),
+            nn.Conv2d(4 * b, 4 * b, 3, padding=1),
+            nn.GroupNorm(4, 4 * b))
+        self.upConv1dSkip = nn.ConvTranspose1d(4 * b, b * expansionFactor, 8, stride=8)
+        if not upsampleProjOnly:
+            self.upConv1d = nn.Sequential(
+                nn.ConvTranspose1d(4 * b, 4 * b, 2, stride=2), nn.Conv1d(4 * b, 4 * b, 3, padding=1), nn.GroupNorm(4, 4 * b), nn.GELU(),
+                nn.ConvTranspose1d(4 * b, 2 * b, 2, stride=2), nn.Conv1d(2 * b, 2 * b, 3, padding=1), nn.GroupNorm(4, 2 * b), nn.GELU(),
+                nn.ConvTranspose1d(2 * b, b, 2, stride=2), nn.Conv1d(b, b, 3, padding=1))
+        self.upsampleProjOnly = upsampleProjOnly
+        self.posEmbedBuilderAttnTF = LearnableSpatialPositionEmbedding(4 * b, coordDim=2, gamma=posEmbedInitGamma, dropoutProb=dropoutProb)
+        self.posEmbedBuilderAttnTE = LearnableSpatialPositionEmbedding(4 * b, coordDim=2, gamma=posEmbedInitGamma, dropoutProb=dropoutProb)
+        self.encoderLayers = nn.ModuleList([
+            BasicBlock(inputSize=4 * b, num_heads=nHead, fourierSize=fourierSize, dropoutProb=dropoutProb, hiddenFactor=hiddenFactor,
+                       hiddenFactorAttn=hiddenFactorAttn, enabled=enabledAttn) for _ in range(nLayers)])
+        self.normEncoder = nn.Identity()
+        self.useGradientCheckpoint = useGradientCheckpoint
+        self.dropout = nn.Dropout(dropoutProb)
+
+    @property
+    def attention(self):
+        routes = {m.attention for m in self.modules() if isinstance(m, MultiHeadAttentionKernel)}
+        return routes.pop() if len(routes) == 1 else "mixed"
+
+    @attention.setter
+    def attention(self, route):
+        if route not in ROUTES:
+            raise ValueError(f"attention must be one of {ROUTES}, not {route!r}")
+        for m in self.modules():
+            if isinstance(m, MultiHeadAttentionKernel):
+                m.attention = route
+
+    def tokens(self, x, outputIndices):
+        """The input of the first layer: [N, T', F' + P, 4 baseSize], the spectrogram tokens followed by the target tokens."""
+        x = x.permute(0, 3, 1, 2)                                 # [N, C, T, F]
+        dev, dt = x.device, x.dtype
+        posF = self.posEmbedBuilder(torch.arange(x.shape[-1], device=dev).to(dt))             # [F, baseSize]
+        h = self.downConv(self.inputConv(x) + posF.transpose(-1, -2).unsqueeze(-2))
+        h = F.pad(h.permute(0, 2, 3, 1), (0, 0, 1, 0, 1, 0))      # [N, T', F', D]: one aggregation track in front of each axis
+        coordT = torch.arange(h.shape[-3], device=dev).to(dt)
+        coordF = torch.arange(h.shape[-2], device=dev).to(dt)
+        h = h + self.posEmbedBuilderAttnTF(coordT, coordF)
+        target = self.posEmbedBuilderAttnTE(coordT, outputIndices.to(dt))
+        return torch.cat([h, target.unsqueeze(0).repeat(h.shape[0], 1, 1, 1)], dim=-2), target.shape[-2]
+
+    def forward(self, x, outputIndices):
+        nT = x.shape[1]
+        hAll, nTarget = self.tokens(x, outputIndices)
+        checkpointed = self.useGradientCheckpoint or self.training
+        for layer in self.encoderLayers:
+            hAll = torch.utils.checkpoint.checkpoint(layer, hAll, use_reentrant=False) if checkpointed else layer(hAll)
+        hTarget = hAll[..., hAll.shape[-2] - nTarget:, :]
+        hTarget = hTarget[..., 1:, :, :].permute(0, 2, 3, 1).flatten(0, 1)        # [N P, D, T' - 1]: without the time aggregation track
+        up = self.upConv1dSkip(hTarget)
+        if not self.upsampleProjOnly:
+            up = self.upConv1d(hTarget) + up
+        return up.unflatten(0, (x.shape[0], nTarget))[..., :nT].permute(0, 1, 3, 2)          # [N, P, T, D]

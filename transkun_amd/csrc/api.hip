@@ -7,6 +7,7 @@
 #include <mutex>
 #include <unordered_map>
 #include "common.h"
+#include "attention_math.h"
 
 namespace semicrf {
 
@@ -77,6 +78,8 @@ void launch_attr_decode(const float* logitsVelocity, const float* ofLogits, int 
 void launch_attr_loss_bwd(const float* gout, int gstride, const float* logitsVelocity, const float* ofLogits, const int* velocity,
                           const float* ofRefined, const float* ofPresence, int K, const int* offsets, int C, float* dLogitsVelocity,
                           float* dOfLogits, hipStream_t stream);
+void launch_axial_attention(const float* q, const float* k, const float* v, float* out, long long n0, long long n1, int Lq, int Lk, int H, int d,
+                            const long long* strides, hipStream_t stream);
 void launch_grad_sqnorm(const float* flat, long long numel, double* partials, hipStream_t stream);
 void launch_clip_from_history(const double* partials, long long numel, const float* norm_in, double q, float* ring, int capacity,
                               int* state, int append, float* stats, hipStream_t stream);
@@ -1389,6 +1392,33 @@ int semicrf_adabelief_step(float* p, const float* g, float* m, float* s, int64_t
     SEMICRF_CHECK_ARG(last == numel, "the last group ends at %lld, not at numel=%lld", (long long)last, (long long)numel);
     launch_adabelief_step(p, g, m, s, numel, coef, groups, (hipStream_t)stream);
     SEMICRF_CHECK_LAUNCH("semicrf_adabelief_step");
+    return SEMICRF_OK;
+}
+
+int semicrf_axial_attention_supported(int Lq, int Lk, int H, int d) { return attention::supported(Lq, Lk, H, d) ? 1 : 0; }
+
+int semicrf_axial_attention(const float* q, const float* k, const float* v, float* out, int64_t n0, int64_t n1, int Lq, int Lk, int H, int d,
+                            int64_t q_stride_s0, int64_t q_stride_s1, int64_t q_stride_l, int64_t k_stride_s0, int64_t k_stride_s1,
+                            int64_t k_stride_l, int64_t v_stride_s0, int64_t v_stride_s1, int64_t v_stride_l, int64_t out_stride_s0,
+                            int64_t out_stride_s1, int64_t out_stride_l, semicrf_stream_t stream)
+{
+    SEMICRF_CHECK_ARG(attention::supported(Lq, Lk, H, d),
+                      "axial_attention: Lq=%d Lk=%d H=%d d=%d is outside the supported set (1 <= Lq, Lk <= %d; d a multiple of 8 in [%d, %d]; "
+                      "H >= 1): see semicrf_axial_attention_supported", Lq, Lk, H, d, attention::ATT_MAX_L, attention::ATT_MIN_D,
+                      attention::ATT_MAX_D);
+    SEMICRF_CHECK_ARG(n0 >= 0 && n1 >= 0, "axial_attention: n0=%lld n1=%lld must be >= 0", (long long)n0, (long long)n1);
+    if (n0 == 0 || n1 == 0) return SEMICRF_OK;
+    SEMICRF_CHECK_ARG(n0 < (1ll << 31) && n1 < (1ll << 31) && n0 * n1 * H < (1ll << 31),
+                      "axial_attention: n0 * n1 * H = %lld * %lld * %d must stay below 2^31", (long long)n0, (long long)n1, H);
+    SEMICRF_CHECK_ARG(q && k && v && out, "axial_attention: q/k/v/out must be non-NULL");
+    SEMICRF_CHECK_ARG((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)out) & 3) == 0, "axial_attention: q/k/v/out must be 4-byte aligned");
+    const long long strides[12] = {q_stride_s0, q_stride_s1, q_stride_l, k_stride_s0, k_stride_s1, k_stride_l,
+                                   v_stride_s0, v_stride_s1, v_stride_l, out_stride_s0, out_stride_s1, out_stride_l};
+    for (int i = 0; i < 12; ++i) SEMICRF_CHECK_ARG(strides[i] >= 0, "axial_attention: stride %d is negative (%lld)", i, strides[i]);
+    for (int i = 2; i < 12; i += 3)
+        SEMICRF_CHECK_ARG(strides[i] < (1ll << 28), "axial_attention: token stride %lld must stay below 2^28 elements", strides[i]);
+    launch_axial_attention(q, k, v, out, n0, n1, Lq, Lk, H, d, strides, (hipStream_t)stream);
+    SEMICRF_CHECK_LAUNCH("semicrf_axial_attention");
     return SEMICRF_OK;
 }
 

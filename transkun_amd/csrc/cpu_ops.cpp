@@ -20,6 +20,7 @@
 #include "optim_math.h"
 #include "attr_decode_math.h"
 #include "attr_heads_math.h"
+#include "attention_math.h"
 #include "cpu_ops.h"
 
 namespace semicrf_cpu {
@@ -1402,6 +1403,56 @@ void adabelief_step(float* p, const float* g, float* m, float* s, int64_t numel,
         const semicrf_adabelief_group k = groups.g[gi];
 #pragma omp parallel for schedule(static) if (hi - lo > 65536)
         for (int64_t i = lo; i < hi; ++i) semicrf::optim::adabelief_update(p[i], g[i], m[i], s[i], coef, k);
+    }
+}
+
+// ---- the backbone's axial attention (semicrf_axial_attention; LayersTransformer.py:173-186) ------------------------------------------
+// The order of operations of attention.hip per output element, in fp32 (attention_math.h): the chain of q . k over the head dimension
+// ascending from +0 (fmaf), * scale, the maximum over the keys below Lk, exp of the difference, the sum as S0 + S1 (the keys of each
+// half wave ascending), the chain of P V over the keys ascending from +0, / sum.  Only the exponential differs from the device's.
+void axial_attention(const float* q, const float* k, const float* v, float* out, int64_t n0, int64_t n1, int Lq, int Lk, int H, int d,
+                     const int64_t* st)
+{
+    using namespace semicrf::attention;
+    const float scale = scale_of(d);
+    const int64_t nwork = n0 * n1 * H;
+#pragma omp parallel
+    {
+        std::vector<float> p((size_t)Lk), acc((size_t)d);
+#pragma omp for schedule(static)
+        for (int64_t w = 0; w < nwork; ++w) {
+            const int h = (int)(w % H);
+            const int64_t s = w / H, s0 = s / n1, s1 = s % n1;
+            const float* qb = q + s0 * st[0] + s1 * st[1] + (int64_t)h * d;
+            const float* kb = k + s0 * st[3] + s1 * st[4] + (int64_t)h * d;
+            const float* vb = v + s0 * st[6] + s1 * st[7] + (int64_t)h * d;
+            float* ob = out + s0 * st[9] + s1 * st[10] + (int64_t)h * d;
+            for (int i = 0; i < Lq; ++i) {
+                const float* qi = qb + (int64_t)i * st[2];
+                float mx = -std::numeric_limits<float>::infinity();
+                for (int j = 0; j < Lk; ++j) {
+                    const float* kj = kb + (int64_t)j * st[5];
+                    float t = 0.0f;
+                    for (int c = 0; c < d; ++c) t = fmaf(kj[c], qi[c], t);
+                    p[j] = t * scale;
+                    mx = std::max(mx, p[j]);
+                }
+                float half[2] = {0.0f, 0.0f};
+                for (int j = 0; j < Lk; ++j) {
+                    p[j] = expf(p[j] - mx);
+                    half[sum_half(j)] += p[j];
+                }
+                const float sum = half[0] + half[1];
+                std::fill(acc.begin(), acc.end(), 0.0f);
+                for (int j = 0; j < Lk; ++j) {
+                    const float* vj = vb + (int64_t)j * st[8];
+                    const float pj = p[j];
+                    for (int c = 0; c < d; ++c) acc[c] = fmaf(pj, vj[c], acc[c]);
+                }
+                float* oi = ob + (int64_t)i * st[11];
+                for (int c = 0; c < d; ++c) oi[c] = acc[c] / sum;
+            }
+        }
     }
 }
 

@@ -70,4 +70,8 @@ void clip_from_history(const double* partials /* or null */, int64_t numel, cons
                        int capacity, int32_t* state, int append, float* stats);
 void adabelief_step(float* p, const float* g, float* m, float* s, int64_t numel, const float* coef /* or null: 1 */,
                     const semicrf_adabelief_groups& groups);
+// the backbone's axial attention (semicrf_axial_attention): the device kernel's order of operations per output element, in fp32
+// (attention_math.h); strides: the twelve element strides q, k, v, out x (s0, s1, l); the caller has checked the supported set
+void axial_attention(const float* q, const float* k, const float* v, float* out, int64_t n0, int64_t n1, int Lq, int Lk, int H, int d,
+                     const int64_t* strides);
 }  // namespace semicrf_cpu

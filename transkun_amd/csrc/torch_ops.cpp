@@ -1036,6 +1036,57 @@ void attribute_heads_cpu(Tensor ctx, int64_t C, int64_t T, int64_t D, int64_t ld
                                  (int)Nv, (int)No, a.lv, a.of, a.sym, a.sc);
 }
 
+// ---- the backbone's axial attention (semicrf_axial_attention) ----------------------------------------------------------------------
+// q, out: [n0, n1, Lq, H d]; k, v: [n0, n1, Lk, H d]: VIEWS -- the three element strides of every tensor are read from the tensor
+// itself (so an access can never leave it); only the last dimension must be contiguous.  Sizes of 1 may carry any stride.
+struct AttentionArgs { const float *q, *k, *v; float* out; int64_t n0, n1; int Lq, Lk, H, d; int64_t st[12]; };
+inline AttentionArgs attention_args(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& out, int64_t H)
+{
+    const Tensor* ts[4] = {&q, &k, &v, &out};
+    const char* names[4] = {"q", "k", "v", "out"};
+    AttentionArgs a{};
+    STD_TORCH_CHECK(q.defined() && q.dim() == 4, "semicrf: `q` must be [n0, n1, Lq, H * d]");
+    a.n0 = q.size(0); a.n1 = q.size(1);
+    const int64_t Lq = q.size(2), Lk = k.defined() && k.dim() == 4 ? k.size(2) : -1, HD = q.size(3);
+    STD_TORCH_CHECK(H >= 1 && H < (1 << 20) && HD % H == 0, "semicrf: the last dimension must be H * d");
+    for (int i = 0; i < 4; ++i) {
+        const Tensor& t = *ts[i];
+        STD_TORCH_CHECK(t.defined() && t.scalar_type() == ScalarType::Float && t.dim() == 4, "semicrf: `", names[i], "` must be a 4-d float32 tensor");
+        STD_TORCH_CHECK(t.size(0) == a.n0 && t.size(1) == a.n1 && t.size(3) == HD && t.size(2) == (i == 0 || i == 3 ? Lq : Lk),
+                        "semicrf: `", names[i], "` does not have the shape of the call");
+        STD_TORCH_CHECK(HD == 1 || t.stride(3) == 1, "semicrf: `", names[i], "` must have a contiguous last dimension");
+        for (int j = 0; j < 3; ++j) {
+            const int64_t s = t.size(j) > 1 ? t.stride(j) : 0;
+            STD_TORCH_CHECK(s >= 0, "semicrf: negative stride");
+            a.st[3 * i + j] = s;
+        }
+    }
+    for (int j = 0; j < 3; ++j) STD_TORCH_CHECK(out.size(j) == 1 || a.st[9 + j] > 0, "semicrf: `out` must not repeat over a dimension");
+    STD_TORCH_CHECK(Lq < (1 << 20) && Lk < (1 << 20), "semicrf: sequence too long");
+    a.Lq = (int)Lq; a.Lk = (int)Lk; a.H = (int)H; a.d = (int)(HD / H);
+    STD_TORCH_CHECK(semicrf_axial_attention_supported(a.Lq, a.Lk, a.H, a.d),
+                    "semicrf: axial_attention does not support Lq=", Lq, " Lk=", Lk, " H=", H, " d=", HD / H,
+                    " (semicrf_axial_attention_supported)");
+    a.q = f32s(q, "q"); a.k = f32s(k, "k"); a.v = f32s(v, "v"); a.out = f32so(out, "out");
+    return a;
+}
+void axial_attention_op(Tensor q, Tensor k, Tensor v, Tensor out, int64_t H)
+{
+    Ctx c(q); c.same(q, k, v, out);
+    const AttentionArgs a = attention_args(q, k, v, out, H);
+    if (a.n0 == 0 || a.n1 == 0) return;
+    check(semicrf_axial_attention(a.q, a.k, a.v, a.out, a.n0, a.n1, a.Lq, a.Lk, a.H, a.d, a.st[0], a.st[1], a.st[2], a.st[3], a.st[4], a.st[5],
+                                  a.st[6], a.st[7], a.st[8], a.st[9], a.st[10], a.st[11], c.stream),
+          "semicrf_axial_attention");
+}
+void axial_attention_cpu(Tensor q, Tensor k, Tensor v, Tensor out, int64_t H)
+{
+    all_cpu(q, k, v, out);
+    const AttentionArgs a = attention_args(q, k, v, out, H);
+    if (a.n0 == 0 || a.n1 == 0) return;
+    semicrf_cpu::axial_attention(a.q, a.k, a.v, a.out, a.n0, a.n1, a.Lq, a.Lk, a.H, a.d, a.st);
+}
+
 // ---- the attribute heads in training (semicrf_attribute_heads_train_fwd / _bwd / _dropout_mask) -------------------------------------
 // seed: the 64 bits of an int; z [K, Hv + Ho] and the gradients are dense and checked for their element counts
 void attribute_heads_train_fwd_op(Tensor ctx, int64_t C, int64_t T, int64_t D, int64_t ldc, Tensor pairs, int64_t K, Tensor offsets, int64_t nSym,
@@ -1240,6 +1291,7 @@ STABLE_TORCH_LIBRARY(semicrf, m)
           "int K, Tensor offsets, Tensor W1, Tensor W2, int Hv, int Ho, int Nv, int No, int seed, float pv, float po, Tensor(a!) dctx, "
           "Tensor(b!) dW1, Tensor(c!) db1, Tensor(d!) dW2, Tensor(e!) db2, Tensor(f!) ws) -> ()");
     m.def("attribute_heads_dropout_mask(Tensor(a!) mask, int seed, int K, int Hv, int Ho, float pv, float po) -> ()");
+    m.def("axial_attention(Tensor q, Tensor k, Tensor v, Tensor(a!) out, int H) -> ()");
     m.def("grad_sqnorm(Tensor flat, int numel, Tensor(a!) partials) -> ()");
     m.def("clip_from_history(Tensor partials, bool has_partials, int numel, Tensor norm_in, bool has_norm, float q, Tensor(a!) ring, "
           "int capacity, Tensor(b!) state, bool append, Tensor(c!) stats) -> ()");
@@ -1279,6 +1331,7 @@ STABLE_TORCH_LIBRARY_IMPL(semicrf, CPU, m)
     m.impl("attribute_heads_train_fwd", TORCH_BOX(&attribute_heads_train_fwd_cpu));
     m.impl("attribute_heads_bwd", TORCH_BOX(&attribute_heads_bwd_cpu));
     m.impl("attribute_heads_dropout_mask", TORCH_BOX(&attribute_heads_dropout_mask_cpu));
+    m.impl("axial_attention", TORCH_BOX(&axial_attention_cpu));
     m.impl("grad_sqnorm", TORCH_BOX(&grad_sqnorm_cpu));
     m.impl("clip_from_history", TORCH_BOX(&clip_from_history_cpu));
     m.impl("adabelief_step", TORCH_BOX(&adabelief_step_cpu));
@@ -1325,6 +1378,7 @@ STABLE_TORCH_LIBRARY_IMPL(semicrf, CUDA, m)
     m.impl("attribute_heads_train_fwd", TORCH_BOX(&attribute_heads_train_fwd_op));
     m.impl("attribute_heads_bwd", TORCH_BOX(&attribute_heads_bwd_op));
     m.impl("attribute_heads_dropout_mask", TORCH_BOX(&attribute_heads_dropout_mask_op));
+    m.impl("axial_attention", TORCH_BOX(&axial_attention_op));
     m.impl("grad_sqnorm", TORCH_BOX(&grad_sqnorm_op));
     m.impl("clip_from_history", TORCH_BOX(&clip_from_history_op));
     m.impl("adabelief_step", TORCH_BOX(&adabelief_step_op));
