@@ -87,7 +87,7 @@ def run_op(dev, c, seed=None, train=True):
     from transkun_amd import attributes
     vp, op = copy.deepcopy(c["vp"]).to(dev), copy.deepcopy(c["op"]).to(dev)
     vp.train(train); op.train(train)
-    ctx = c["ctx"].to(dev).requires_grad_()
+    ctx = c["ctx"].detach().to(dev).requires_grad_()            # a leaf of its own: the cached case stays as it is
     lv, of, sym, sc = attributes.attribute_heads_train(ctx, c["pairs"].to(dev), c["offsets"].to(dev), vp, op, c["K"],
                                                        seed=c["seed"] if seed is None else seed)
     grads = torch.autograd.grad([lv, of], [ctx] + params_of(vp, op), [c["dlv"].to(dev), c["dof"].to(dev)])

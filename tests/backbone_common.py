@@ -30,6 +30,20 @@ HEAD_CASES = [(L, H, d) for L in (33, 149) for d in (8, 16, 24, 64) for H in (1,
 CROSS = [(1, 149), (149, 1), (65, 33), (89, 149)]                     # (Lq, Lk)
 BATCHES = [((1,), 33), ((3,), 33), ((7, 10), 33), ((7, 10), 89)]      # (leading shape, L): 1, 3 and 70 = 7 x 10 sequences
 
+# every instantiation <NKT = ceil(Lk / 32), DB = 1 (d <= 32) | 2, VEC> of the kernel: both edges of every key tile at every head
+# dimension, H = 2, three sequences, both SCALES, on aligned tensors (VEC) and with q and k one float off 16 bytes (4-byte loads)
+MATRIX_D = [8, 16, 24, 32, 40, 48, 56, 64]
+MATRIX_LK = [1, 32, 33, 64, 65, 96, 97, 128, 129, 160, 161, 192, 193, 224, 225, 256]
+MATRIX_LQ = 33                                                        # a full query tile on wave 0, a one-row tile on wave 1
+MATRIX_H = 2
+# the second query pass of a wave (Lq > 128) and partial query tiles at NKT = 4, 6, 7, 8; H = 2, three sequences, scale 1
+PASSES = [(Lq, Lk, d) for Lq in (1, 127, 128, 129, 160, 256) for Lk in (100, 180, 210, 256) for d in (32, 64)]
+LARGEST = (256, 256, 4, 64, (3,))                                     # (Lq, Lk, H, d, leading shape): 100 KB of LDS, the most registers
+CORESIDENT = (149, 149, 8, 64, (7, 10))                               # 560 workgroups of 75 KB of LDS: two of them share a CU
+HEAD_COUNTS = [(40, 70, 64, 8), (40, 70, 1, 64)]                      # (Lq, Lk, H, d): many heads, one head
+CONTRACT = (65, 97, 2, 24, (3,))                                      # the strided contract's shape: NKT = 4, DB = 1
+TOKEN_STRIDE_LIMIT = 1 << 28                                          # elements: the C entry point takes token strides below it
+
 
 def split_heads(t, H):
     return t.unflatten(-1, (H, t.shape[-1] // H)).transpose(-2, -3)
@@ -94,6 +108,19 @@ def raw_op(q4, k4, v4, o4, H):
 
 def bits_equal(a, b):
     return a.shape == b.shape and torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
+
+
+def one_float_off(x):
+    """The values of x in a view one float off a 16-byte boundary (rows of one float more than x's): the construction of
+    _check_strided_views."""
+    view = torch.cat([torch.zeros(*x.shape[:-1], 1, dtype=x.dtype, device=x.device), x], dim=-1)[..., 1:]
+    assert view.data_ptr() % 16 != 0 and view.data_ptr() % 4 == 0
+    return view
+
+
+def same_bits_mask(a, b):
+    """Elementwise: the same 32 bits (NaN payloads included)."""
+    return a.contiguous().view(torch.int32) == b.contiguous().view(torch.int32)
 
 
 # ---- the fixtures -------------------------------------------------------------------------------------------------------------------

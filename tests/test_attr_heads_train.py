@@ -248,7 +248,7 @@ def _check_views(dev):
     # a Linear without a bias gets no gradient; the others' gradients do not change
     vpn = copy.deepcopy(vp)
     vpn[0].bias = None
-    ctx = c["ctx"].to(dev).requires_grad_()
+    ctx = c["ctx"].detach().to(dev).requires_grad_()            # a leaf of its own: the cached case stays as it is
     lv4, of4, _, _ = A.attribute_heads_train(ctx, pairs, offsets, vpn, op, K, seed=c["seed"])
     (lv4 * dlv).sum().add((of4 * dof).sum()).backward()
     assert vpn[0].bias is None and vpn[0].weight.grad is not None and vpn[-1].bias.grad is not None and ctx.grad is not None
@@ -257,7 +257,7 @@ def _check_views(dev):
     with pytest.raises(TypeError, match="float32"):
         A.attribute_heads_train(ctx, pairs, offsets, copy.deepcopy(vp).bfloat16(), op, K, seed=1)
     # double backward
-    ctx = c["ctx"].to(dev).requires_grad_()
+    ctx = c["ctx"].detach().to(dev).requires_grad_()            # a leaf of its own: the cached case stays as it is
     lv5, of5, _, _ = A.attribute_heads_train(ctx, pairs, offsets, vp, op, K, seed=c["seed"])
     (g5,) = torch.autograd.grad([lv5, of5], [ctx], [dlv, dof], create_graph=True)
     with pytest.raises(RuntimeError):

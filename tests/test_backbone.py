@@ -1,6 +1,8 @@
 """The backbone and its axial attention: transkun_amd.backbone (csrc/attention.hip on the GPU, the host mirror of csrc/cpu_ops.cpp on
-CPU tensors) -- the op against float64 at the tile edges and the model's lengths, its strided contract, padding, determinism and
-argument checks, the fall-backs of backbone.axial_attention, and the modules against the reference's fixtures.
+CPU tensors) -- the op against float64 at the tile edges and the model's lengths, in every instantiation <key tiles, output blocks,
+16- or 4-byte loads> of the kernel and at the limits of its LDS and register budget, its strided contract (stride 0, misalignment,
+non-finite values, the token-stride limit), padding, determinism and argument checks, the fall-backs of backbone.axial_attention,
+and the modules against the reference's fixtures.
 
 Every numerical case runs on the CPU path (unmarked) and on the device (marked gpu).  Yardsticks and gates: backbone_common.
 Measured numbers: DESIGN.md section 3, "Backbone attention", and profiles/attention_bench.json."""
@@ -135,6 +137,121 @@ def test_op_model_shape_gpu(gpu):
         assert e <= c["gate"], (tag, e, c["e32"])
 
 
+# ---- 1b. every instantiation <NKT, DB, VEC> of the kernel, and the limits of its budget -----------------------------------------------
+def _gated(got, c, tag):
+    """got against the case's float64 truth under the case's own gate; returns error / gate."""
+    assert got.shape == c["truth"].shape and got.dtype == torch.float32, tag
+    assert bool(torch.isfinite(got).all()), tag
+    e = float((got.cpu().double() - c["truth"]).abs().max())
+    print(f"axial_attention [{got.device.type}] {tag}: error {e:.3e}  torch fp32 {c['e32']:.3e}  gate {c['gate']:.3e}  "
+          f"error/gate {e / c['gate']:.3f}")
+    assert e <= c["gate"], (tag, e, c["e32"], c["gate"])
+    return e / c["gate"]
+
+
+def _matrix(dev, d, Lk, aligned):
+    """NKT = ceil(Lk / 32), DB = 1 (d <= 32) or 2, VEC = aligned.  The misaligned form (q and k one float off a 16-byte boundary: the
+    4-byte loads) is gated like the aligned one and must give its bits."""
+    Lq, H = common.MATRIX_LQ, common.MATRIX_H
+    for scale in common.SCALES:
+        c = common.op_case(Lq, Lk, H, d, (3,), scale)
+        q, k, v = (c[n].to(dev) for n in "qkv")
+        assert q.data_ptr() % 16 == 0 and k.data_ptr() % 16 == 0 and q.stride(-2) % 4 == 0 and k.stride(-2) % 4 == 0
+        tag = f"Lq={Lq} Lk={Lk} H={H} d={d} scale={scale:g} "
+        want = common.fused(q, k, v, H)
+        if aligned:
+            _gated(want, c, tag + "aligned")
+        else:
+            got = common.fused(common.one_float_off(q), common.one_float_off(k), v, H)
+            _gated(got, c, tag + "q, k one float off 16 bytes")
+            assert common.bits_equal(got, want), tag + "q, k one float off 16 bytes: not the bits of the aligned call"
+
+
+def _passes(dev, Lq, Lk, d):
+    c = common.op_case(Lq, Lk, 2, d, (3,), 1.0)
+    _gated(common.fused(c["q"].to(dev), c["k"].to(dev), c["v"].to(dev), 2), c, f"Lq={Lq} Lk={Lk} H=2 d={d} scale=1")
+
+
+def _largest(dev, scale):
+    Lq, Lk, H, d, lead = common.LARGEST
+    c = common.op_case(Lq, Lk, H, d, lead, scale)
+    _gated(common.fused(c["q"].to(dev), c["k"].to(dev), c["v"].to(dev), H), c, f"Lq={Lq} Lk={Lk} H={H} d={d} scale={scale:g}")
+
+
+def _coresident(dev):
+    """70 sequences x 8 heads = 560 workgroups, each with 75 KB of LDS (NKT = 5, d = 64, two per CU): against float64, and sequence 0
+    computed alone gives the bits of its slice of the full result."""
+    Lq, Lk, H, d, lead = common.CORESIDENT
+    c = common.op_case(Lq, Lk, H, d, lead, 1.0)
+    q, k, v = (c[n].to(dev) for n in "qkv")
+    full = common.fused(q, k, v, H)
+    _gated(full, c, f"Lq={Lq} Lk={Lk} H={H} d={d} sequences={lead}")
+    alone = common.fused(q[0, :1], k[0, :1], v[0, :1], H)
+    assert common.bits_equal(alone, full[0, :1])
+
+
+def _head_counts(dev, Lq, Lk, H, d):
+    c = common.op_case(Lq, Lk, H, d, (3,), 1.0)
+    _gated(common.fused(c["q"].to(dev), c["k"].to(dev), c["v"].to(dev), H), c, f"Lq={Lq} Lk={Lk} H={H} d={d} scale=1")
+
+
+@pytest.mark.parametrize("aligned", [True, False], ids=["aligned", "misaligned"])
+@pytest.mark.parametrize("Lk", common.MATRIX_LK)
+@pytest.mark.parametrize("d", common.MATRIX_D)
+def test_op_instantiation_matrix_cpu(d, Lk, aligned):
+    _matrix(CPU, d, Lk, aligned)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("aligned", [True, False], ids=["aligned", "misaligned"])
+@pytest.mark.parametrize("Lk", common.MATRIX_LK)
+@pytest.mark.parametrize("d", common.MATRIX_D)
+def test_op_instantiation_matrix_gpu(gpu, d, Lk, aligned):
+    _matrix(gpu, d, Lk, aligned)
+
+
+@pytest.mark.parametrize("Lq,Lk,d", common.PASSES)
+def test_op_query_passes_cpu(Lq, Lk, d):
+    _passes(CPU, Lq, Lk, d)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("Lq,Lk,d", common.PASSES)
+def test_op_query_passes_gpu(gpu, Lq, Lk, d):
+    _passes(gpu, Lq, Lk, d)
+
+
+@pytest.mark.parametrize("scale", common.SCALES)
+def test_op_largest_configuration_cpu(scale):
+    _largest(CPU, scale)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("scale", common.SCALES)
+def test_op_largest_configuration_gpu(gpu, scale):
+    _largest(gpu, scale)
+
+
+def test_op_coresident_workgroups_cpu():
+    _coresident(CPU)
+
+
+@pytest.mark.gpu
+def test_op_coresident_workgroups_gpu(gpu):
+    _coresident(gpu)
+
+
+@pytest.mark.parametrize("Lq,Lk,H,d", common.HEAD_COUNTS)
+def test_op_head_counts_cpu(Lq, Lk, H, d):
+    _head_counts(CPU, Lq, Lk, H, d)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("Lq,Lk,H,d", common.HEAD_COUNTS)
+def test_op_head_counts_gpu(gpu, Lq, Lk, H, d):
+    _head_counts(gpu, Lq, Lk, H, d)
+
+
 # ---- 2. layout ------------------------------------------------------------------------------------------------------------------------
 def _check_strided_views(dev):
     """The same values as a contiguous [S, L, H d] and as the time-axis view of a [N, L, S / N, H d] buffer: the same bits; output into
@@ -175,6 +292,121 @@ def test_strided_views_cpu():
 @pytest.mark.gpu
 def test_strided_views_gpu(gpu):
     _check_strided_views(gpu)
+
+
+def _contract_case(dev):
+    Lq, Lk, H, d, lead = common.CONTRACT
+    c = common.op_case(Lq, Lk, H, d, lead, 1.0)
+    return c, H, d, tuple(c[n].to(dev) for n in "qkv")
+
+
+def _check_stride_zero(dev):
+    """k and v, then q, expanded over the sequence dimension (stride 0): the bits of their contiguous copies, which pass the gate."""
+    c, H, d, (q, k, v) = _contract_case(dev)
+    k0, v0 = k[:1].expand(3, -1, -1), v[:1].expand(3, -1, -1)
+    assert k0.stride(0) == 0 and v0.stride(0) == 0
+    want = common.fused(q, k0.contiguous(), v0.contiguous(), H)
+    _gated(want, common.finish_case(c["q"], c["k"][:1].expand(3, -1, -1).contiguous(), c["v"][:1].expand(3, -1, -1).contiguous(), H),
+           "k, v of sequence 0 for all sequences")
+    assert common.bits_equal(common.fused(q, k0, v0, H), want)
+    q0 = q[:1].expand(3, -1, -1)
+    assert q0.stride(0) == 0
+    got = common.fused(q0, k, v, H)
+    assert got.shape == q.shape and got.is_contiguous() and got.device == q.device      # a dense tensor, not a repeated view
+    assert common.bits_equal(got, common.fused(q0.contiguous(), k, v, H))
+    assert common.bits_equal(got[0], common.fused(q, k, v, H)[0])
+
+
+def test_stride_zero_cpu():
+    _check_stride_zero(CPU)
+
+
+@pytest.mark.gpu
+def test_stride_zero_gpu(gpu):
+    _check_stride_zero(gpu)
+
+
+def _check_alignment_conditions(dev):
+    """Each tensor one float off a 16-byte boundary, and an odd token stride from an aligned base, one condition at a time: the bits
+    of the aligned call."""
+    c, H, d, (q, k, v) = _contract_case(dev)
+    S, Lq, Lk, HD = q.shape[0], q.shape[1], k.shape[1], H * d
+    want = common.fused(q, k, v, H)
+    _gated(want, c, "aligned")
+    assert common.bits_equal(common.fused(q, k, common.one_float_off(v), H), want), "v one float off 16 bytes"
+    assert common.bits_equal(common.fused(common.one_float_off(q), k, v, H), want), "q one float off 16 bytes"
+    assert common.bits_equal(common.fused(q, common.one_float_off(k), v, H), want), "k one float off 16 bytes"
+    # the raw op writing into a view one float off 16 bytes
+    big = torch.full((S, Lq, HD + 1), -7.0, device=dev)
+    o = big[..., 1:]
+    assert o.data_ptr() % 16 != 0
+    common.raw_op(q.unsqueeze(0), k.unsqueeze(0), v.unsqueeze(0), o.unsqueeze(0), H)
+    assert common.bits_equal(o, want), "out one float off 16 bytes"
+    assert bool((big[..., 0] == -7.0).all())
+    # an odd token stride (a parent of width H d + 1) from an aligned base
+    for name in "kq":
+        x = {"q": q, "k": k}[name]
+        parent = torch.zeros(*x.shape[:-1], HD + 1, device=dev)
+        parent[..., :HD] = x
+        view = parent[..., :HD]
+        assert view.data_ptr() % 16 == 0 and view.stride(-2) == HD + 1
+        got = common.fused(view, k, v, H) if name == "q" else common.fused(q, view, v, H)
+        assert common.bits_equal(got, want), f"{name} with token stride H d + 1"
+
+
+def test_alignment_conditions_cpu():
+    _check_alignment_conditions(CPU)
+
+
+@pytest.mark.gpu
+def test_alignment_conditions_gpu(gpu):
+    _check_alignment_conditions(gpu)
+
+
+def _check_non_finite_stay_put(dev):
+    """A NaN in k, a NaN in q and a +inf in v reach the outputs they belong to and no other: everything else keeps the clean run's bits."""
+    from transkun_amd import backbone
+    c, H, d, (q, k, v) = _contract_case(dev)
+    clean = common.fused(q, k, v, H)
+    assert bool(torch.isfinite(clean).all())
+    head1 = slice(d, 2 * d)
+    # k at (sequence 1, key 5, head 1): every query of that sequence and head
+    kn = k.clone()
+    kn[1, 5, head1] = float("nan")
+    got = common.fused(q, kn, v, H)
+    hit = torch.zeros_like(clean, dtype=torch.bool)
+    hit[1, :, head1] = True
+    assert torch.equal(torch.isnan(got), hit), "NaN in k"
+    assert bool(common.same_bits_mask(got, clean)[~hit].all()), "NaN in k"
+    # q at (sequence 2, query 7, one column of head 0): that row of that head
+    qn = q.clone()
+    qn[2, 7, 3] = float("nan")
+    got = common.fused(qn, k, v, H)
+    hit = torch.zeros_like(clean, dtype=torch.bool)
+    hit[2, 7, :d] = True
+    assert torch.equal(torch.isnan(got), hit), "NaN in q"
+    assert bool(common.same_bits_mask(got, clean)[~hit].all()), "NaN in q"
+    # one +inf in v: the inf / NaN pattern of the stock fp32 route on identical inputs
+    vi = v.clone()
+    vi[0, 11, d + 2] = float("inf")
+    got = common.fused(q, k, vi, H)
+    with torch.no_grad():
+        stock = backbone.attention_torch(q, k, vi, H)
+    assert not bool(torch.isfinite(stock).all())
+    assert torch.equal(torch.isnan(got), torch.isnan(stock)), "+inf in v"
+    assert torch.equal(torch.isposinf(got), torch.isposinf(stock)) and torch.equal(torch.isneginf(got), torch.isneginf(stock)), "+inf in v"
+    hit = torch.zeros_like(clean, dtype=torch.bool)
+    hit[0, :, d + 2] = True                                       # an output column reads its own column of v only
+    assert bool(common.same_bits_mask(got, clean)[~hit].all()), "+inf in v"
+
+
+def test_non_finite_stay_put_cpu():
+    _check_non_finite_stay_put(CPU)
+
+
+@pytest.mark.gpu
+def test_non_finite_stay_put_gpu(gpu):
+    _check_non_finite_stay_put(gpu)
 
 
 def _check_poison(dev):
@@ -291,6 +523,10 @@ def test_unsupported_direct_call_is_rejected():
     assert _direct(lib, fake, fake, fake, fake, 1 << 20, 1 << 12, 8, 8, 1, 8, st) == 1 and b"2^31" in lib.semicrf_last_error()
     bad = list(st); bad[5] = -96
     assert _direct(lib, fake, fake, fake, fake, 1, 1, 8, 8, 1, 8, bad) == 1 and b"negative" in lib.semicrf_last_error()
+    for i, name in ((2, "q"), (5, "k"), (8, "v"), (11, "out")):                      # a token stride of 2^28 elements, one tensor at a time
+        bad = list(st); bad[i] = common.TOKEN_STRIDE_LIMIT
+        assert _direct(lib, fake, fake, fake, fake, 1, 1, 8, 8, 1, 8, bad) == 1, name
+        assert b"2^28" in lib.semicrf_last_error(), name
     assert _direct(lib, fake, fake, fake, fake, 0, 5, 8, 8, 1, 8, st) == 0           # no sequences: nothing to do, nothing launched
     # the torch op checks the same set (and the shapes) before anything runs
     ops = _lib.ops()
@@ -360,6 +596,51 @@ def test_fallbacks_cpu():
 @pytest.mark.gpu
 def test_fallbacks_gpu(gpu):
     _check_fallbacks(gpu)
+
+
+def test_token_stride_limit_is_read_from_the_views():
+    """Which views backbone.axial_attention keeps from the device op: a token stride of 2^28 elements or more at a length above one
+    (meta tensors: no memory behind them)."""
+    from transkun_amd import backbone
+    lim = common.TOKEN_STRIDE_LIMIT
+    assert backbone.ATTENTION_TOKEN_STRIDE_LIMIT == lim
+    buf = torch.empty(2 * lim + 64, device="meta")
+    ok = torch.empty(1, 5, 48, device="meta")
+    for stride, L, fits in ((lim, 2, False), (lim + 4, 2, False), (lim - 4, 2, True), (lim, 1, True), (2 * lim, 1, True)):
+        view = buf.as_strided((1, L, 48), (0, stride, 1))
+        for args in ((view, ok, ok), (ok, view, ok), (ok, ok, view)):
+            assert backbone._token_strides_fit(*args) == fits, (stride, L)
+
+
+def _check_token_stride(gpu, which):
+    """A view whose two tokens lie 2^28 elements apart (1 GiB, of which only the two rows are ever written): outside the device
+    op's reach, so backbone.axial_attention answers by the stock route instead of raising."""
+    from transkun_amd import backbone
+    lim = common.TOKEN_STRIDE_LIMIT
+    g = torch.Generator().manual_seed(2828)
+    Lq, Lk = (2, 5) if which == "q" else (5, 2)
+    host = dict(q=torch.randn(1, Lq, 48, generator=g), k=torch.randn(1, Lk, 48, generator=g), v=torch.randn(1, Lk, 48, generator=g))
+    c = common.finish_case(host["q"], host["k"], host["v"], 2)
+    dev = {n: t.to(gpu) for n, t in host.items()}
+    buf = torch.empty(lim + 64, device=gpu)                       # 1 GiB + 256 B, uninitialised
+    far = buf.as_strided((1, 2, 48), (2 * lim, lim, 1))
+    far.copy_(dev[which])
+    assert far.stride(-2) == lim and torch.equal(far, dev[which])
+    dev[which] = far
+    with pytest.raises(RuntimeError, match=r"2\^28"):             # the op itself turns the view down before it launches anything
+        common.raw_op(dev["q"].unsqueeze(0), dev["k"].unsqueeze(0), dev["v"].unsqueeze(0), torch.empty(1, 1, Lq, 48, device=gpu), 2)
+    with torch.no_grad():
+        got = backbone.axial_attention(dev["q"], dev["k"], dev["v"], 2)
+        assert torch.equal(got, backbone.attention_torch(dev["q"], dev["k"], dev["v"], 2))
+    _gated(got, c, f"token stride 2^28 of {which}")
+    del far, buf, dev
+    torch.cuda.empty_cache()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("which", ["q", "v"])
+def test_token_stride_beyond_the_limit_gpu(gpu, which):
+    _check_token_stride(gpu, which)
 
 
 # ---- 4. the modules against the reference's fixtures ----------------------------------------------------------------------------------

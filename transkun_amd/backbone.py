@@ -14,9 +14,9 @@ csrc/cpu_ops.cpp on the CPU), whose contract is token-major with three strides p
 time-axis half, and none of the copies eager PyTorch makes for the projections and the attention of a transposed tensor.
 
 Forward only: under autograd (gradients enabled and an input requiring grad), for dtypes other than float32, for shapes outside the
-op's supported set and for broadcasting keys, `axial_attention` takes the stock route -- `F.scaled_dot_product_attention` on head-split
-views, exactly the reference's call -- so training works as before.  `attention = "fused" | "torch"` on every attention module, and on
-`Backbone` for all of its layers, picks the route.
+op's supported set, for broadcasting keys and for device views whose tokens lie 2^28 elements apart or more, `axial_attention` takes
+the stock route -- `F.scaled_dot_product_attention` on head-split views, exactly the reference's call -- so training works as before.
+`attention = "fused" | "torch"` on every attention module, and on `Backbone` for all of its layers, picks the route.
 
 Hidden size and head dimension come from the constructor as in the reference: head_dim = ceil(ceil(hiddenFactor * embed_dim) /
 num_heads), hidden size = head_dim * num_heads (the model: embed_dim 160, 4 heads, hiddenFactorAttn 1 -> d = 40).
@@ -74,6 +74,14 @@ def _as_sequences(t: torch.Tensor, split: int):
     return torch.as_strided(t, (a[0], b[0], t.shape[-2], t.shape[-1]), (a[1], b[1], t.stride(-2), 1), t.storage_offset())
 
 
+ATTENTION_TOKEN_STRIDE_LIMIT = 1 << 28                          # elements: semicrf_axial_attention takes token strides below it
+
+
+def _token_strides_fit(*tensors) -> bool:
+    """Every tensor's token stride is below the device op's limit (the stride of a single token counts for nothing)."""
+    return all(t.shape[-2] <= 1 or t.stride(-2) < ATTENTION_TOKEN_STRIDE_LIMIT for t in tensors)
+
+
 def _fused_applies(q, k, v, num_heads) -> bool:
     if not (q.dtype == k.dtype == v.dtype == torch.float32) or not (q.device == k.device == v.device):
         return False
@@ -83,6 +91,8 @@ def _fused_applies(q, k, v, num_heads) -> bool:
         return False                                            # broadcasting batch dimensions: the stock route
     if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad):
         return False                                            # forward only
+    if q.device.type == "cuda" and not _token_strides_fit(q, k, v):
+        return False                                            # tokens 2^28 elements apart or more: outside the device op's addressing
     return attention_supported(q.shape[-2], k.shape[-2], num_heads, q.shape[-1] // num_heads)
 
 
@@ -93,8 +103,9 @@ def axial_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, num_heads
     out in memory like q (so the result of a transposed view transposes back into a contiguous tensor).
 
     route = "fused": the HIP op (the host kernel for CPU tensors) whenever it applies; the stock route (attention_torch) when the
-    shape is outside the supported set, the dtype is not float32, k / v broadcast against q, or gradients are enabled and an input
-    requires grad.  route = "torch": always the stock route.  Always usable, always differentiable."""
+    shape is outside the supported set, the dtype is not float32, k / v broadcast against q, gradients are enabled and an input
+    requires grad, or -- on the device -- q, k or v has more than one token and a token stride of 2^28 elements or more (the kernel
+    forms V addresses from a 32-bit lane offset).  route = "torch": always the stock route.  Always usable, always differentiable."""
     if route not in ROUTES:
         raise ValueError(f"route must be one of {ROUTES}, not {route!r}")
     if route == "torch" or not _fused_applies(q, k, v, num_heads):
