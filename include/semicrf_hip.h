@@ -996,6 +996,37 @@ int semicrf_axial_attention(const float* q, const float* k, const float* v, floa
                             int64_t k_stride_l, int64_t v_stride_s0, int64_t v_stride_s1, int64_t v_stride_l, int64_t out_stride_s0,
                             int64_t out_stride_s1, int64_t out_stride_l, semicrf_stream_t stream);
 
+/*
+ * The backward of semicrf_axial_attention: dq, dk, dv from q, k, v, `out` AS THE FORWARD WROTE IT and the cotangent dout.  Per sequence
+ * and head, scale = (float)(1 / sqrt(d)), sc, m, p and sum recomputed with the forward's own chain (the forward saves nothing):
+ *   P[i][j] = p[i][j] / sum_i     D_i = dout_i . out_i     dP[i][j] = dout_i . v_j     dS[i][j] = P[i][j] (dP[i][j] - D_i)
+ *   dv_j = sum_i P[i][j] dout_i   dq_i = scale sum_j dS[i][j] k_j                      dk_j = scale sum_i dS[i][j] q_i
+ * Layout and strides as in the forward, three ELEMENT strides for each of the eight tensors (q, dout, out, dq: Lq tokens; k, v, dk, dv:
+ * Lk tokens).  Strides of q, k, v are >= 0 (0 repeats); out, dout, dq, dk, dv are real, non-overlapping tensors.  A token stride stays
+ * below 2^28 elements; all offsets are 64-bit.  Any of dq, dk, dv may be NULL: nothing is computed or written for it.
+ *
+ * Supported (semicrf_axial_attention_bwd_supported returns 1): exactly the forward's set -- 1 <= Lq, Lk <= SEMICRF_ATTENTION_MAX_L; d a
+ * multiple of 8 in [8, SEMICRF_ATTENTION_MAX_D]; H >= 1.  n0 n1 H < 2^31.  n0 n1 == 0 launches nothing.
+ *
+ * Exact fp32 on the matrix pipe, one fixed chain per gradient element (csrc/attention_math.h): D_i and dP fmaf chains over the head
+ * dimension ascending from +0; P = p / sum (a division); dS = P * (dP - D_i); dq_i, dk_j, dv_j fmaf chains from +0 over the keys
+ * (queries) in the order bwd_order -- blocks of 32 ascending, inside a block 0, 4, 1, 5, 2, 6, 3, 7, 8, 12, .. -- then one
+ * multiplication by scale for dq and dk.  Rows past Lq / Lk are never read or written, padded keys are masked before the maximum, the
+ * head dimension is padded with zeros in registers only.  One workgroup per (sequence, head) forms all of its dk and dv: no atomics,
+ * and a sequence's gradients are bit-identical from run to run, whatever n0, n1, its position in the batch and the strides are.
+ * One launch on `stream`; no workspace, no synchronisation, no allocation.
+ * SEMICRF_EINVAL, with nothing launched and dq / dk / dv untouched: a shape outside the supported set, a NULL q / k / v / out / dout, a
+ * misaligned pointer, a negative count or stride, a token stride >= 2^28, n0 n1 H >= 2^31.
+ */
+int semicrf_axial_attention_bwd_supported(int Lq, int Lk, int H, int d);
+int semicrf_axial_attention_bwd(const float* q, const float* k, const float* v, const float* out, const float* dout, float* dq, float* dk,
+                                float* dv, int64_t n0, int64_t n1, int Lq, int Lk, int H, int d, int64_t q_stride_s0, int64_t q_stride_s1,
+                                int64_t q_stride_l, int64_t k_stride_s0, int64_t k_stride_s1, int64_t k_stride_l, int64_t v_stride_s0,
+                                int64_t v_stride_s1, int64_t v_stride_l, int64_t out_stride_s0, int64_t out_stride_s1, int64_t out_stride_l,
+                                int64_t dout_stride_s0, int64_t dout_stride_s1, int64_t dout_stride_l, int64_t dq_stride_s0,
+                                int64_t dq_stride_s1, int64_t dq_stride_l, int64_t dk_stride_s0, int64_t dk_stride_s1, int64_t dk_stride_l,
+                                int64_t dv_stride_s0, int64_t dv_stride_s1, int64_t dv_stride_l, semicrf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -138,6 +138,8 @@ _SIGS = {
     "semicrf_adabelief_step": (_i, [_vp, _vp, _vp, _vp, _i64, _vp, AdaBeliefGroups, _vp]),
     "semicrf_axial_attention_supported": (_i, [_i, _i, _i, _i]),
     "semicrf_axial_attention": (_i, [_vp, _vp, _vp, _vp, _i64, _i64, _i, _i, _i, _i] + [_i64] * 12 + [_vp]),
+    "semicrf_axial_attention_bwd_supported": (_i, [_i, _i, _i, _i]),
+    "semicrf_axial_attention_bwd": (_i, [_vp] * 8 + [_i64, _i64, _i, _i, _i, _i] + [_i64] * 24 + [_vp]),
     "interval_score_bwd_ws": (_i, [_vp, _vp, _vp, _i, _i, _i, _i64, _i64, ctypes.c_float, _i, _vp, _vp, _vp, _i64, _i64, _i64, _vp, ctypes.c_size_t, _vp]),
     "interval_score_bwd_workspace_bytes": (ctypes.c_size_t, [_i, _i, _i]),
     "segment_onset_filter": (_i, [_vp, _vp, _i, _i, _vp, _i64, _vp, _vp, _vp]),

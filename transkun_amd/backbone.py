@@ -13,10 +13,15 @@ csrc/cpu_ops.cpp on the CPU), whose contract is token-major with three strides p
 `BasicBlock` keeps the hidden state [N, T', F', D] and contiguous from its input to its output -- no `transpose(-3, -2)` around the
 time-axis half, and none of the copies eager PyTorch makes for the projections and the attention of a transposed tensor.
 
-Forward only: under autograd (gradients enabled and an input requiring grad), for dtypes other than float32, for shapes outside the
-op's supported set, for broadcasting keys and for device views whose tokens lie 2^28 elements apart or more, `axial_attention` takes
-the stock route -- `F.scaled_dot_product_attention` on head-split views, exactly the reference's call -- so training works as before.
-`attention = "fused" | "torch"` on every attention module, and on `Backbone` for all of its layers, picks the route.
+`attention = "fused" | "fused-train" | "torch"` on every attention module, and on `Backbone` for all of its layers, picks the route.
+"fused" (the default) is forward only: under autograd (gradients enabled and an input requiring grad) it takes the stock route --
+`F.scaled_dot_product_attention` on head-split views, exactly the reference's call -- so training works as before, bit for bit.
+"fused-train" is "fused" wherever no gradient is wanted, and under autograd a `torch.autograd.Function` around the same forward op
+whose backward is `torch.ops.semicrf.axial_attention_bwd` (csrc/attention_bwd.hip, the host mirror on the CPU): dq, dk and dv are
+written by strides into tensors laid out like q, k and v, so `BasicBlock` keeps its no-transpose form in training too.  The backward
+recomputes the softmax from q and k and takes `out` as the forward wrote it; nothing else is saved, and a second derivative raises.
+Every route answers by the stock call for dtypes other than float32, for shapes outside the op's supported set, for broadcasting keys
+and for device views whose tokens lie 2^28 elements apart or more.  `ATTENTION_ROUTES` counts which way the calls went.
 
 Hidden size and head dimension come from the constructor as in the reference: head_dim = ceil(ceil(hiddenFactor * embed_dim) /
 num_heads), hidden size = head_dim * num_heads (the model: embed_dim 160, 4 heads, hiddenFactorAttn 1 -> d = 40).
@@ -32,14 +37,22 @@ import torch.utils.checkpoint
 
 from . import _lib
 
-ROUTES = ("fused", "torch")
+ROUTES = ("fused", "fused-train", "torch")
 DEFAULT_ATTENTION = "fused"
+# calls of axial_attention by the way they went ("fused": the forward op alone; "fused-train": the autograd Function; "torch": the stock
+# call) and, under "bwd", the launches of the HIP backward; tests read it
+ATTENTION_ROUTES = {"fused": 0, "fused-train": 0, "torch": 0, "bwd": 0}
 
 
 # ---- the attention ------------------------------------------------------------------------------------------------------------------
 def attention_supported(Lq: int, Lk: int, num_heads: int, head_dim: int) -> bool:
     """semicrf_axial_attention_supported: 1 <= Lq, Lk <= 256, head_dim a multiple of 8 in [8, 64], num_heads >= 1."""
     return bool(_lib.load().semicrf_axial_attention_supported(int(Lq), int(Lk), int(num_heads), int(head_dim)))
+
+
+def attention_bwd_supported(Lq: int, Lk: int, num_heads: int, head_dim: int) -> bool:
+    """semicrf_axial_attention_bwd_supported: the forward's set."""
+    return bool(_lib.load().semicrf_axial_attention_bwd_supported(int(Lq), int(Lk), int(num_heads), int(head_dim)))
 
 
 def attention_torch(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, num_heads: int) -> torch.Tensor:
@@ -82,34 +95,27 @@ def _token_strides_fit(*tensors) -> bool:
     return all(t.shape[-2] <= 1 or t.stride(-2) < ATTENTION_TOKEN_STRIDE_LIMIT for t in tensors)
 
 
-def _fused_applies(q, k, v, num_heads) -> bool:
+def _wants_grad(q, k, v) -> bool:
+    return torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad)
+
+
+def _fused_applies(q, k, v, num_heads, train=False) -> bool:
     if not (q.dtype == k.dtype == v.dtype == torch.float32) or not (q.device == k.device == v.device):
         return False
     if q.device.type not in ("cuda", "cpu") or q.dim() < 2 or k.shape != v.shape or q.numel() == 0 or k.numel() == 0:
         return False
     if k.shape[:-2] != q.shape[:-2] or k.shape[-1] != q.shape[-1] or q.shape[-1] % num_heads != 0:
         return False                                            # broadcasting batch dimensions: the stock route
-    if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad):
+    if not train and _wants_grad(q, k, v):
         return False                                            # forward only
     if q.device.type == "cuda" and not _token_strides_fit(q, k, v):
         return False                                            # tokens 2^28 elements apart or more: outside the device op's addressing
-    return attention_supported(q.shape[-2], k.shape[-2], num_heads, q.shape[-1] // num_heads)
+    dims = (q.shape[-2], k.shape[-2], num_heads, q.shape[-1] // num_heads)
+    return attention_supported(*dims) and (not train or attention_bwd_supported(*dims))
 
 
-def axial_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, num_heads: int, route: str = "fused") -> torch.Tensor:
-    """softmax(q k^T / sqrt(d)) v per head and sequence.  q [..., Lq, H d], k and v [..., Lk, H d], arbitrary strided views whose last
-    dimension is contiguous: the leading dimensions are handed to the op as its two sequence dimensions by strides alone (a tensor
-    whose leading dimensions cannot be expressed that way is made contiguous first, that tensor only).  Returns [..., Lq, H d], laid
-    out in memory like q (so the result of a transposed view transposes back into a contiguous tensor).
-
-    route = "fused": the HIP op (the host kernel for CPU tensors) whenever it applies; the stock route (attention_torch) when the
-    shape is outside the supported set, the dtype is not float32, k / v broadcast against q, gradients are enabled and an input
-    requires grad, or -- on the device -- q, k or v has more than one token and a token stride of 2^28 elements or more (the kernel
-    forms V addresses from a 32-bit lane offset).  route = "torch": always the stock route.  Always usable, always differentiable."""
-    if route not in ROUTES:
-        raise ValueError(f"route must be one of {ROUTES}, not {route!r}")
-    if route == "torch" or not _fused_applies(q, k, v, num_heads):
-        return attention_torch(q, k, v, num_heads)
+def _fused_forward(q, k, v, num_heads):
+    """The forward op on q, k, v as they lie in memory -> (out, split, (q4, k4, v4)): the 4-d views the op was given."""
     nlead = q.dim() - 2
     best = None
     for split in range(nlead + 1):
@@ -127,7 +133,79 @@ def axial_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, num_heads
         out = torch.empty(q.shape, dtype=q.dtype, device=q.device)
         o4 = _as_sequences(out, split)
     _lib.ops().axial_attention(q4, k4, v4, o4, num_heads)
-    return out
+    return out, split, (q4, k4, v4)
+
+
+def _layout_of(t):
+    """(shape, strides) of empty_like(t): t's own layout when t is dense, contiguous otherwise (nothing is allocated)."""
+    e = torch.empty_like(t, device="meta")
+    return tuple(e.shape), tuple(e.stride())
+
+
+def _real_strides(x4) -> bool:
+    return all(n == 1 or s > 0 for n, s in zip(x4.shape[:3], x4.stride()[:3]))
+
+
+class _AxialAttentionTrain(torch.autograd.Function):
+    """The forward op, and axial_attention_bwd as its backward (route "fused-train")."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, num_heads):
+        out, split, (q4, k4, v4) = _fused_forward(q, k, v, num_heads)
+        ctx.save_for_backward(q4, k4, v4, out)
+        ctx.split, ctx.num_heads = split, num_heads
+        ctx.layouts = [_layout_of(t) for t in (q, k, v)]
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout):
+        q4, k4, v4, out = ctx.saved_tensors
+        split = ctx.split
+        o4 = _as_sequences(out, split)
+        g4 = _as_sequences(dout, split)                         # by its strides, under the forward's split
+        if g4 is None or not _real_strides(g4) or (dout.device.type == "cuda" and not _token_strides_fit(g4)):
+            g4 = _as_sequences(dout.contiguous(), split)
+        grads, grads4 = [], []
+        for need, (shape, strides) in zip(ctx.needs_input_grad[:3], ctx.layouts):
+            g = x4 = None
+            if need:
+                g = torch.empty_strided(shape, strides, dtype=dout.dtype, device=dout.device)
+                x4 = _as_sequences(g, split)
+                if x4 is None:
+                    g = torch.empty(shape, dtype=dout.dtype, device=dout.device)
+                    x4 = _as_sequences(g, split)
+            grads.append(g)
+            grads4.append(x4)
+        _lib.ops().axial_attention_bwd(q4, k4, v4, o4, g4, grads4[0], grads4[1], grads4[2], ctx.num_heads)
+        ATTENTION_ROUTES["bwd"] += 1
+        return grads[0], grads[1], grads[2], None
+
+
+def axial_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, num_heads: int, route: str = "fused") -> torch.Tensor:
+    """softmax(q k^T / sqrt(d)) v per head and sequence.  q [..., Lq, H d], k and v [..., Lk, H d], arbitrary strided views whose last
+    dimension is contiguous: the leading dimensions are handed to the op as its two sequence dimensions by strides alone (a tensor
+    whose leading dimensions cannot be expressed that way is made contiguous first, that tensor only).  Returns [..., Lq, H d], laid
+    out in memory like q (so the result of a transposed view transposes back into a contiguous tensor).
+
+    route = "fused": the HIP op (the host kernel for CPU tensors) whenever it applies; the stock route (attention_torch) when the
+    shape is outside the supported set, the dtype is not float32, k / v broadcast against q, gradients are enabled and an input
+    requires grad, or -- on the device -- q, k or v has more than one token and a token stride of 2^28 elements or more (the kernel
+    forms V addresses from a 32-bit lane offset).  route = "fused-train": "fused", except that under autograd the op runs inside an
+    autograd Function whose backward is the HIP op axial_attention_bwd (once differentiable; gradients laid out like q, k, v; None
+    for an input that needs none) wherever the forward applies and semicrf_axial_attention_bwd_supported holds, and the stock route
+    elsewhere.  route = "torch": always the stock route.  Always usable, always differentiable."""
+    if route not in ROUTES:
+        raise ValueError(f"route must be one of {ROUTES}, not {route!r}")
+    train = route == "fused-train" and _wants_grad(q, k, v)
+    if route == "torch" or not _fused_applies(q, k, v, num_heads, train):
+        ATTENTION_ROUTES["torch"] += 1
+        return attention_torch(q, k, v, num_heads)
+    if train:
+        ATTENTION_ROUTES["fused-train"] += 1
+        return _AxialAttentionTrain.apply(q, k, v, num_heads)
+    ATTENTION_ROUTES["fused"] += 1
+    return _fused_forward(q, k, v, num_heads)[0]
 
 
 # ---- the modules --------------------------------------------------------------------------------------------------------------------
@@ -203,7 +281,8 @@ class MultiHeadAttentionKernel(nn.Module):
     kernel = None (exact softmax attention) is implemented, as in the reference: with any other kernel the parameters exist (a
     checkpoint loads) and forward raises NotImplementedError.
 
-    attention: "fused" (axial_attention's HIP op where it applies) or "torch" (the stock route)."""
+    attention: "fused" (axial_attention's HIP op where it applies; the stock route under autograd), "fused-train" (the HIP op and its
+    HIP backward under autograd) or "torch" (the stock route)."""
 
     def __init__(self, embed_dim, num_heads, dropout=0., k_dim=None, v_dim=None, fourierSize=32, kernel="fourier", hiddenFactor=1):
         super().__init__()
@@ -257,9 +336,9 @@ class BasicBlock(nn.Module):
     "F": along the frequency axis; "T": along the time axis; "All0" / "0All": between the rest and the first frequency track;
     "FT": over all tokens (kernel "positive": not implemented, as in the reference).
 
-    With attention = "fused" the "F" and "T" halves run on the [N, T, F, D] buffer as it is: everything but the attention is per
-    token, and the two halves differ only in which dimension the attention is told is the sequence.  With "torch" the block follows
-    the reference's order of operations, `transpose(-3, -2)` around the time-axis half included."""
+    With attention = "fused" or "fused-train" the "F" and "T" halves run on the [N, T, F, D] buffer as it is: everything but the
+    attention is per token, and the two halves differ only in which dimension the attention is told is the sequence.  With "torch"
+    the block follows the reference's order of operations, `transpose(-3, -2)` around the time-axis half included."""
 
     def __init__(self, inputSize, num_heads, fourierSize, hiddenFactor=2, hiddenFactorAttn=1, approxKernels=[None, None, None, None],
                  enabled=["F", "T", "All0", "0All"], dropoutProb=0.0):
@@ -306,7 +385,7 @@ class BasicBlock(nn.Module):
         if "F" in self.enabled:
             h = self.fnnBlockF(self.mhaBlockF(h, mem))
         rest = [e for e in self.enabled if e not in ("F", "T")]
-        if self.attention == "fused":
+        if self.attention in ("fused", "fused-train"):
             if "T" in self.enabled:                              # the same buffers, the other axis: nothing is transposed
                 h = self.fnnBlockT(self.mhaBlockT(h, mem, None, -3))
             if not rest:
@@ -342,7 +421,7 @@ class Backbone(nn.Module):
     prepended on each axis; P target tokens per frame row (position embeddings of (time, output index)) are appended along the
     frequency axis; nLayers BasicBlocks; the target tokens are upsampled 8x in time by a transposed convolution and cut to T.
 
-    attention: "fused" | "torch" for all layers (the property reads "mixed" when they differ)."""
+    attention: "fused" | "fused-train" | "torch" for all layers (the property reads "mixed" when they differ)."""
 
     def __init__(self, inputSize, baseSize, posEmbedInitGamma, nHead, fourierSize=16, hiddenFactor=2, hiddenFactorAttn=1,
                  expansionFactor=1, dropoutProb=0.0, nLayers=4, enabledAttn=["F", "T"], useGradientCheckpoint=True, downsampleF=True,

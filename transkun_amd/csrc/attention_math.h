@@ -40,5 +40,25 @@ ATTENTION_HD float scale_of(int d) { return (float)(1.0 / sqrt((double)d)); }
 ATTENTION_HD int sum_half(int key) { return (key >> 2) & 1; }
 ATTENTION_HD int key_tiles(int Lk) { return (Lk + ATT_TILE - 1) / ATT_TILE; }
 
+// ---- the backward (attention_bwd.hip, semicrf_cpu::axial_attention_bwd) ----------------------------------------------------------------
+// sc, m, p and sum are the forward's, recomputed by its chain (the product k[j][c] * q[i][c] commutes, so the pass that holds a key per
+// lane forms the same bits as the pass that holds a query per lane).  Then, per sequence and head:
+//   D[i]     = fmaf-chain over c = 0 .. d-1 ascending from +0 of dout[i][c] * out[i][c]          (out as the forward wrote it)
+//   dP[i][j] = fmaf-chain over c = 0 .. d-1 ascending from +0 of v[j][c] * dout[i][c]
+//   P[i][j]  = p[i][j] / sum[i]                                   one division, not a multiplication by a reciprocal
+//   dS[i][j] = P[i][j] * (dP[i][j] - D[i])                        one subtraction, one multiplication
+//   dq[i][c] = scale * fmaf-chain from +0 over t = 0 .. of dS[i][j] * k[j][c],    j = bwd_order(t), the j >= Lk left out
+//   dk[j][c] = scale * fmaf-chain from +0 over t = 0 .. of dS[i][j] * q[i][c],    i = bwd_order(t), the i >= Lq left out
+//   dv[j][c] =         fmaf-chain from +0 over t = 0 .. of P[i][j]  * dout[i][c], i = bwd_order(t), the i >= Lq left out
+// bwd_order: blocks of ATT_TILE ascending; inside a block the accumulator-row order of a 32 x 32 matrix-pipe result, whose register r
+// holds row (r & 3) + 8 (r >> 2) in lanes 0-31 and that row + 4 in lanes 32-63 -- the two k indices of one 32x32x2 product, so a score
+// block's registers feed the next product as they are: 0, 4, 1, 5, 2, 6, 3, 7, 8, 12, 9, 13, ..  It depends on nothing but t.
+// On the device the left-out entries take part with exact zeros (a padded key has P = dS = 0, a padded query dout = 0 and D = 0).
+ATTENTION_HD int bwd_order(int t)
+{
+    const int r = (t & (ATT_TILE - 1)) >> 1;
+    return (t & ~(ATT_TILE - 1)) + (r & 3) + 8 * (r >> 2) + 4 * (t & 1);
+}
+
 }  // namespace attention
 }  // namespace semicrf

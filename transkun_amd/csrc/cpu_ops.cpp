@@ -1456,4 +1456,92 @@ void axial_attention(const float* q, const float* k, const float* v, float* out,
     }
 }
 
+// The order of operations of attention_bwd.hip per gradient element (attention_math.h): the forward's sc, m, p, sum; D and dP chains
+// over the head dimension ascending; P = p / sum; dS = P (dP - D); dq, dk, dv chains in bwd_order, * scale for dq and dk.  P and dS of
+// one (sequence, head) are kept [Lq][Lk] so that dk and dv walk the queries in their fixed order.  st: q, k, v, out, dout, dq, dk, dv.
+void axial_attention_bwd(const float* q, const float* k, const float* v, const float* out, const float* dout, float* dq, float* dk, float* dv,
+                         int64_t n0, int64_t n1, int Lq, int Lk, int H, int d, const int64_t* st)
+{
+    using namespace semicrf::attention;
+    const float scale = scale_of(d);
+    const int64_t nwork = n0 * n1 * H;
+    const int Lqp = key_tiles(Lq) * ATT_TILE, Lkp = key_tiles(Lk) * ATT_TILE;
+#pragma omp parallel
+    {
+        std::vector<float> P((size_t)Lq * Lk), dS((size_t)Lq * Lk), acc((size_t)d), acc2((size_t)d);
+#pragma omp for schedule(static)
+        for (int64_t w = 0; w < nwork; ++w) {
+            const int h = (int)(w % H);
+            const int64_t s = w / H, s0 = s / n1, s1 = s % n1, hd = (int64_t)h * d;
+            auto base = [&](auto* p, int t) { return p + s0 * st[3 * t] + s1 * st[3 * t + 1] + hd; };
+            const float *qb = base(q, 0), *kb = base(k, 1), *vb = base(v, 2), *ob = base(out, 3), *gb = base(dout, 4);
+            for (int i = 0; i < Lq; ++i) {
+                const float* qi = qb + (int64_t)i * st[2];
+                const float* gi = gb + (int64_t)i * st[14];
+                const float* oi = ob + (int64_t)i * st[11];
+                float* p = &P[(size_t)i * Lk];
+                float* ds = &dS[(size_t)i * Lk];
+                float mx = -std::numeric_limits<float>::infinity();
+                for (int j = 0; j < Lk; ++j) {
+                    const float* kj = kb + (int64_t)j * st[5];
+                    float t = 0.0f;
+                    for (int c = 0; c < d; ++c) t = fmaf(kj[c], qi[c], t);
+                    p[j] = t * scale;
+                    mx = std::max(mx, p[j]);
+                }
+                float half[2] = {0.0f, 0.0f};
+                for (int j = 0; j < Lk; ++j) {
+                    p[j] = expf(p[j] - mx);
+                    half[sum_half(j)] += p[j];
+                }
+                const float sum = half[0] + half[1];
+                float D = 0.0f;
+                for (int c = 0; c < d; ++c) D = fmaf(gi[c], oi[c], D);
+                for (int j = 0; j < Lk; ++j) {
+                    const float* vj = vb + (int64_t)j * st[8];
+                    float dp = 0.0f;
+                    for (int c = 0; c < d; ++c) dp = fmaf(vj[c], gi[c], dp);
+                    p[j] = p[j] / sum;
+                    ds[j] = p[j] * (dp - D);
+                }
+                if (dq) {
+                    std::fill(acc.begin(), acc.end(), 0.0f);
+                    for (int t = 0; t < Lkp; ++t) {
+                        const int j = bwd_order(t);
+                        if (j >= Lk) continue;
+                        const float* kj = kb + (int64_t)j * st[5];
+                        for (int c = 0; c < d; ++c) acc[c] = fmaf(ds[j], kj[c], acc[c]);
+                    }
+                    float* dqi = base(dq, 5) + (int64_t)i * st[17];
+                    for (int c = 0; c < d; ++c) dqi[c] = acc[c] * scale;
+                }
+            }
+            if (!dk && !dv) continue;
+            for (int j = 0; j < Lk; ++j) {
+                std::fill(acc.begin(), acc.end(), 0.0f);
+                std::fill(acc2.begin(), acc2.end(), 0.0f);
+                for (int t = 0; t < Lqp; ++t) {
+                    const int i = bwd_order(t);
+                    if (i >= Lq) continue;
+                    const float* qi = qb + (int64_t)i * st[2];
+                    const float* gi = gb + (int64_t)i * st[14];
+                    const float dsij = dS[(size_t)i * Lk + j], pij = P[(size_t)i * Lk + j];
+                    for (int c = 0; c < d; ++c) {
+                        acc[c] = fmaf(dsij, qi[c], acc[c]);
+                        acc2[c] = fmaf(pij, gi[c], acc2[c]);
+                    }
+                }
+                if (dk) {
+                    float* dkj = base(dk, 6) + (int64_t)j * st[20];
+                    for (int c = 0; c < d; ++c) dkj[c] = acc[c] * scale;
+                }
+                if (dv) {
+                    float* dvj = base(dv, 7) + (int64_t)j * st[23];
+                    for (int c = 0; c < d; ++c) dvj[c] = acc2[c];
+                }
+            }
+        }
+    }
+}
+
 }  // namespace semicrf_cpu

@@ -14,6 +14,7 @@
 #include "../../include/semicrf_hip.h"
 #include "cpu_ops.h"
 
+#include <optional>
 #include <vector>
 
 using torch::stable::Tensor;
@@ -1087,6 +1088,71 @@ void axial_attention_cpu(Tensor q, Tensor k, Tensor v, Tensor out, int64_t H)
     semicrf_cpu::axial_attention(a.q, a.k, a.v, a.out, a.n0, a.n1, a.Lq, a.Lk, a.H, a.d, a.st);
 }
 
+// its backward (semicrf_axial_attention_bwd): q, out, dout, dq [n0, n1, Lq, H d]; k, v, dk, dv [n0, n1, Lk, H d], all views with their
+// own strides; a gradient that is not wanted is None (a NULL pointer: nothing is computed for it)
+struct AttentionBwdArgs { const float *q, *k, *v, *out, *dout; float *dq, *dk, *dv; int64_t n0, n1; int Lq, Lk, H, d; int64_t st[24]; };
+inline AttentionBwdArgs attention_bwd_args(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& out, const Tensor& dout,
+                                           const std::optional<Tensor>& dq, const std::optional<Tensor>& dk, const std::optional<Tensor>& dv,
+                                           int64_t H)
+{
+    const Tensor* ts[8] = {&q, &k, &v, &out, &dout, dq ? &*dq : nullptr, dk ? &*dk : nullptr, dv ? &*dv : nullptr};
+    const char* names[8] = {"q", "k", "v", "out", "dout", "dq", "dk", "dv"};
+    const bool on_q[8] = {true, false, false, true, true, true, false, false};
+    AttentionBwdArgs a{};
+    STD_TORCH_CHECK(q.defined() && q.dim() == 4, "semicrf: `q` must be [n0, n1, Lq, H * d]");
+    a.n0 = q.size(0); a.n1 = q.size(1);
+    const int64_t Lq = q.size(2), Lk = k.defined() && k.dim() == 4 ? k.size(2) : -1, HD = q.size(3);
+    STD_TORCH_CHECK(H >= 1 && H < (1 << 20) && HD % H == 0, "semicrf: the last dimension must be H * d");
+    for (int i = 0; i < 8; ++i) {
+        if (!ts[i]) continue;
+        const Tensor& t = *ts[i];
+        STD_TORCH_CHECK(t.defined() && t.scalar_type() == ScalarType::Float && t.dim() == 4, "semicrf: `", names[i], "` must be a 4-d float32 tensor");
+        STD_TORCH_CHECK(t.size(0) == a.n0 && t.size(1) == a.n1 && t.size(3) == HD && t.size(2) == (on_q[i] ? Lq : Lk),
+                        "semicrf: `", names[i], "` does not have the shape of the call");
+        STD_TORCH_CHECK(HD == 1 || t.stride(3) == 1, "semicrf: `", names[i], "` must have a contiguous last dimension");
+        for (int j = 0; j < 3; ++j) {
+            const int64_t s = t.size(j) > 1 ? t.stride(j) : 0;
+            STD_TORCH_CHECK(s >= 0, "semicrf: negative stride");
+            STD_TORCH_CHECK(i < 3 || t.size(j) == 1 || s > 0, "semicrf: `", names[i], "` must not repeat over a dimension");
+            a.st[3 * i + j] = s;
+        }
+    }
+    STD_TORCH_CHECK(Lq < (1 << 20) && Lk < (1 << 20), "semicrf: sequence too long");
+    a.Lq = (int)Lq; a.Lk = (int)Lk; a.H = (int)H; a.d = (int)(HD / H);
+    STD_TORCH_CHECK(semicrf_axial_attention_bwd_supported(a.Lq, a.Lk, a.H, a.d),
+                    "semicrf: axial_attention_bwd does not support Lq=", Lq, " Lk=", Lk, " H=", H, " d=", HD / H,
+                    " (semicrf_axial_attention_bwd_supported)");
+    a.q = f32s(q, "q"); a.k = f32s(k, "k"); a.v = f32s(v, "v"); a.out = f32s(out, "out"); a.dout = f32s(dout, "dout");
+    a.dq = dq ? f32so(*dq, "dq") : nullptr; a.dk = dk ? f32so(*dk, "dk") : nullptr; a.dv = dv ? f32so(*dv, "dv") : nullptr;
+    return a;
+}
+void axial_attention_bwd_op(Tensor q, Tensor k, Tensor v, Tensor out, Tensor dout, std::optional<Tensor> dq, std::optional<Tensor> dk,
+                            std::optional<Tensor> dv, int64_t H)
+{
+    Ctx c(q); c.same(q, k, v, out, dout);
+    if (dq) c.same(q, *dq);
+    if (dk) c.same(q, *dk);
+    if (dv) c.same(q, *dv);
+    const AttentionBwdArgs a = attention_bwd_args(q, k, v, out, dout, dq, dk, dv, H);
+    if (a.n0 == 0 || a.n1 == 0) return;
+    const int64_t* s = a.st;
+    check(semicrf_axial_attention_bwd(a.q, a.k, a.v, a.out, a.dout, a.dq, a.dk, a.dv, a.n0, a.n1, a.Lq, a.Lk, a.H, a.d, s[0], s[1], s[2], s[3],
+                                      s[4], s[5], s[6], s[7], s[8], s[9], s[10], s[11], s[12], s[13], s[14], s[15], s[16], s[17], s[18],
+                                      s[19], s[20], s[21], s[22], s[23], c.stream),
+          "semicrf_axial_attention_bwd");
+}
+void axial_attention_bwd_cpu(Tensor q, Tensor k, Tensor v, Tensor out, Tensor dout, std::optional<Tensor> dq, std::optional<Tensor> dk,
+                             std::optional<Tensor> dv, int64_t H)
+{
+    all_cpu(q, k, v, out, dout);
+    if (dq) all_cpu(*dq);
+    if (dk) all_cpu(*dk);
+    if (dv) all_cpu(*dv);
+    const AttentionBwdArgs a = attention_bwd_args(q, k, v, out, dout, dq, dk, dv, H);
+    if (a.n0 == 0 || a.n1 == 0) return;
+    semicrf_cpu::axial_attention_bwd(a.q, a.k, a.v, a.out, a.dout, a.dq, a.dk, a.dv, a.n0, a.n1, a.Lq, a.Lk, a.H, a.d, a.st);
+}
+
 // ---- the attribute heads in training (semicrf_attribute_heads_train_fwd / _bwd / _dropout_mask) -------------------------------------
 // seed: the 64 bits of an int; z [K, Hv + Ho] and the gradients are dense and checked for their element counts
 void attribute_heads_train_fwd_op(Tensor ctx, int64_t C, int64_t T, int64_t D, int64_t ldc, Tensor pairs, int64_t K, Tensor offsets, int64_t nSym,
@@ -1292,6 +1358,7 @@ STABLE_TORCH_LIBRARY(semicrf, m)
           "Tensor(b!) dW1, Tensor(c!) db1, Tensor(d!) dW2, Tensor(e!) db2, Tensor(f!) ws) -> ()");
     m.def("attribute_heads_dropout_mask(Tensor(a!) mask, int seed, int K, int Hv, int Ho, float pv, float po) -> ()");
     m.def("axial_attention(Tensor q, Tensor k, Tensor v, Tensor(a!) out, int H) -> ()");
+    m.def("axial_attention_bwd(Tensor q, Tensor k, Tensor v, Tensor out, Tensor dout, Tensor(a!)? dq, Tensor(b!)? dk, Tensor(c!)? dv, int H) -> ()");
     m.def("grad_sqnorm(Tensor flat, int numel, Tensor(a!) partials) -> ()");
     m.def("clip_from_history(Tensor partials, bool has_partials, int numel, Tensor norm_in, bool has_norm, float q, Tensor(a!) ring, "
           "int capacity, Tensor(b!) state, bool append, Tensor(c!) stats) -> ()");
@@ -1332,6 +1399,7 @@ STABLE_TORCH_LIBRARY_IMPL(semicrf, CPU, m)
     m.impl("attribute_heads_bwd", TORCH_BOX(&attribute_heads_bwd_cpu));
     m.impl("attribute_heads_dropout_mask", TORCH_BOX(&attribute_heads_dropout_mask_cpu));
     m.impl("axial_attention", TORCH_BOX(&axial_attention_cpu));
+    m.impl("axial_attention_bwd", TORCH_BOX(&axial_attention_bwd_cpu));
     m.impl("grad_sqnorm", TORCH_BOX(&grad_sqnorm_cpu));
     m.impl("clip_from_history", TORCH_BOX(&clip_from_history_cpu));
     m.impl("adabelief_step", TORCH_BOX(&adabelief_step_cpu));
@@ -1379,6 +1447,7 @@ STABLE_TORCH_LIBRARY_IMPL(semicrf, CUDA, m)
     m.impl("attribute_heads_bwd", TORCH_BOX(&attribute_heads_bwd_op));
     m.impl("attribute_heads_dropout_mask", TORCH_BOX(&attribute_heads_dropout_mask_op));
     m.impl("axial_attention", TORCH_BOX(&axial_attention_op));
+    m.impl("axial_attention_bwd", TORCH_BOX(&axial_attention_bwd_op));
     m.impl("grad_sqnorm", TORCH_BOX(&grad_sqnorm_op));
     m.impl("clip_from_history", TORCH_BOX(&clip_from_history_op));
     m.impl("adabelief_step", TORCH_BOX(&adabelief_step_op));
