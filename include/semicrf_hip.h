@@ -1027,6 +1027,42 @@ int semicrf_axial_attention_bwd(const float* q, const float* k, const float* v, 
                                 int64_t dq_stride_s1, int64_t dq_stride_l, int64_t dk_stride_s0, int64_t dk_stride_s1, int64_t dk_stride_l,
                                 int64_t dv_stride_s0, int64_t dv_stride_s1, int64_t dv_stride_l, semicrf_stream_t stream);
 
+/*
+ * The feed-forward ResBlock of the backbone's transformer layers in eval mode, as one launch.  Replaces: RMSNorm, Linear, GELU,
+ * Linear, the multiplication by the LayerScale and the residual addition of ResBlock around the feed-forward module
+ * (LayersTransformer.py), about ten launches and three round trips of the [tokens, hidden] activation.  For every token t = (i0, i1),
+ * i0 < n0, i1 < n1, with x_t its D values:
+ *   out_t = x_t + (W2 gelu(W1 (x_t / sqrt(mean(x_t^2) + eps)) + b1) + b2) * scale
+ * fp32, no dropout.  W1 [hidden][D], b1 [hidden], W2 [D][hidden], b2 [D] and scale [D] are contiguous and read as nn.Linear and
+ * ResBlock store them; nothing is repacked or cached between calls.  x and out are [n0, n1, D] VIEWS with a contiguous last dimension
+ * and two ELEMENT row strides each: token (i0, i1) starts at base + i0 stride_0 + i1 stride_1.  One [T'][F'][D] buffer goes in as
+ * n0 = T', n1 = F' (strides F' D, D) and its transpose(-3, -2) view as n0 = F', n1 = T' (strides D, F' D): no copy; the op is per
+ * token, so a caller is free to hand the tokens of a batch over in the order of their addresses.  All offsets are 64-bit.
+ *
+ * Supported (semicrf_ffn_residual_supported returns 1): D a multiple of 8 in [8, SEMICRF_FFN_MAX_D]; hidden a multiple of 8 in
+ * [8, SEMICRF_FFN_MAX_HIDDEN].  1 <= n0, n1 and n0 n1 < 2^37.
+ *
+ * Exact fp32 on the matrix pipe (v_mfma_f32_32x32x2_f32), one fixed chain of operations per output element (csrc/ffn_math.h): the sum
+ * of squares as four strided fmaf chains added pairwise; 1 / sqrt(ss / D + eps); both products fmaf chains over the ascending
+ * contraction index from +0, the second one per hidden chunk of SEMICRF_FFN_HIDDEN_CHUNK columns, the chunks' sums added in ascending
+ * order; gelu in its exact erf form (erfc below 0); bias, scale and residual as one addition, one multiplication, one addition.  A workgroup owns
+ * SEMICRF_FFN_ROW_TILE rows; rows past the last token, the columns past D and past hidden are zeros formed in registers, never read and
+ * never stored.  No atomics, no workspace; the tile sizes depend on nothing: a token's result is bit-identical from run to run, whatever
+ * the other tokens, n0, n1 and the strides are.  16-byte loads when the bases are 16-byte aligned and the strides multiples of 4,
+ * 4-byte loads otherwise (the same numbers).  One launch on `stream`; no synchronisation, no allocation.
+ * SEMICRF_EINVAL, with nothing launched and `out` untouched: a shape outside the supported set, a NULL or misaligned (4 bytes) pointer,
+ * n0 or n1 <= 0, n0 n1 >= 2^37, a negative stride or one of 2^40 elements or more, a row stride of `out` below D where that dimension
+ * has more than one entry, `out` overlapping `x`.
+ */
+#define SEMICRF_FFN_ROW_TILE 64
+#define SEMICRF_FFN_HIDDEN_CHUNK 64
+#define SEMICRF_FFN_MAX_D 256
+#define SEMICRF_FFN_MAX_HIDDEN 4096
+int semicrf_ffn_residual_supported(int D, int hidden);
+int semicrf_ffn_residual(const float* x, float* out, int64_t n0, int64_t n1, int64_t x_stride_0, int64_t x_stride_1, int64_t out_stride_0,
+                         int64_t out_stride_1, int D, int hidden, const float* W1, const float* b1, const float* W2, const float* b2,
+                         const float* scale, float eps, semicrf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

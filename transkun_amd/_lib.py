@@ -35,7 +35,11 @@ HEADS_SLICE = 64                                # SEMICRF_HEADS_SLICE: hidden co
 HEADS_BWD_ROW_CHUNK = 512                       # SEMICRF_HEADS_BWD_ROW_CHUNK: rows per partial plane of semicrf_attribute_heads_bwd's row sums
 ATTENTION_MAX_L = 256                           # SEMICRF_ATTENTION_MAX_L: the longest sequence of semicrf_axial_attention
 ATTENTION_MAX_D = 64                            # SEMICRF_ATTENTION_MAX_D: its largest head dimension (a multiple of 8)
-TOL_MAX = 8                                     # SEMICRF_TOL_MAX
+FFN_ROW_TILE = 64                               # SEMICRF_FFN_ROW_TILE: token rows per workgroup of semicrf_ffn_residual
+FFN_HIDDEN_CHUNK = 64                           # SEMICRF_FFN_HIDDEN_CHUNK: hidden columns per step of its walk
+FFN_MAX_D = 256                                 # SEMICRF_FFN_MAX_D (D a multiple of 8)
+FFN_MAX_HIDDEN = 4096                           # SEMICRF_FFN_MAX_HIDDEN (hidden a multiple of 8)
+TOL_MAX = 8                                    # SEMICRF_TOL_MAX
 LEN_MODES = {"linear": 0, "sqrt": 1, "none": 2}
 
 _vp = ctypes.c_void_p
@@ -140,6 +144,8 @@ _SIGS = {
     "semicrf_axial_attention": (_i, [_vp, _vp, _vp, _vp, _i64, _i64, _i, _i, _i, _i] + [_i64] * 12 + [_vp]),
     "semicrf_axial_attention_bwd_supported": (_i, [_i, _i, _i, _i]),
     "semicrf_axial_attention_bwd": (_i, [_vp] * 8 + [_i64, _i64, _i, _i, _i, _i] + [_i64] * 24 + [_vp]),
+    "semicrf_ffn_residual_supported": (_i, [_i, _i]),
+    "semicrf_ffn_residual": (_i, [_vp, _vp] + [_i64] * 6 + [_i, _i] + [_vp] * 5 + [ctypes.c_float, _vp]),
     "interval_score_bwd_ws": (_i, [_vp, _vp, _vp, _i, _i, _i, _i64, _i64, ctypes.c_float, _i, _vp, _vp, _vp, _i64, _i64, _i64, _vp, ctypes.c_size_t, _vp]),
     "interval_score_bwd_workspace_bytes": (ctypes.c_size_t, [_i, _i, _i]),
     "segment_onset_filter": (_i, [_vp, _vp, _i, _i, _vp, _i64, _vp, _vp, _vp]),

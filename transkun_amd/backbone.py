@@ -23,6 +23,14 @@ recomputes the softmax from q and k and takes `out` as the forward wrote it; not
 Every route answers by the stock call for dtypes other than float32, for shapes outside the op's supported set, for broadcasting keys
 and for device views whose tokens lie 2^28 elements apart or more.  `ATTENTION_ROUTES` counts which way the calls went.
 
+The feed-forward half of a layer has a fused route too.  `feedForward = "fused" | "torch"` on a `ResBlock`, and on `BasicBlock` and
+`Backbone` for all of their feed-forward blocks, picks it; the default is "torch", the stock expression.  "fused" runs a block whose
+module is the `Linear, GELU, Dropout, Linear` sequence through `feed_forward_residual`: RMSNorm, both Linears, the GELU, the LayerScale
+and the residual addition as ONE op, `torch.ops.semicrf.ffn_residual` (csrc/ffn.hip on a GPU, the host mirror on the CPU), on the
+hidden state as it lies in memory -- the [tokens, hidden] activation is never written.  It is forward only and eval only: under
+autograd, with an active dropout, for dtypes other than float32, for shapes outside the op's supported set, for any other module and
+for extra arguments the block runs the stock expression.  `FEED_FORWARD_ROUTES` counts which way the calls went.
+
 Hidden size and head dimension come from the constructor as in the reference: head_dim = ceil(ceil(hiddenFactor * embed_dim) /
 num_heads), hidden size = head_dim * num_heads (the model: embed_dim 160, 4 heads, hiddenFactorAttn 1 -> d = 40).
 """
@@ -208,6 +216,90 @@ def axial_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, num_heads
     return _fused_forward(q, k, v, num_heads)[0]
 
 
+# ---- the feed-forward block -----------------------------------------------------------------------------------------------------------
+FEED_FORWARD_KINDS = ("fused", "torch")
+DEFAULT_FEED_FORWARD = "torch"
+# calls of feed_forward_residual, and of the ResBlocks set to "fused", by the way they went; tests read it
+FEED_FORWARD_ROUTES = {"fused": 0, "torch": 0}
+FEED_FORWARD_ROW_TILE = _lib.FFN_ROW_TILE                       # token rows per workgroup of the op
+FEED_FORWARD_HIDDEN_CHUNK = _lib.FFN_HIDDEN_CHUNK               # hidden columns per step of its walk
+
+
+def feed_forward_supported(D: int, hidden: int) -> bool:
+    """semicrf_ffn_residual_supported: D a multiple of 8 in [8, 256], hidden a multiple of 8 in [8, 4096]."""
+    return bool(_lib.load().semicrf_ffn_residual_supported(int(D), int(hidden)))
+
+
+def feed_forward_torch(x, w1, b1, w2, b2, scale, eps=1e-6):
+    """The stock route: ResBlock's expression around Linear, GELU, Linear in eval mode, op for op."""
+    xn = x * torch.rsqrt(x.pow(2).mean(dim=-1, keepdim=True) + eps)
+    return x + F.linear(F.gelu(F.linear(xn, w1, b1)), w2, b2) * scale
+
+
+def _as_rows(t: torch.Tensor, order):
+    """t [..., D] as the op's view [n0, n1, D] with the leading dimensions taken in `order` (the op is per token), or None."""
+    lead = [(t.shape[i], t.stride(i)) for i in order if t.shape[i] != 1]
+    merged = []
+    for n, s in lead:                                           # merge what lies evenly spaced
+        if merged and merged[-1][1] == s * n:
+            merged[-1] = (merged[-1][0] * n, s)
+        else:
+            merged.append((n, s))
+    if len(merged) > 2:
+        return None
+    while len(merged) < 2:
+        merged.insert(0, (1, 0))
+    (n0, s0), (n1, s1) = merged
+    return torch.as_strided(t, (n0, n1, t.shape[-1]), (s0, s1, 1), t.storage_offset())
+
+
+def _ffn_applies(x, w1, b1, w2, b2, scale) -> bool:
+    ts = (x, w1, b1, w2, b2, scale)
+    if any(t.dtype != torch.float32 for t in ts) or any(t.device != x.device for t in ts):
+        return False
+    if x.device.type not in ("cuda", "cpu") or x.dim() < 1 or x.numel() == 0 or w1.dim() != 2 or w2.dim() != 2:
+        return False
+    D, hidden = x.shape[-1], w1.shape[0]
+    if w1.shape != (hidden, D) or w2.shape != (D, hidden) or b1.shape != (hidden,) or b2.shape != (D,) or scale.shape != (D,):
+        return False
+    if torch.is_grad_enabled() and any(t.requires_grad for t in ts):
+        return False                                            # forward only
+    return feed_forward_supported(D, hidden)
+
+
+def _ffn_fused(x, w1, b1, w2, b2, scale, eps):
+    if x.shape[-1] != 1 and x.stride(-1) != 1:
+        x = x.contiguous()
+    order = sorted(range(x.dim() - 1), key=lambda i: -x.stride(i))          # the tokens in the order of their addresses
+    out = torch.empty_like(x)                                   # x's own layout when x is dense
+    x3, o3 = _as_rows(x, order), _as_rows(out, order)
+    if x3 is None or o3 is None or x3.shape != o3.shape:
+        x = x.contiguous()
+        out = torch.empty_like(x)
+        order = list(range(x.dim() - 1))
+        x3, o3 = _as_rows(x, order), _as_rows(out, order)
+    _lib.ops().ffn_residual(x3, w1.contiguous(), b1.contiguous(), w2.contiguous(), b2.contiguous(), scale.contiguous(), float(eps), o3)
+    return out
+
+
+def feed_forward_residual(x, w1, b1, w2, b2, scale, eps=1e-6, route="fused"):
+    """x + (W2 gelu(W1 rmsnorm(x) + b1) + b2) * scale per token: the feed-forward ResBlock in eval mode.  x [..., D] with a contiguous
+    last dimension, any strides in front (a tensor whose rows cannot be handed over as two strides is made contiguous first); w1
+    [hidden, D], b1 [hidden], w2 [D, hidden], b2 [D], scale [D] as nn.Linear and ResBlock hold them.  Returns [..., D], laid out in
+    memory like x.
+
+    route = "fused": the HIP op (the host kernel for CPU tensors) whenever it applies; the stock route (feed_forward_torch) when a
+    dtype is not float32, the shape is outside the supported set (feed_forward_supported), or gradients are enabled and an input or
+    a parameter requires grad.  route = "torch": always the stock route.  Always usable, always differentiable."""
+    if route not in FEED_FORWARD_KINDS:
+        raise ValueError(f"route must be one of {FEED_FORWARD_KINDS}, not {route!r}")
+    if route == "torch" or not _ffn_applies(x, w1, b1, w2, b2, scale):
+        FEED_FORWARD_ROUTES["torch"] += 1
+        return feed_forward_torch(x, w1, b1, w2, b2, scale, eps)
+    FEED_FORWARD_ROUTES["fused"] += 1
+    return _ffn_fused(x, w1, b1, w2, b2, scale, eps)
+
+
 # ---- the modules --------------------------------------------------------------------------------------------------------------------
 class RMSNorm(nn.Module):
     """x / sqrt(mean(x^2) + eps) over the last dimension; no parameters."""
@@ -263,7 +355,12 @@ class LearnableSpatialPositionEmbedding(nn.Module):
 
 
 class ResBlock(nn.Module):
-    """x + dropout(module(norm(x), *args)) * scale: pre-norm residual with LayerScale (initialised to 1e-2).  Only x is normalised."""
+    """x + dropout(module(norm(x), *args)) * scale: pre-norm residual with LayerScale (initialised to 1e-2).  Only x is normalised.
+
+    feedForward: "torch" (the default: the expression above as it stands) or "fused": when the module is the `Linear, GELU, Dropout,
+    Linear` sequence of a feed-forward block, no extra arguments are passed and no dropout is active (eval mode or p = 0), the block
+    is feed_forward_residual's one op wherever that applies (float32, a supported shape, no gradient wanted); the expression above
+    in every other case."""
 
     def __init__(self, module, size, prenorm=True, dropoutProb=0.0):
         super().__init__()
@@ -271,8 +368,33 @@ class ResBlock(nn.Module):
         self.norm = RMSNorm()
         self.scale = nn.Parameter(torch.ones(size) * 1e-2)
         self.dropout = nn.Dropout(dropoutProb)
+        self.feedForward = DEFAULT_FEED_FORWARD
+
+    def is_feed_forward(self) -> bool:
+        """The module is the Linear, GELU (exact), Dropout, Linear sequence of _feed_forward."""
+        m = self.module
+        return (isinstance(m, nn.Sequential) and len(m) == 4 and isinstance(m[0], nn.Linear) and isinstance(m[1], nn.GELU)
+                and getattr(m[1], "approximate", "none") == "none" and isinstance(m[2], nn.Dropout) and isinstance(m[3], nn.Linear)
+                and m[0].bias is not None and m[3].bias is not None and type(self.norm) is RMSNorm)
+
+    def _fused_feed_forward(self, x, args):
+        if self.feedForward != "fused" or args or not self.is_feed_forward():
+            return None
+        m = self.module
+        if self.training and (self.dropout.p > 0 or m[2].p > 0):
+            return None
+        params = (m[0].weight, m[0].bias, m[3].weight, m[3].bias, self.scale)
+        if not _ffn_applies(x, *params):
+            return None
+        FEED_FORWARD_ROUTES["fused"] += 1
+        return _ffn_fused(x, *params, self.norm.eps)
 
     def forward(self, x, *args):
+        if self.feedForward != DEFAULT_FEED_FORWARD:             # a block left at "torch" touches nothing, the counters included
+            out = self._fused_feed_forward(x, args)
+            if out is not None:
+                return out
+            FEED_FORWARD_ROUTES["torch"] += 1
         return x + self.dropout(self.module(self.norm(x), *args)) * self.scale
 
 
@@ -377,6 +499,21 @@ class BasicBlock(nn.Module):
         for m in self.attention_modules():
             m.attention = route
 
+    def feed_forward_blocks(self):
+        return [m for m in self.modules() if isinstance(m, ResBlock) and m.is_feed_forward()]
+
+    @property
+    def feedForward(self):
+        kinds = {m.feedForward for m in self.feed_forward_blocks()}
+        return kinds.pop() if len(kinds) == 1 else "mixed"
+
+    @feedForward.setter
+    def feedForward(self, kind):
+        if kind not in FEED_FORWARD_KINDS:
+            raise ValueError(f"feedForward must be one of {FEED_FORWARD_KINDS}, not {kind!r}")
+        for m in self.feed_forward_blocks():
+            m.feedForward = kind
+
     def forward(self, x, mem=None, crossAttn=False):
         nT, nF = x.shape[-3], x.shape[-2]
         if mem is None:
@@ -421,7 +558,8 @@ class Backbone(nn.Module):
     prepended on each axis; P target tokens per frame row (position embeddings of (time, output index)) are appended along the
     frequency axis; nLayers BasicBlocks; the target tokens are upsampled 8x in time by a transposed convolution and cut to T.
 
-    attention: "fused" | "fused-train" | "torch" for all layers (the property reads "mixed" when they differ)."""
+    attention: "fused" | "fused-train" | "torch" for all layers (the property reads "mixed" when they differ).
+    feedForward: "torch" | "fused" for the feed-forward blocks of all layers, likewise."""
 
     def __init__(self, inputSize, baseSize, posEmbedInitGamma, nHead, fourierSize=16, hiddenFactor=2, hiddenFactorAttn=1,
                  expansionFactor=1, dropoutProb=0.0, nLayers=4, enabledAttn=["F", "T"], useGradientCheckpoint=True, downsampleF=True,
@@ -467,6 +605,21 @@ class Backbone(nn.Module):
         for m in self.modules():
             if isinstance(m, MultiHeadAttentionKernel):
                 m.attention = route
+
+    def feed_forward_blocks(self):
+        return [m for m in self.modules() if isinstance(m, ResBlock) and m.is_feed_forward()]
+
+    @property
+    def feedForward(self):
+        kinds = {m.feedForward for m in self.feed_forward_blocks()}
+        return kinds.pop() if len(kinds) == 1 else "mixed"
+
+    @feedForward.setter
+    def feedForward(self, kind):
+        if kind not in FEED_FORWARD_KINDS:
+            raise ValueError(f"feedForward must be one of {FEED_FORWARD_KINDS}, not {kind!r}")
+        for m in self.feed_forward_blocks():
+            m.feedForward = kind
 
     def tokens(self, x, outputIndices):
         """The input of the first layer: [N, T', F' + P, 4 baseSize], the spectrogram tokens followed by the target tokens."""

@@ -8,6 +8,7 @@
 #include <unordered_map>
 #include "common.h"
 #include "attention_math.h"
+#include "ffn_math.h"
 
 namespace semicrf {
 
@@ -82,6 +83,9 @@ void launch_axial_attention(const float* q, const float* k, const float* v, floa
                             const long long* strides, hipStream_t stream);
 void launch_axial_attention_bwd(const float* q, const float* k, const float* v, const float* out, const float* dout, float* dq, float* dk, float* dv,
                                 long long n0, long long n1, int Lq, int Lk, int H, int d, const long long* strides, hipStream_t stream);
+void launch_ffn_residual(const float* x, float* out, long long n0, long long n1, long long xs0, long long xs1, long long os0, long long os1,
+                         int D, int H, const float* W1, const float* b1, const float* W2, const float* b2, const float* scale, float eps,
+                         hipStream_t stream);
 void launch_grad_sqnorm(const float* flat, long long numel, double* partials, hipStream_t stream);
 void launch_clip_from_history(const double* partials, long long numel, const float* norm_in, double q, float* ring, int capacity,
                               int* state, int append, float* stats, hipStream_t stream);
@@ -1455,6 +1459,35 @@ int semicrf_axial_attention_bwd(const float* q, const float* k, const float* v, 
     if (!dq && !dk && !dv) return SEMICRF_OK;
     launch_axial_attention_bwd(q, k, v, out, dout, dq, dk, dv, n0, n1, Lq, Lk, H, d, strides, (hipStream_t)stream);
     SEMICRF_CHECK_LAUNCH("semicrf_axial_attention_bwd");
+    return SEMICRF_OK;
+}
+
+int semicrf_ffn_residual_supported(int D, int hidden) { return ffn::supported(D, hidden) ? 1 : 0; }
+
+int semicrf_ffn_residual(const float* x, float* out, int64_t n0, int64_t n1, int64_t x_stride_0, int64_t x_stride_1, int64_t out_stride_0,
+                         int64_t out_stride_1, int D, int hidden, const float* W1, const float* b1, const float* W2, const float* b2,
+                         const float* scale, float eps, semicrf_stream_t stream)
+{
+    SEMICRF_CHECK_ARG(ffn::supported(D, hidden),
+                      "ffn_residual: D=%d hidden=%d is outside the supported set (D a multiple of 8 in [%d, %d]; hidden a multiple of 8 in "
+                      "[%d, %d]): see semicrf_ffn_residual_supported", D, hidden, ffn::FFN_MIN_D, ffn::FFN_MAX_D, ffn::FFN_MIN_H, ffn::FFN_MAX_H);
+    SEMICRF_CHECK_ARG(n0 >= 1 && n1 >= 1, "ffn_residual: n0=%lld n1=%lld must be >= 1", (long long)n0, (long long)n1);
+    SEMICRF_CHECK_ARG(n0 < (1ll << 37) && n1 < (1ll << 37) && n0 * n1 < (1ll << 37), "ffn_residual: n0 * n1 = %lld * %lld must stay below 2^37",
+                      (long long)n0, (long long)n1);
+    SEMICRF_CHECK_ARG(x && out && W1 && b1 && W2 && b2 && scale, "ffn_residual: x/out/W1/b1/W2/b2/scale must be non-NULL");
+    SEMICRF_CHECK_ARG((((uintptr_t)x | (uintptr_t)out | (uintptr_t)W1 | (uintptr_t)b1 | (uintptr_t)W2 | (uintptr_t)b2 | (uintptr_t)scale) & 3) == 0,
+                      "ffn_residual: every pointer must be 4-byte aligned");
+    const long long st[4] = {n0 > 1 ? x_stride_0 : 0, n1 > 1 ? x_stride_1 : 0, n0 > 1 ? out_stride_0 : 0, n1 > 1 ? out_stride_1 : 0};
+    for (int i = 0; i < 4; ++i)
+        SEMICRF_CHECK_ARG(st[i] >= 0 && st[i] < (1ll << 40), "ffn_residual: stride %d = %lld must be in [0, 2^40)", i, st[i]);
+    SEMICRF_CHECK_ARG((n0 == 1 || st[2] >= D) && (n1 == 1 || st[3] >= D), "ffn_residual: a row stride of `out` (%lld, %lld) is below D=%d", st[2],
+                      st[3], D);
+    // the element ranges the two views span (strides below 2^40, counts below 2^37: no overflow)
+    const long long xext = (n0 - 1) * st[0] + (n1 - 1) * st[1] + D, oext = (n0 - 1) * st[2] + (n1 - 1) * st[3] + D;
+    const uintptr_t xb = (uintptr_t)x, ob = (uintptr_t)out;
+    SEMICRF_CHECK_ARG(xb + (uintptr_t)xext * 4 <= ob || ob + (uintptr_t)oext * 4 <= xb, "ffn_residual: `out` overlaps `x`");
+    launch_ffn_residual(x, out, n0, n1, st[0], st[1], st[2], st[3], D, hidden, W1, b1, W2, b2, scale, eps, (hipStream_t)stream);
+    SEMICRF_CHECK_LAUNCH("semicrf_ffn_residual");
     return SEMICRF_OK;
 }
 

@@ -21,6 +21,7 @@
 #include "attr_decode_math.h"
 #include "attr_heads_math.h"
 #include "attention_math.h"
+#include "ffn_math.h"
 #include "cpu_ops.h"
 
 namespace semicrf_cpu {
@@ -1540,6 +1541,50 @@ void axial_attention_bwd(const float* q, const float* k, const float* v, const f
                     for (int c = 0; c < d; ++c) dvj[c] = acc2[c];
                 }
             }
+        }
+    }
+}
+
+// ---- the backbone's feed-forward ResBlock (semicrf_ffn_residual) --------------------------------------------------------------------
+// The order of operations of ffn.hip per output element, in fp32 (ffn_math.h): the sum of squares as four strided chains added pairwise,
+// rs = 1 / sqrt(ss / D + eps), xn = x rs, the chain of W1 xn over k ascending from +0 (fmaf), + b1, gelu, per hidden chunk the chain of
+// W2 g over its columns ascending from +0 (on over the zero padding of the last chunk), the chunks' sums added in ascending order from
+// +0, (+ b2) * scale, + x.  Only erf and erfc differ from the device's.
+void ffn_residual(const float* x, float* out, int64_t n0, int64_t n1, int64_t xs0, int64_t xs1, int64_t os0, int64_t os1, int D, int H,
+                  const float* W1, const float* b1, const float* W2, const float* b2, const float* scale, float eps)
+{
+    using namespace semicrf::ffn;
+    const int64_t ntok = n0 * n1;
+#pragma omp parallel
+    {
+        std::vector<float> xn((size_t)D), g((size_t)FFN_CHUNK), acc((size_t)D);
+#pragma omp for schedule(static)
+        for (int64_t t = 0; t < ntok; ++t) {
+            const int64_t i0 = t / n1, i1 = t % n1;
+            const float* xt = x + i0 * xs0 + i1 * xs1;
+            float* ot = out + i0 * os0 + i1 * os1;
+            float s[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+            for (int k = 0; k < D; ++k) s[k & 3] = fmaf(xt[k], xt[k], s[k & 3]);
+            const float rs = rs_of(sumsq_combine(s[0], s[1], s[2], s[3]), D, eps);
+            for (int k = 0; k < D; ++k) xn[k] = xt[k] * rs;
+            std::fill(acc.begin(), acc.end(), 0.0f);
+            for (int j0 = 0; j0 < H; j0 += FFN_CHUNK) {
+                const int wv = std::min(FFN_CHUNK, H - j0);
+                for (int j = 0; j < wv; ++j) {
+                    const float* w = W1 + (int64_t)(j0 + j) * D;
+                    float h = 0.0f;
+                    for (int k = 0; k < D; ++k) h = fmaf(xn[k], w[k], h);
+                    g[j] = semicrf::attr_heads::gelu<float>(h + b1[j0 + j]);
+                }
+                for (int n = 0; n < D; ++n) {
+                    const float* w = W2 + (int64_t)n * H + j0;
+                    float a = 0.0f;                          // the chunk's own sum, from +0
+                    for (int j = 0; j < wv; ++j) a = fmaf(g[j], w[j], a);
+                    if (wv < FFN_CHUNK) a = fmaf(0.0f, 0.0f, a);          // the device's zero padding: -0 becomes +0, nothing else changes
+                    acc[n] += a;                             // chunks ascending
+                }
+            }
+            for (int n = 0; n < D; ++n) ot[n] = epilogue(xt[n], acc[n], b2[n], scale[n]);
         }
     }
 }

@@ -1088,6 +1088,57 @@ void axial_attention_cpu(Tensor q, Tensor k, Tensor v, Tensor out, int64_t H)
     semicrf_cpu::axial_attention(a.q, a.k, a.v, a.out, a.n0, a.n1, a.Lq, a.Lk, a.H, a.d, a.st);
 }
 
+// ---- the backbone's feed-forward ResBlock (semicrf_ffn_residual) --------------------------------------------------------------------
+// x, out: [n0, n1, D] VIEWS with a contiguous last dimension (their two row strides are read from the tensors); W1 [hidden, D],
+// b1 [hidden], W2 [D, hidden], b2 [D], scale [D] contiguous, as nn.Linear and ResBlock store them
+struct FfnArgs { const float *x, *W1, *b1, *W2, *b2, *scale; float* out; int64_t n0, n1, st[4]; int D, H; };
+inline FfnArgs ffn_args(const Tensor& x, const Tensor& W1, const Tensor& b1, const Tensor& W2, const Tensor& b2, const Tensor& scale,
+                        const Tensor& out)
+{
+    FfnArgs a{};
+    STD_TORCH_CHECK(x.defined() && x.dim() == 3 && out.defined() && out.dim() == 3, "semicrf: `x` and `out` must be [n0, n1, D]");
+    STD_TORCH_CHECK(x.scalar_type() == ScalarType::Float && out.scalar_type() == ScalarType::Float, "semicrf: `x` and `out` must be float32");
+    STD_TORCH_CHECK(W1.defined() && W1.dim() == 2 && W2.defined() && W2.dim() == 2, "semicrf: `W1` must be [hidden, D], `W2` [D, hidden]");
+    const int64_t D = x.size(2), H = W1.size(0);
+    a.n0 = x.size(0); a.n1 = x.size(1);
+    STD_TORCH_CHECK(out.size(0) == a.n0 && out.size(1) == a.n1 && out.size(2) == D, "semicrf: `out` does not have the shape of `x`");
+    STD_TORCH_CHECK(D >= 1 && D < (1 << 20) && H >= 1 && H < (1 << 20) && W1.size(1) == D && W2.size(0) == D && W2.size(1) == H,
+                    "semicrf: `W1` / `W2` do not have the shape of the call");
+    STD_TORCH_CHECK(semicrf_ffn_residual_supported((int)D, (int)H), "semicrf: ffn_residual does not support D=", D, " hidden=", H,
+                    " (semicrf_ffn_residual_supported)");
+    STD_TORCH_CHECK(x.stride(2) == 1 && out.stride(2) == 1, "semicrf: `x` and `out` must have a contiguous last dimension");
+    for (int j = 0; j < 2; ++j) {
+        a.st[j] = x.size(j) > 1 ? x.stride(j) : 0;
+        a.st[2 + j] = out.size(j) > 1 ? out.stride(j) : 0;
+        STD_TORCH_CHECK(a.st[j] >= 0 && a.st[2 + j] >= 0, "semicrf: negative stride");
+        STD_TORCH_CHECK(out.size(j) == 1 || a.st[2 + j] >= D, "semicrf: `out` must not repeat or interleave its rows");
+    }
+    a.D = (int)D; a.H = (int)H;
+    a.W1 = f32(W1, H * D, "W1"); a.b1 = f32(b1, H, "b1"); a.W2 = f32(W2, D * H, "W2"); a.b2 = f32(b2, D, "b2"); a.scale = f32(scale, D, "scale");
+    STD_TORCH_CHECK(b1.numel() == H && b2.numel() == D && scale.numel() == D, "semicrf: `b1` / `b2` / `scale` do not have the shape of the call");
+    a.x = x.numel() > 0 ? (const float*)x.data_ptr() : nullptr;
+    a.out = out.numel() > 0 ? (float*)out.data_ptr() : nullptr;
+    return a;
+}
+void ffn_residual_op(Tensor x, Tensor W1, Tensor b1, Tensor W2, Tensor b2, Tensor scale, double eps, Tensor out)
+{
+    Ctx c(x); c.same(x, W1, b1, W2, b2, scale, out);
+    const FfnArgs a = ffn_args(x, W1, b1, W2, b2, scale, out);
+    if (a.n0 == 0 || a.n1 == 0) return;
+    check(semicrf_ffn_residual(a.x, a.out, a.n0, a.n1, a.st[0], a.st[1], a.st[2], a.st[3], a.D, a.H, a.W1, a.b1, a.W2, a.b2, a.scale, (float)eps,
+                               c.stream),
+          "semicrf_ffn_residual");
+}
+void ffn_residual_cpu(Tensor x, Tensor W1, Tensor b1, Tensor W2, Tensor b2, Tensor scale, double eps, Tensor out)
+{
+    all_cpu(x, W1, b1, W2, b2, scale, out);
+    const FfnArgs a = ffn_args(x, W1, b1, W2, b2, scale, out);
+    if (a.n0 == 0 || a.n1 == 0) return;
+    const int64_t xext = (a.n0 - 1) * a.st[0] + (a.n1 - 1) * a.st[1] + a.D, oext = (a.n0 - 1) * a.st[2] + (a.n1 - 1) * a.st[3] + a.D;
+    STD_TORCH_CHECK(a.x + xext <= a.out || a.out + oext <= a.x, "semicrf: ffn_residual: `out` overlaps `x`");
+    semicrf_cpu::ffn_residual(a.x, a.out, a.n0, a.n1, a.st[0], a.st[1], a.st[2], a.st[3], a.D, a.H, a.W1, a.b1, a.W2, a.b2, a.scale, (float)eps);
+}
+
 // its backward (semicrf_axial_attention_bwd): q, out, dout, dq [n0, n1, Lq, H d]; k, v, dk, dv [n0, n1, Lk, H d], all views with their
 // own strides; a gradient that is not wanted is None (a NULL pointer: nothing is computed for it)
 struct AttentionBwdArgs { const float *q, *k, *v, *out, *dout; float *dq, *dk, *dv; int64_t n0, n1; int Lq, Lk, H, d; int64_t st[24]; };
@@ -1359,6 +1410,7 @@ STABLE_TORCH_LIBRARY(semicrf, m)
     m.def("attribute_heads_dropout_mask(Tensor(a!) mask, int seed, int K, int Hv, int Ho, float pv, float po) -> ()");
     m.def("axial_attention(Tensor q, Tensor k, Tensor v, Tensor(a!) out, int H) -> ()");
     m.def("axial_attention_bwd(Tensor q, Tensor k, Tensor v, Tensor out, Tensor dout, Tensor(a!)? dq, Tensor(b!)? dk, Tensor(c!)? dv, int H) -> ()");
+    m.def("ffn_residual(Tensor x, Tensor W1, Tensor b1, Tensor W2, Tensor b2, Tensor scale, float eps, Tensor(a!) out) -> ()");
     m.def("grad_sqnorm(Tensor flat, int numel, Tensor(a!) partials) -> ()");
     m.def("clip_from_history(Tensor partials, bool has_partials, int numel, Tensor norm_in, bool has_norm, float q, Tensor(a!) ring, "
           "int capacity, Tensor(b!) state, bool append, Tensor(c!) stats) -> ()");
@@ -1400,6 +1452,7 @@ STABLE_TORCH_LIBRARY_IMPL(semicrf, CPU, m)
     m.impl("attribute_heads_dropout_mask", TORCH_BOX(&attribute_heads_dropout_mask_cpu));
     m.impl("axial_attention", TORCH_BOX(&axial_attention_cpu));
     m.impl("axial_attention_bwd", TORCH_BOX(&axial_attention_bwd_cpu));
+    m.impl("ffn_residual", TORCH_BOX(&ffn_residual_cpu));
     m.impl("grad_sqnorm", TORCH_BOX(&grad_sqnorm_cpu));
     m.impl("clip_from_history", TORCH_BOX(&clip_from_history_cpu));
     m.impl("adabelief_step", TORCH_BOX(&adabelief_step_cpu));
@@ -1448,6 +1501,7 @@ STABLE_TORCH_LIBRARY_IMPL(semicrf, CUDA, m)
     m.impl("attribute_heads_dropout_mask", TORCH_BOX(&attribute_heads_dropout_mask_op));
     m.impl("axial_attention", TORCH_BOX(&axial_attention_op));
     m.impl("axial_attention_bwd", TORCH_BOX(&axial_attention_bwd_op));
+    m.impl("ffn_residual", TORCH_BOX(&ffn_residual_op));
     m.impl("grad_sqnorm", TORCH_BOX(&grad_sqnorm_op));
     m.impl("clip_from_history", TORCH_BOX(&clip_from_history_op));
     m.impl("adabelief_step", TORCH_BOX(&adabelief_step_op));
