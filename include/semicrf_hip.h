@@ -1063,6 +1063,45 @@ int semicrf_ffn_residual(const float* x, float* out, int64_t n0, int64_t n1, int
                          int64_t out_stride_1, int D, int hidden, const float* W1, const float* b1, const float* W2, const float* b2,
                          const float* scale, float eps, semicrf_stream_t stream);
 
+/*
+ * The audio front end (Util.py:78-170 behind the gain of ModelTransformer.py:159-164) as one launch.  Replaces: the gain normalisation,
+ * the product of the frames with the analysis windows, the orthonormal real transform, |.|^2, the channel mean, the matrix product with
+ * the mel filterbank and the log compression -- a dozen launches and two round trips of a [N, C, nFrame, nWin, W] tensor.  For every
+ * recording n, channel c, frame t, window w and band m:
+ *   x[j]   = frames[n, c, t, j] (with a gain: (x[j] - shift[n]) / denom[n]), times windows[w, j]     j < W
+ *   p[k]   = |rfft(x)[k]|^2 / W                                                                     k <= W / 2
+ *   p[k]   = mean over c of p[k] when to_mono (the output then has one channel)
+ *   mel    = sum over r < fb_len[m] of p[fb_start[m] + r] fb_val[fb_off[m] + r]
+ *   out[n, c, t, m, w] = log_flag ? (log(mel + eps) - log eps) / (-log eps) : mel
+ * fp32.  `frames` is a VIEW with sample stride 1 and three ELEMENT strides (recording, channel, frame): the overlapping view of padded
+ * audio (frame stride = hop) is read in place.  windows [nWin][W] and twiddles [W / 2][2] (cos, -sin of 2 pi k / W, computed in float64
+ * and rounded) are contiguous; the library keeps no state.  The filterbank comes column by column: band m weighs the fb_len[m] rows from
+ * fb_start[m] with the values from fb_val[fb_off[m]] (zeros inside the range included; fb_len 0 gives 0; `total` values in all; a range
+ * that leaves the spectrum or the value array is cut).  shift / denom [N] are both given or both NULL.  out is contiguous
+ * [N][to_mono ? 1 : C][nFrame][nMel][nWin].
+ *
+ * Supported (semicrf_log_mel_supported returns 1): W a power of two in [256, SEMICRF_LOGMEL_MAX_W]; nWin in [1, SEMICRF_LOGMEL_MAX_WINDOWS];
+ * C in [1, SEMICRF_LOGMEL_MAX_CHANNELS]; nMel in [1, SEMICRF_LOGMEL_MAX_BANDS]; the longest column support at most W / 2 + 1 and the sum
+ * of all supports at most SEMICRF_LOGMEL_MAX_SUPPORT.  N, nFrame >= 1 and N nFrame < 2^31.
+ *
+ * One fixed chain of operations per output element (csrc/logmel_math.h): a half-length complex radix-2 transform in LDS plus the split
+ * pass, channels never share a transform; the band sums are fmaf chains over ascending rows; the logarithm is evaluated in float64 and
+ * rounded once.  One workgroup per (recording, frame); no atomics, no workspace: a frame's result is bit-identical from run to run,
+ * whatever the batch, its position and the strides are.  One launch on `stream`; no synchronisation, no allocation.
+ * SEMICRF_EINVAL, with nothing launched and `out` untouched: a shape outside the supported set, a NULL or misaligned (4 bytes) pointer,
+ * only one of shift / denom, a negative stride or one of 2^40 elements or more, eps <= 0 with log_flag, `out` overlapping `frames`.
+ */
+#define SEMICRF_LOGMEL_MAX_W 4096
+#define SEMICRF_LOGMEL_MAX_WINDOWS 8
+#define SEMICRF_LOGMEL_MAX_CHANNELS 16
+#define SEMICRF_LOGMEL_MAX_BANDS 512
+#define SEMICRF_LOGMEL_MAX_SUPPORT 65536
+int semicrf_log_mel_supported(int W, int nWin, int C, int nMel, int max_len, int total);
+int semicrf_log_mel(const float* frames, int64_t stride_n, int64_t stride_c, int64_t stride_frame, int N, int C, int nFrame, int W,
+                    const float* windows, int nWin, const float* twiddles, const int32_t* fb_start, const int32_t* fb_len, const int32_t* fb_off,
+                    const float* fb_val, int nMel, int total, const float* shift, const float* denom, int log_flag, float eps, int to_mono,
+                    float* out, semicrf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -39,6 +39,11 @@ FFN_ROW_TILE = 64                               # SEMICRF_FFN_ROW_TILE: token ro
 FFN_HIDDEN_CHUNK = 64                           # SEMICRF_FFN_HIDDEN_CHUNK: hidden columns per step of its walk
 FFN_MAX_D = 256                                 # SEMICRF_FFN_MAX_D (D a multiple of 8)
 FFN_MAX_HIDDEN = 4096                           # SEMICRF_FFN_MAX_HIDDEN (hidden a multiple of 8)
+LOGMEL_MAX_W = 4096                             # SEMICRF_LOGMEL_MAX_W: the longest analysis window of semicrf_log_mel (a power of two from 256)
+LOGMEL_MAX_WINDOWS = 8                          # SEMICRF_LOGMEL_MAX_WINDOWS
+LOGMEL_MAX_CHANNELS = 16                        # SEMICRF_LOGMEL_MAX_CHANNELS
+LOGMEL_MAX_BANDS = 512                          # SEMICRF_LOGMEL_MAX_BANDS
+LOGMEL_MAX_SUPPORT = 65536                      # SEMICRF_LOGMEL_MAX_SUPPORT: the filterbank's non-zero ranges, all columns together
 TOL_MAX = 8                                    # SEMICRF_TOL_MAX
 LEN_MODES = {"linear": 0, "sqrt": 1, "none": 2}
 
@@ -146,6 +151,8 @@ _SIGS = {
     "semicrf_axial_attention_bwd": (_i, [_vp] * 8 + [_i64, _i64, _i, _i, _i, _i] + [_i64] * 24 + [_vp]),
     "semicrf_ffn_residual_supported": (_i, [_i, _i]),
     "semicrf_ffn_residual": (_i, [_vp, _vp] + [_i64] * 6 + [_i, _i] + [_vp] * 5 + [ctypes.c_float, _vp]),
+    "semicrf_log_mel_supported": (_i, [_i] * 6),
+    "semicrf_log_mel": (_i, [_vp] + [_i64] * 3 + [_i] * 4 + [_vp, _i] + [_vp] * 5 + [_i, _i, _vp, _vp, _i, ctypes.c_float, _i, _vp, _vp]),
     "interval_score_bwd_ws": (_i, [_vp, _vp, _vp, _i, _i, _i, _i64, _i64, ctypes.c_float, _i, _vp, _vp, _vp, _i64, _i64, _i64, _vp, ctypes.c_size_t, _vp]),
     "interval_score_bwd_workspace_bytes": (ctypes.c_size_t, [_i, _i, _i]),
     "segment_onset_filter": (_i, [_vp, _vp, _i, _i, _vp, _i64, _vp, _vp, _vp]),

@@ -9,6 +9,7 @@
 #include "common.h"
 #include "attention_math.h"
 #include "ffn_math.h"
+#include "logmel_math.h"
 
 namespace semicrf {
 
@@ -86,6 +87,9 @@ void launch_axial_attention_bwd(const float* q, const float* k, const float* v, 
 void launch_ffn_residual(const float* x, float* out, long long n0, long long n1, long long xs0, long long xs1, long long os0, long long os1,
                          int D, int H, const float* W1, const float* b1, const float* W2, const float* b2, const float* scale, float eps,
                          hipStream_t stream);
+void launch_log_mel(const float* frames, long long sn, long long sc, long long sf, int N, int C, int nFrame, int W, const float* windows, int nWin,
+                    const float* tw, const int* fb_start, const int* fb_len, const int* fb_off, const float* fb_val, int nMel, int total,
+                    const float* shift, const float* denom, int log_flag, float eps, int to_mono, float* out, hipStream_t stream);
 void launch_grad_sqnorm(const float* flat, long long numel, double* partials, hipStream_t stream);
 void launch_clip_from_history(const double* partials, long long numel, const float* norm_in, double q, float* ring, int capacity,
                               int* state, int append, float* stats, hipStream_t stream);
@@ -1488,6 +1492,42 @@ int semicrf_ffn_residual(const float* x, float* out, int64_t n0, int64_t n1, int
     SEMICRF_CHECK_ARG(xb + (uintptr_t)xext * 4 <= ob || ob + (uintptr_t)oext * 4 <= xb, "ffn_residual: `out` overlaps `x`");
     launch_ffn_residual(x, out, n0, n1, st[0], st[1], st[2], st[3], D, hidden, W1, b1, W2, b2, scale, eps, (hipStream_t)stream);
     SEMICRF_CHECK_LAUNCH("semicrf_ffn_residual");
+    return SEMICRF_OK;
+}
+
+int semicrf_log_mel_supported(int W, int nWin, int C, int nMel, int max_len, int total)
+{
+    return logmel::supported(W, nWin, C, nMel, max_len, total) ? 1 : 0;
+}
+
+int semicrf_log_mel(const float* frames, int64_t stride_n, int64_t stride_c, int64_t stride_frame, int N, int C, int nFrame, int W,
+                    const float* windows, int nWin, const float* twiddles, const int32_t* fb_start, const int32_t* fb_len, const int32_t* fb_off,
+                    const float* fb_val, int nMel, int total, const float* shift, const float* denom, int log_flag, float eps, int to_mono,
+                    float* out, semicrf_stream_t stream)
+{
+    SEMICRF_CHECK_ARG(logmel::supported(W, nWin, C, nMel, 0, total),
+                      "log_mel: W=%d nWin=%d C=%d nMel=%d total=%d is outside the supported set (W a power of two in [256, 4096]; nWin in [1, %d]; "
+                      "C in [1, %d]; nMel in [1, %d]; total support in [0, %d]): see semicrf_log_mel_supported", W, nWin, C, nMel, total,
+                      logmel::LM_MAX_WIN, logmel::LM_MAX_C, logmel::LM_MAX_MEL, logmel::LM_MAX_TOTAL);
+    SEMICRF_CHECK_ARG(N >= 1 && nFrame >= 1 && (long long)N * nFrame < (1ll << 31), "log_mel: N=%d nFrame=%d must be >= 1 and N nFrame < 2^31", N, nFrame);
+    SEMICRF_CHECK_ARG(frames && windows && twiddles && fb_start && fb_len && fb_off && out && (fb_val || total == 0),
+                      "log_mel: frames/windows/twiddles/fb_start/fb_len/fb_off/fb_val/out must be non-NULL");
+    SEMICRF_CHECK_ARG((shift == nullptr) == (denom == nullptr), "log_mel: shift and denom come together or not at all");
+    SEMICRF_CHECK_ARG((((uintptr_t)frames | (uintptr_t)windows | (uintptr_t)twiddles | (uintptr_t)fb_start | (uintptr_t)fb_len | (uintptr_t)fb_off |
+                        (uintptr_t)fb_val | (uintptr_t)shift | (uintptr_t)denom | (uintptr_t)out) & 3) == 0,
+                      "log_mel: every pointer must be 4-byte aligned");
+    const long long st[3] = {N > 1 ? stride_n : 0, C > 1 ? stride_c : 0, nFrame > 1 ? stride_frame : 0};
+    for (int i = 0; i < 3; ++i)
+        SEMICRF_CHECK_ARG(st[i] >= 0 && st[i] < (1ll << 40), "log_mel: stride %d = %lld must be in [0, 2^40)", i, st[i]);
+    SEMICRF_CHECK_ARG(!log_flag || eps > 0.0f, "log_mel: eps=%g must be positive for the log compression", (double)eps);
+    // the element ranges the input view and the output span (strides below 2^40, counts below 2^31: no overflow)
+    const long long fext = (N - 1) * st[0] + (C - 1) * st[1] + (nFrame - 1) * st[2] + W;
+    const long long oext = (long long)N * (to_mono ? 1 : C) * nFrame * nMel * nWin;
+    const uintptr_t fb = (uintptr_t)frames, ob = (uintptr_t)out;
+    SEMICRF_CHECK_ARG(fb + (uintptr_t)fext * 4 <= ob || ob + (uintptr_t)oext * 4 <= fb, "log_mel: `out` overlaps `frames`");
+    launch_log_mel(frames, st[0], st[1], st[2], N, C, nFrame, W, windows, nWin, twiddles, fb_start, fb_len, fb_off, fb_val, nMel, total, shift, denom,
+                   log_flag ? 1 : 0, eps, to_mono ? 1 : 0, out, (hipStream_t)stream);
+    SEMICRF_CHECK_LAUNCH("semicrf_log_mel");
     return SEMICRF_OK;
 }
 

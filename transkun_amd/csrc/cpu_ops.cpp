@@ -22,6 +22,7 @@
 #include "attr_heads_math.h"
 #include "attention_math.h"
 #include "ffn_math.h"
+#include "logmel_math.h"
 #include "cpu_ops.h"
 
 namespace semicrf_cpu {
@@ -1585,6 +1586,83 @@ void ffn_residual(const float* x, float* out, int64_t n0, int64_t n1, int64_t xs
                 }
             }
             for (int n = 0; n < D; ++n) ot[n] = epilogue(xt[n], acc[n], b2[n], scale[n]);
+        }
+    }
+}
+
+// ---- the audio front end (semicrf_log_mel) -------------------------------------------------------------------------------------------
+// The order of operations of logmel.hip per output element, in fp32 (logmel_math.h): gain and window, the half-length radix-2 transform
+// in place (decimation in frequency, one stage at a time: the device's three stages per step visit the same pairs), the split pass, the
+// power, the channel mean, the band chains, the log compression.  Nothing differs from the device's arithmetic.
+void log_mel(const float* frames, int64_t sn, int64_t sc, int64_t sf, int N, int C, int nFrame, int W, const float* windows, int nWin,
+             const float* tw, const int32_t* fb_start, const int32_t* fb_len, const int32_t* fb_off, const float* fb_val, int nMel, int total,
+             const float* shift, const float* denom, int log_flag, float eps, int to_mono, float* out)
+{
+    using namespace semicrf::logmel;
+    const int M = W / 2, P = log2_of_window(W) - 1;
+    const bool gain = shift != nullptr;
+    const float inv_w = 1.0f / (float)W, fC = (float)C, le = (float)std::log((double)eps);
+    auto twc = [tw](int k) { cf w; w.re = tw[2 * k]; w.im = tw[2 * k + 1]; return w; };
+    const int64_t row = (int64_t)nMel * nWin, nf = (int64_t)N * nFrame;
+    const int Cout = to_mono ? 1 : C;
+#pragma omp parallel
+    {
+        std::vector<cf> Z((size_t)M);
+        std::vector<float> PW((size_t)M + 1);
+        auto spectrum = [&](const float* x, const float* win, float sh, float dn, bool first, bool last) {
+            for (int i = 0; i < M; ++i) {
+                Z[i].re = lm_sample(x[2 * i], gain, sh, dn, win[2 * i]);
+                Z[i].im = lm_sample(x[2 * i + 1], gain, sh, dn, win[2 * i + 1]);
+            }
+            for (int b = P - 1; b >= 0; --b) {
+                const int h = 1 << b, step = P - b;
+                for (int i = 0; i < M; ++i)
+                    if (!(i & h)) lm_butterfly(Z[i], Z[i + h], twc((i & (h - 1)) << step));
+            }
+            for (int k = 0; k <= M; ++k) {
+                cf v;
+                if (k == 0 || k == M) {
+                    v.re = k == 0 ? Z[0].re + Z[0].im : Z[0].re - Z[0].im;
+                    v.im = 0.0f;
+                } else {
+                    v = lm_split(Z[lm_brev(k, P)], Z[lm_brev(M - k, P)], twc(k));
+                }
+                float p = lm_power(v, inv_w);
+                if (!first) p = PW[k] + p;
+                if (last) p = p / fC;
+                PW[k] = p;
+            }
+        };
+        auto bands = [&](int w, float* o) {
+            for (int m = 0; m < nMel; ++m) {
+                int s, len;
+                const int off = fb_off[m];
+                lm_band(fb_start[m], fb_len[m], off, M, total, s, len);
+                float acc = 0.0f;
+                for (int r = 0; r < len; ++r) acc = fmaf(PW[s + r], fb_val[off + r], acc);
+                o[(int64_t)m * nWin + w] = log_flag ? lm_compress(acc, eps, le) : acc;
+            }
+        };
+#pragma omp for schedule(static)
+        for (int64_t f = 0; f < nf; ++f) {
+            const int n = (int)(f / nFrame), t = (int)(f % nFrame);
+            const float sh = gain ? shift[n] : 0.0f, dn = gain ? denom[n] : 1.0f;
+            const float* xn = frames + n * sn + t * sf;
+            if (to_mono) {
+                float* o = out + ((int64_t)n * nFrame + t) * row;
+                for (int w = 0; w < nWin; ++w) {
+                    for (int c = 0; c < C; ++c) spectrum(xn + c * sc, windows + (int64_t)w * W, sh, dn, c == 0, c == C - 1);
+                    bands(w, o);
+                }
+            } else {
+                for (int c = 0; c < C; ++c) {
+                    float* o = out + (((int64_t)n * Cout + c) * nFrame + t) * row;
+                    for (int w = 0; w < nWin; ++w) {
+                        spectrum(xn + c * sc, windows + (int64_t)w * W, sh, dn, true, false);
+                        bands(w, o);
+                    }
+                }
+            }
         }
     }
 }

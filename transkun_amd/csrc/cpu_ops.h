@@ -82,4 +82,9 @@ void axial_attention_bwd(const float* q, const float* k, const float* v, const f
 // (ffn_math.h); x and out [n0, n1, D] with their two element row strides; the caller has checked the supported set
 void ffn_residual(const float* x, float* out, int64_t n0, int64_t n1, int64_t xs0, int64_t xs1, int64_t os0, int64_t os1, int D, int H,
                   const float* W1, const float* b1, const float* W2, const float* b2, const float* scale, float eps);
+// the audio front end (semicrf_log_mel): the device kernel's order of operations per output element, in fp32 (logmel_math.h); frames
+// by its three element strides, out contiguous [N][to_mono ? 1 : C][nFrame][nMel][nWin]; the caller has checked the supported set
+void log_mel(const float* frames, int64_t sn, int64_t sc, int64_t sf, int N, int C, int nFrame, int W, const float* windows, int nWin,
+             const float* tw, const int32_t* fb_start, const int32_t* fb_len, const int32_t* fb_off, const float* fb_val, int nMel, int total,
+             const float* shift, const float* denom, int log_flag, float eps, int to_mono, float* out);
 }  // namespace semicrf_cpu

@@ -1139,6 +1139,75 @@ void ffn_residual_cpu(Tensor x, Tensor W1, Tensor b1, Tensor W2, Tensor b2, Tens
     semicrf_cpu::ffn_residual(a.x, a.out, a.n0, a.n1, a.st[0], a.st[1], a.st[2], a.st[3], a.D, a.H, a.W1, a.b1, a.W2, a.b2, a.scale, (float)eps);
 }
 
+// ---- the audio front end (semicrf_log_mel) -------------------------------------------------------------------------------------------
+// frames: a [N, C, nFrame, W] VIEW with sample stride 1 (its three other strides are read from the tensor: the overlapping unfold view
+// goes in as it is); windows [nWin, W], tw [W / 2, 2], fb_start / fb_len / fb_off [nMel] int32, fb_val [total], shift / denom [N] when
+// has_gain, out [N, to_mono ? 1 : C, nFrame, nMel, nWin], all contiguous
+struct LogMelCall {
+    const float *frames, *windows, *tw, *fb_val, *shift, *denom; const int32_t *fb_start, *fb_len, *fb_off; float* out;
+    int64_t st[3]; int N, C, nFrame, W, nWin, nMel, total;
+};
+inline LogMelCall log_mel_args(const Tensor& frames, const Tensor& windows, const Tensor& tw, const Tensor& fb_start, const Tensor& fb_len,
+                               const Tensor& fb_off, const Tensor& fb_val, int64_t max_len, const Tensor& shift, const Tensor& denom,
+                               bool has_gain, bool to_mono, const Tensor& out)
+{
+    LogMelCall a{};
+    STD_TORCH_CHECK(frames.defined() && frames.dim() == 4, "semicrf: `frames` must be [N, C, nFrame, W]");
+    STD_TORCH_CHECK(frames.scalar_type() == ScalarType::Float, "semicrf: `frames` must be float32");
+    STD_TORCH_CHECK(windows.defined() && windows.dim() == 2, "semicrf: `windows` must be [nWin, W]");
+    const int64_t N = frames.size(0), C = frames.size(1), nFrame = frames.size(2), W = frames.size(3), nWin = windows.size(0);
+    const int64_t nMel = fb_start.numel(), total = fb_val.numel();
+    STD_TORCH_CHECK(windows.size(1) == W && N < (1ll << 31) && C < (1 << 20) && nFrame < (1ll << 31) && W < (1 << 20) && nWin < (1 << 20) &&
+                    nMel < (1 << 20) && total < (1ll << 31) && max_len >= 0 && max_len < (1ll << 31), "semicrf: log_mel: bad shape");
+    STD_TORCH_CHECK(semicrf_log_mel_supported((int)W, (int)nWin, (int)C, (int)nMel, (int)max_len, (int)total), "semicrf: log_mel does not support W=", W,
+                    " nWin=", nWin, " C=", C, " nMel=", nMel, " max_len=", max_len, " total=", total, " (semicrf_log_mel_supported)");
+    STD_TORCH_CHECK(W == 1 || frames.stride(3) == 1, "semicrf: `frames` must have sample stride 1");
+    for (int j = 0; j < 3; ++j) {
+        a.st[j] = frames.size(j) > 1 ? frames.stride(j) : 0;
+        STD_TORCH_CHECK(a.st[j] >= 0, "semicrf: negative stride");
+    }
+    a.N = (int)N; a.C = (int)C; a.nFrame = (int)nFrame; a.W = (int)W; a.nWin = (int)nWin; a.nMel = (int)nMel; a.total = (int)total;
+    a.windows = f32(windows, nWin * W, "windows");
+    a.tw = f32(tw, W, "tw");
+    STD_TORCH_CHECK(tw.numel() == W, "semicrf: `tw` must be [W / 2, 2]");
+    a.fb_start = i32(fb_start, nMel, "fb_start"); a.fb_len = i32(fb_len, nMel, "fb_len"); a.fb_off = i32(fb_off, nMel, "fb_off");
+    STD_TORCH_CHECK(fb_len.numel() == nMel && fb_off.numel() == nMel, "semicrf: `fb_start` / `fb_len` / `fb_off` must have one entry per band");
+    a.fb_val = f32(fb_val, total, "fb_val");
+    if (has_gain) {
+        a.shift = f32(shift, N, "shift"); a.denom = f32(denom, N, "denom");
+        STD_TORCH_CHECK(shift.numel() == N && denom.numel() == N, "semicrf: `shift` / `denom` must have one entry per recording");
+    }
+    const int64_t on = N * (to_mono ? 1 : C) * nFrame * nMel * nWin;
+    a.out = f32w(out, on, "out");
+    STD_TORCH_CHECK(out.numel() == on, "semicrf: `out` must be [N, C or 1, nFrame, nMel, nWin]");
+    a.frames = frames.numel() > 0 ? (const float*)frames.data_ptr() : nullptr;
+    return a;
+}
+void log_mel_op(Tensor frames, Tensor windows, Tensor tw, Tensor fb_start, Tensor fb_len, Tensor fb_off, Tensor fb_val, int64_t max_len,
+                Tensor shift, Tensor denom, bool has_gain, bool log_flag, double eps, bool to_mono, Tensor out)
+{
+    Ctx c(frames); c.same(frames, windows, tw, fb_start, fb_len, fb_off, fb_val, out);
+    if (has_gain) c.same(frames, shift, denom);
+    const LogMelCall a = log_mel_args(frames, windows, tw, fb_start, fb_len, fb_off, fb_val, max_len, shift, denom, has_gain, to_mono, out);
+    if (a.N == 0 || a.nFrame == 0) return;
+    check(semicrf_log_mel(a.frames, a.st[0], a.st[1], a.st[2], a.N, a.C, a.nFrame, a.W, a.windows, a.nWin, a.tw, a.fb_start, a.fb_len, a.fb_off,
+                          a.fb_val, a.nMel, a.total, a.shift, a.denom, log_flag ? 1 : 0, (float)eps, to_mono ? 1 : 0, a.out, c.stream),
+          "semicrf_log_mel");
+}
+void log_mel_cpu(Tensor frames, Tensor windows, Tensor tw, Tensor fb_start, Tensor fb_len, Tensor fb_off, Tensor fb_val, int64_t max_len,
+                 Tensor shift, Tensor denom, bool has_gain, bool log_flag, double eps, bool to_mono, Tensor out)
+{
+    all_cpu(frames, windows, tw, fb_start, fb_len, fb_off, fb_val, out);
+    if (has_gain) all_cpu(shift, denom);
+    const LogMelCall a = log_mel_args(frames, windows, tw, fb_start, fb_len, fb_off, fb_val, max_len, shift, denom, has_gain, to_mono, out);
+    if (a.N == 0 || a.nFrame == 0) return;
+    STD_TORCH_CHECK(!log_flag || eps > 0.0, "semicrf: log_mel: eps must be positive for the log compression");
+    const int64_t fext = (a.N - 1) * a.st[0] + (a.C - 1) * a.st[1] + (a.nFrame - 1) * a.st[2] + a.W;
+    STD_TORCH_CHECK(a.frames + fext <= a.out || a.out + out.numel() <= a.frames, "semicrf: log_mel: `out` overlaps `frames`");
+    semicrf_cpu::log_mel(a.frames, a.st[0], a.st[1], a.st[2], a.N, a.C, a.nFrame, a.W, a.windows, a.nWin, a.tw, a.fb_start, a.fb_len, a.fb_off,
+                         a.fb_val, a.nMel, a.total, a.shift, a.denom, log_flag ? 1 : 0, (float)eps, to_mono ? 1 : 0, a.out);
+}
+
 // its backward (semicrf_axial_attention_bwd): q, out, dout, dq [n0, n1, Lq, H d]; k, v, dk, dv [n0, n1, Lk, H d], all views with their
 // own strides; a gradient that is not wanted is None (a NULL pointer: nothing is computed for it)
 struct AttentionBwdArgs { const float *q, *k, *v, *out, *dout; float *dq, *dk, *dv; int64_t n0, n1; int Lq, Lk, H, d; int64_t st[24]; };
@@ -1411,6 +1480,8 @@ STABLE_TORCH_LIBRARY(semicrf, m)
     m.def("axial_attention(Tensor q, Tensor k, Tensor v, Tensor(a!) out, int H) -> ()");
     m.def("axial_attention_bwd(Tensor q, Tensor k, Tensor v, Tensor out, Tensor dout, Tensor(a!)? dq, Tensor(b!)? dk, Tensor(c!)? dv, int H) -> ()");
     m.def("ffn_residual(Tensor x, Tensor W1, Tensor b1, Tensor W2, Tensor b2, Tensor scale, float eps, Tensor(a!) out) -> ()");
+    m.def("log_mel(Tensor frames, Tensor windows, Tensor tw, Tensor fb_start, Tensor fb_len, Tensor fb_off, Tensor fb_val, int max_len, "
+          "Tensor shift, Tensor denom, bool has_gain, bool log_flag, float eps, bool to_mono, Tensor(a!) out) -> ()");
     m.def("grad_sqnorm(Tensor flat, int numel, Tensor(a!) partials) -> ()");
     m.def("clip_from_history(Tensor partials, bool has_partials, int numel, Tensor norm_in, bool has_norm, float q, Tensor(a!) ring, "
           "int capacity, Tensor(b!) state, bool append, Tensor(c!) stats) -> ()");
@@ -1453,6 +1524,7 @@ STABLE_TORCH_LIBRARY_IMPL(semicrf, CPU, m)
     m.impl("axial_attention", TORCH_BOX(&axial_attention_cpu));
     m.impl("axial_attention_bwd", TORCH_BOX(&axial_attention_bwd_cpu));
     m.impl("ffn_residual", TORCH_BOX(&ffn_residual_cpu));
+    m.impl("log_mel", TORCH_BOX(&log_mel_cpu));
     m.impl("grad_sqnorm", TORCH_BOX(&grad_sqnorm_cpu));
     m.impl("clip_from_history", TORCH_BOX(&clip_from_history_cpu));
     m.impl("adabelief_step", TORCH_BOX(&adabelief_step_cpu));
@@ -1502,6 +1574,7 @@ STABLE_TORCH_LIBRARY_IMPL(semicrf, CUDA, m)
     m.impl("axial_attention", TORCH_BOX(&axial_attention_op));
     m.impl("axial_attention_bwd", TORCH_BOX(&axial_attention_bwd_op));
     m.impl("ffn_residual", TORCH_BOX(&ffn_residual_op));
+    m.impl("log_mel", TORCH_BOX(&log_mel_op));
     m.impl("grad_sqnorm", TORCH_BOX(&grad_sqnorm_op));
     m.impl("clip_from_history", TORCH_BOX(&clip_from_history_op));
     m.impl("adabelief_step", TORCH_BOX(&adabelief_step_op));
