@@ -15,9 +15,34 @@
  *   - stream is a hipStream_t passed as void*; every call only ENQUEUES work on it
  *     (no host synchronisation), so calls compose with torch's current stream.
  *   - ws / ws_bytes: caller-owned scratch of at least semicrf_workspace_bytes(op,T,B) bytes,
- *     256-byte aligned; contents are undefined afterwards.
+ *     256-byte aligned (SEMICRF_WS_ALIGN); contents are undefined afterwards.
  *   - Return value: SEMICRF_OK or an error code; semicrf_last_error() gives the message of the
  *     last failing call on this thread.  Nothing is written on SEMICRF_EINVAL.
+ *
+ * Memory contract of the semi-CRF entry points (semicrf_*; tests/test_memory_contract.py pins every sentence)
+ *   - ws: every entry point that takes one refuses a non-NULL ws whose address is not a multiple of SEMICRF_WS_ALIGN with
+ *     SEMICRF_EINVAL, together with the other argument checks and ahead of any HIP call -- the entry points that ignore their ws
+ *     (semicrf_alpha_from, semicrf_eval_path) included; where an entry point compares ws_bytes before it launches, a ws that is
+ *     also too short stays SEMICRF_EWORKSPACE.  The library hands out its sub-buffers at 256-byte offsets from the base, and
+ *     64-bit device-scope atomics sit on them.  Exactly semicrf_workspace_bytes(op,T,B) bytes are enough: nothing past ws + ws_bytes
+ *     is read or written.  The results do not depend on what an unleased ws held before the call.
+ *   - Operands and outputs (score, noise, v, q, logZ, gout, weights, every float / int32 output, start / end / offsets): ANY 4-byte
+ *     aligned address.  The kernels' 16-byte accesses to four neighbouring chains are typed for 4-byte alignment (an odd NBatch
+ *     puts every row at another phase anyway) and every atomic on them is a 4-byte one; the fixed summation orders name no
+ *     alignment: results are bit-identical whatever the bases are modulo 16.  The exceptions are stated where they apply: `pairs`
+ *     INPUTS of semicrf_mbr_select and semicrf_compare_paths are 8-byte aligned (one 8-byte load per pair; enforced).
+ *   - Nothing outside the elements a call is documented to write is written, and nothing outside the elements it is documented to
+ *     read reaches a result.  What a call leaves UNTOUCHED (it keeps the bits it had):
+ *       an optional output passed as NULL / "not wanted" (v of semicrf_logz_fwd / _logprob_fwd, q_out of semicrf_logz_bwd);
+ *       pairs rows (and probs entries) from min(total, cap) up to cap, total = the last offset, of every packed list;
+ *       the cells begin > end of dScore under SEMICRF_GRAD_UPPER_IS_ZERO, where the persistent sweep runs (T >= 2, NBatch >= 2,
+ *       implementation 0) -- the flag is a permission: the row-sequential kernels write the +0.0f the caller promised;
+ *       semicrf_eval_path_bwd: every cell of dScore that is not a path cell (dNoise: every element is read and written back,
+ *       += gout on every gap and -= gout on the covered ones);
+ *       out[i] past K of semicrf_interval_marginals[_tol]; Cn / noiseP / dNoise when T = 1 (they have no elements).
+ *     Everything else of an output is written by every call: logZ [B], v / beta / q_out [T][B], dScore / C [T][T][B] (zeros
+ *     included, without the flag), dNoise / Cn / noiseP [T-1][B], offsets (all B+1, nSample*B+1, k*B+1 entries), scores [k][B],
+ *     npaths [B], node / begin / end / single [T][B], entropy / E / H / out / logProb [B].
  */
 #ifndef SEMICRF_HIP_H
 #define SEMICRF_HIP_H
@@ -58,6 +83,8 @@ extern "C" {
 #define SEMICRF_OP_MARGINAL_DECODE_TOL 11   /* semicrf_marginal_decode_tol */
 #define SEMICRF_OP_ATTRIBUTE_HEADS 12       /* semicrf_attribute_heads: T = rows K, B = Hv + Ho (see there) */
 #define SEMICRF_OP_ATTRIBUTE_HEADS_BWD 13   /* semicrf_attribute_heads_bwd: T = rows K, B = Hv + Ho (see there) */
+
+#define SEMICRF_WS_ALIGN 256           /* required alignment of every `ws` of the semicrf_* entry points (enforced: SEMICRF_EINVAL) */
 
 #define SEMICRF_TOL_MAX 8              /* largest onset / offset tolerance (frames) of the *_tol entry points */
 
@@ -499,7 +526,9 @@ int semicrf_logprob_bwd_f(const float* score, const float* noise, const float* v
  *     bit 30      SEMICRF_PTAB_COVERED: the gap between frames f and f + 1 lies inside an interval (begin <= f < end).
  *   semicrf_logprob_fwd_t: semicrf_logprob_fwd, and when ptab is non-NULL the launch also writes every word of ptab (no fill
  *     needed, no extra launch).  ptab belongs to the call: keep it with v / logZ for the backward, not in the workspace.  Non-NULL
- *     only where semicrf_logprob_path_table_supported(T, B) returns 1 (SEMICRF_EINVAL otherwise).
+ *     only where the persistent sweep runs (T >= 2, NBatch >= 2, implementation 0: SEMICRF_EINVAL otherwise);
+ *     semicrf_logprob_path_table_supported(T, B) returns 1 where the backward call will also USE the table -- where it returns 0
+ *     but the sweep runs (an odd NBatch, a short sequence) the table is written and the backward call ignores it.
  *   semicrf_logprob_bwd_t: semicrf_logprob_bwd_f with the table of the forward call of the SAME pairs (or NULL: exactly
  *     semicrf_logprob_bwd_f).  Launches that cannot use it -- short sequences, whose band is stored by the ring itself; the
  *     row-sequential implementation; more chains than one launch takes -- ignore it and scatter as before.

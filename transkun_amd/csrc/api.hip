@@ -370,6 +370,16 @@ static int check_common(const float* score, const float* noise, int T, int B)
     return SEMICRF_OK;
 }
 
+// ws of the semi-CRF entry points: Carver hands out sub-buffers at aligned OFFSETS from the base, and 64-bit device-scope atomics
+// sit on them -- a base below the alignment the header promises (SEMICRF_WS_ALIGN) is refused with the other argument checks, ahead
+// of any HIP call.  A NULL ws is not looked at here: the entry points that need one say so themselves.
+static int check_ws(const void* ws, const char* what)
+{
+    SEMICRF_CHECK_ARG(((uintptr_t)ws & (uintptr_t)(SEMICRF_WS_ALIGN - 1)) == 0, "%s: ws must be %d-byte aligned (it is %p)", what,
+                      SEMICRF_WS_ALIGN, ws);
+    return SEMICRF_OK;
+}
+
 // the intervals of semicrf_logprob_fwd, when the sweep's launch can compute the path scores on the side (*folded = 1)
 struct PathFold { const int32_t* pairs; int64_t K; const int32_t* offsets; float* logProb; int folded; int32_t* ptab; };
 
@@ -378,6 +388,7 @@ static int logz_fwd_impl(const float* score, const float* noise, int T, int B, f
 {
     if (int rc = check_common(score, noise, T, B)) return rc;
     SEMICRF_CHECK_ARG(logZ != nullptr, "logZ is NULL");
+    if (int rc = check_ws(ws, "semicrf_logz_fwd")) return rc;
     if (int rc = sweep_prologue("semicrf_logz_fwd", (hipStream_t)stream)) return rc;
     Carver cv(ws, ws_bytes);
     // the sweep's own workspace comes FIRST: a leased ws is only clean where the previous launch left it clean, so its place
@@ -419,6 +430,7 @@ static int logz_bwd_impl(const float* score, const float* noise, const float* v,
 {
     if (int rc = check_common(score, noise, T, B)) return rc;
     SEMICRF_CHECK_ARG((flags & ~SEMICRF_GRAD_UPPER_IS_ZERO) == 0, "unknown flags %d", flags);
+    if (int rc = check_ws(ws, "semicrf_logz_bwd")) return rc;
     if (int rc = sweep_prologue("semicrf_logz_bwd", (hipStream_t)stream)) return rc;
     const int keep_upper = (flags & SEMICRF_GRAD_UPPER_IS_ZERO) ? 1 : 0;
     SEMICRF_CHECK_ARG(v && logZ && gout && dScore, "v/logZ/gout/dScore must be non-NULL");
@@ -532,6 +544,7 @@ int semicrf_beta(const float* score, const float* noise, int T, int B, float* be
 {
     if (int rc = check_common(score, noise, T, B)) return rc;
     SEMICRF_CHECK_ARG(beta, "beta must be non-NULL");
+    if (int rc = check_ws(ws, "semicrf_beta")) return rc;
     if (int rc = sweep_prologue("semicrf_beta", (hipStream_t)stream)) return rc;
     Carver cv(ws, ws_bytes);
     const bool fast = use_persist(T, B);
@@ -560,6 +573,7 @@ int semicrf_viterbi(const float* score, const float* noise, int T, int B, const 
     if (int rc = check_common(score, noise, T, B)) return rc;
     SEMICRF_CHECK_ARG(pairs && offsets && cap >= 0, "pairs/offsets must be non-NULL");
     SEMICRF_CHECK_ARG((long long)B * 2 * T < (1ll << 31), "B*2T exceeds int32 offsets");
+    if (int rc = check_ws(ws, "semicrf_viterbi")) return rc;
     if (int rc = sweep_prologue("semicrf_viterbi", (hipStream_t)stream)) return rc;
     Carver cv(ws, ws_bytes);
     float* u = cv.take<float>((size_t)T * B);
@@ -600,6 +614,7 @@ int semicrf_sample(const float* score, const float* noise, const float* v, int T
     SEMICRF_CHECK_ARG((long long)T * ((B + 63) / 64) < (1ll << 31), "T*ceil(B/64) exceeds the grid");
     SEMICRF_CHECK_ARG(ws != nullptr, "workspace is NULL");
     if (ws_bytes < sample_workspace_bytes(T, nSample * B)) { set_error("workspace too small for sample"); return SEMICRF_EWORKSPACE; }
+    if (int rc = check_ws(ws, "semicrf_sample")) return rc;
     launch_sample(score, noise, v, T, B, (long long)k0, nSample, (unsigned long long)key, end, pairs, (long long)cap, offsets, ws,
                   (hipStream_t)stream);
     SEMICRF_CHECK_LAUNCH("semicrf_sample");
@@ -617,6 +632,7 @@ int semicrf_viterbi_nbest(const float* score, const float* noise, int T, int B, 
     SEMICRF_CHECK_ARG((long long)k * B * 2 * T < (1ll << 31), "k*B*2T exceeds int32 offsets");
     SEMICRF_CHECK_ARG(ws != nullptr, "workspace is NULL");
     if (ws_bytes < nbest_workspace_bytes(T, k * B)) { set_error("workspace too small for viterbi_nbest"); return SEMICRF_EWORKSPACE; }
+    if (int rc = check_ws(ws, "semicrf_viterbi_nbest")) return rc;
     launch_viterbi_nbest(score, noise, T, B, k, start, forward ? 1 : 0, pairs, (long long)cap, offsets, scores, npaths, ws,
                          (hipStream_t)stream);
     SEMICRF_CHECK_LAUNCH("semicrf_viterbi_nbest");
@@ -633,6 +649,7 @@ int semicrf_posteriors(const float* score, const float* noise, const float* v, c
     SEMICRF_CHECK_ARG((long long)((T + 63) / 64) * ((T + 63) / 64 + 1) / 2 < 65536, "T=%d too large for the posterior pass", T);
     SEMICRF_CHECK_ARG(ws != nullptr, "workspace is NULL");
     if (ws_bytes < posterior_workspace_bytes(T, B)) { set_error("workspace too small for posteriors"); return SEMICRF_EWORKSPACE; }
+    if (int rc = check_ws(ws, "semicrf_posteriors")) return rc;
     launch_posteriors(score, noise, v, q, logZ, T, B, node, begin, end, single, noiseP, entropy, ws, (hipStream_t)stream);
     SEMICRF_CHECK_LAUNCH("semicrf_posteriors");
     return SEMICRF_OK;
@@ -646,6 +663,7 @@ int semicrf_expectation(const float* score, const float* noise, const float* wei
     SEMICRF_CHECK_ARG(E && H, "an output is NULL");
     SEMICRF_CHECK_ARG(ws != nullptr, "workspace is NULL");
     if (ws_bytes < expectation_workspace_bytes(T, B)) { set_error("workspace too small for expectation"); return SEMICRF_EWORKSPACE; }
+    if (int rc = check_ws(ws, "semicrf_expectation")) return rc;
     launch_expectation(score, noise, weight ? weight : score, noiseWeight, v, q, T, B, E, H, ws, (hipStream_t)stream);
     SEMICRF_CHECK_LAUNCH("semicrf_expectation");
     return SEMICRF_OK;
@@ -658,6 +676,7 @@ int semicrf_alpha_from(const float* score, const float* noise, const int32_t* st
     if (int rc = check_common(score, noise, T, B)) return rc;
     SEMICRF_CHECK_ARG(start != nullptr, "start is NULL");
     SEMICRF_CHECK_ARG(v && logZ, "an output is NULL");
+    if (int rc = check_ws(ws, "semicrf_alpha_from")) return rc;
     launch_alpha_from(score, noise, start, T, B, v, logZ, (hipStream_t)stream);
     SEMICRF_CHECK_LAUNCH("semicrf_alpha_from");
     return SEMICRF_OK;
@@ -672,6 +691,7 @@ int semicrf_covariance(const float* score, const float* noise, const float* weig
     SEMICRF_CHECK_ARG(T < 65536, "T=%d too large for the covariance pass", T);
     SEMICRF_CHECK_ARG(ws != nullptr, "workspace is NULL");
     if (ws_bytes < expectation_workspace_bytes(T, B)) { set_error("workspace too small for covariance"); return SEMICRF_EWORKSPACE; }
+    if (int rc = check_ws(ws, "semicrf_covariance")) return rc;
     launch_covariance(score, noise, weight ? weight : score, noiseWeight, gout, T, B, C, Cn, ws, (hipStream_t)stream);
     SEMICRF_CHECK_LAUNCH("semicrf_covariance");
     return SEMICRF_OK;
@@ -701,6 +721,7 @@ int semicrf_marginal_decode(const float* score, const float* noise, const float*
     SEMICRF_CHECK_ARG((long long)((T + 63) / 64) * ((T + 63) / 64 + 1) / 2 < 65536, "T=%d too large for the marginal decode", T);
     SEMICRF_CHECK_ARG(ws != nullptr, "workspace is NULL");
     if (ws_bytes < marginal_decode_workspace_bytes(T, B)) { set_error("workspace too small for marginal_decode"); return SEMICRF_EWORKSPACE; }
+    if (int rc = check_ws(ws, "semicrf_marginal_decode")) return rc;
     launch_marginal_decode(score, v, q, logZ, T, B, tau, tau_stride, pairs, probs, (long long)cap, offsets, ws, (hipStream_t)stream);
     SEMICRF_CHECK_LAUNCH("semicrf_marginal_decode");
     return SEMICRF_OK;
@@ -738,6 +759,7 @@ int semicrf_marginal_decode_tol(const float* score, const float* noise, const fl
     SEMICRF_CHECK_ARG((long long)((T + 63) / 64) * ((T + 63) / 64 + 1) / 2 < 65536, "T=%d too large for the marginal decode", T);
     SEMICRF_CHECK_ARG(ws != nullptr, "workspace is NULL");
     if (ws_bytes < marginal_decode_tol_workspace_bytes(T, B)) { set_error("workspace too small for marginal_decode_tol"); return SEMICRF_EWORKSPACE; }
+    if (int rc = check_ws(ws, "semicrf_marginal_decode_tol")) return rc;
     launch_marginal_decode_tol(score, v, q, logZ, T, B, tau, tau_stride, tol_begin, tol_end, pairs, probs, (long long)cap, offsets, ws,
                                (hipStream_t)stream);
     SEMICRF_CHECK_LAUNCH("semicrf_marginal_decode_tol");
@@ -757,6 +779,7 @@ int semicrf_mbr_select(const int32_t* pairs, const float* weight, const int32_t*
     SEMICRF_CHECK_ARG(pairs_out && probs_out && offsets_out && gain && cap >= 0, "pairs_out/probs_out/offsets_out/gain must be non-NULL and cap >= 0");
     SEMICRF_CHECK_ARG(ws != nullptr, "workspace is NULL");
     if (ws_bytes < mbr_select_workspace_bytes(T, B)) { set_error("workspace too small for mbr_select"); return SEMICRF_EWORKSPACE; }
+    if (int rc = check_ws(ws, "semicrf_mbr_select")) return rc;
     launch_mbr_select(pairs, weight, offsets, (long long)K, T, B, tau, tau_stride, pairs_out, probs_out, (long long)cap, offsets_out, gain,
                       ws, (hipStream_t)stream);
     SEMICRF_CHECK_LAUNCH("semicrf_mbr_select");
@@ -785,6 +808,7 @@ int semicrf_eval_path(const float* score, const float* noise, int T, int B, cons
     SEMICRF_CHECK_ARG(offsets && out, "offsets/out must be non-NULL");
     SEMICRF_CHECK_ARG(K >= 0 && K < (1ll << 31) && (K == 0 || pairs), "bad interval count");
     (void)ws; (void)ws_bytes;
+    if (int rc = check_ws(ws, "semicrf_eval_path")) return rc;
     launch_eval_path(score, noise, T, B, (int)K, pairs, offsets, out, (hipStream_t)stream);
     SEMICRF_CHECK_LAUNCH("semicrf_eval_path");
     return SEMICRF_OK;
