@@ -34,6 +34,88 @@ def test_library_builds_and_exports_header_symbols():
     assert loaded.semicrf_workspace_bytes(_lib.OP_VITERBI, 1024, 352) > 0
 
 
+def test_ctypes_prototypes_come_from_the_header():
+    """_lib._SIGS is parsed from include/semicrf_hip.h (transkun_amd/_abi.py).  Six prototypes are written out here by hand, so that
+    the parser is held against something that is not itself; the count is held against this module's own regex."""
+    from transkun_amd import _lib
+    vp, i, i64, sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_size_t
+    pinned = {
+        "semicrf_last_error": (ctypes.c_char_p, []),
+        "semicrf_workspace_bytes": (sz, [i, i, i]),
+        "semicrf_logz_fwd": (i, [vp, vp, i, i, vp, vp, vp, sz, vp]),
+        "semicrf_sample": (i, [vp, vp, vp, i, i, i64, i, ctypes.c_uint64, vp, vp, i64, vp, vp, sz, vp]),
+        "semicrf_adabelief_step": (i, [vp, vp, vp, vp, i64, vp, _lib.AdaBeliefGroups, vp]),
+        "semicrf_axial_attention_bwd": (i, [vp] * 8 + [i64] * 2 + [i] * 4 + [i64] * 24 + [vp]),
+    }
+    for name, sig in pinned.items():
+        assert _lib._SIGS[name] == sig, name
+    assert _lib._SIGS["semicrf_sample"][1][7] is ctypes.c_uint64
+    assert _lib._SIGS["semicrf_adabelief_step"][1][6] is _lib.AdaBeliefGroups
+    declared = _declared_functions()
+    assert len(_lib._SIGS) == len(declared) == len(_lib.EXPORTED)
+    assert _lib.EXPORTED == tuple(_lib._SIGS)
+    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "semicrf_hip.h")).read(), flags=re.S)
+    order = [n for n in re.findall(r"\b([a-z_0-9]+)\s*\([^;{]*\)\s*;", src) if n in set(declared)]
+    assert list(_lib.EXPORTED) == order                       # the header's order
+
+
+def test_header_parser_never_guesses():
+    from transkun_amd import _abi
+    with pytest.raises(_abi.SemiCRFLibraryError, match=r"f.*long double"):
+        _abi.prototypes("int f(long double x);", {})
+    with pytest.raises(_abi.SemiCRFLibraryError):
+        _abi.prototypes("int g(struct_by_value s);", {})
+    assert _abi.prototypes("const char* h(void); void k(const unsigned char* p, size_t n);", {}) == {
+        "h": (ctypes.c_char_p, []), "k": (None, [ctypes.c_void_p, ctypes.c_size_t])}
+    got = _abi.constants("#define SEMICRF_X foo(1)\n#define SEMICRF_Y ((1 << 4) - 1) /* c */\n#define SEMICRF_Z 0x10\n"
+                         "#define SEMICRF_W 1.5\n#define SEMICRF_V 010\n#define OTHER 3\n#define SEMICRF_GUARD\n")
+    assert got == {"Y": 15, "Z": 16}
+
+
+def test_constants_come_from_the_header():
+    from transkun_amd import _lib, attributes, scorer
+    import importlib
+    mod = importlib.import_module("transkun_amd.CRF.NeuralSemiCRFInterval")
+    assert _lib.OP_LOGZ_FWD == 0 and _lib.OP_VITERBI == 2 and _lib.OP_ATTRIBUTE_HEADS_BWD == 13
+    assert _lib.TOL_MAX == 8 and _lib.HEADS_ROW_TILE == 64 and _lib.OPTIM_MAX_GROUPS == 8 and _lib.ABI_VERSION == 2
+    assert _lib.LEN_MODES == {"linear": 0, "sqrt": 1, "none": 2}
+    assert scorer.BF16X3 == 4 and scorer.LEN_BF16X3 == 16 and scorer.PROJ_TN_BF16X3 == 0x40000000
+    assert attributes.VELOCITY_CRITERIA == {"hamming": 0, "mse": 1, "match": 2, "mae": 3}
+    assert mod.GRAD_UPPER_IS_ZERO == 1
+    assert _lib.PTAB_COVERED == 1 << 30 and _lib.PTAB_NONE == (1 << 30) - 1
+
+
+def test_structures_match_the_header():
+    """The two ctypes.Structure classes stay hand-written: their fields are held against the header's typedef struct text, in
+    name, order and C type, and their sizes against the layout the header spells out (it pads explicitly with pad_)."""
+    from transkun_amd import _lib
+    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "semicrf_hip.h")).read(), flags=re.S)
+    ctype = {"int64_t": ctypes.c_int64, "int32_t": ctypes.c_int32, "float": ctypes.c_float}
+    size = {"int64_t": 8, "int32_t": 4, "float": 4}
+
+    def members(name):
+        body = re.search(r"typedef\s+struct\s+%s\s*\{(.*?)\}\s*%s\s*;" % (name, name), src, flags=re.S).group(1)
+        out = []
+        for decl in body.split(";"):
+            if decl.strip():
+                kind, names = decl.split(None, 1)
+                out += [(kind, n.strip()) for n in names.split(",")]
+        return out
+
+    group = members("semicrf_adabelief_group")
+    assert [(n, ctype[k]) for k, n in group] == list(_lib.AdaBeliefGroup._fields_)
+    group_bytes = sum(size[k] for k, _ in group)
+    assert ctypes.sizeof(_lib.AdaBeliefGroup) == group_bytes == 48
+
+    groups = members("semicrf_adabelief_groups")
+    assert groups == [("int32_t", "n"), ("int32_t", "pad_"), ("semicrf_adabelief_group", "g[SEMICRF_OPTIM_MAX_GROUPS]")]
+    fields = list(_lib.AdaBeliefGroups._fields_)
+    assert [f[0] for f in fields] == ["n", "pad_", "g"]
+    assert fields[0][1] is ctypes.c_int32 and fields[1][1] is ctypes.c_int32
+    assert fields[2][1]._type_ is _lib.AdaBeliefGroup and fields[2][1]._length_ == _lib.OPTIM_MAX_GROUPS
+    assert ctypes.sizeof(_lib.AdaBeliefGroups) == 4 + 4 + _lib.OPTIM_MAX_GROUPS * group_bytes
+
+
 def test_invalid_arguments_are_rejected_without_gpu():
     from transkun_amd import _lib
     lib = _lib.load()

@@ -189,7 +189,7 @@ def _logz_fwd_raw(score, noise, want_v: bool):
 #     gradient into it) moves the counter, and the buffer is then written in full (zeros included) on its next use.
 # The pool keeps `P.detach()` (same storage, same version counter, its own TensorImpl) and not P itself: autograd takes a
 # gradient as .grad without a copy only when nobody else holds the tensor object.
-GRAD_UPPER_IS_ZERO = 1          # include/semicrf_hip.h: SEMICRF_GRAD_UPPER_IS_ZERO
+GRAD_UPPER_IS_ZERO = _lib.GRAD_UPPER_IS_ZERO
 
 
 # torch._C._storage_Use_Count is a private binding (present in every torch 2.x this was run on): without it the pool cannot know

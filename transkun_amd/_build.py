@@ -32,35 +32,59 @@ def sources():
     return sorted(glob.glob(os.path.join(CSRC, "*.hip")))
 
 
+def _headers():
+    return glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(HERE, "..", "include", "*.h"))
+
+
 def _stale() -> bool:
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    deps = sources() + glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(HERE, "..", "include", "*.h"))
-    return any(os.path.getmtime(d) > t for d in deps)
+    return any(os.path.getmtime(d) > t for d in sources() + _headers())
 
 
-def build_variant(name: str, defines, verbose: bool = False) -> str:
-    """Development helper: build libsemicrf_<name>.so with extra -D defines (timing ablations)."""
-    objdir = os.path.join(HERE, "csrc", "_obj_" + name)
+def _compile_and_link(objdir: str, out: str, defines=(), warn=(), incremental: bool = False, verbose: bool = False) -> str:
+    """The one hipcc recipe: every source to an object in `objdir` (all compilers at once), then one shared library, moved to
+    `out` when it is whole.  incremental: an object newer than its source and every header is kept."""
     os.makedirs(objdir, exist_ok=True)
-    flags = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-fno-fast-math", "-ffp-contract=off",
-             "-Wno-unused-function"] + ["-D" + d for d in defines]
+    flags = (["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-fno-fast-math", "-ffp-contract=off"] + list(warn)
+             + ["-Wno-unused-function"] + ["-D" + d for d in defines])
+    hdrs = _headers()
     objs, procs = [], []
     for src in sources():
         obj = os.path.join(objdir, os.path.basename(src)[:-4] + ".o")
         objs.append(obj)
+        if incremental and os.path.exists(obj) and os.path.getmtime(obj) > max(os.path.getmtime(x) for x in [src] + hdrs):
+            continue
         cmd = [_hipcc()] + flags + EXTRA_FLAGS.get(os.path.basename(src), []) + ["-c", src, "-o", obj]
+        if verbose:
+            print(" ".join(cmd))
         procs.append(subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT))
+    failed = False
     for p in procs:
-        out, _ = p.communicate()
-        if p.returncode != 0:
-            sys.stderr.write(out.decode())
-            raise RuntimeError("hipcc failed")
+        text, _ = p.communicate()
+        if p.returncode != 0 or (verbose and text):
+            sys.stderr.write(text.decode())
+        failed = failed or p.returncode != 0
+    if failed:
+        raise RuntimeError("hipcc failed (" + os.path.basename(out) + ")")
+    tmp = out + ".tmp"
+    # --no-undefined: a function that csrc/launchers.h declares and a caller uses, but no file defines with that signature,
+    # fails the link here instead of the first load of the library
+    cmd = [_hipcc(), "--offload-arch=" + ARCH, "-shared", "-fPIC", "-Wl,--no-undefined", "-o", tmp] + objs
+    if verbose:
+        print(" ".join(cmd))
+    subprocess.check_call(cmd)
+    os.replace(tmp, out)
+    return out
+
+
+def build_variant(name: str, defines, verbose: bool = False) -> str:
+    """Development helper: build libsemicrf_<name>.so with extra -D defines (timing ablations)."""
     vdir = os.path.join(HERE, "_variants", name)
     os.makedirs(vdir, exist_ok=True)
-    out = os.path.join(vdir, "libsemicrf_hip.so")
-    subprocess.check_call([_hipcc(), "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", out] + objs)
+    out = _compile_and_link(os.path.join(CSRC, "_obj_" + name), os.path.join(vdir, "libsemicrf_hip.so"), defines=defines,
+                            verbose=verbose)
     # the torch-ops shim next to it (it finds "libsemicrf_hip.so" by $ORIGIN): SEMICRF_LIB=<vdir>/libsemicrf_hip.so
     shutil.copy(build_torch_shim(), os.path.join(vdir, "libsemicrf_torch.so"))
     return out
@@ -117,30 +141,10 @@ def build_debug(force: bool = False, verbose: bool = False) -> str:
     scorer (scorer_mfma.hip: interval_score_tile_kernel<64|128>), all of semicrf_debug_score_variant's choices and the launch
     geometry knobs of tools/ (read from the environment).  The parity tests load it explicitly (through ctypes, the same C ABI)
     as the bit-level reference of the default kernels; nothing under transkun_amd/ uses it."""
-    deps = sources() + glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(HERE, "..", "include", "*.h"))
+    deps = sources() + _headers()
     if not force and os.path.exists(DEBUG_LIB) and os.path.getmtime(DEBUG_LIB) > max(os.path.getmtime(d) for d in deps):
         return DEBUG_LIB
-    objdir = os.path.join(CSRC, "_obj_debug")
-    os.makedirs(objdir, exist_ok=True)
-    flags = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-fno-fast-math", "-ffp-contract=off", "-Wno-unused-function",
-             "-DSEMICRF_DEBUG_BUILD=1"]
-    objs, procs = [], []
-    for src in sources():
-        obj = os.path.join(objdir, os.path.basename(src)[:-4] + ".o")
-        objs.append(obj)
-        cmd = [_hipcc()] + flags + EXTRA_FLAGS.get(os.path.basename(src), []) + ["-c", src, "-o", obj]
-        if verbose:
-            print(" ".join(cmd))
-        procs.append(subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT))
-    for p in procs:
-        out, _ = p.communicate()
-        if p.returncode != 0:
-            sys.stderr.write(out.decode())
-            raise RuntimeError("hipcc failed (debug library)")
-    tmp = DEBUG_LIB + ".tmp"
-    subprocess.check_call([_hipcc(), "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", tmp] + objs)
-    os.replace(tmp, DEBUG_LIB)
-    return DEBUG_LIB
+    return _compile_and_link(os.path.join(CSRC, "_obj_debug"), DEBUG_LIB, defines=["SEMICRF_DEBUG_BUILD=1"], verbose=verbose)
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
@@ -154,40 +158,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
 def _build_hip(force: bool = False, verbose: bool = False) -> str:
     if not force and not _stale():
         return LIB
-    objdir = os.path.join(HERE, "csrc", "_obj")
-    os.makedirs(objdir, exist_ok=True)
-    flags = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-fno-fast-math",
-             "-ffp-contract=off", "-Wall", "-Wno-unused-function"]
-    procs = []
-    objs = []
-    for src in sources():
-        obj = os.path.join(objdir, os.path.basename(src)[:-4] + ".o")
-        objs.append(obj)
-        hdrs = glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(HERE, "..", "include", "*.h"))
-        if (not force and os.path.exists(obj)
-                and os.path.getmtime(obj) > max(os.path.getmtime(x) for x in [src] + hdrs)):
-            continue
-        extra = EXTRA_FLAGS.get(os.path.basename(src), [])
-        cmd = [_hipcc()] + flags + extra + ["-c", src, "-o", obj]
-        if verbose:
-            print(" ".join(cmd))
-        procs.append((src, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)))
-    failed = False
-    for src, p in procs:
-        out, _ = p.communicate()
-        if p.returncode != 0 or (verbose and out):
-            sys.stderr.write(out.decode())
-        if p.returncode != 0:
-            failed = True
-    if failed:
-        raise RuntimeError("hipcc failed")
-    tmp = LIB + ".tmp"
-    cmd = [_hipcc(), "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", tmp] + objs
-    if verbose:
-        print(" ".join(cmd))
-    subprocess.check_call(cmd)
-    os.replace(tmp, LIB)
-    return LIB
+    return _compile_and_link(os.path.join(CSRC, "_obj"), LIB, warn=["-Wall"], incremental=not force, verbose=verbose)
 
 
 if __name__ == "__main__":

@@ -180,7 +180,7 @@ def attribute_log_prob_torch(logitsVelocity, ofLogits, velocity, ofRefined, ofPr
 # ----------------------------------------------------------------------------------------------------------------------
 # the attribute-head readout of transcription (TransKun.transcribeFrames, ModelTransformer.py:590-651)
 # ----------------------------------------------------------------------------------------------------------------------
-VELOCITY_CRITERIA = {"hamming": 0, "mse": 1, "match": 2, "mae": 3}          # SEMICRF_VEL_*
+VELOCITY_CRITERIA = {"hamming": _lib.VEL_HAMMING, "mse": _lib.VEL_MSE, "match": _lib.VEL_MATCH, "mae": _lib.VEL_MAE}
 
 
 def attribute_decode(logitsVelocity: torch.Tensor, ofLogits: torch.Tensor, criterion: str = "hamming"):

@@ -23,6 +23,7 @@
 // fp32, running-maximum log-sum-exp on __expf; fixed summation order: two calls are bit-identical.
 #include <mutex>
 #include "posterior_cell.h"
+#include "launchers.h"
 
 namespace semicrf {
 

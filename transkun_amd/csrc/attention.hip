@@ -22,6 +22,7 @@
 // whatever the batch, its position in it and the strides are.  LDS: 32 kt (d + 1) + 4 (32 max(d + 1, 40) + 32) floats: 48 KB at
 // L = 149, d = 40 (two workgroups per CU, which the 256 registers of that instantiation allow), 100 KB at the largest shape.
 #include "common.h"
+#include "launchers.h"
 #include "attention_math.h"
 
 namespace semicrf {

@@ -24,6 +24,7 @@
 // the largest shape.  Rows past Lq / Lk are never loaded; padded keys are masked before the maximum; padded head columns are zeros in
 // registers; a padded query has dout = 0 and D = 0, so it adds exact zeros to dk and dv.
 #include "common.h"
+#include "launchers.h"
 #include "attention_math.h"
 
 namespace semicrf {

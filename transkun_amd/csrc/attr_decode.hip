@@ -16,6 +16,7 @@
 // No atomics, no LDS, nothing shared between rows: a row's result depends on that row alone and is bit-identical from run to run.
 // Memory is never indexed by a computed class.
 #include "common.h"
+#include "launchers.h"
 #include "attr_decode_math.h"
 
 namespace semicrf {

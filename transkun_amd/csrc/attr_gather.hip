@@ -9,6 +9,7 @@
 //   symIdx[i] = c % nSym,   scatterIdx[i] = c      (the reference's symIdx_all / scatterIdx_all, int64)
 // One wave per interval, 16-byte accesses; HBM-bound (reads 2 D floats, writes 3 D per interval).
 #include "common.h"
+#include "launchers.h"
 #include "chain_search.h"
 
 namespace semicrf {

@@ -23,6 +23,7 @@
 // chain of operations -- bit-identical whatever K is, wherever the row sits and whatever other rows hold.  Ragged edges (3D, the
 // last slice of a head, the rows past K, N) are padded with exact zeros; rows past K are computed on zeros and never stored.
 #include "common.h"
+#include "launchers.h"
 #include "chain_search.h"
 #include "attr_heads_math.h"
 

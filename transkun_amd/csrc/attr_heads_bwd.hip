@@ -17,6 +17,7 @@
 //   reduce    the planes added in ascending chunk order -> dW1, db1, dW2, db2
 // Tile sizes do not depend on K; ragged edges are padded with exact zeros.
 #include "common.h"
+#include "launchers.h"
 #include "chain_search.h"
 #include "attr_heads_math.h"
 

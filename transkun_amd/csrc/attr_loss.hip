@@ -11,6 +11,7 @@
 // binary search in offsets, logsumexp recomputed (128 exps per row are cheaper than a saved array is to carry around):
 //   dLogitsVelocity = g (onehot(v) - softmax),  dOfLogits = g (x - sigmoid + logC') | g (p - sigmoid)
 #include "common.h"
+#include "launchers.h"
 #include "chain_search.h"
 #include "attr_loss_math.h"
 

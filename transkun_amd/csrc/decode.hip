@@ -9,6 +9,7 @@
 // other endpoint chosen at t.
 #include <atomic>
 #include "common.h"
+#include "launchers.h"
 
 namespace semicrf {
 
@@ -201,9 +202,6 @@ __global__ __launch_bounds__(256) void pack_kernel(const int* __restrict__ regio
         }
     }
 }
-
-void launch_pack(const int* region, const int* counts, int T, int B, int forward, int* pairs, long long cap, int* offsets,
-                 hipStream_t stream, const unsigned* err, int nerr, int err_stride);
 
 void launch_backtrack(const int* code, int T, int B, const int* start, int forward, int* region,
                       int* counts, int* pairs, long long cap, int* offsets, hipStream_t stream,

@@ -8,6 +8,7 @@
 // at most T-1 values per chain.  Sums are accumulated in double (torch's CPU cumsum does the same), in an order
 // that is fixed by the thread layout: evalPath is bit-reproducible run to run.
 #include "common.h"
+#include "launchers.h"
 #include "pathscore.h"
 
 namespace semicrf {

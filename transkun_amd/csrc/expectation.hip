@@ -27,6 +27,7 @@
 //   covariance_noise_kernel   Cn, one thread per (gap, chain).
 // No atomics, fixed summation order: two calls are bit-identical.
 #include "common.h"
+#include "launchers.h"
 
 namespace semicrf {
 

@@ -22,6 +22,7 @@
 // Epilogue: x + (acc + b2) * scale from Xs, stored by rows.  Ragged edges (rows past the last token, the last chunk of hidden, the
 // last column block of D) are exact zeros formed in registers.
 #include "common.h"
+#include "launchers.h"
 #include "ffn_math.h"
 
 namespace semicrf {

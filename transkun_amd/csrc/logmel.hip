@@ -16,6 +16,7 @@
 // (top step): no conflict but for two lanes of the top step that wrap; twiddle reads are 2-way at worst.  The split pass reads Z in
 // bit-reversed order (8-way, one pass in P / 3 + 2).
 #include "common.h"
+#include "launchers.h"
 #include "logmel_math.h"
 
 namespace semicrf {

@@ -24,6 +24,7 @@
 // No atomics: every word has one writer and every sum a fixed order; the result is a pure function of the inputs.
 // marginal_tol.hip (semicrf_marginal_decode_tol) reuses the scans and the workspace layout with a count and a write pass of its own.
 #include "common.h"
+#include "launchers.h"
 #include "posterior_cell.h"
 
 namespace semicrf {

@@ -22,12 +22,10 @@
 // The scans and the offsets kernel of marginal_decode.hip are reused (marginal_decode_scans); the workspace is that of
 // semicrf_marginal_decode.  No atomics: every word has one writer and every sum a fixed order.
 #include "common.h"
+#include "launchers.h"
 #include "posterior_cell.h"
 
 namespace semicrf {
-
-size_t marginal_decode_workspace_bytes(int T, int B);                                       // marginal_decode.hip
-void marginal_decode_scans(int* cnt, int* coltot, int* tot, const float* v, int T, int B, int* offsets, hipStream_t stream);
 
 namespace {
 constexpr int XT = 64;                      // tile edge (frames): marginal_decode.hip's, the masks are 64-bit row words

@@ -3,6 +3,7 @@
 // reads the lower triangle of score once, writes the full [T][T][B] gradient once
 // (zeros above the diagonal are part of the reference's contract).
 #include "common.h"
+#include "launchers.h"
 
 namespace semicrf {
 

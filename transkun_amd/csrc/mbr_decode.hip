@@ -24,11 +24,9 @@
 //
 // Registers / scratch (hipcc -O3, gfx950, -Rpass-analysis=kernel-resource-usage): see DESIGN.md §3 "MBR path decoding".
 #include "common.h"
+#include "launchers.h"
 
 namespace semicrf {
-
-void launch_backtrack(const int* code, int T, int B, const int* start, int forward, int* region, int* counts, int* pairs,
-                      long long cap, int* offsets, hipStream_t stream, const unsigned* err, int nerr, int err_stride);
 
 namespace {
 constexpr int MBR_CODE_DIAG = 0x40000000;   // decode.hip: CODE_DIAG

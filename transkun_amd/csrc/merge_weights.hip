@@ -14,6 +14,7 @@
 //     dWk[r][i] = sum_j Wq[r][j] dWm[i][j] + bq[r] dbm[i]        dbk[r] = sum_j Wq[r][j] dWm[size][j] + bq[r] dbm[size]
 //     dwd = dWm[size + 1],  dbd = dbm[size + 1]
 #include "common.h"
+#include "launchers.h"
 
 namespace semicrf {
 

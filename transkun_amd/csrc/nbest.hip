@@ -19,6 +19,7 @@
 // Walk: one workgroup per chain stages the chain's T x k code table in LDS; lane r walks rank r from the start frame, the state
 // being (frame, rank), and writes decode.hip's region layout (walk order), so its offsets / pack kernels finish the job.
 #include "common.h"
+#include "launchers.h"
 
 namespace semicrf {
 
@@ -259,9 +260,6 @@ __global__ __launch_bounds__(64) void nbest_walk_kernel(const int* __restrict__ 
     }
     counts[idx] = n;
 }
-
-void launch_pack(const int* region, const int* counts, int T, int B, int forward, int* pairs, long long cap, int* offsets,
-                 hipStream_t stream, const unsigned* err, int nerr, int err_stride);
 
 static int nbest_kp(int k) { return k <= 1 ? 1 : k <= 2 ? 2 : k <= 4 ? 4 : k <= 8 ? 8 : 16; }
 

@@ -11,6 +11,7 @@
 //                      index -- no table in memory -- and an access that crosses a boundary gives each element its own group.
 #include <algorithm>
 #include "common.h"
+#include "launchers.h"
 #include "optim_math.h"
 
 namespace semicrf {

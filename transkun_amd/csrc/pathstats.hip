@@ -27,6 +27,7 @@
 // three walks of a chain are independent of one another and advance in ONE loop, so their loads overlap.  Every pair is one 8-byte
 // load.  A chain's lists are validated in full before anything is counted; no workspace, no atomics, no host synchronisation.
 #include "common.h"
+#include "launchers.h"
 
 namespace semicrf {
 

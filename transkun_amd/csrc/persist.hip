@@ -32,6 +32,7 @@
 #include <atomic>
 #include <stdlib.h>
 #include "common.h"
+#include "launchers.h"
 #include "pathscore.h"
 
 #ifndef SEMICRF_PANEL_PROBES

@@ -21,6 +21,7 @@
 //   posterior_entropy_kernel  per chain the sum of those partials, in frame order.
 // The result is a pure function of the inputs (two calls are bit-identical).
 #include "common.h"
+#include "launchers.h"
 #include "posterior_cell.h"
 
 namespace semicrf {

@@ -16,6 +16,7 @@
 // and the same data is walked with ds_read_b32.  Everything a lane asks for outside its matrix is masked by the buffer's range
 // check (the row part of every offset travels in the VGPR), so that no value from outside ever meets a matrix instruction.
 #include "common.h"
+#include "launchers.h"
 
 #include <type_traits>
 
@@ -627,9 +628,6 @@ size_t proj_tn_workspace_bytes(long long M, int R, int N)
 
 // dW[R (+2)][N] = A[:, :R]^T X, db = column sums of A (first R columns, + the two extra columns extra_col0, +1 when >= 0); rows
 // of dW beyond R + 2 up to total_rows are set to zero
-int launch_proj_tn3_core(const float* A, long long lda, long long M, int R, const float* X, long long ldx, int N, float* part, int Mp,
-                         float* pbias, int bias_pitch, int S, int kslice, hipStream_t stream);      // proj_gemm3.hip
-
 int launch_proj_tn(const float* A, long long lda, long long M, int R, int extra_col0, int total_rows, const float* X, long long ldx, int N,
                    float* dW, long long lddw, float* db, void* ws, size_t ws_bytes, hipStream_t stream)
 {

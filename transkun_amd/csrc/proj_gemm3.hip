@@ -10,13 +10,12 @@
 // chunk's share arrives as plain 16-byte copies; only the A rows (one unit of eight values per lane and chunk) are split in the
 // loop: 0.9 vector instructions per matrix instruction of the workgroup where the scorer's backward has 2.75.
 #include "common.h"
+#include "launchers.h"
 #include "bf16x3.h"
 
 #include <type_traits>
 
 namespace semicrf {
-
-int proj_ncu();
 
 namespace pj3 {
 
@@ -681,9 +680,6 @@ __global__ __launch_bounds__(512, 2) void proj_tn3_kernel(ArgsT P_)
 }
 
 }  // namespace pj3
-
-bool proj_gemm_supported(long long M, int K, int N, const void* A, long long lda, const void* B, long long ldb, const void* out,
-                         long long ldout);
 
 size_t proj_nn3_workspace_bytes(int K, int N)
 {

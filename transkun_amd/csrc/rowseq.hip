@@ -10,6 +10,7 @@
 // Recurrences (NeuralSemiCRFInterval.py):  LSE/FWD :402-410 (alpha), LSE/BWD the flipped half
 // :386-414 (beta), MAX/BWD viterbiBackward :27-51, MAX/FWD viterbi :122-144.
 #include "common.h"
+#include "launchers.h"
 
 namespace semicrf {
 

@@ -11,6 +11,7 @@
 // Random numbers: u = (splitmix64(idx, key) >> 40) * 2^-24, idx = ((k*B + c)*T + t)*2 + r (k the global draw index, r = 0 for the
 // predecessor, 1 for the singleton) -- the same uniforms as the host kernel (cpu_ops.cpp) and transkun_amd.synth.hash_u64_*.
 #include "common.h"
+#include "launchers.h"
 
 namespace semicrf {
 
@@ -154,9 +155,6 @@ __global__ __launch_bounds__(64 * SMP_WAVES) void sample_code_kernel(const float
         code[((size_t)k * B + c) * T + t] = (pred + 1) | (diag ? SMP_CODE_DIAG : 0);
     }
 }
-
-void launch_backtrack(const int* code, int T, int B, const int* start, int forward, int* region, int* counts, int* pairs,
-                      long long cap, int* offsets, hipStream_t stream, const unsigned* err, int nerr, int err_stride);
 
 size_t sample_workspace_bytes(int T, int nB)
 {

@@ -6,6 +6,7 @@
 // impl 1 (this kernel): one thread per output element, fp32 FMA chain over d.  Valid for any
 // shape; the MFMA kernel in scorer_mfma.hip is the product path when D % 64 == 0.
 #include "common.h"
+#include "launchers.h"
 
 namespace semicrf {
 

@@ -12,6 +12,7 @@
 // result with exact-fp32 v_mfma_f32_32x32x2_f32 (A = the G tile from LDS, B = the rows of k or q straight from
 // global memory, 128-byte runs).  Every output element is written once (no atomics): results are deterministic.
 #include "common.h"
+#include "launchers.h"
 
 namespace semicrf {
 

@@ -16,6 +16,7 @@
 // consecutive lanes on consecutive b): no second copy.  The triangular structure shows up as the contraction range
 // of an output tile (dq: b < 128 (i+1); dk: e >= 128 i); items are dealt longest first.
 #include "common.h"
+#include "launchers.h"
 #include "bf16x3.h"
 
 #include <type_traits>

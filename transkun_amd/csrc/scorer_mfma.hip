@@ -12,6 +12,7 @@
 // segments), lower triangle only unless the caller asks for the full square.
 #include <atomic>
 #include "common.h"
+#include "launchers.h"
 #include "scorer_tiles.h"
 #include "bf16x3.h"
 
@@ -1318,10 +1319,6 @@ static int launch_score_tile3(const float* q, const float* k, const float* diag,
                        mode | (dbg << 8), full, S, ntiles, nquadp, Cs, G, rowc, ldrc);
     return 0;
 }
-
-void launch_interval_score_tiled(const float* q, const float* k, const float* diag, const float* rowc, int C, int T, int D,
-                                 long long ldq, long long ldk, long long ldd, long long ldrc, float qscale, int mode, int full,
-                                 float* S, hipStream_t stream, int group, int pitch);      // scorer_tiled.hip
 
 // test hook: force one of the forward kernels (0 register loads, 32 streaming, 64 / 128 shared-operand tiles, 2 the tiles with
 // the epilogue inside the contraction loop (scorer_tiled.hip); -1 = auto)

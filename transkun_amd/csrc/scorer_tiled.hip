@@ -35,6 +35,7 @@
 // with the operand requests into a ring of small LDS buffers, so the loop contains no register load at all and the vmcnt
 // waits count exactly the LDS-DMA pieces (+ the stores, which have a whole chunk to retire).
 #include "common.h"
+#include "launchers.h"
 #include "scorer_tiles.h"
 
 #include <type_traits>

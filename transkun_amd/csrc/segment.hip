@@ -12,6 +12,7 @@
 //                           vector that the next semicrf_viterbi takes as `start` without a host round trip.
 // One thread per chain: the per-symbol `lastEnd` clamp is a sequential recurrence over at most 2T short intervals.
 #include "common.h"
+#include "launchers.h"
 
 namespace semicrf {
 

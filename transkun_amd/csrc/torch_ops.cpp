@@ -85,95 +85,255 @@ inline float* fp(const Tensor& t) { return t.defined() && t.numel() > 0 ? (float
 inline const float* cfp(const Tensor& t) { return t.defined() && t.numel() > 0 ? (const float*)t.data_ptr() : nullptr; }
 inline int32_t* ip(const Tensor& t) { return t.defined() && t.numel() > 0 ? (int32_t*)t.data_ptr() : nullptr; }
 
-// ---- semi-CRF, GPU (dispatch key CUDA = HIP tensors) ------------------------------------------------------------------
+// ---- semi-CRF: the ops registered for both dispatch keys ----------------------------------------------------------------
+// Per op ONE `*_args` function performs every check that does not depend on where the tensors live and returns the raw pointers
+// and sizes; the two twins follow it.  The GPU twin (dispatch key CUDA = HIP tensors) adds the device handling (Ctx / same), the
+// workspace and the call of the C ABI.  The `_cpu` twin (dispatch key CPU) adds all_cpu, the checks that read the tensors'
+// contents (offsets, intervals, forced frames: host-readable only here) and the product's own host kernels (cpu_ops.cpp) --
+// selected by the tensors' device, never a fallback for GPU tensors; its workspace argument is ignored (pass an empty tensor).
+// A check that only one twin makes is written in that twin.
+inline int64_t pairs_cap(const Tensor& pairs)
+{
+    STD_TORCH_CHECK(pairs.dim() == 2 && pairs.size(1) == 2, "semicrf: pairs must be [cap, 2]");
+    return pairs.size(0);
+}
+inline int64_t pairs_cap1(const Tensor& pairs)
+{
+    STD_TORCH_CHECK(pairs.dim() == 2 && pairs.size(1) == 2 && pairs.size(0) >= 1, "semicrf: pairs must be [cap, 2], cap >= 1");
+    return pairs.size(0);
+}
+// host-readable checks of the `_cpu` twins
+inline void frames_in_range(const int32_t* f, const Dims& d, const char* what)       // forced start / end frames (null: none)
+{
+    if (f)
+        for (int c = 0; c < d.B; ++c) STD_TORCH_CHECK(f[c] >= 0 && f[c] < d.T, "semicrf: ", what, " out of range");
+}
+inline void check_offsets_cover(const int32_t* offsets, int64_t K, int B)
+{
+    STD_TORCH_CHECK(offsets[0] == 0 && offsets[B] == K, "semicrf: offsets do not match the interval count");
+    for (int c = 0; c < B; ++c) STD_TORCH_CHECK(offsets[c] <= offsets[c + 1], "semicrf: offsets must ascend");
+}
+inline void check_path(const int32_t* pairs, int64_t K, const int32_t* offsets, int T, int B)      // 0 <= begin <= end < T
+{
+    check_offsets_cover(offsets, K, B);
+    for (int64_t i = 0; i < K; ++i)
+        STD_TORCH_CHECK(pairs[2 * i] >= 0 && pairs[2 * i] <= pairs[2 * i + 1] && pairs[2 * i + 1] < T, "semicrf: interval out of range");
+}
+inline void check_cells(const int32_t* pairs, int64_t K, const int32_t* offsets, int T, int B)     // any order of begin and end
+{
+    check_offsets_cover(offsets, K, B);
+    for (int64_t i = 0; i < 2 * K; ++i) STD_TORCH_CHECK(pairs[i] >= 0 && pairs[i] < T, "semicrf: interval out of range");
+}
+
+struct LogzFwdArgs { Dims d; const float *score, *noise; float *logZ, *v; };                  // v: null when not wanted
+inline LogzFwdArgs logz_fwd_args(const Tensor& score, const Tensor& noise, const Tensor& logZ, const Tensor& v, bool want_v)
+{
+    const Dims d = crf_dims(score, noise);
+    return LogzFwdArgs{d, cfp(score), cfp(noise), f32w(logZ, d.B, "logZ"), want_v ? f32w(v, (int64_t)d.T * d.B, "v") : nullptr};
+}
 void logz_fwd(Tensor score, Tensor noise, Tensor logZ, Tensor v, bool want_v, Tensor ws)
 {
     Ctx c(score); c.same(score, noise, logZ, v, ws);
+    const LogzFwdArgs a = logz_fwd_args(score, noise, logZ, v, want_v);
+    check(semicrf_logz_fwd(a.score, a.noise, a.d.T, a.d.B, a.logZ, a.v, bytes(ws, "ws"), (size_t)ws.numel(), c.stream), "semicrf_logz_fwd");
+}
+void logz_fwd_cpu(Tensor score, Tensor noise, Tensor logZ, Tensor v, bool want_v, Tensor ws)
+{
+    all_cpu(score, noise, logZ, v);
+    const LogzFwdArgs a = logz_fwd_args(score, noise, logZ, v, want_v);
+    std::vector<float> scratch;
+    if (!want_v) scratch.resize((size_t)a.d.T * a.d.B);
+    semicrf_cpu::logz_fwd(a.score, a.noise, a.d.T, a.d.B, a.logZ, want_v ? a.v : scratch.data());
+}
+
+struct LogzBwdArgs { Dims d; const float *score, *noise, *v, *logZ, *gout; float *dScore, *dNoise, *q; };      // q: null when not wanted
+inline LogzBwdArgs logz_bwd_args(const Tensor& score, const Tensor& noise, const Tensor& v, const Tensor& logZ, const Tensor& gout,
+                                 const Tensor& dScore, const Tensor& dNoise, const Tensor& q, bool want_q)
+{
     const Dims d = crf_dims(score, noise);
     const int64_t TB = (int64_t)d.T * d.B;
-    check(semicrf_logz_fwd(cfp(score), cfp(noise), d.T, d.B, f32w(logZ, d.B, "logZ"), want_v ? f32w(v, TB, "v") : nullptr, bytes(ws, "ws"),
-                           (size_t)ws.numel(), c.stream),
-          "semicrf_logz_fwd");
+    return LogzBwdArgs{d, cfp(score), cfp(noise), f32(v, TB, "v"), f32(logZ, d.B, "logZ"), f32(gout, d.B, "gout"),
+                       f32w(dScore, TB * d.T, "dScore"), f32w(dNoise, TB - d.B, "dNoise"), want_q ? f32w(q, TB, "q") : nullptr};
 }
 void logz_bwd(Tensor score, Tensor noise, Tensor v, Tensor logZ, Tensor gout, Tensor dScore, Tensor dNoise, Tensor q, bool want_q,
               int64_t flags, Tensor ws)
 {
     Ctx c(score); c.same(score, noise, v, logZ, gout, dScore, dNoise, q, ws);
-    const Dims d = crf_dims(score, noise);
-    const int64_t TB = (int64_t)d.T * d.B;
-    check(semicrf_logz_bwd_f(cfp(score), cfp(noise), f32(v, TB, "v"), f32(logZ, d.B, "logZ"), f32(gout, d.B, "gout"), d.T, d.B,
-                             f32w(dScore, TB * d.T, "dScore"), f32w(dNoise, TB - d.B, "dNoise"), want_q ? f32w(q, TB, "q") : nullptr,
-                             (int)flags, bytes(ws, "ws"), (size_t)ws.numel(), c.stream),
+    const LogzBwdArgs a = logz_bwd_args(score, noise, v, logZ, gout, dScore, dNoise, q, want_q);
+    check(semicrf_logz_bwd_f(a.score, a.noise, a.v, a.logZ, a.gout, a.d.T, a.d.B, a.dScore, a.dNoise, a.q, (int)flags, bytes(ws, "ws"),
+                             (size_t)ws.numel(), c.stream),
           "semicrf_logz_bwd");
+}
+void logz_bwd_cpu(Tensor score, Tensor noise, Tensor v, Tensor logZ, Tensor gout, Tensor dScore, Tensor dNoise, Tensor q, bool want_q,
+                  int64_t flags, Tensor ws)       // flags: a permission (SEMICRF_GRAD_UPPER_IS_ZERO); the host kernels write everything
+{
+    all_cpu(score, noise, v, logZ, gout, dScore, dNoise, q);
+    const LogzBwdArgs a = logz_bwd_args(score, noise, v, logZ, gout, dScore, dNoise, q, want_q);
+    std::vector<float> scratch;
+    if (!want_q) scratch.resize((size_t)a.d.T * a.d.B);
+    semicrf_cpu::logz_bwd(a.score, a.noise, a.v, a.logZ, a.gout, a.d.T, a.d.B, a.dScore, a.dNoise, want_q ? a.q : scratch.data());
+}
+
+struct BetaArgs { Dims d; const float *score, *noise; float* beta; };
+inline BetaArgs beta_args(const Tensor& score, const Tensor& noise, const Tensor& out)
+{
+    const Dims d = crf_dims(score, noise);
+    return BetaArgs{d, cfp(score), cfp(noise), f32w(out, (int64_t)d.T * d.B, "beta")};
 }
 void beta(Tensor score, Tensor noise, Tensor out, Tensor ws)
 {
     Ctx c(score); c.same(score, noise, out, ws);
+    const BetaArgs a = beta_args(score, noise, out);
+    check(semicrf_beta(a.score, a.noise, a.d.T, a.d.B, a.beta, bytes(ws, "ws"), (size_t)ws.numel(), c.stream), "semicrf_beta");
+}
+void beta_cpu(Tensor score, Tensor noise, Tensor out, Tensor ws)
+{
+    all_cpu(score, noise, out);
+    const BetaArgs a = beta_args(score, noise, out);
+    semicrf_cpu::logz_bwd(a.score, a.noise, nullptr, nullptr, nullptr, a.d.T, a.d.B, nullptr, nullptr, a.beta);
+}
+
+struct AlphaFromArgs { Dims d; const float *score, *noise; const int32_t* start; float *v, *logZ; };
+inline AlphaFromArgs alpha_from_args(const Tensor& score, const Tensor& noise, const Tensor& start, const Tensor& v, const Tensor& logZ)
+{
     const Dims d = crf_dims(score, noise);
-    check(semicrf_beta(cfp(score), cfp(noise), d.T, d.B, f32w(out, (int64_t)d.T * d.B, "beta"), bytes(ws, "ws"), (size_t)ws.numel(), c.stream),
-          "semicrf_beta");
+    return AlphaFromArgs{d, cfp(score), cfp(noise), i32(start, d.B, "start"), f32w(v, (int64_t)d.T * d.B, "v"), f32w(logZ, d.B, "logZ")};
 }
 void alpha_from(Tensor score, Tensor noise, Tensor start, Tensor v, Tensor logZ, Tensor ws)
 {
     Ctx c(score); c.same(score, noise, start, v, logZ, ws);
-    const Dims d = crf_dims(score, noise);
-    check(semicrf_alpha_from(cfp(score), cfp(noise), i32(start, d.B, "start"), d.T, d.B, f32w(v, (int64_t)d.T * d.B, "v"),
-                             f32w(logZ, d.B, "logZ"), bytes(ws, "ws"), (size_t)ws.numel(), c.stream),
+    const AlphaFromArgs a = alpha_from_args(score, noise, start, v, logZ);
+    check(semicrf_alpha_from(a.score, a.noise, a.start, a.d.T, a.d.B, a.v, a.logZ, bytes(ws, "ws"), (size_t)ws.numel(), c.stream),
           "semicrf_alpha_from");
+}
+void alpha_from_cpu(Tensor score, Tensor noise, Tensor start, Tensor v, Tensor logZ, Tensor ws)
+{
+    all_cpu(score, noise, start, v, logZ);
+    const AlphaFromArgs a = alpha_from_args(score, noise, start, v, logZ);
+    semicrf_cpu::alpha_from(a.score, a.noise, a.start, a.d.T, a.d.B, a.v, a.logZ);
+}
+
+struct ViterbiArgs { Dims d; const float *score, *noise; const int32_t* start; int32_t* pairs; int64_t cap; int32_t* offsets; };
+inline ViterbiArgs viterbi_args(const Tensor& score, const Tensor& noise, const Tensor& start, bool has_start, const Tensor& pairs,
+                                const Tensor& offsets)
+{
+    const Dims d = crf_dims(score, noise);
+    const int64_t cap = pairs_cap(pairs);
+    return ViterbiArgs{d, cfp(score), cfp(noise), has_start ? i32(start, d.B, "start") : nullptr, i32(pairs, 0, "pairs"), cap,
+                       i32(offsets, d.B + 1, "offsets")};
 }
 void viterbi(Tensor score, Tensor noise, Tensor start, bool has_start, bool forward, Tensor pairs, Tensor offsets, Tensor ws)
 {
     Ctx c(score); c.same(score, noise, pairs, offsets, ws);
     if (has_start) c.same(score, start);
-    const Dims d = crf_dims(score, noise);
-    STD_TORCH_CHECK(pairs.dim() == 2 && pairs.size(1) == 2, "semicrf: pairs must be [cap, 2]");
-    check(semicrf_viterbi(cfp(score), cfp(noise), d.T, d.B, has_start ? i32(start, d.B, "start") : nullptr, forward ? 1 : 0,
-                          i32(pairs, 0, "pairs"), (int64_t)pairs.size(0), i32(offsets, d.B + 1, "offsets"), bytes(ws, "ws"),
+    const ViterbiArgs a = viterbi_args(score, noise, start, has_start, pairs, offsets);
+    check(semicrf_viterbi(a.score, a.noise, a.d.T, a.d.B, a.start, forward ? 1 : 0, a.pairs, a.cap, a.offsets, bytes(ws, "ws"),
                           (size_t)ws.numel(), c.stream),
           "semicrf_viterbi");
 }
+void viterbi_cpu(Tensor score, Tensor noise, Tensor start, bool has_start, bool forward, Tensor pairs, Tensor offsets, Tensor ws)
+{
+    all_cpu(score, noise, pairs, offsets);
+    if (has_start) all_cpu(start);
+    const ViterbiArgs a = viterbi_args(score, noise, start, has_start, pairs, offsets);
+    frames_in_range(a.start, a.d, "forcedStartPos");
+    semicrf_cpu::viterbi(a.score, a.noise, a.d.T, a.d.B, a.start, forward ? 1 : 0, a.pairs, a.cap, a.offsets);
+}
+
 // posterior sampling (semicrf_sample): key is the 64-bit key as a signed int (two's complement); end: B ints when has_end
+struct SampleArgs { Dims d; const float *score, *noise, *v; const int32_t* end; int32_t* pairs; int64_t cap; int32_t* offsets; };
+inline SampleArgs sample_args(const Tensor& score, const Tensor& noise, const Tensor& v, int64_t k0, int64_t nSample, const Tensor& end,
+                              bool has_end, const Tensor& pairs, const Tensor& offsets)
+{
+    const Dims d = crf_dims(score, noise);
+    STD_TORCH_CHECK(nSample >= 1 && nSample < (1 << 30) && k0 >= 0, "semicrf: bad nSample / k0");
+    const int64_t cap = pairs_cap(pairs);
+    return SampleArgs{d, cfp(score), cfp(noise), f32(v, (int64_t)d.T * d.B, "v"), has_end ? i32(end, d.B, "end") : nullptr,
+                      i32(pairs, 0, "pairs"), cap, i32(offsets, nSample * d.B + 1, "offsets")};
+}
 void sample(Tensor score, Tensor noise, Tensor v, int64_t k0, int64_t nSample, int64_t key, Tensor end, bool has_end, Tensor pairs,
             Tensor offsets, Tensor ws)
 {
     Ctx c(score); c.same(score, noise, v, pairs, offsets, ws);
     if (has_end) c.same(score, end);
-    const Dims d = crf_dims(score, noise);
-    STD_TORCH_CHECK(nSample >= 1 && nSample < (1 << 30) && k0 >= 0, "semicrf: bad nSample / k0");
-    STD_TORCH_CHECK(pairs.dim() == 2 && pairs.size(1) == 2, "semicrf: pairs must be [cap, 2]");
-    check(semicrf_sample(cfp(score), cfp(noise), f32(v, (int64_t)d.T * d.B, "v"), d.T, d.B, k0, (int)nSample, (uint64_t)key,
-                         has_end ? i32(end, d.B, "end") : nullptr, i32(pairs, 0, "pairs"), (int64_t)pairs.size(0),
-                         i32(offsets, nSample * d.B + 1, "offsets"), bytes(ws, "ws"), (size_t)ws.numel(), c.stream),
+    const SampleArgs a = sample_args(score, noise, v, k0, nSample, end, has_end, pairs, offsets);
+    check(semicrf_sample(a.score, a.noise, a.v, a.d.T, a.d.B, k0, (int)nSample, (uint64_t)key, a.end, a.pairs, a.cap, a.offsets,
+                         bytes(ws, "ws"), (size_t)ws.numel(), c.stream),
           "semicrf_sample");
 }
+void sample_cpu(Tensor score, Tensor noise, Tensor v, int64_t k0, int64_t nSample, int64_t key, Tensor end, bool has_end, Tensor pairs,
+                Tensor offsets, Tensor ws)
+{
+    all_cpu(score, noise, v, pairs, offsets);
+    if (has_end) all_cpu(end);
+    const SampleArgs a = sample_args(score, noise, v, k0, nSample, end, has_end, pairs, offsets);
+    STD_TORCH_CHECK(nSample * a.d.B * 2 * a.d.T < (1ll << 31), "semicrf: nSample*B*2T exceeds int32 offsets");      // this twin only
+    frames_in_range(a.end, a.d, "forcedEndPos");
+    semicrf_cpu::sample(a.score, a.noise, a.v, a.d.T, a.d.B, k0, (int)nSample, (uint64_t)key, a.end, a.pairs, a.cap, a.offsets);
+}
+
 // k-best Viterbi (semicrf_viterbi_nbest): rank-major offsets [k*B+1], scores [k][B], npaths [B]
+struct NbestArgs { Dims d; const float *score, *noise; const int32_t* start; int32_t* pairs; int64_t cap; int32_t* offsets; float* scores; int32_t* npaths; };
+inline NbestArgs viterbi_nbest_args(const Tensor& score, const Tensor& noise, int64_t k, const Tensor& start, bool has_start,
+                                    const Tensor& pairs, const Tensor& offsets, const Tensor& scores, const Tensor& npaths)
+{
+    const Dims d = crf_dims(score, noise);
+    STD_TORCH_CHECK(k >= 1 && k <= 16, "semicrf: k must be in [1, 16]");
+    const int64_t cap = pairs_cap(pairs);
+    return NbestArgs{d, cfp(score), cfp(noise), has_start ? i32(start, d.B, "start") : nullptr, i32(pairs, 0, "pairs"), cap,
+                     i32(offsets, k * d.B + 1, "offsets"), f32w(scores, k * d.B, "scores"), i32(npaths, d.B, "npaths")};
+}
 void viterbi_nbest(Tensor score, Tensor noise, int64_t k, Tensor start, bool has_start, bool forward, Tensor pairs, Tensor offsets,
                    Tensor scores, Tensor npaths, Tensor ws)
 {
     Ctx c(score); c.same(score, noise, pairs, offsets, scores, npaths, ws);
     if (has_start) c.same(score, start);
-    const Dims d = crf_dims(score, noise);
-    STD_TORCH_CHECK(k >= 1 && k <= 16, "semicrf: k must be in [1, 16]");
-    STD_TORCH_CHECK(pairs.dim() == 2 && pairs.size(1) == 2, "semicrf: pairs must be [cap, 2]");
-    check(semicrf_viterbi_nbest(cfp(score), cfp(noise), d.T, d.B, (int)k, has_start ? i32(start, d.B, "start") : nullptr,
-                                forward ? 1 : 0, i32(pairs, 0, "pairs"), (int64_t)pairs.size(0), i32(offsets, k * d.B + 1, "offsets"),
-                                f32w(scores, k * d.B, "scores"), i32(npaths, d.B, "npaths"), bytes(ws, "ws"), (size_t)ws.numel(),
-                                c.stream),
+    const NbestArgs a = viterbi_nbest_args(score, noise, k, start, has_start, pairs, offsets, scores, npaths);
+    check(semicrf_viterbi_nbest(a.score, a.noise, a.d.T, a.d.B, (int)k, a.start, forward ? 1 : 0, a.pairs, a.cap, a.offsets, a.scores,
+                                a.npaths, bytes(ws, "ws"), (size_t)ws.numel(), c.stream),
           "semicrf_viterbi_nbest");
 }
+void viterbi_nbest_cpu(Tensor score, Tensor noise, int64_t k, Tensor start, bool has_start, bool forward, Tensor pairs, Tensor offsets,
+                       Tensor scores, Tensor npaths, Tensor ws)
+{
+    all_cpu(score, noise, pairs, offsets, scores, npaths);
+    if (has_start) all_cpu(start);
+    const NbestArgs a = viterbi_nbest_args(score, noise, k, start, has_start, pairs, offsets, scores, npaths);
+    STD_TORCH_CHECK(k * a.d.B * 2 * a.d.T < (1ll << 31), "semicrf: k*B*2T exceeds int32 offsets");                  // this twin only
+    frames_in_range(a.start, a.d, "forcedStartPos");
+    semicrf_cpu::viterbi_nbest(a.score, a.noise, a.d.T, a.d.B, (int)k, a.start, forward ? 1 : 0, a.pairs, a.cap, a.offsets, a.scores,
+                               a.npaths);
+}
+
 // posterior marginals and entropy (semicrf_posteriors): v, q, logZ of the same score / noise
+struct PosteriorsArgs { Dims d; const float *score, *noise, *v, *q, *logZ; float *node, *begin, *end, *single, *noiseP, *entropy; };
+inline PosteriorsArgs posteriors_args(const Tensor& score, const Tensor& noise, const Tensor& v, const Tensor& q, const Tensor& logZ,
+                                      const Tensor& node, const Tensor& begin, const Tensor& end, const Tensor& single,
+                                      const Tensor& noiseP, const Tensor& entropy)
+{
+    const Dims d = crf_dims(score, noise);
+    const int64_t TB = (int64_t)d.T * d.B;
+    return PosteriorsArgs{d, cfp(score), cfp(noise), f32(v, TB, "v"), f32(q, TB, "q"), f32(logZ, d.B, "logZ"), f32w(node, TB, "node"),
+                          f32w(begin, TB, "begin"), f32w(end, TB, "end"), f32w(single, TB, "single"), f32w(noiseP, TB - d.B, "noiseP"),
+                          f32w(entropy, d.B, "entropy")};
+}
 void posteriors(Tensor score, Tensor noise, Tensor v, Tensor q, Tensor logZ, Tensor node, Tensor begin, Tensor end, Tensor single,
                 Tensor noiseP, Tensor entropy, Tensor ws)
 {
     Ctx c(score); c.same(score, noise, v, q, logZ, node, begin, end, single, noiseP, entropy, ws);
-    const Dims d = crf_dims(score, noise);
-    const int64_t TB = (int64_t)d.T * d.B;
-    check(semicrf_posteriors(cfp(score), cfp(noise), f32(v, TB, "v"), f32(q, TB, "q"), f32(logZ, d.B, "logZ"), d.T, d.B,
-                             f32w(node, TB, "node"), f32w(begin, TB, "begin"), f32w(end, TB, "end"), f32w(single, TB, "single"),
-                             f32w(noiseP, TB - d.B, "noiseP"), f32w(entropy, d.B, "entropy"), bytes(ws, "ws"), (size_t)ws.numel(),
-                             c.stream),
+    const PosteriorsArgs a = posteriors_args(score, noise, v, q, logZ, node, begin, end, single, noiseP, entropy);
+    check(semicrf_posteriors(a.score, a.noise, a.v, a.q, a.logZ, a.d.T, a.d.B, a.node, a.begin, a.end, a.single, a.noiseP, a.entropy,
+                             bytes(ws, "ws"), (size_t)ws.numel(), c.stream),
           "semicrf_posteriors");
 }
+void posteriors_cpu(Tensor score, Tensor noise, Tensor v, Tensor q, Tensor logZ, Tensor node, Tensor begin, Tensor end, Tensor single,
+                    Tensor noiseP, Tensor entropy, Tensor ws)
+{
+    all_cpu(score, noise, v, q, logZ, node, begin, end, single, noiseP, entropy);
+    const PosteriorsArgs a = posteriors_args(score, noise, v, q, logZ, node, begin, end, single, noiseP, entropy);
+    semicrf_cpu::posteriors(a.score, a.noise, a.v, a.q, a.logZ, a.d.T, a.d.B, a.node, a.begin, a.end, a.single, a.noiseP, a.entropy);
+}
+
 // posterior expectation / covariance (semicrf_expectation, semicrf_covariance): weight may BE score (read once); nweight is
 // read when has_nw.  ws: the state the pair shares (semicrf_workspace_bytes(SEMICRF_OP_EXPECTATION); the host kernels:
 // (4 T B + 2 B) doubles)
@@ -183,29 +343,72 @@ inline const float* weight_of(const Tensor& weight, const Tensor& score, int64_t
     STD_TORCH_CHECK(weight.numel() == score.numel(), "semicrf: weight must have the shape of score");
     return w;
 }
+inline double* state_cpu(const Tensor& ws, const Dims& d)
+{
+    want(ws, ScalarType::Byte, (int64_t)((4 * (int64_t)d.T * d.B + 2 * d.B) * sizeof(double)), "ws");
+    STD_TORCH_CHECK(((uintptr_t)ws.data_ptr() & 7) == 0, "semicrf: `ws` must be 8-byte aligned");
+    return (double*)ws.data_ptr();
+}
+struct ExpectationArgs { Dims d; const float *score, *noise, *weight, *nweight; float *E, *H; };
+inline ExpectationArgs expectation_args(const Tensor& score, const Tensor& noise, const Tensor& weight, const Tensor& nweight, bool has_nw,
+                                        const Tensor& E, const Tensor& H)
+{
+    const Dims d = crf_dims(score, noise);
+    const int64_t TB = (int64_t)d.T * d.B;
+    return ExpectationArgs{d, cfp(score), cfp(noise), weight_of(weight, score, TB * d.T), has_nw ? f32(nweight, TB - d.B, "noiseWeight") : nullptr,
+                           f32w(E, d.B, "E"), f32w(H, d.B, "H")};
+}
 void expectation(Tensor score, Tensor noise, Tensor weight, Tensor nweight, bool has_nw, Tensor v, Tensor q, Tensor E, Tensor H, Tensor ws)
 {
     Ctx c(score); c.same(score, noise, weight, v, q, E, H, ws);
     if (has_nw) c.same(score, nweight);
+    const ExpectationArgs a = expectation_args(score, noise, weight, nweight, has_nw, E, H);
+    const int64_t TB = (int64_t)a.d.T * a.d.B;
+    check(semicrf_expectation(a.score, a.noise, a.weight, a.nweight, f32(v, TB, "v"), f32(q, TB, "q"),        // v, q: this twin only
+                              a.d.T, a.d.B, a.E, a.H, bytes(ws, "ws"), (size_t)ws.numel(), c.stream),
+          "semicrf_expectation");
+}
+void expectation_cpu(Tensor score, Tensor noise, Tensor weight, Tensor nweight, bool has_nw, Tensor v, Tensor q, Tensor E, Tensor H,
+                     Tensor ws)
+{
+    all_cpu(score, noise, weight, nweight, v, q, E, H, ws);       // the host kernels keep their own alpha / beta: v, q are not read
+    const ExpectationArgs a = expectation_args(score, noise, weight, nweight, has_nw, E, H);
+    semicrf_cpu::expectation(a.score, a.noise, a.weight, a.nweight, a.d.T, a.d.B, a.E, a.H, state_cpu(ws, a.d));
+}
+struct CovarianceArgs { Dims d; const float *score, *noise, *weight, *nweight, *gout; float *C, *Cn; };
+inline CovarianceArgs covariance_args(const Tensor& score, const Tensor& noise, const Tensor& weight, const Tensor& nweight, bool has_nw,
+                                      const Tensor& gout, const Tensor& C, const Tensor& Cn)
+{
     const Dims d = crf_dims(score, noise);
     const int64_t TB = (int64_t)d.T * d.B;
-    check(semicrf_expectation(cfp(score), cfp(noise), weight_of(weight, score, TB * d.T), has_nw ? f32(nweight, TB - d.B, "noiseWeight") : nullptr,
-                              f32(v, TB, "v"), f32(q, TB, "q"), d.T, d.B, f32w(E, d.B, "E"), f32w(H, d.B, "H"), bytes(ws, "ws"),
-                              (size_t)ws.numel(), c.stream),
-          "semicrf_expectation");
+    return CovarianceArgs{d, cfp(score), cfp(noise), weight_of(weight, score, TB * d.T), has_nw ? f32(nweight, TB - d.B, "noiseWeight") : nullptr,
+                          f32(gout, d.B, "gout"), f32w(C, TB * d.T, "C"), f32w(Cn, TB - d.B, "Cn")};
 }
 void covariance(Tensor score, Tensor noise, Tensor weight, Tensor nweight, bool has_nw, Tensor gout, Tensor C, Tensor Cn, Tensor ws)
 {
     Ctx c(score); c.same(score, noise, weight, gout, C, Cn, ws);
     if (has_nw) c.same(score, nweight);
-    const Dims d = crf_dims(score, noise);
-    const int64_t TB = (int64_t)d.T * d.B;
-    check(semicrf_covariance(cfp(score), cfp(noise), weight_of(weight, score, TB * d.T), has_nw ? f32(nweight, TB - d.B, "noiseWeight") : nullptr,
-                             f32(gout, d.B, "gout"), d.T, d.B, f32w(C, TB * d.T, "C"), f32w(Cn, TB - d.B, "Cn"), bytes(ws, "ws"),
-                             (size_t)ws.numel(), c.stream),
+    const CovarianceArgs a = covariance_args(score, noise, weight, nweight, has_nw, gout, C, Cn);
+    check(semicrf_covariance(a.score, a.noise, a.weight, a.nweight, a.gout, a.d.T, a.d.B, a.C, a.Cn, bytes(ws, "ws"), (size_t)ws.numel(),
+                             c.stream),
           "semicrf_covariance");
 }
-inline Dims marg_dims(const Tensor& score, const Tensor& v, const Tensor& q, const Tensor& logZ)
+void covariance_cpu(Tensor score, Tensor noise, Tensor weight, Tensor nweight, bool has_nw, Tensor gout, Tensor C, Tensor Cn, Tensor ws)
+{
+    all_cpu(score, noise, weight, nweight, gout, C, Cn, ws);
+    const CovarianceArgs a = covariance_args(score, noise, weight, nweight, has_nw, gout, C, Cn);
+    semicrf_cpu::covariance(a.score, a.noise, a.weight, a.nweight, a.gout, a.d.T, a.d.B, state_cpu(ws, a.d), a.C, a.Cn);
+}
+
+// interval marginals (semicrf_interval_marginals[_tol]): pairs / offsets as eval_path; tol_begin, tol_end in 0 .. SEMICRF_TOL_MAX
+inline void check_tol(int64_t tb, int64_t te)
+{
+    STD_TORCH_CHECK(tb >= 0 && tb <= SEMICRF_TOL_MAX && te >= 0 && te <= SEMICRF_TOL_MAX, "semicrf: tolerance (", tb, ", ", te,
+                    ") outside [0, ", SEMICRF_TOL_MAX, "]");
+}
+struct MarginalsArgs { Dims d; const float *score, *v, *q, *logZ; const int32_t *pairs, *offsets; float* out; };
+inline MarginalsArgs interval_marginals_args(const Tensor& score, const Tensor& v, const Tensor& q, const Tensor& logZ, const Tensor& pairs,
+                                             int64_t K, const Tensor& offsets, const Tensor& out, int64_t tol_begin = 0, int64_t tol_end = 0)
 {
     STD_TORCH_CHECK(score.dim() == 3 && score.size(0) == score.size(1), "semicrf: score must be [T, T, B]");
     const int64_t T = score.size(0), B = score.size(2);
@@ -214,75 +417,115 @@ inline Dims marg_dims(const Tensor& score, const Tensor& v, const Tensor& q, con
     want(v, ScalarType::Float, T * B, "v");
     want(q, ScalarType::Float, T * B, "q");
     want(logZ, ScalarType::Float, B, "logZ");
-    return Dims{(int)T, (int)B};
+    STD_TORCH_CHECK(K >= 0, "semicrf: negative interval count");
+    check_tol(tol_begin, tol_end);
+    return MarginalsArgs{Dims{(int)T, (int)B}, cfp(score), cfp(v), cfp(q), cfp(logZ), i32(pairs, 2 * K, "pairs"), i32(offsets, B + 1, "offsets"),
+                         f32w(out, K, "out")};
 }
-// interval marginals (semicrf_interval_marginals): pairs / offsets as eval_path
 void interval_marginals(Tensor score, Tensor v, Tensor q, Tensor logZ, Tensor pairs, int64_t K, Tensor offsets, Tensor out)
 {
     Ctx c(score); c.same(score, v, q, logZ, pairs, offsets, out);
-    const Dims d = marg_dims(score, v, q, logZ);
-    STD_TORCH_CHECK(K >= 0, "semicrf: negative interval count");
-    check(semicrf_interval_marginals(cfp(score), cfp(v), cfp(q), cfp(logZ), d.T, d.B, i32(pairs, 2 * K, "pairs"), K,
-                                     i32(offsets, d.B + 1, "offsets"), f32w(out, K, "out"), c.stream),
+    const MarginalsArgs a = interval_marginals_args(score, v, q, logZ, pairs, K, offsets, out);
+    check(semicrf_interval_marginals(a.score, a.v, a.q, a.logZ, a.d.T, a.d.B, a.pairs, K, a.offsets, a.out, c.stream),
           "semicrf_interval_marginals");
 }
-// marginal-threshold decoding (semicrf_marginal_decode): tau holds 1 value (all chains) or B (per chain); pairs [cap, 2], probs [cap]
+void interval_marginals_cpu(Tensor score, Tensor v, Tensor q, Tensor logZ, Tensor pairs, int64_t K, Tensor offsets, Tensor out)
+{
+    all_cpu(score, v, q, logZ, pairs, offsets, out);
+    const MarginalsArgs a = interval_marginals_args(score, v, q, logZ, pairs, K, offsets, out);
+    check_cells(a.pairs, K, a.offsets, a.d.T, a.d.B);
+    semicrf_cpu::interval_marginals(a.score, a.v, a.q, a.logZ, a.d.T, a.d.B, a.pairs, a.offsets, a.out);
+}
+void interval_marginals_tol(Tensor score, Tensor v, Tensor q, Tensor logZ, Tensor pairs, int64_t K, Tensor offsets, int64_t tol_begin,
+                            int64_t tol_end, Tensor out)
+{
+    Ctx c(score); c.same(score, v, q, logZ, pairs, offsets, out);
+    const MarginalsArgs a = interval_marginals_args(score, v, q, logZ, pairs, K, offsets, out, tol_begin, tol_end);
+    check(semicrf_interval_marginals_tol(a.score, a.v, a.q, a.logZ, a.d.T, a.d.B, a.pairs, K, a.offsets, (int)tol_begin, (int)tol_end, a.out,
+                                         c.stream),
+          "semicrf_interval_marginals_tol");
+}
+void interval_marginals_tol_cpu(Tensor score, Tensor v, Tensor q, Tensor logZ, Tensor pairs, int64_t K, Tensor offsets, int64_t tol_begin,
+                                int64_t tol_end, Tensor out)
+{
+    all_cpu(score, v, q, logZ, pairs, offsets, out);
+    const MarginalsArgs a = interval_marginals_args(score, v, q, logZ, pairs, K, offsets, out, tol_begin, tol_end);
+    check_cells(a.pairs, K, a.offsets, a.d.T, a.d.B);
+    if (tol_begin == 0 && tol_end == 0)
+        semicrf_cpu::interval_marginals(a.score, a.v, a.q, a.logZ, a.d.T, a.d.B, a.pairs, a.offsets, a.out);
+    else
+        semicrf_cpu::interval_marginals_tol(a.score, a.v, a.q, a.logZ, a.d.T, a.d.B, a.pairs, a.offsets, (int)tol_begin, (int)tol_end, a.out);
+}
+
+// marginal-threshold decoding (semicrf_marginal_decode[_tol]): tau holds 1 value (all chains) or B (per chain); pairs [cap, 2], probs [cap]
 inline int tau_stride_of(const Tensor& tau, int B)
 {
     want(tau, ScalarType::Float, 1, "tau");
     STD_TORCH_CHECK(tau.numel() == 1 || tau.numel() == B, "semicrf: tau must hold 1 value or one per chain (", B, "), got ", tau.numel());
     return tau.numel() == B && B > 1 ? 1 : 0;
 }
+struct MarginalDecodeArgs { Dims d; const float *score, *noise, *v, *q, *logZ, *tau; int tau_stride; int32_t* pairs; float* probs; int64_t cap; int32_t* offsets; };
+inline MarginalDecodeArgs marginal_decode_args(const Tensor& score, const Tensor& noise, const Tensor& v, const Tensor& q, const Tensor& logZ,
+                                               const Tensor& tau, const Tensor& pairs, const Tensor& probs, const Tensor& offsets,
+                                               int64_t tol_begin = 0, int64_t tol_end = 0)
+{
+    const Dims d = crf_dims(score, noise);
+    const int64_t TB = (int64_t)d.T * d.B;
+    const int64_t cap = pairs_cap1(pairs);
+    check_tol(tol_begin, tol_end);
+    return MarginalDecodeArgs{d, cfp(score), cfp(noise), f32(v, TB, "v"), f32(q, TB, "q"), f32(logZ, d.B, "logZ"), cfp(tau), tau_stride_of(tau, d.B),
+                              i32(pairs, 2 * cap, "pairs"), f32w(probs, cap, "probs"), cap, i32(offsets, d.B + 1, "offsets")};
+}
+// (the `_cpu` twins only) the host kernels count cells in int32
+inline void check_cell_count(const Dims& d)
+{
+    STD_TORCH_CHECK((int64_t)d.T * (d.T + 1) / 2 * d.B < (1ll << 31), "semicrf: T (T+1) / 2 * B exceeds int32 offsets");
+}
 void marginal_decode(Tensor score, Tensor noise, Tensor v, Tensor q, Tensor logZ, Tensor tau, Tensor pairs, Tensor probs, Tensor offsets,
                      Tensor ws)
 {
     Ctx c(score); c.same(score, noise, v, q, logZ, tau, pairs, probs, offsets, ws);
-    const Dims d = crf_dims(score, noise);
-    const int64_t TB = (int64_t)d.T * d.B;
-    STD_TORCH_CHECK(pairs.dim() == 2 && pairs.size(1) == 2 && pairs.size(0) >= 1, "semicrf: pairs must be [cap, 2], cap >= 1");
-    const int64_t cap = pairs.size(0);
-    check(semicrf_marginal_decode(cfp(score), cfp(noise), f32(v, TB, "v"), f32(q, TB, "q"), f32(logZ, d.B, "logZ"), d.T, d.B,
-                                  cfp(tau), tau_stride_of(tau, d.B), i32(pairs, 2 * cap, "pairs"), f32w(probs, cap, "probs"), cap,
-                                  i32(offsets, d.B + 1, "offsets"), bytes(ws, "ws"), (size_t)ws.numel(), c.stream),
+    const MarginalDecodeArgs a = marginal_decode_args(score, noise, v, q, logZ, tau, pairs, probs, offsets);
+    check(semicrf_marginal_decode(a.score, a.noise, a.v, a.q, a.logZ, a.d.T, a.d.B, a.tau, a.tau_stride, a.pairs, a.probs, a.cap, a.offsets,
+                                  bytes(ws, "ws"), (size_t)ws.numel(), c.stream),
           "semicrf_marginal_decode");
 }
-// the tolerance-aware forms (semicrf_interval_marginals_tol / semicrf_marginal_decode_tol): tol_begin, tol_end in 0 .. SEMICRF_TOL_MAX
-inline void check_tol(int64_t tb, int64_t te)
+void marginal_decode_cpu(Tensor score, Tensor noise, Tensor v, Tensor q, Tensor logZ, Tensor tau, Tensor pairs, Tensor probs,
+                         Tensor offsets, Tensor ws)
 {
-    STD_TORCH_CHECK(tb >= 0 && tb <= SEMICRF_TOL_MAX && te >= 0 && te <= SEMICRF_TOL_MAX, "semicrf: tolerance (", tb, ", ", te,
-                    ") outside [0, ", SEMICRF_TOL_MAX, "]");
-}
-void interval_marginals_tol(Tensor score, Tensor v, Tensor q, Tensor logZ, Tensor pairs, int64_t K, Tensor offsets, int64_t tol_begin,
-                            int64_t tol_end, Tensor out)
-{
-    Ctx c(score); c.same(score, v, q, logZ, pairs, offsets, out);
-    const Dims d = marg_dims(score, v, q, logZ);
-    STD_TORCH_CHECK(K >= 0, "semicrf: negative interval count");
-    check_tol(tol_begin, tol_end);
-    check(semicrf_interval_marginals_tol(cfp(score), cfp(v), cfp(q), cfp(logZ), d.T, d.B, i32(pairs, 2 * K, "pairs"), K,
-                                         i32(offsets, d.B + 1, "offsets"), (int)tol_begin, (int)tol_end, f32w(out, K, "out"), c.stream),
-          "semicrf_interval_marginals_tol");
+    all_cpu(score, noise, v, q, logZ, tau, pairs, probs, offsets);
+    const MarginalDecodeArgs a = marginal_decode_args(score, noise, v, q, logZ, tau, pairs, probs, offsets);
+    check_cell_count(a.d);
+    semicrf_cpu::marginal_decode(a.score, a.v, a.q, a.logZ, a.d.T, a.d.B, a.tau, a.tau_stride, a.pairs, a.probs, a.cap, a.offsets);
 }
 void marginal_decode_tol(Tensor score, Tensor noise, Tensor v, Tensor q, Tensor logZ, Tensor tau, int64_t tol_begin, int64_t tol_end,
                          Tensor pairs, Tensor probs, Tensor offsets, Tensor ws)
 {
     Ctx c(score); c.same(score, noise, v, q, logZ, tau, pairs, probs, offsets, ws);
-    const Dims d = crf_dims(score, noise);
-    const int64_t TB = (int64_t)d.T * d.B;
-    STD_TORCH_CHECK(pairs.dim() == 2 && pairs.size(1) == 2 && pairs.size(0) >= 1, "semicrf: pairs must be [cap, 2], cap >= 1");
-    check_tol(tol_begin, tol_end);
-    const int64_t cap = pairs.size(0);
-    check(semicrf_marginal_decode_tol(cfp(score), cfp(noise), f32(v, TB, "v"), f32(q, TB, "q"), f32(logZ, d.B, "logZ"), d.T, d.B,
-                                      cfp(tau), tau_stride_of(tau, d.B), (int)tol_begin, (int)tol_end, i32(pairs, 2 * cap, "pairs"),
-                                      f32w(probs, cap, "probs"), cap, i32(offsets, d.B + 1, "offsets"), bytes(ws, "ws"),
-                                      (size_t)ws.numel(), c.stream),
+    const MarginalDecodeArgs a = marginal_decode_args(score, noise, v, q, logZ, tau, pairs, probs, offsets, tol_begin, tol_end);
+    check(semicrf_marginal_decode_tol(a.score, a.noise, a.v, a.q, a.logZ, a.d.T, a.d.B, a.tau, a.tau_stride, (int)tol_begin, (int)tol_end,
+                                      a.pairs, a.probs, a.cap, a.offsets, bytes(ws, "ws"), (size_t)ws.numel(), c.stream),
           "semicrf_marginal_decode_tol");
 }
+void marginal_decode_tol_cpu(Tensor score, Tensor noise, Tensor v, Tensor q, Tensor logZ, Tensor tau, int64_t tol_begin, int64_t tol_end,
+                             Tensor pairs, Tensor probs, Tensor offsets, Tensor ws)
+{
+    all_cpu(score, noise, v, q, logZ, tau, pairs, probs, offsets);
+    const MarginalDecodeArgs a = marginal_decode_args(score, noise, v, q, logZ, tau, pairs, probs, offsets, tol_begin, tol_end);
+    check_cell_count(a.d);
+    if (tol_begin == 0 && tol_end == 0)
+        semicrf_cpu::marginal_decode(a.score, a.v, a.q, a.logZ, a.d.T, a.d.B, a.tau, a.tau_stride, a.pairs, a.probs, a.cap, a.offsets);
+    else
+        semicrf_cpu::marginal_decode_tol(a.score, a.v, a.q, a.logZ, a.d.T, a.d.B, a.tau, a.tau_stride, (int)tol_begin, (int)tol_end, a.pairs,
+                                         a.probs, a.cap, a.offsets);
+}
+
 // MBR path decoding (semicrf_mbr_select) over a lattice of marginal_decode: pairs [K, 2], weight [K], offsets [B + 1]; tau as above;
 // pairs_out [cap, 2], probs_out [cap], offsets_out [B + 1], gain [B]
-struct MbrDims { int64_t K, cap; int B; };
-inline MbrDims mbr_dims(const Tensor& pairs, const Tensor& weight, const Tensor& offsets, int64_t T, const Tensor& pairs_out,
-                        const Tensor& probs_out, const Tensor& offsets_out, const Tensor& gain)
+struct MbrArgs { int64_t K, cap; int B; const int32_t* pairs; const float* weight; const int32_t* offsets; const float* tau; int tau_stride;
+                 int32_t* pairs_out; float* probs_out; int32_t* offsets_out; float* gain; };
+inline MbrArgs mbr_select_args(const Tensor& pairs, const Tensor& weight, const Tensor& offsets, int64_t T, const Tensor& tau,
+                               const Tensor& pairs_out, const Tensor& probs_out, const Tensor& offsets_out, const Tensor& gain)
 {
     STD_TORCH_CHECK(pairs.dim() == 2 && pairs.size(1) == 2, "semicrf: pairs must be [K, 2]");
     STD_TORCH_CHECK(pairs_out.dim() == 2 && pairs_out.size(1) == 2 && pairs_out.size(0) >= 1, "semicrf: pairs_out must be [cap, 2], cap >= 1");
@@ -295,21 +538,32 @@ inline MbrDims mbr_dims(const Tensor& pairs, const Tensor& weight, const Tensor&
     want(probs_out, ScalarType::Float, cap, "probs_out");
     want(offsets_out, ScalarType::Int, B + 1, "offsets_out");
     want(gain, ScalarType::Float, B, "gain");
-    return MbrDims{K, cap, (int)B};
+    return MbrArgs{K, cap, (int)B, ip(pairs), cfp(weight), ip(offsets), cfp(tau), tau_stride_of(tau, (int)B), ip(pairs_out), fp(probs_out),
+                   ip(offsets_out), fp(gain)};
 }
 void mbr_select(Tensor pairs, Tensor weight, Tensor offsets, int64_t T, Tensor tau, Tensor pairs_out, Tensor probs_out, Tensor offsets_out,
                 Tensor gain, Tensor ws)
 {
     Ctx c(offsets); c.same(offsets, pairs, weight, tau, pairs_out, probs_out, offsets_out, gain, ws);
-    const MbrDims d = mbr_dims(pairs, weight, offsets, T, pairs_out, probs_out, offsets_out, gain);
-    check(semicrf_mbr_select(ip(pairs), cfp(weight), ip(offsets), d.K, (int)T, d.B, cfp(tau), tau_stride_of(tau, d.B), ip(pairs_out),
-                             fp(probs_out), d.cap, ip(offsets_out), fp(gain), bytes(ws, "ws"), (size_t)ws.numel(), c.stream),
+    const MbrArgs a = mbr_select_args(pairs, weight, offsets, T, tau, pairs_out, probs_out, offsets_out, gain);
+    check(semicrf_mbr_select(a.pairs, a.weight, a.offsets, a.K, (int)T, a.B, a.tau, a.tau_stride, a.pairs_out, a.probs_out, a.cap,
+                             a.offsets_out, a.gain, bytes(ws, "ws"), (size_t)ws.numel(), c.stream),
           "semicrf_mbr_select");
 }
+void mbr_select_cpu(Tensor pairs, Tensor weight, Tensor offsets, int64_t T, Tensor tau, Tensor pairs_out, Tensor probs_out,
+                    Tensor offsets_out, Tensor gain, Tensor ws)
+{
+    all_cpu(pairs, weight, offsets, tau, pairs_out, probs_out, offsets_out, gain);
+    const MbrArgs a = mbr_select_args(pairs, weight, offsets, T, tau, pairs_out, probs_out, offsets_out, gain);
+    semicrf_cpu::mbr_select(a.pairs, a.weight, a.offsets, a.K, (int)T, a.B, a.tau, a.tau_stride, a.pairs_out, a.probs_out, a.cap,
+                            a.offsets_out, a.gain);
+}
+
 // path comparison (semicrf_compare_paths): two packed lists, pairs [K, 2] / offsets [B + 1] each; stats [B, 7].  The pairs buffers
 // must hold offsets[B] entries -- the total lives on the device, so the caller vouches for it (the Python mirror does)
-inline int cmp_dims(const Tensor& est_pairs, const Tensor& est_offsets, const Tensor& ref_pairs, const Tensor& ref_offsets, int64_t T,
-                    int64_t tol_begin, int64_t tol_end, const Tensor& stats)
+struct ComparePathsArgs { int B; const int32_t *est_pairs, *est_offsets, *ref_pairs, *ref_offsets; int32_t* stats; };
+inline ComparePathsArgs compare_paths_args(const Tensor& est_pairs, const Tensor& est_offsets, const Tensor& ref_pairs,
+                                           const Tensor& ref_offsets, int64_t T, int64_t tol_begin, int64_t tol_end, const Tensor& stats)
 {
     STD_TORCH_CHECK(est_pairs.dim() == 2 && est_pairs.size(1) == 2 && ref_pairs.dim() == 2 && ref_pairs.size(1) == 2,
                     "semicrf: pairs must be [K, 2]");
@@ -323,25 +577,58 @@ inline int cmp_dims(const Tensor& est_pairs, const Tensor& est_offsets, const Te
     want(stats, ScalarType::Int, 7 * B, "stats");
     check_tol(tol_begin, tol_end);
     STD_TORCH_CHECK((((uintptr_t)ip(est_pairs) | (uintptr_t)ip(ref_pairs)) & 7) == 0, "semicrf: pairs must be 8-byte aligned");
-    return (int)B;
+    return ComparePathsArgs{(int)B, ip(est_pairs), ip(est_offsets), ip(ref_pairs), ip(ref_offsets), ip(stats)};
 }
 void compare_paths(Tensor est_pairs, Tensor est_offsets, Tensor ref_pairs, Tensor ref_offsets, int64_t T, int64_t tol_begin,
                    int64_t tol_end, Tensor stats)
 {
     Ctx c(est_offsets); c.same(est_offsets, est_pairs, ref_pairs, ref_offsets, stats);
-    const int B = cmp_dims(est_pairs, est_offsets, ref_pairs, ref_offsets, T, tol_begin, tol_end, stats);
-    check(semicrf_compare_paths(ip(est_pairs), ip(est_offsets), ip(ref_pairs), ip(ref_offsets), (int)T, B, (int)tol_begin, (int)tol_end,
-                                ip(stats), c.stream),
+    const ComparePathsArgs a = compare_paths_args(est_pairs, est_offsets, ref_pairs, ref_offsets, T, tol_begin, tol_end, stats);
+    check(semicrf_compare_paths(a.est_pairs, a.est_offsets, a.ref_pairs, a.ref_offsets, (int)T, a.B, (int)tol_begin, (int)tol_end, a.stats,
+                                c.stream),
           "semicrf_compare_paths");
+}
+void compare_paths_cpu(Tensor est_pairs, Tensor est_offsets, Tensor ref_pairs, Tensor ref_offsets, int64_t T, int64_t tol_begin,
+                       int64_t tol_end, Tensor stats)
+{
+    all_cpu(est_pairs, est_offsets, ref_pairs, ref_offsets, stats);
+    const ComparePathsArgs a = compare_paths_args(est_pairs, est_offsets, ref_pairs, ref_offsets, T, tol_begin, tol_end, stats);
+    // on the host the totals can be looked at: the promise the device entry point takes from its caller is checked here
+    STD_TORCH_CHECK(a.est_offsets[a.B] <= est_pairs.size(0) && a.ref_offsets[a.B] <= ref_pairs.size(0),
+                    "semicrf: offsets[B] exceeds the pairs buffer");
+    semicrf_cpu::compare_paths(a.est_pairs, a.est_offsets, a.ref_pairs, a.ref_offsets, (int)T, a.B, (int)tol_begin, (int)tol_end, a.stats);
+}
+
+struct EvalPathArgs { Dims d; const float *score, *noise; const int32_t *pairs, *offsets; float* out; };
+inline EvalPathArgs eval_path_args(const Tensor& score, const Tensor& noise, const Tensor& pairs, int64_t K, const Tensor& offsets,
+                                   const Tensor& out)
+{
+    const Dims d = crf_dims(score, noise);
+    STD_TORCH_CHECK(K >= 0, "semicrf: negative interval count");
+    return EvalPathArgs{d, cfp(score), cfp(noise), i32(pairs, 2 * K, "pairs"), i32(offsets, d.B + 1, "offsets"), f32w(out, d.B, "out")};
 }
 void eval_path(Tensor score, Tensor noise, Tensor pairs, int64_t K, Tensor offsets, Tensor out, Tensor ws)
 {
     Ctx c(score); c.same(score, noise, pairs, offsets, out);
-    const Dims d = crf_dims(score, noise);
-    STD_TORCH_CHECK(K >= 0, "semicrf: negative interval count");
-    check(semicrf_eval_path(cfp(score), cfp(noise), d.T, d.B, i32(pairs, 2 * K, "pairs"), K, i32(offsets, d.B + 1, "offsets"),
-                            f32w(out, d.B, "out"), ws.numel() > 0 ? ws.data_ptr() : nullptr, (size_t)ws.numel(), c.stream),
+    const EvalPathArgs a = eval_path_args(score, noise, pairs, K, offsets, out);
+    check(semicrf_eval_path(a.score, a.noise, a.d.T, a.d.B, a.pairs, K, a.offsets, a.out, ws.numel() > 0 ? ws.data_ptr() : nullptr,
+                            (size_t)ws.numel(), c.stream),
           "semicrf_eval_path");
+}
+void eval_path_cpu(Tensor score, Tensor noise, Tensor pairs, int64_t K, Tensor offsets, Tensor out, Tensor ws)
+{
+    all_cpu(score, noise, pairs, offsets, out);
+    const EvalPathArgs a = eval_path_args(score, noise, pairs, K, offsets, out);
+    check_path(a.pairs, K, a.offsets, a.d.T, a.d.B);
+    semicrf_cpu::eval_path(a.score, a.noise, a.d.T, a.d.B, a.pairs, a.offsets, a.out);
+}
+struct EvalPathBwdArgs { const float* gout; const int32_t *pairs, *offsets; float *dScore, *dNoise; };      // dScore / dNoise: null when absent
+inline EvalPathBwdArgs eval_path_bwd_args(const Tensor& gout, int64_t T, int64_t B, const Tensor& pairs, int64_t K, const Tensor& offsets,
+                                          const Tensor& dScore, bool has_ds, const Tensor& dNoise, bool has_dn)
+{
+    STD_TORCH_CHECK(T >= 1 && B >= 1 && K >= 0 && T < (1 << 29) && B < (1ll << 31), "semicrf: bad sizes");
+    return EvalPathBwdArgs{f32(gout, B, "gout"), i32(pairs, 2 * K, "pairs"), i32(offsets, B + 1, "offsets"),
+                           has_ds ? f32w(dScore, T * T * B, "dScore") : nullptr, has_dn ? f32w(dNoise, (T - 1) * B, "dNoise") : nullptr};
 }
 void eval_path_bwd(Tensor gout, int64_t T, int64_t B, Tensor pairs, int64_t K, Tensor offsets, Tensor dScore, bool has_ds, Tensor dNoise,
                    bool has_dn)
@@ -349,295 +636,87 @@ void eval_path_bwd(Tensor gout, int64_t T, int64_t B, Tensor pairs, int64_t K, T
     Ctx c(gout); c.same(gout, pairs, offsets);
     if (has_ds) c.same(gout, dScore);
     if (has_dn) c.same(gout, dNoise);
-    STD_TORCH_CHECK(T >= 1 && B >= 1 && K >= 0 && T < (1 << 29) && B < (1ll << 31), "semicrf: bad sizes");
-    check(semicrf_eval_path_bwd(f32(gout, B, "gout"), (int)T, (int)B, i32(pairs, 2 * K, "pairs"), K, i32(offsets, B + 1, "offsets"),
-                                has_ds ? f32w(dScore, T * T * B, "dScore") : nullptr, has_dn ? f32w(dNoise, (T - 1) * B, "dNoise") : nullptr,
-                                c.stream),
-          "semicrf_eval_path_bwd");
+    const EvalPathBwdArgs a = eval_path_bwd_args(gout, T, B, pairs, K, offsets, dScore, has_ds, dNoise, has_dn);
+    check(semicrf_eval_path_bwd(a.gout, (int)T, (int)B, a.pairs, K, a.offsets, a.dScore, a.dNoise, c.stream), "semicrf_eval_path_bwd");
+}
+void eval_path_bwd_cpu(Tensor gout, int64_t T, int64_t B, Tensor pairs, int64_t K, Tensor offsets, Tensor dScore, bool has_ds, Tensor dNoise,
+                       bool has_dn)
+{
+    all_cpu(gout, pairs, offsets);                                 // (unlike the GPU twin, dScore / dNoise are not in this list)
+    const EvalPathBwdArgs a = eval_path_bwd_args(gout, T, B, pairs, K, offsets, dScore, has_ds, dNoise, has_dn);
+    check_path(a.pairs, K, a.offsets, (int)T, (int)B);
+    semicrf_cpu::eval_path_bwd(a.gout, (int)T, (int)B, a.pairs, a.offsets, a.dScore, a.dNoise);
 }
 
 // logProb as one call each way (semicrf_logprob_fwd / _bwd): gout holds B values (gstride 1) or ONE (gstride 0)
-// ptab / has_ptab: the path table of semicrf_logprob_fwd_t / _bwd_t (int32 [T][B]; has_ptab false: none, pass any int32 tensor)
+// ptab / has_ptab: the path table of semicrf_logprob_fwd_t / _bwd_t (int32 [T][B]; has_ptab false: none, pass any int32 tensor).
+// It belongs to the GPU twins: the CPU kernels scatter the path's terms themselves, a path table is refused there, not ignored.
+struct LogprobFwdArgs { Dims d; const float *score, *noise; const int32_t *pairs, *offsets; float *logProb, *logZ, *v; };
+inline LogprobFwdArgs logprob_fwd_args(const Tensor& score, const Tensor& noise, const Tensor& pairs, int64_t K, const Tensor& offsets,
+                                       const Tensor& logProb, const Tensor& logZ, const Tensor& v, bool want_v)
+{
+    const Dims d = crf_dims(score, noise);
+    STD_TORCH_CHECK(K >= 0, "semicrf: negative interval count");
+    return LogprobFwdArgs{d, cfp(score), cfp(noise), i32(pairs, 2 * K, "pairs"), i32(offsets, d.B + 1, "offsets"), f32w(logProb, d.B, "logProb"),
+                          f32w(logZ, d.B, "logZ"), want_v ? f32w(v, (int64_t)d.T * d.B, "v") : nullptr};
+}
 void logprob_fwd(Tensor score, Tensor noise, Tensor pairs, int64_t K, Tensor offsets, Tensor logProb, Tensor logZ, Tensor v, bool want_v,
                  Tensor ws, Tensor ptab, bool has_ptab)
 {
     Ctx c(score); c.same(score, noise, pairs, offsets, logProb, logZ, v, ws);
     if (has_ptab) c.same(score, ptab);
-    const Dims d = crf_dims(score, noise);
-    STD_TORCH_CHECK(K >= 0, "semicrf: negative interval count");
-    check(semicrf_logprob_fwd_t(cfp(score), cfp(noise), d.T, d.B, i32(pairs, 2 * K, "pairs"), K, i32(offsets, d.B + 1, "offsets"),
-                                f32w(logProb, d.B, "logProb"), f32w(logZ, d.B, "logZ"), want_v ? f32w(v, (int64_t)d.T * d.B, "v") : nullptr,
-                                has_ptab ? i32(ptab, (int64_t)d.T * d.B, "ptab") : nullptr, bytes(ws, "ws"), (size_t)ws.numel(), c.stream),
+    const LogprobFwdArgs a = logprob_fwd_args(score, noise, pairs, K, offsets, logProb, logZ, v, want_v);
+    check(semicrf_logprob_fwd_t(a.score, a.noise, a.d.T, a.d.B, a.pairs, K, a.offsets, a.logProb, a.logZ, a.v,
+                                has_ptab ? i32(ptab, (int64_t)a.d.T * a.d.B, "ptab") : nullptr, bytes(ws, "ws"), (size_t)ws.numel(), c.stream),
           "semicrf_logprob_fwd");
+}
+void logprob_fwd_cpu(Tensor score, Tensor noise, Tensor pairs, int64_t K, Tensor offsets, Tensor logProb, Tensor logZ, Tensor v, bool want_v,
+                     Tensor ws, Tensor ptab, bool has_ptab)
+{
+    STD_TORCH_CHECK(!has_ptab, "semicrf: the path table belongs to the GPU sweeps");
+    all_cpu(score, noise, logZ, v, pairs, offsets, logProb);
+    const LogprobFwdArgs a = logprob_fwd_args(score, noise, pairs, K, offsets, logProb, logZ, v, want_v);
+    check_path(a.pairs, K, a.offsets, a.d.T, a.d.B);
+    std::vector<float> scratch;
+    if (!want_v) scratch.resize((size_t)a.d.T * a.d.B);
+    semicrf_cpu::logz_fwd(a.score, a.noise, a.d.T, a.d.B, a.logZ, want_v ? a.v : scratch.data());
+    semicrf_cpu::eval_path(a.score, a.noise, a.d.T, a.d.B, a.pairs, a.offsets, a.logProb);
+    for (int c = 0; c < a.d.B; ++c) a.logProb[c] -= a.logZ[c];
+}
+struct LogprobBwdArgs { Dims d; const float *score, *noise, *v, *logZ, *gout; const int32_t *pairs, *offsets; float *dScore, *dNoise; };
+inline LogprobBwdArgs logprob_bwd_args(const Tensor& score, const Tensor& noise, const Tensor& v, const Tensor& logZ, const Tensor& gout,
+                                       int64_t gstride, const Tensor& pairs, int64_t K, const Tensor& offsets, const Tensor& dScore,
+                                       const Tensor& dNoise)
+{
+    const Dims d = crf_dims(score, noise);
+    const int64_t TB = (int64_t)d.T * d.B;
+    STD_TORCH_CHECK(K >= 0 && (gstride == 0 || gstride == 1), "semicrf: bad interval count / gout stride");
+    return LogprobBwdArgs{d, cfp(score), cfp(noise), f32(v, TB, "v"), f32(logZ, d.B, "logZ"), f32(gout, gstride ? d.B : 1, "gout"),
+                          i32(pairs, 2 * K, "pairs"), i32(offsets, d.B + 1, "offsets"), f32w(dScore, TB * d.T, "dScore"),
+                          f32w(dNoise, TB - d.B, "dNoise")};
 }
 void logprob_bwd(Tensor score, Tensor noise, Tensor v, Tensor logZ, Tensor gout, int64_t gstride, Tensor pairs, int64_t K, Tensor offsets,
                  Tensor dScore, Tensor dNoise, int64_t flags, Tensor ws, Tensor ptab, bool has_ptab)
 {
     Ctx c(score); c.same(score, noise, v, logZ, gout, pairs, offsets, dScore, dNoise, ws);
     if (has_ptab) c.same(score, ptab);
-    const Dims d = crf_dims(score, noise);
-    const int64_t TB = (int64_t)d.T * d.B;
-    STD_TORCH_CHECK(K >= 0 && (gstride == 0 || gstride == 1), "semicrf: bad interval count / gout stride");
-    check(semicrf_logprob_bwd_t(cfp(score), cfp(noise), f32(v, TB, "v"), f32(logZ, d.B, "logZ"), f32(gout, gstride ? d.B : 1, "gout"),
-                                (int)gstride, d.T, d.B, i32(pairs, 2 * K, "pairs"), K, i32(offsets, d.B + 1, "offsets"),
-                                f32w(dScore, TB * d.T, "dScore"), f32w(dNoise, TB - d.B, "dNoise"), (int)flags,
-                                has_ptab ? i32(ptab, TB, "ptab") : nullptr, bytes(ws, "ws"), (size_t)ws.numel(), c.stream),
+    const LogprobBwdArgs a = logprob_bwd_args(score, noise, v, logZ, gout, gstride, pairs, K, offsets, dScore, dNoise);
+    check(semicrf_logprob_bwd_t(a.score, a.noise, a.v, a.logZ, a.gout, (int)gstride, a.d.T, a.d.B, a.pairs, K, a.offsets, a.dScore, a.dNoise,
+                                (int)flags, has_ptab ? i32(ptab, (int64_t)a.d.T * a.d.B, "ptab") : nullptr, bytes(ws, "ws"),
+                                (size_t)ws.numel(), c.stream),
           "semicrf_logprob_bwd");
-}
-
-// ---- semi-CRF, CPU (dispatch key CPU): the product's own host kernels (cpu_ops.cpp) -- selected by the tensors' device, never
-// a fallback for GPU tensors.  The workspace argument is ignored (pass an empty tensor).
-void logz_fwd_cpu(Tensor score, Tensor noise, Tensor logZ, Tensor v, bool want_v, Tensor ws)
-{
-    all_cpu(score, noise, logZ, v);
-    const Dims d = crf_dims(score, noise);
-    const int64_t TB = (int64_t)d.T * d.B;
-    std::vector<float> scratch;
-    float* vv;
-    if (want_v) vv = f32w(v, TB, "v");
-    else { scratch.resize((size_t)TB); vv = scratch.data(); }
-    semicrf_cpu::logz_fwd(cfp(score), cfp(noise), d.T, d.B, f32w(logZ, d.B, "logZ"), vv);
-}
-void logz_bwd_cpu(Tensor score, Tensor noise, Tensor v, Tensor logZ, Tensor gout, Tensor dScore, Tensor dNoise, Tensor q, bool want_q,
-                  int64_t flags, Tensor ws)       // flags: a permission (SEMICRF_GRAD_UPPER_IS_ZERO); the host kernels write everything
-{
-    all_cpu(score, noise, v, logZ, gout, dScore, dNoise, q);
-    const Dims d = crf_dims(score, noise);
-    const int64_t TB = (int64_t)d.T * d.B;
-    std::vector<float> scratch;
-    float* qq;
-    if (want_q) qq = f32w(q, TB, "q");
-    else { scratch.resize((size_t)TB); qq = scratch.data(); }
-    semicrf_cpu::logz_bwd(cfp(score), cfp(noise), f32(v, TB, "v"), f32(logZ, d.B, "logZ"), f32(gout, d.B, "gout"), d.T, d.B,
-                          f32w(dScore, TB * d.T, "dScore"), f32w(dNoise, TB - d.B, "dNoise"), qq);
-}
-void beta_cpu(Tensor score, Tensor noise, Tensor out, Tensor ws)
-{
-    all_cpu(score, noise, out);
-    const Dims d = crf_dims(score, noise);
-    semicrf_cpu::logz_bwd(cfp(score), cfp(noise), nullptr, nullptr, nullptr, d.T, d.B, nullptr, nullptr, f32w(out, (int64_t)d.T * d.B, "beta"));
-}
-void alpha_from_cpu(Tensor score, Tensor noise, Tensor start, Tensor v, Tensor logZ, Tensor ws)
-{
-    all_cpu(score, noise, start, v, logZ);
-    const Dims d = crf_dims(score, noise);
-    semicrf_cpu::alpha_from(cfp(score), cfp(noise), i32(start, d.B, "start"), d.T, d.B, f32w(v, (int64_t)d.T * d.B, "v"),
-                            f32w(logZ, d.B, "logZ"));
-}
-void viterbi_cpu(Tensor score, Tensor noise, Tensor start, bool has_start, bool forward, Tensor pairs, Tensor offsets, Tensor ws)
-{
-    all_cpu(score, noise, pairs, offsets);
-    if (has_start) all_cpu(start);
-    const Dims d = crf_dims(score, noise);
-    STD_TORCH_CHECK(pairs.dim() == 2 && pairs.size(1) == 2, "semicrf: pairs must be [cap, 2]");
-    const int32_t* st = has_start ? i32(start, d.B, "start") : nullptr;
-    if (st)
-        for (int c = 0; c < d.B; ++c) STD_TORCH_CHECK(st[c] >= 0 && st[c] < d.T, "semicrf: forcedStartPos out of range");
-    semicrf_cpu::viterbi(cfp(score), cfp(noise), d.T, d.B, st, forward ? 1 : 0, i32(pairs, 0, "pairs"), (int64_t)pairs.size(0),
-                         i32(offsets, d.B + 1, "offsets"));
-}
-void sample_cpu(Tensor score, Tensor noise, Tensor v, int64_t k0, int64_t nSample, int64_t key, Tensor end, bool has_end, Tensor pairs,
-                Tensor offsets, Tensor ws)
-{
-    all_cpu(score, noise, v, pairs, offsets);
-    if (has_end) all_cpu(end);
-    const Dims d = crf_dims(score, noise);
-    STD_TORCH_CHECK(nSample >= 1 && nSample < (1 << 30) && k0 >= 0, "semicrf: bad nSample / k0");
-    STD_TORCH_CHECK(nSample * d.B * 2 * d.T < (1ll << 31), "semicrf: nSample*B*2T exceeds int32 offsets");
-    STD_TORCH_CHECK(pairs.dim() == 2 && pairs.size(1) == 2, "semicrf: pairs must be [cap, 2]");
-    const int32_t* e = has_end ? i32(end, d.B, "end") : nullptr;
-    if (e)
-        for (int c = 0; c < d.B; ++c) STD_TORCH_CHECK(e[c] >= 0 && e[c] < d.T, "semicrf: forcedEndPos out of range");
-    semicrf_cpu::sample(cfp(score), cfp(noise), f32(v, (int64_t)d.T * d.B, "v"), d.T, d.B, k0, (int)nSample, (uint64_t)key, e,
-                        i32(pairs, 0, "pairs"), (int64_t)pairs.size(0), i32(offsets, nSample * d.B + 1, "offsets"));
-}
-void viterbi_nbest_cpu(Tensor score, Tensor noise, int64_t k, Tensor start, bool has_start, bool forward, Tensor pairs, Tensor offsets,
-                       Tensor scores, Tensor npaths, Tensor ws)
-{
-    all_cpu(score, noise, pairs, offsets, scores, npaths);
-    if (has_start) all_cpu(start);
-    const Dims d = crf_dims(score, noise);
-    STD_TORCH_CHECK(k >= 1 && k <= 16, "semicrf: k must be in [1, 16]");
-    STD_TORCH_CHECK(k * d.B * 2 * d.T < (1ll << 31), "semicrf: k*B*2T exceeds int32 offsets");
-    STD_TORCH_CHECK(pairs.dim() == 2 && pairs.size(1) == 2, "semicrf: pairs must be [cap, 2]");
-    const int32_t* st = has_start ? i32(start, d.B, "start") : nullptr;
-    if (st)
-        for (int c = 0; c < d.B; ++c) STD_TORCH_CHECK(st[c] >= 0 && st[c] < d.T, "semicrf: forcedStartPos out of range");
-    semicrf_cpu::viterbi_nbest(cfp(score), cfp(noise), d.T, d.B, (int)k, st, forward ? 1 : 0, i32(pairs, 0, "pairs"),
-                               (int64_t)pairs.size(0), i32(offsets, k * d.B + 1, "offsets"), f32w(scores, k * d.B, "scores"),
-                               i32(npaths, d.B, "npaths"));
-}
-inline void check_path(const int32_t* pairs, int64_t K, const int32_t* offsets, int T, int B)
-{
-    STD_TORCH_CHECK(offsets[0] == 0 && offsets[B] == K, "semicrf: offsets do not match the interval count");
-    for (int c = 0; c < B; ++c) STD_TORCH_CHECK(offsets[c] <= offsets[c + 1], "semicrf: offsets must ascend");
-    for (int64_t i = 0; i < K; ++i)
-        STD_TORCH_CHECK(pairs[2 * i] >= 0 && pairs[2 * i] <= pairs[2 * i + 1] && pairs[2 * i + 1] < T, "semicrf: interval out of range");
-}
-void posteriors_cpu(Tensor score, Tensor noise, Tensor v, Tensor q, Tensor logZ, Tensor node, Tensor begin, Tensor end, Tensor single,
-                    Tensor noiseP, Tensor entropy, Tensor ws)
-{
-    all_cpu(score, noise, v, q, logZ, node, begin, end, single, noiseP, entropy);
-    const Dims d = crf_dims(score, noise);
-    const int64_t TB = (int64_t)d.T * d.B;
-    semicrf_cpu::posteriors(cfp(score), cfp(noise), f32(v, TB, "v"), f32(q, TB, "q"), f32(logZ, d.B, "logZ"), d.T, d.B,
-                            f32w(node, TB, "node"), f32w(begin, TB, "begin"), f32w(end, TB, "end"), f32w(single, TB, "single"),
-                            f32w(noiseP, TB - d.B, "noiseP"), f32w(entropy, d.B, "entropy"));
-}
-inline double* state_cpu(const Tensor& ws, const Dims& d)
-{
-    want(ws, ScalarType::Byte, (int64_t)((4 * (int64_t)d.T * d.B + 2 * d.B) * sizeof(double)), "ws");
-    STD_TORCH_CHECK(((uintptr_t)ws.data_ptr() & 7) == 0, "semicrf: `ws` must be 8-byte aligned");
-    return (double*)ws.data_ptr();
-}
-void expectation_cpu(Tensor score, Tensor noise, Tensor weight, Tensor nweight, bool has_nw, Tensor v, Tensor q, Tensor E, Tensor H,
-                     Tensor ws)
-{
-    all_cpu(score, noise, weight, nweight, v, q, E, H, ws);
-    const Dims d = crf_dims(score, noise);
-    const int64_t TB = (int64_t)d.T * d.B;
-    semicrf_cpu::expectation(cfp(score), cfp(noise), weight_of(weight, score, TB * d.T), has_nw ? f32(nweight, TB - d.B, "noiseWeight") : nullptr,
-                             d.T, d.B, f32w(E, d.B, "E"), f32w(H, d.B, "H"), state_cpu(ws, d));
-}
-void covariance_cpu(Tensor score, Tensor noise, Tensor weight, Tensor nweight, bool has_nw, Tensor gout, Tensor C, Tensor Cn, Tensor ws)
-{
-    all_cpu(score, noise, weight, nweight, gout, C, Cn, ws);
-    const Dims d = crf_dims(score, noise);
-    const int64_t TB = (int64_t)d.T * d.B;
-    semicrf_cpu::covariance(cfp(score), cfp(noise), weight_of(weight, score, TB * d.T), has_nw ? f32(nweight, TB - d.B, "noiseWeight") : nullptr,
-                            f32(gout, d.B, "gout"), d.T, d.B, state_cpu(ws, d), f32w(C, TB * d.T, "C"), f32w(Cn, TB - d.B, "Cn"));
-}
-void interval_marginals_cpu(Tensor score, Tensor v, Tensor q, Tensor logZ, Tensor pairs, int64_t K, Tensor offsets, Tensor out)
-{
-    all_cpu(score, v, q, logZ, pairs, offsets, out);
-    const Dims d = marg_dims(score, v, q, logZ);
-    STD_TORCH_CHECK(K >= 0, "semicrf: negative interval count");
-    const int32_t* pp = i32(pairs, 2 * K, "pairs");
-    const int32_t* oo = i32(offsets, d.B + 1, "offsets");
-    STD_TORCH_CHECK(oo[0] == 0 && oo[d.B] == K, "semicrf: offsets do not match the interval count");
-    for (int c = 0; c < d.B; ++c) STD_TORCH_CHECK(oo[c] <= oo[c + 1], "semicrf: offsets must ascend");
-    for (int64_t i = 0; i < 2 * K; ++i) STD_TORCH_CHECK(pp[i] >= 0 && pp[i] < d.T, "semicrf: interval out of range");
-    semicrf_cpu::interval_marginals(cfp(score), cfp(v), cfp(q), cfp(logZ), d.T, d.B, pp, oo, f32w(out, K, "out"));
-}
-void marginal_decode_cpu(Tensor score, Tensor noise, Tensor v, Tensor q, Tensor logZ, Tensor tau, Tensor pairs, Tensor probs,
-                         Tensor offsets, Tensor ws)
-{
-    all_cpu(score, noise, v, q, logZ, tau, pairs, probs, offsets);
-    const Dims d = crf_dims(score, noise);
-    const int64_t TB = (int64_t)d.T * d.B;
-    STD_TORCH_CHECK((int64_t)d.T * (d.T + 1) / 2 * d.B < (1ll << 31), "semicrf: T (T+1) / 2 * B exceeds int32 offsets");
-    STD_TORCH_CHECK(pairs.dim() == 2 && pairs.size(1) == 2 && pairs.size(0) >= 1, "semicrf: pairs must be [cap, 2], cap >= 1");
-    const int64_t cap = pairs.size(0);
-    const int ts = tau_stride_of(tau, d.B);
-    semicrf_cpu::marginal_decode(cfp(score), f32(v, TB, "v"), f32(q, TB, "q"), f32(logZ, d.B, "logZ"), d.T, d.B, cfp(tau), ts,
-                                 i32(pairs, 2 * cap, "pairs"), f32w(probs, cap, "probs"), cap, i32(offsets, d.B + 1, "offsets"));
-}
-void interval_marginals_tol_cpu(Tensor score, Tensor v, Tensor q, Tensor logZ, Tensor pairs, int64_t K, Tensor offsets, int64_t tol_begin,
-                                int64_t tol_end, Tensor out)
-{
-    all_cpu(score, v, q, logZ, pairs, offsets, out);
-    const Dims d = marg_dims(score, v, q, logZ);
-    STD_TORCH_CHECK(K >= 0, "semicrf: negative interval count");
-    check_tol(tol_begin, tol_end);
-    const int32_t* pp = i32(pairs, 2 * K, "pairs");
-    const int32_t* oo = i32(offsets, d.B + 1, "offsets");
-    STD_TORCH_CHECK(oo[0] == 0 && oo[d.B] == K, "semicrf: offsets do not match the interval count");
-    for (int c = 0; c < d.B; ++c) STD_TORCH_CHECK(oo[c] <= oo[c + 1], "semicrf: offsets must ascend");
-    for (int64_t i = 0; i < 2 * K; ++i) STD_TORCH_CHECK(pp[i] >= 0 && pp[i] < d.T, "semicrf: interval out of range");
-    if (tol_begin == 0 && tol_end == 0)
-        semicrf_cpu::interval_marginals(cfp(score), cfp(v), cfp(q), cfp(logZ), d.T, d.B, pp, oo, f32w(out, K, "out"));
-    else
-        semicrf_cpu::interval_marginals_tol(cfp(score), cfp(v), cfp(q), cfp(logZ), d.T, d.B, pp, oo, (int)tol_begin, (int)tol_end,
-                                            f32w(out, K, "out"));
-}
-void marginal_decode_tol_cpu(Tensor score, Tensor noise, Tensor v, Tensor q, Tensor logZ, Tensor tau, int64_t tol_begin, int64_t tol_end,
-                             Tensor pairs, Tensor probs, Tensor offsets, Tensor ws)
-{
-    all_cpu(score, noise, v, q, logZ, tau, pairs, probs, offsets);
-    const Dims d = crf_dims(score, noise);
-    const int64_t TB = (int64_t)d.T * d.B;
-    STD_TORCH_CHECK((int64_t)d.T * (d.T + 1) / 2 * d.B < (1ll << 31), "semicrf: T (T+1) / 2 * B exceeds int32 offsets");
-    STD_TORCH_CHECK(pairs.dim() == 2 && pairs.size(1) == 2 && pairs.size(0) >= 1, "semicrf: pairs must be [cap, 2], cap >= 1");
-    check_tol(tol_begin, tol_end);
-    const int64_t cap = pairs.size(0);
-    const int ts = tau_stride_of(tau, d.B);
-    if (tol_begin == 0 && tol_end == 0)
-        semicrf_cpu::marginal_decode(cfp(score), f32(v, TB, "v"), f32(q, TB, "q"), f32(logZ, d.B, "logZ"), d.T, d.B, cfp(tau), ts,
-                                     i32(pairs, 2 * cap, "pairs"), f32w(probs, cap, "probs"), cap, i32(offsets, d.B + 1, "offsets"));
-    else
-        semicrf_cpu::marginal_decode_tol(cfp(score), f32(v, TB, "v"), f32(q, TB, "q"), f32(logZ, d.B, "logZ"), d.T, d.B, cfp(tau), ts,
-                                         (int)tol_begin, (int)tol_end, i32(pairs, 2 * cap, "pairs"), f32w(probs, cap, "probs"), cap,
-                                         i32(offsets, d.B + 1, "offsets"));
-}
-void mbr_select_cpu(Tensor pairs, Tensor weight, Tensor offsets, int64_t T, Tensor tau, Tensor pairs_out, Tensor probs_out,
-                    Tensor offsets_out, Tensor gain, Tensor ws)
-{
-    all_cpu(pairs, weight, offsets, tau, pairs_out, probs_out, offsets_out, gain);
-    const MbrDims d = mbr_dims(pairs, weight, offsets, T, pairs_out, probs_out, offsets_out, gain);
-    const int ts = tau_stride_of(tau, d.B);
-    semicrf_cpu::mbr_select(ip(pairs), cfp(weight), ip(offsets), d.K, (int)T, d.B, cfp(tau), ts, ip(pairs_out), fp(probs_out), d.cap,
-                            ip(offsets_out), fp(gain));
-}
-void compare_paths_cpu(Tensor est_pairs, Tensor est_offsets, Tensor ref_pairs, Tensor ref_offsets, int64_t T, int64_t tol_begin,
-                       int64_t tol_end, Tensor stats)
-{
-    all_cpu(est_pairs, est_offsets, ref_pairs, ref_offsets, stats);
-    const int B = cmp_dims(est_pairs, est_offsets, ref_pairs, ref_offsets, T, tol_begin, tol_end, stats);
-    // on the host the totals can be looked at: the promise the device entry point takes from its caller is checked here
-    const int32_t *eo = ip(est_offsets), *ro = ip(ref_offsets);
-    STD_TORCH_CHECK(eo[B] <= est_pairs.size(0) && ro[B] <= ref_pairs.size(0), "semicrf: offsets[B] exceeds the pairs buffer");
-    semicrf_cpu::compare_paths(ip(est_pairs), eo, ip(ref_pairs), ro, (int)T, B, (int)tol_begin, (int)tol_end, ip(stats));
-}
-void eval_path_cpu(Tensor score, Tensor noise, Tensor pairs, int64_t K, Tensor offsets, Tensor out, Tensor ws)
-{
-    all_cpu(score, noise, pairs, offsets, out);
-    const Dims d = crf_dims(score, noise);
-    STD_TORCH_CHECK(K >= 0, "semicrf: negative interval count");
-    const int32_t* pp = i32(pairs, 2 * K, "pairs");
-    const int32_t* oo = i32(offsets, d.B + 1, "offsets");
-    check_path(pp, K, oo, d.T, d.B);
-    semicrf_cpu::eval_path(cfp(score), cfp(noise), d.T, d.B, pp, oo, f32w(out, d.B, "out"));
-}
-void eval_path_bwd_cpu(Tensor gout, int64_t T, int64_t B, Tensor pairs, int64_t K, Tensor offsets, Tensor dScore, bool has_ds, Tensor dNoise,
-                       bool has_dn)
-{
-    all_cpu(gout, pairs, offsets);
-    STD_TORCH_CHECK(T >= 1 && B >= 1 && K >= 0 && T < (1 << 29) && B < (1ll << 31), "semicrf: bad sizes");
-    const int32_t* pp = i32(pairs, 2 * K, "pairs");
-    const int32_t* oo = i32(offsets, B + 1, "offsets");
-    check_path(pp, K, oo, (int)T, (int)B);
-    semicrf_cpu::eval_path_bwd(f32(gout, B, "gout"), (int)T, (int)B, pp, oo, has_ds ? f32w(dScore, T * T * B, "dScore") : nullptr,
-                               has_dn ? f32w(dNoise, (T - 1) * B, "dNoise") : nullptr);
-}
-
-// (the CPU kernels scatter the path's terms themselves: a path table is refused, not ignored)
-void logprob_fwd_cpu(Tensor score, Tensor noise, Tensor pairs, int64_t K, Tensor offsets, Tensor logProb, Tensor logZ, Tensor v, bool want_v,
-                     Tensor ws, Tensor ptab, bool has_ptab)
-{
-    STD_TORCH_CHECK(!has_ptab, "semicrf: the path table belongs to the GPU sweeps");
-    logz_fwd_cpu(score, noise, logZ, v, want_v, ws);
-    eval_path_cpu(score, noise, pairs, K, offsets, logProb, ws);
-    float* lp = (float*)logProb.data_ptr();
-    const float* lz = (const float*)logZ.data_ptr();
-    for (int64_t c = 0; c < score.size(2); ++c) lp[c] -= lz[c];
 }
 void logprob_bwd_cpu(Tensor score, Tensor noise, Tensor v, Tensor logZ, Tensor gout, int64_t gstride, Tensor pairs, int64_t K, Tensor offsets,
                      Tensor dScore, Tensor dNoise, int64_t flags, Tensor ws, Tensor ptab, bool has_ptab)
 {
     STD_TORCH_CHECK(!has_ptab, "semicrf: the path table belongs to the GPU sweeps");
     all_cpu(score, noise, v, logZ, gout, pairs, offsets, dScore, dNoise);
-    const Dims d = crf_dims(score, noise);
-    const int64_t TB = (int64_t)d.T * d.B;
-    STD_TORCH_CHECK(K >= 0 && (gstride == 0 || gstride == 1), "semicrf: bad interval count / gout stride");
-    const float* g = f32(gout, gstride ? d.B : 1, "gout");
-    std::vector<float> gp((size_t)d.B), gn((size_t)d.B), q((size_t)TB);
-    for (int c = 0; c < d.B; ++c) { gp[(size_t)c] = g[(size_t)c * gstride]; gn[(size_t)c] = -gp[(size_t)c]; }
-    const int32_t* pp = i32(pairs, 2 * K, "pairs");
-    const int32_t* oo = i32(offsets, d.B + 1, "offsets");
-    check_path(pp, K, oo, d.T, d.B);
-    semicrf_cpu::logz_bwd(cfp(score), cfp(noise), f32(v, TB, "v"), f32(logZ, d.B, "logZ"), gn.data(), d.T, d.B, f32w(dScore, TB * d.T, "dScore"),
-                          f32w(dNoise, TB - d.B, "dNoise"), q.data());
-    semicrf_cpu::eval_path_bwd(gp.data(), d.T, d.B, pp, oo, fp(dScore), fp(dNoise));
+    const LogprobBwdArgs a = logprob_bwd_args(score, noise, v, logZ, gout, gstride, pairs, K, offsets, dScore, dNoise);
+    check_path(a.pairs, K, a.offsets, a.d.T, a.d.B);
+    std::vector<float> gp((size_t)a.d.B), gn((size_t)a.d.B), q((size_t)a.d.T * a.d.B);
+    for (int c = 0; c < a.d.B; ++c) { gp[(size_t)c] = a.gout[(size_t)c * gstride]; gn[(size_t)c] = -gp[(size_t)c]; }
+    semicrf_cpu::logz_bwd(a.score, a.noise, a.v, a.logZ, gn.data(), a.d.T, a.d.B, a.dScore, a.dNoise, q.data());
+    semicrf_cpu::eval_path_bwd(gp.data(), a.d.T, a.d.B, a.pairs, a.offsets, a.dScore, a.dNoise);
 }
 
 // ---- interval scorer ---------------------------------------------------------------------------------------------------

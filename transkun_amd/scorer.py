@@ -107,8 +107,8 @@ def bwd_workspace(C: int, T: int, D: int, device) -> torch.Tensor:
     return torch.empty(n, dtype=torch.uint8, device=device)
 
 
-BF16X3 = 4      # SEMICRF_SCORE_BF16X3: OR into full_square
-LEN_BF16X3 = 16 # SEMICRF_LEN_BF16X3: OR into the backward's length-scaling mode (the two products on the three-limb bf16 kernels)
+BF16X3 = _lib.SCORE_BF16X3      # OR into full_square
+LEN_BF16X3 = _lib.LEN_BF16X3    # OR into the backward's length-scaling mode (the two products on the three-limb bf16 kernels)
 BWD_BF16X3 = 8  # this package's autograd nodes only (never handed to the library): "the backward of this forward uses LEN_BF16X3"
 PROJ_BF16X3 = 32  # this package's autograd nodes only: the projection's forward and input gradient on proj_gemm3.hip (scorer_proj_nn3)
 CONTRACTIONS = {"fp32": 0, "bf16x3": BF16X3 | BWD_BF16X3, "bf16x3-fwd": BF16X3, "bf16x3-bwd": BWD_BF16X3,
@@ -298,7 +298,7 @@ def proj_input_grad(dy2: torch.Tensor, W: torch.Tensor, out: torch.Tensor = None
     return dx
 
 
-PROJ_TN_BF16X3 = 0x40000000     # SEMICRF_PROJ_TN_BF16X3: OR into proj_tn's total_rows
+PROJ_TN_BF16X3 = _lib.PROJ_TN_BF16X3    # OR into proj_tn's total_rows
 
 
 def proj_weight_grad(dy2: torch.Tensor, x2: torch.Tensor, n_main: int, prec: int = 0):
