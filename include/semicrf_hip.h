@@ -792,6 +792,9 @@ int interval_features_gather_bwd(const float* gout, const float* ctx, int C, int
  * Backward, for the upstream gradient g[c] = gout[c * gstride] (gstride 0: one value for every chain, as -logp.sum(-1).mean() gives):
  *   dLogitsVelocity [K][128] = g (onehot(v) - softmax),  dOfLogits [K][4] = g (x_j - sigmoid(l_j) + logC'(l_j)) | g (p_j - sigmoid(l'_j))
  * (d out / d base = 1 is the caller's).  Both calls only enqueue kernels on `stream`: no synchronisation, allocation or workspace.
+ * Alignment: logitsVelocity and dLogitsVelocity must be 8-byte aligned (a lane reads / writes two classes at once); anything else is
+ * SEMICRF_EINVAL and nothing is launched.  Every other buffer takes any 4-byte aligned base.  Written: rowLogProb[0:K] and
+ * out[0:C]; dLogitsVelocity[0:128 K] and dOfLogits[0:4 K]; nothing else (tests/test_step_contract.py).
  */
 int semicrf_attribute_loss_fwd(const float* logitsVelocity, const float* ofLogits, const int32_t* velocity, const float* ofRefined,
                                const float* ofPresence, int64_t K, const int32_t* offsets, int C, const float* base, float* rowLogProb,
@@ -820,6 +823,10 @@ int semicrf_attribute_loss_bwd(const float* gout, int gstride, const float* logi
  * NULL and is not written.  ofValue: float [K][2], ofPresence: bytes [K][2].  SEMICRF_EINVAL for an unknown criterion or a missing
  * output; K == 0 launches nothing.  One launch on `stream`: no synchronisation, allocation, workspace or atomics; a row's result
  * depends on that row alone and is bit-identical from run to run.
+ * Alignment: logitsVelocity must be 8-byte aligned (a lane reads two classes at once) and velocityClass is an int64 array, 8-byte
+ * aligned as such; a logitsVelocity that is not is SEMICRF_EINVAL and nothing is launched.  ofLogits, velocityMean and ofValue take
+ * any 4-byte aligned base, ofPresence any address.  Written: K elements of the criterion's velocity output, ofValue[0:2 K] and
+ * exactly 2 K bytes of ofPresence; nothing else (tests/test_step_contract.py).
  */
 #define SEMICRF_VEL_HAMMING 0
 #define SEMICRF_VEL_MSE 1
@@ -946,7 +953,9 @@ int segment_events(const int32_t* pairs, int64_t K, const int32_t* offsets, int 
  *
  * semicrf_grad_sqnorm.  partials[i] = the sum of squares of workgroup i's share of flat[0:numel], squares and sums in double (1e30 does
  *   not overflow).  The number of partials and every order of addition depend on numel (and the alignment of flat) only: no atomics,
- *   the same bits every run.  partials: SEMICRF_SQNORM_MAX_PARTIALS doubles.
+ *   the same bits every run.  partials: SEMICRF_SQNORM_MAX_PARTIALS doubles (8-byte aligned), of which the first
+ *   min(max(ceil(numel / 32768), 1), SEMICRF_SQNORM_MAX_PARTIALS) are written; the ones past that count are not written (and not read
+ *   by semicrf_clip_from_history).  flat is read only, at any 4-byte aligned base; nothing behind flat[numel] is read.
  *
  * semicrf_clip_from_history (one workgroup).  The adaptive clip value and the norm history, MovingBuffer(initValue, maxLen) on the device:
  *   ring [capacity] fp32 (capacity <= SEMICRF_HISTORY_MAX), state = {count, head} (int32; a fresh history is ring[0] = 40, state = {1, 0}).

@@ -1,4 +1,4 @@
-"""Guard-band arena for the memory-contract tests (tests/test_memory_contract.py).
+"""Guard-band arena for the memory-contract tests (tests/test_memory_contract.py, tests/test_step_contract.py).
 
 One int32 tensor per case, filled with a 32-bit word pattern; every operand, output and workspace of the case is a contiguous view
 ("carve") into it, at a chosen address phase modulo 16, with guards of at least max(4 KiB, one [T][B] row plane) on either side.
@@ -19,7 +19,9 @@ NAN_PATTERN = 0x7FC5A5A5
 MAX_PATTERN = 0x7F7FFFFF
 PATTERNS = {"nan": NAN_PATTERN, "max": MAX_PATTERN}
 
-_ITEM = {torch.float32: 4, torch.int32: 4, torch.uint8: 1}
+# float64 / int64 carves (tests/test_step_contract.py) are 8-byte items: their phases modulo 16 are 0 and 8, each element holds the
+# word pattern twice
+_ITEM = {torch.float32: 4, torch.int32: 4, torch.uint8: 1, torch.float64: 8, torch.int64: 8}
 
 
 def _numel(shape):
@@ -34,13 +36,14 @@ def pattern_bytes(pattern: int) -> np.ndarray:
 
 
 def fill_pattern_(t: torch.Tensor, pattern: int) -> torch.Tensor:
-    """Fill a float32 / int32 tensor with the word pattern, bit for bit."""
+    """Fill a float32 / int32 (or float64 / int64: two words an element) tensor with the word pattern, bit for bit."""
     t.view(torch.int32).fill_(int(np.array([pattern], dtype=np.uint32).view(np.int32)[0]))
     return t
 
 
 def bits(t: torch.Tensor) -> torch.Tensor:
-    """A tensor's bits as int32 (uint8 stays), for comparisons that must not treat NaN != NaN or -0 == +0."""
+    """A tensor's bits as int32 (uint8 stays; an 8-byte element gives two words, so the last dimension doubles), for comparisons
+    that must not treat NaN != NaN or -0 == +0."""
     return t if t.dtype == torch.uint8 else t.contiguous().view(torch.int32)
 
 

@@ -89,6 +89,13 @@ def _f32c(t: torch.Tensor) -> torch.Tensor:
     return t if t.is_contiguous() else t.contiguous()
 
 
+def _f32c8(t: torch.Tensor) -> torch.Tensor:
+    """_f32c for logitsVelocity: the kernels read a float2 per lane, so the C ABI wants an 8-byte aligned base (include/semicrf_hip.h).
+    A contiguous view that starts 4 bytes off (buf[1:1 + K * 128].view(K, 128)) is copied into a fresh tensor; aligned inputs are not."""
+    t = _f32c(t)
+    return t if t.data_ptr() % 8 == 0 else t.clone(memory_format=torch.contiguous_format)
+
+
 class _AttributeLogProb(torch.autograd.Function):
     """out [C] = base + the per-chain sums of (lpVel + lpOF) + lpPres over the chain's rows (semicrf_attribute_loss_fwd / _bwd;
     the CPU dispatch key runs the same formulas on the host).  Once differentiable, w.r.t. logitsVelocity, ofLogits and base."""
@@ -97,7 +104,7 @@ class _AttributeLogProb(torch.autograd.Function):
     def forward(ctx, logitsVelocity, ofLogits, base, velocity, ofRefined, ofPresence, offsets):
         K, C = logitsVelocity.shape[0], offsets.shape[0] - 1
         dev = logitsVelocity.device
-        lv, of = _f32c(logitsVelocity), _f32c(ofLogits)
+        lv, of = _f32c8(logitsVelocity), _f32c(ofLogits)
         b = None if base is None else _f32c(base).reshape(C)
         ctx.in_dtypes = (logitsVelocity.dtype, ofLogits.dtype, None if base is None else base.dtype)
         ctx.base_shape = None if base is None else base.shape
@@ -146,7 +153,8 @@ def attribute_log_prob(logitsVelocity: torch.Tensor, ofLogits: torch.Tensor, vel
     The ContinuousBernoulli normaliser follows torch's fp32 definition, clamp at eps = 2^-23 included, but is evaluated from the
     logit without torch's cancellation.  The sum has a fixed order ((vel + of) + presence per row, rows ascending, base last) and
     uses no atomics: results are bit-identical between runs and a chain's value does not depend on the rest of the batch.
-    Nothing here synchronises with the host; velocities outside 0..127 give NaN (pack_attribute_targets checks them on the host)."""
+    Nothing here synchronises with the host; velocities outside 0..127 give NaN (pack_attribute_targets checks them on the host).
+    A logitsVelocity whose data pointer is off 8 bytes (a view that starts at an odd element) is copied first: the C ABI's rule."""
     K = logitsVelocity.shape[0]
     C = offsets.shape[0] - 1
     assert logitsVelocity.shape == (K, 128) and ofLogits.shape == (K, 4), "logitsVelocity [K, 128] and ofLogits [K, 4] expected"
@@ -195,7 +203,8 @@ def attribute_decode(logitsVelocity: torch.Tensor, ofLogits: torch.Tensor, crite
 
     Both tensors on one device, a GPU (csrc/attr_decode.hip) or the CPU (the host kernel: the same formulas in double).  Row-wise,
     without atomics: a row's result depends on that row alone and is bit-identical from run to run; nothing synchronises with the
-    host.  An unknown criterion raises with the reference's message."""
+    host.  An unknown criterion raises with the reference's message.  A logitsVelocity whose data pointer is off 8 bytes is copied
+    first (the C ABI's rule)."""
     if criterion not in VELOCITY_CRITERIA:
         raise Exception("Unrecognized criterion: {}".format(criterion))
     K = logitsVelocity.shape[0]
@@ -208,7 +217,7 @@ def attribute_decode(logitsVelocity: torch.Tensor, ofLogits: torch.Tensor, crite
     ofValue = torch.empty(K, 2, dtype=torch.float32, device=dev)
     ofPresence = torch.empty(K, 2, dtype=torch.uint8, device=dev)
     if K > 0:
-        _lib.ops().attribute_decode(_f32c(logitsVelocity), _f32c(ofLogits), K, VELOCITY_CRITERIA[criterion], cls, mean, ofValue, ofPresence)
+        _lib.ops().attribute_decode(_f32c8(logitsVelocity), _f32c(ofLogits), K, VELOCITY_CRITERIA[criterion], cls, mean, ofValue, ofPresence)
     return (mean if mse else cls), ofValue, ofPresence.view(torch.bool)
 
 
