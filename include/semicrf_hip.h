@@ -1066,6 +1066,48 @@ int semicrf_axial_attention_bwd(const float* q, const float* k, const float* v, 
                                 int64_t dv_stride_s0, int64_t dv_stride_s1, int64_t dv_stride_l, semicrf_stream_t stream);
 
 /*
+ * semicrf_axial_attention for bfloat16 tensors (forward only): the same sequences, heads, layout and strides, every element of q, k,
+ * v and out one bf16 value (uint16_t: the upper half of the fp32 bit pattern).  TOKEN-MAJOR, head h the slice [h d, (h + 1) d); three
+ * ELEMENT strides per tensor (s0, s1, token), so both axes of one [N][T'][F'][H d] buffer are served without a copy; strides are >= 0,
+ * a 0 repeats a tensor over that dimension (not for out); Lq != Lk is allowed; a token stride stays below 2^28 elements.  All offsets
+ * are 64-bit.
+ *
+ * Supported (semicrf_axial_attention_bf16_supported returns 1): the fp32 op's set -- 1 <= Lq, Lk <= SEMICRF_ATTENTION_MAX_L; d a
+ * multiple of 8 in [8, SEMICRF_ATTENTION_MAX_D]; H >= 1.  n0 n1 H < 2^31.  n0 n1 == 0 launches nothing.
+ *
+ * The chain (csrc/attention_bf16_math.h), per sequence, head and query i:
+ *   s_j    = (sum over c of q_ic k_jc) * (float)(1 / sqrt(d))   products of bf16 values are exact in fp32; fp32 accumulation
+ *   m      = max over j < Lk of s_j                             keys from Lk to the tile edge are masked to -inf before the maximum
+ *   p_j    = expf(s_j - m)                                      fp32
+ *   ph_j   = bf16_rne(p_j)                                      the weight the second product consumes
+ *   sum    = sum over j of (float)ph_j                          fp32, of the ROUNDED weights, in one fixed order: the keys of a
+ *                                                               32-key block whose ((j >> 2) & 1) is 0 ascending, block after block,
+ *                                                               then those whose bit is 1, then the two partial sums added
+ *   o_c    = sum over j of ph_j v_jc                            fp32 accumulation
+ *   out_ic = bf16_rne(o_c / sum)                                one correctly rounded fp32 division, one rounding to bf16
+ * so the weights that enter P V sum to `sum`, and a V that is constant over the keys comes back exactly.  NaN and inf propagate to the
+ * outputs they belong to (a non-finite q row: that query; a non-finite k row: every query of that sequence and head; a non-finite v
+ * element: its column of that sequence and head) and to no other output.
+ * On the device both products run on v_mfma_f32_32x32x16_bf16; the head dimension is padded with zeros to a multiple of 16 and the
+ * keys to a multiple of 32, in registers and LDS only.  Rows past Lq, rows past Lk and columns behind d are never read, rows past Lq
+ * never stored.  No atomics, no workspace, one launch on `stream`; tile sizes depend on Lk and d alone: a sequence's result is
+ * bit-identical from run to run, whatever n0, n1, its position in the batch, the strides and the alignment are.
+ * The device and the host mirror (the CPU key of torch.ops.semicrf.axial_attention_bf16) are NOT bit-identical to each other: the
+ * matrix instruction's internal summation is not the mirror's ascending fp32 chain, and expf differs.  Both answer to the same
+ * accuracy gates and give the same exact answers wherever every partial sum is exact.
+ * Pointers need 2-byte alignment only.  Q, K and V rows are read with 16-byte loads when q, k, v are 16-byte aligned and all their
+ * strides are multiples of 8, with 2-byte loads otherwise; `out` is written with 8-byte stores when it is 8-byte aligned and its
+ * strides are multiples of 4, with 2-byte stores otherwise: the same bits either way.
+ * SEMICRF_EINVAL, with nothing launched and `out` untouched: a shape outside the supported set, a NULL or misaligned (odd) pointer, a
+ * negative count or stride, a token stride >= 2^28, n0 n1 H >= 2^31.
+ */
+int semicrf_axial_attention_bf16_supported(int Lq, int Lk, int H, int d);
+int semicrf_axial_attention_bf16(const uint16_t* q, const uint16_t* k, const uint16_t* v, uint16_t* out, int64_t n0, int64_t n1, int Lq, int Lk,
+                                 int H, int d, int64_t q_stride_s0, int64_t q_stride_s1, int64_t q_stride_l, int64_t k_stride_s0,
+                                 int64_t k_stride_s1, int64_t k_stride_l, int64_t v_stride_s0, int64_t v_stride_s1, int64_t v_stride_l,
+                                 int64_t out_stride_s0, int64_t out_stride_s1, int64_t out_stride_l, semicrf_stream_t stream);
+
+/*
  * The feed-forward ResBlock of the backbone's transformer layers in eval mode, as one launch.  Replaces: RMSNorm, Linear, GELU,
  * Linear, the multiplication by the LayerScale and the residual addition of ResBlock around the feed-forward module
  * (LayersTransformer.py), about ten launches and three round trips of the [tokens, hidden] activation.  For every token t = (i0, i1),

@@ -20,8 +20,17 @@ time-axis half, and none of the copies eager PyTorch makes for the projections a
 whose backward is `torch.ops.semicrf.axial_attention_bwd` (csrc/attention_bwd.hip, the host mirror on the CPU): dq, dk and dv are
 written by strides into tensors laid out like q, k and v, so `BasicBlock` keeps its no-transpose form in training too.  The backward
 recomputes the softmax from q and k and takes `out` as the forward wrote it; nothing else is saved, and a second derivative raises.
-Every route answers by the stock call for dtypes other than float32, for shapes outside the op's supported set, for broadcasting keys
-and for device views whose tokens lie 2^28 elements apart or more.  `ATTENTION_ROUTES` counts which way the calls went.
+Every route answers by the stock call for dtypes other than float32 (bfloat16 has a knob of its own, below), for shapes outside the
+op's supported set, for broadcasting keys and for device views whose tokens lie 2^28 elements apart or more.  `ATTENTION_ROUTES`
+counts which way the calls went.
+
+bfloat16 tensors (a model cast to bf16, or run under `torch.autocast(dtype=torch.bfloat16)`) have a fused forward of their own,
+`torch.ops.semicrf.axial_attention_bf16` (csrc/attention_bf16.hip: both products on the bf16 matrix instruction, the same token-major
+strided contract; the host mirror on the CPU).  It is a separate knob: `attentionBf16 = "torch" | "fused"` on every attention module,
+and on `BasicBlock` and `Backbone` for all of theirs; the default is "torch", under which bf16 tensors take the stock route as they
+always have.  "fused" sends bf16 calls to the op wherever the fp32 op would apply (route not "torch", no gradient wanted, supported
+shape, no broadcasting keys, token strides within the limit); it is forward only, so under autograd both "fused" and "fused-train"
+answer by the stock route for bf16.  `ATTENTION_BF16_ROUTES` counts the bf16 calls made with the knob at "fused".
 
 The feed-forward half of a layer has a fused route too.  `feedForward = "fused" | "torch"` on a `ResBlock`, and on `BasicBlock` and
 `Backbone` for all of their feed-forward blocks, picks it; the default is "torch", the stock expression.  "fused" runs a block whose
@@ -50,12 +59,21 @@ DEFAULT_ATTENTION = "fused"
 # calls of axial_attention by the way they went ("fused": the forward op alone; "fused-train": the autograd Function; "torch": the stock
 # call) and, under "bwd", the launches of the HIP backward; tests read it
 ATTENTION_ROUTES = {"fused": 0, "fused-train": 0, "torch": 0, "bwd": 0}
+BF16_KINDS = ("torch", "fused")
+DEFAULT_ATTENTION_BF16 = "torch"
+# calls of axial_attention on bfloat16 tensors with bf16 = "fused", by the way they went; tests read it
+ATTENTION_BF16_ROUTES = {"fused": 0, "torch": 0}
 
 
 # ---- the attention ------------------------------------------------------------------------------------------------------------------
 def attention_supported(Lq: int, Lk: int, num_heads: int, head_dim: int) -> bool:
     """semicrf_axial_attention_supported: 1 <= Lq, Lk <= 256, head_dim a multiple of 8 in [8, 64], num_heads >= 1."""
     return bool(_lib.load().semicrf_axial_attention_supported(int(Lq), int(Lk), int(num_heads), int(head_dim)))
+
+
+def attention_bf16_supported(Lq: int, Lk: int, num_heads: int, head_dim: int) -> bool:
+    """semicrf_axial_attention_bf16_supported: the fp32 op's set."""
+    return bool(_lib.load().semicrf_axial_attention_bf16_supported(int(Lq), int(Lk), int(num_heads), int(head_dim)))
 
 
 def attention_bwd_supported(Lq: int, Lk: int, num_heads: int, head_dim: int) -> bool:
@@ -107,8 +125,8 @@ def _wants_grad(q, k, v) -> bool:
     return torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad)
 
 
-def _fused_applies(q, k, v, num_heads, train=False) -> bool:
-    if not (q.dtype == k.dtype == v.dtype == torch.float32) or not (q.device == k.device == v.device):
+def _fused_applies(q, k, v, num_heads, train=False, dtype=torch.float32) -> bool:
+    if not (q.dtype == k.dtype == v.dtype == dtype) or not (q.device == k.device == v.device):
         return False
     if q.device.type not in ("cuda", "cpu") or q.dim() < 2 or k.shape != v.shape or q.numel() == 0 or k.numel() == 0:
         return False
@@ -119,11 +137,14 @@ def _fused_applies(q, k, v, num_heads, train=False) -> bool:
     if q.device.type == "cuda" and not _token_strides_fit(q, k, v):
         return False                                            # tokens 2^28 elements apart or more: outside the device op's addressing
     dims = (q.shape[-2], k.shape[-2], num_heads, q.shape[-1] // num_heads)
+    if dtype == torch.bfloat16:
+        return not train and attention_bf16_supported(*dims)    # forward only
     return attention_supported(*dims) and (not train or attention_bwd_supported(*dims))
 
 
 def _fused_forward(q, k, v, num_heads):
-    """The forward op on q, k, v as they lie in memory -> (out, split, (q4, k4, v4)): the 4-d views the op was given."""
+    """The forward op (the bf16 op for bfloat16 tensors) on q, k, v as they lie in memory -> (out, split, (q4, k4, v4)): the 4-d views
+    the op was given."""
     nlead = q.dim() - 2
     best = None
     for split in range(nlead + 1):
@@ -140,7 +161,10 @@ def _fused_forward(q, k, v, num_heads):
     if o4 is None:
         out = torch.empty(q.shape, dtype=q.dtype, device=q.device)
         o4 = _as_sequences(out, split)
-    _lib.ops().axial_attention(q4, k4, v4, o4, num_heads)
+    if q.dtype == torch.bfloat16:
+        _lib.ops().axial_attention_bf16(q4, k4, v4, o4, num_heads)
+    else:
+        _lib.ops().axial_attention(q4, k4, v4, o4, num_heads)
     return out, split, (q4, k4, v4)
 
 
@@ -190,7 +214,8 @@ class _AxialAttentionTrain(torch.autograd.Function):
         return grads[0], grads[1], grads[2], None
 
 
-def axial_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, num_heads: int, route: str = "fused") -> torch.Tensor:
+def axial_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, num_heads: int, route: str = "fused",
+                    bf16: str = "torch") -> torch.Tensor:
     """softmax(q k^T / sqrt(d)) v per head and sequence.  q [..., Lq, H d], k and v [..., Lk, H d], arbitrary strided views whose last
     dimension is contiguous: the leading dimensions are handed to the op as its two sequence dimensions by strides alone (a tensor
     whose leading dimensions cannot be expressed that way is made contiguous first, that tensor only).  Returns [..., Lq, H d], laid
@@ -202,9 +227,23 @@ def axial_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, num_heads
     forms V addresses from a 32-bit lane offset).  route = "fused-train": "fused", except that under autograd the op runs inside an
     autograd Function whose backward is the HIP op axial_attention_bwd (once differentiable; gradients laid out like q, k, v; None
     for an input that needs none) wherever the forward applies and semicrf_axial_attention_bwd_supported holds, and the stock route
-    elsewhere.  route = "torch": always the stock route.  Always usable, always differentiable."""
+    elsewhere.  route = "torch": always the stock route.  Always usable, always differentiable.
+
+    bf16 = "torch" (the default): bfloat16 tensors take the stock route, as every dtype other than float32 does.  bf16 = "fused": when
+    q, k and v are all bfloat16, route is not "torch" and no gradient is wanted, the call is the HIP op axial_attention_bf16 (the host
+    kernel for CPU tensors) under the same conditions as the fp32 op -- same device, no broadcasting keys, a supported shape, token
+    strides within the limit -- and returns bf16 laid out like q; in every other case, under autograd with either fused route
+    included, the call is what it is with bf16 = "torch"."""
     if route not in ROUTES:
         raise ValueError(f"route must be one of {ROUTES}, not {route!r}")
+    if bf16 not in BF16_KINDS:
+        raise ValueError(f"bf16 must be one of {BF16_KINDS}, not {bf16!r}")
+    if bf16 == "fused" and q.dtype == k.dtype == v.dtype == torch.bfloat16:
+        if route != "torch" and _fused_applies(q, k, v, num_heads, dtype=torch.bfloat16):
+            ATTENTION_BF16_ROUTES["fused"] += 1
+            ATTENTION_ROUTES["fused"] += 1
+            return _fused_forward(q, k, v, num_heads)[0]
+        ATTENTION_BF16_ROUTES["torch"] += 1
     train = route == "fused-train" and _wants_grad(q, k, v)
     if route == "torch" or not _fused_applies(q, k, v, num_heads, train):
         ATTENTION_ROUTES["torch"] += 1
@@ -404,7 +443,9 @@ class MultiHeadAttentionKernel(nn.Module):
     checkpoint loads) and forward raises NotImplementedError.
 
     attention: "fused" (axial_attention's HIP op where it applies; the stock route under autograd), "fused-train" (the HIP op and its
-    HIP backward under autograd) or "torch" (the stock route)."""
+    HIP backward under autograd) or "torch" (the stock route).
+    attentionBf16: "torch" (bfloat16 tensors take the stock route: the default) or "fused" (axial_attention's bf16 HIP op where it
+    applies, forward only)."""
 
     def __init__(self, embed_dim, num_heads, dropout=0., k_dim=None, v_dim=None, fourierSize=32, kernel="fourier", hiddenFactor=1):
         super().__init__()
@@ -422,6 +463,7 @@ class MultiHeadAttentionKernel(nn.Module):
             self.gamma = nn.Parameter(torch.tensor(1.0))
             self.norm = RMSNorm()
         self.attention = DEFAULT_ATTENTION
+        self.attentionBf16 = DEFAULT_ATTENTION_BF16
         self._reset_parameters()
 
     def _reset_parameters(self):
@@ -443,7 +485,7 @@ class MultiHeadAttentionKernel(nn.Module):
         q, k, v = query @ self.q_proj_weight, key @ self.k_proj_weight, value @ self.v_proj_weight
         if seq_dim == -3:
             q, k, v = q.transpose(-3, -2), k.transpose(-3, -2), v.transpose(-3, -2)
-        fetched = axial_attention(q, k, v, self.num_heads, route=self.attention)
+        fetched = axial_attention(q, k, v, self.num_heads, route=self.attention, bf16=self.attentionBf16)
         if seq_dim == -3:
             fetched = fetched.transpose(-3, -2)
         return self.out_proj(fetched)
@@ -460,7 +502,8 @@ class BasicBlock(nn.Module):
 
     With attention = "fused" or "fused-train" the "F" and "T" halves run on the [N, T, F, D] buffer as it is: everything but the
     attention is per token, and the two halves differ only in which dimension the attention is told is the sequence.  With "torch"
-    the block follows the reference's order of operations, `transpose(-3, -2)` around the time-axis half included."""
+    the block follows the reference's order of operations, `transpose(-3, -2)` around the time-axis half included.
+    attentionBf16 = "torch" | "fused" sets the bfloat16 knob of all its attention modules."""
 
     def __init__(self, inputSize, num_heads, fourierSize, hiddenFactor=2, hiddenFactorAttn=1, approxKernels=[None, None, None, None],
                  enabled=["F", "T", "All0", "0All"], dropoutProb=0.0):
@@ -498,6 +541,19 @@ class BasicBlock(nn.Module):
             raise ValueError(f"attention must be one of {ROUTES}, not {route!r}")
         for m in self.attention_modules():
             m.attention = route
+
+    @property
+    def attentionBf16(self):
+        kinds = {m.attentionBf16 for m in self.modules() if isinstance(m, MultiHeadAttentionKernel)}
+        return kinds.pop() if len(kinds) == 1 else "mixed"
+
+    @attentionBf16.setter
+    def attentionBf16(self, kind):
+        if kind not in BF16_KINDS:
+            raise ValueError(f"attentionBf16 must be one of {BF16_KINDS}, not {kind!r}")
+        for m in self.modules():
+            if isinstance(m, MultiHeadAttentionKernel):
+                m.attentionBf16 = kind
 
     def feed_forward_blocks(self):
         return [m for m in self.modules() if isinstance(m, ResBlock) and m.is_feed_forward()]
@@ -559,6 +615,7 @@ class Backbone(nn.Module):
     frequency axis; nLayers BasicBlocks; the target tokens are upsampled 8x in time by a transposed convolution and cut to T.
 
     attention: "fused" | "fused-train" | "torch" for all layers (the property reads "mixed" when they differ).
+    attentionBf16: "torch" | "fused" for the bfloat16 calls of all layers, likewise.
     feedForward: "torch" | "fused" for the feed-forward blocks of all layers, likewise."""
 
     def __init__(self, inputSize, baseSize, posEmbedInitGamma, nHead, fourierSize=16, hiddenFactor=2, hiddenFactorAttn=1,
@@ -605,6 +662,19 @@ class Backbone(nn.Module):
         for m in self.modules():
             if isinstance(m, MultiHeadAttentionKernel):
                 m.attention = route
+
+    @property
+    def attentionBf16(self):
+        kinds = {m.attentionBf16 for m in self.modules() if isinstance(m, MultiHeadAttentionKernel)}
+        return kinds.pop() if len(kinds) == 1 else "mixed"
+
+    @attentionBf16.setter
+    def attentionBf16(self, kind):
+        if kind not in BF16_KINDS:
+            raise ValueError(f"attentionBf16 must be one of {BF16_KINDS}, not {kind!r}")
+        for m in self.modules():
+            if isinstance(m, MultiHeadAttentionKernel):
+                m.attentionBf16 = kind
 
     def feed_forward_blocks(self):
         return [m for m in self.modules() if isinstance(m, ResBlock) and m.is_feed_forward()]

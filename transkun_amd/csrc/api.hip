@@ -1302,6 +1302,34 @@ int semicrf_axial_attention(const float* q, const float* k, const float* v, floa
     return SEMICRF_OK;
 }
 
+int semicrf_axial_attention_bf16_supported(int Lq, int Lk, int H, int d) { return attention::supported(Lq, Lk, H, d) ? 1 : 0; }
+
+int semicrf_axial_attention_bf16(const uint16_t* q, const uint16_t* k, const uint16_t* v, uint16_t* out, int64_t n0, int64_t n1, int Lq, int Lk,
+                                 int H, int d, int64_t q_stride_s0, int64_t q_stride_s1, int64_t q_stride_l, int64_t k_stride_s0,
+                                 int64_t k_stride_s1, int64_t k_stride_l, int64_t v_stride_s0, int64_t v_stride_s1, int64_t v_stride_l,
+                                 int64_t out_stride_s0, int64_t out_stride_s1, int64_t out_stride_l, semicrf_stream_t stream)
+{
+    SEMICRF_CHECK_ARG(attention::supported(Lq, Lk, H, d),
+                      "axial_attention_bf16: Lq=%d Lk=%d H=%d d=%d is outside the supported set (1 <= Lq, Lk <= %d; d a multiple of 8 in "
+                      "[%d, %d]; H >= 1): see semicrf_axial_attention_bf16_supported", Lq, Lk, H, d, attention::ATT_MAX_L, attention::ATT_MIN_D,
+                      attention::ATT_MAX_D);
+    SEMICRF_CHECK_ARG(n0 >= 0 && n1 >= 0, "axial_attention_bf16: n0=%lld n1=%lld must be >= 0", (long long)n0, (long long)n1);
+    if (n0 == 0 || n1 == 0) return SEMICRF_OK;
+    SEMICRF_CHECK_ARG(n0 < (1ll << 31) && n1 < (1ll << 31) && n0 * n1 * H < (1ll << 31),
+                      "axial_attention_bf16: n0 * n1 * H = %lld * %lld * %d must stay below 2^31", (long long)n0, (long long)n1, H);
+    SEMICRF_CHECK_ARG(q && k && v && out, "axial_attention_bf16: q/k/v/out must be non-NULL");
+    SEMICRF_CHECK_ARG((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)out) & 1) == 0,
+                      "axial_attention_bf16: q/k/v/out must be 2-byte aligned");
+    const long long strides[12] = {q_stride_s0, q_stride_s1, q_stride_l, k_stride_s0, k_stride_s1, k_stride_l,
+                                   v_stride_s0, v_stride_s1, v_stride_l, out_stride_s0, out_stride_s1, out_stride_l};
+    for (int i = 0; i < 12; ++i) SEMICRF_CHECK_ARG(strides[i] >= 0, "axial_attention_bf16: stride %d is negative (%lld)", i, strides[i]);
+    for (int i = 2; i < 12; i += 3)
+        SEMICRF_CHECK_ARG(strides[i] < (1ll << 28), "axial_attention_bf16: token stride %lld must stay below 2^28 elements", strides[i]);
+    launch_axial_attention_bf16(q, k, v, out, n0, n1, Lq, Lk, H, d, strides, (hipStream_t)stream);
+    SEMICRF_CHECK_LAUNCH("semicrf_axial_attention_bf16");
+    return SEMICRF_OK;
+}
+
 int semicrf_axial_attention_bwd_supported(int Lq, int Lk, int H, int d) { return attention::supported(Lq, Lk, H, d) ? 1 : 0; }
 
 int semicrf_axial_attention_bwd(const float* q, const float* k, const float* v, const float* out, const float* dout, float* dq, float* dk,

@@ -21,6 +21,7 @@
 #include "attr_decode_math.h"
 #include "attr_heads_math.h"
 #include "attention_math.h"
+#include "attention_bf16_math.h"
 #include "ffn_math.h"
 #include "logmel_math.h"
 #include "cpu_ops.h"
@@ -1453,6 +1454,56 @@ void axial_attention(const float* q, const float* k, const float* v, float* out,
                 }
                 float* oi = ob + (int64_t)i * st[11];
                 for (int c = 0; c < d; ++c) oi[c] = acc[c] / sum;
+            }
+        }
+    }
+}
+
+// semicrf_axial_attention_bf16: the chain of attention_bf16_math.h.  The products of bf16 values are exact in fp32; both sums over them
+// are plain fp32 additions ascending from +0 (the device sums 16 products inside one matrix instruction: equal wherever the partial
+// sums are exact, equal to rounding elsewhere); the weights are rounded to bf16 BEFORE they are summed and before they meet V.
+void axial_attention_bf16(const uint16_t* q, const uint16_t* k, const uint16_t* v, uint16_t* out, int64_t n0, int64_t n1, int Lq, int Lk, int H,
+                          int d, const int64_t* st)
+{
+    using namespace semicrf::attention;
+    const float scale = scale_of(d);
+    const int64_t nwork = n0 * n1 * H;
+#pragma omp parallel
+    {
+        std::vector<float> p((size_t)Lk), acc((size_t)d), qf((size_t)d);
+#pragma omp for schedule(static)
+        for (int64_t w = 0; w < nwork; ++w) {
+            const int h = (int)(w % H);
+            const int64_t s = w / H, s0 = s / n1, s1 = s % n1;
+            const uint16_t* qb = q + s0 * st[0] + s1 * st[1] + (int64_t)h * d;
+            const uint16_t* kb = k + s0 * st[3] + s1 * st[4] + (int64_t)h * d;
+            const uint16_t* vb = v + s0 * st[6] + s1 * st[7] + (int64_t)h * d;
+            uint16_t* ob = out + s0 * st[9] + s1 * st[10] + (int64_t)h * d;
+            for (int i = 0; i < Lq; ++i) {
+                const uint16_t* qi = qb + (int64_t)i * st[2];
+                for (int c = 0; c < d; ++c) qf[c] = bf16_to_float(qi[c]);
+                float mx = -std::numeric_limits<float>::infinity();
+                for (int j = 0; j < Lk; ++j) {
+                    const uint16_t* kj = kb + (int64_t)j * st[5];
+                    float t = 0.0f;
+                    for (int c = 0; c < d; ++c) t += bf16_to_float(kj[c]) * qf[c];
+                    p[j] = t * scale;
+                    mx = fmaxf(mx, p[j]);                            // as the device: a NaN score does not become the maximum
+                }
+                float half[2] = {0.0f, 0.0f};
+                for (int j = 0; j < Lk; ++j) {
+                    p[j] = bf16_to_float(bf16_rne(expf(p[j] - mx)));
+                    half[sum_half(j)] += p[j];
+                }
+                const float sum = half[0] + half[1];
+                std::fill(acc.begin(), acc.end(), 0.0f);
+                for (int j = 0; j < Lk; ++j) {
+                    const uint16_t* vj = vb + (int64_t)j * st[8];
+                    const float pj = p[j];
+                    for (int c = 0; c < d; ++c) acc[c] += pj * bf16_to_float(vj[c]);
+                }
+                uint16_t* oi = ob + (int64_t)i * st[11];
+                for (int c = 0; c < d; ++c) oi[c] = bf16_rne(acc[c] / sum);
             }
         }
     }

@@ -74,6 +74,10 @@ void adabelief_step(float* p, const float* g, float* m, float* s, int64_t numel,
 // (attention_math.h); strides: the twelve element strides q, k, v, out x (s0, s1, l); the caller has checked the supported set
 void axial_attention(const float* q, const float* k, const float* v, float* out, int64_t n0, int64_t n1, int Lq, int Lk, int H, int d,
                      const int64_t* strides);
+// the same attention of bfloat16 tensors (semicrf_axial_attention_bf16): the chain of attention_bf16_math.h in plain C++ -- fp32
+// accumulation ascending, the conversions to bf16 written out (round to nearest even); strides as above, in bf16 elements
+void axial_attention_bf16(const uint16_t* q, const uint16_t* k, const uint16_t* v, uint16_t* out, int64_t n0, int64_t n1, int Lq, int Lk, int H,
+                          int d, const int64_t* strides);
 // its backward (semicrf_axial_attention_bwd): the same chain in the same orders; any of dq, dk, dv may be null; strides: the twenty-four
 // element strides q, k, v, out, dout, dq, dk, dv x (s0, s1, l)
 void axial_attention_bwd(const float* q, const float* k, const float* v, const float* out, const float* dout, float* dq, float* dk, float* dv,

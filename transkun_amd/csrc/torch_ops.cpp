@@ -1119,8 +1119,10 @@ void attribute_heads_cpu(Tensor ctx, int64_t C, int64_t T, int64_t D, int64_t ld
 // ---- the backbone's axial attention (semicrf_axial_attention) ----------------------------------------------------------------------
 // q, out: [n0, n1, Lq, H d]; k, v: [n0, n1, Lk, H d]: VIEWS -- the three element strides of every tensor are read from the tensor
 // itself (so an access can never leave it); only the last dimension must be contiguous.  Sizes of 1 may carry any stride.
-struct AttentionArgs { const float *q, *k, *v; float* out; int64_t n0, n1; int Lq, Lk, H, d; int64_t st[12]; };
-inline AttentionArgs attention_args(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& out, int64_t H)
+// (the bf16 op, semicrf_axial_attention_bf16, takes the same views of bfloat16 tensors: `dtype` is the one all four must have)
+struct AttentionArgs { const void *q, *k, *v; void* out; int64_t n0, n1; int Lq, Lk, H, d; int64_t st[12]; };
+inline AttentionArgs attention_args(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& out, int64_t H,
+                                    ScalarType dtype = ScalarType::Float)
 {
     const Tensor* ts[4] = {&q, &k, &v, &out};
     const char* names[4] = {"q", "k", "v", "out"};
@@ -1131,7 +1133,8 @@ inline AttentionArgs attention_args(const Tensor& q, const Tensor& k, const Tens
     STD_TORCH_CHECK(H >= 1 && H < (1 << 20) && HD % H == 0, "semicrf: the last dimension must be H * d");
     for (int i = 0; i < 4; ++i) {
         const Tensor& t = *ts[i];
-        STD_TORCH_CHECK(t.defined() && t.scalar_type() == ScalarType::Float && t.dim() == 4, "semicrf: `", names[i], "` must be a 4-d float32 tensor");
+        STD_TORCH_CHECK(t.defined() && t.scalar_type() == dtype && t.dim() == 4, "semicrf: `", names[i], "` must be a 4-d ",
+                        dtype == ScalarType::Float ? "float32" : "bfloat16", " tensor");
         STD_TORCH_CHECK(t.size(0) == a.n0 && t.size(1) == a.n1 && t.size(3) == HD && t.size(2) == (i == 0 || i == 3 ? Lq : Lk),
                         "semicrf: `", names[i], "` does not have the shape of the call");
         STD_TORCH_CHECK(HD == 1 || t.stride(3) == 1, "semicrf: `", names[i], "` must have a contiguous last dimension");
@@ -1147,7 +1150,7 @@ inline AttentionArgs attention_args(const Tensor& q, const Tensor& k, const Tens
     STD_TORCH_CHECK(semicrf_axial_attention_supported(a.Lq, a.Lk, a.H, a.d),
                     "semicrf: axial_attention does not support Lq=", Lq, " Lk=", Lk, " H=", H, " d=", HD / H,
                     " (semicrf_axial_attention_supported)");
-    a.q = f32s(q, "q"); a.k = f32s(k, "k"); a.v = f32s(v, "v"); a.out = f32so(out, "out");
+    a.q = q.data_ptr(); a.k = k.data_ptr(); a.v = v.data_ptr(); a.out = out.data_ptr();      // defined and of `dtype`: checked above
     return a;
 }
 void axial_attention_op(Tensor q, Tensor k, Tensor v, Tensor out, int64_t H)
@@ -1155,7 +1158,7 @@ void axial_attention_op(Tensor q, Tensor k, Tensor v, Tensor out, int64_t H)
     Ctx c(q); c.same(q, k, v, out);
     const AttentionArgs a = attention_args(q, k, v, out, H);
     if (a.n0 == 0 || a.n1 == 0) return;
-    check(semicrf_axial_attention(a.q, a.k, a.v, a.out, a.n0, a.n1, a.Lq, a.Lk, a.H, a.d, a.st[0], a.st[1], a.st[2], a.st[3], a.st[4], a.st[5],
+    check(semicrf_axial_attention((const float*)a.q, (const float*)a.k, (const float*)a.v, (float*)a.out, a.n0, a.n1, a.Lq, a.Lk, a.H, a.d, a.st[0], a.st[1], a.st[2], a.st[3], a.st[4], a.st[5],
                                   a.st[6], a.st[7], a.st[8], a.st[9], a.st[10], a.st[11], c.stream),
           "semicrf_axial_attention");
 }
@@ -1164,7 +1167,25 @@ void axial_attention_cpu(Tensor q, Tensor k, Tensor v, Tensor out, int64_t H)
     all_cpu(q, k, v, out);
     const AttentionArgs a = attention_args(q, k, v, out, H);
     if (a.n0 == 0 || a.n1 == 0) return;
-    semicrf_cpu::axial_attention(a.q, a.k, a.v, a.out, a.n0, a.n1, a.Lq, a.Lk, a.H, a.d, a.st);
+    semicrf_cpu::axial_attention((const float*)a.q, (const float*)a.k, (const float*)a.v, (float*)a.out, a.n0, a.n1, a.Lq, a.Lk, a.H, a.d, a.st);
+}
+void axial_attention_bf16_op(Tensor q, Tensor k, Tensor v, Tensor out, int64_t H)
+{
+    Ctx c(q); c.same(q, k, v, out);
+    const AttentionArgs a = attention_args(q, k, v, out, H, ScalarType::BFloat16);
+    if (a.n0 == 0 || a.n1 == 0) return;
+    check(semicrf_axial_attention_bf16((const uint16_t*)a.q, (const uint16_t*)a.k, (const uint16_t*)a.v, (uint16_t*)a.out, a.n0, a.n1, a.Lq, a.Lk,
+                                       a.H, a.d, a.st[0], a.st[1], a.st[2], a.st[3], a.st[4], a.st[5], a.st[6], a.st[7], a.st[8], a.st[9], a.st[10],
+                                       a.st[11], c.stream),
+          "semicrf_axial_attention_bf16");
+}
+void axial_attention_bf16_cpu(Tensor q, Tensor k, Tensor v, Tensor out, int64_t H)
+{
+    all_cpu(q, k, v, out);
+    const AttentionArgs a = attention_args(q, k, v, out, H, ScalarType::BFloat16);
+    if (a.n0 == 0 || a.n1 == 0) return;
+    semicrf_cpu::axial_attention_bf16((const uint16_t*)a.q, (const uint16_t*)a.k, (const uint16_t*)a.v, (uint16_t*)a.out, a.n0, a.n1, a.Lq, a.Lk, a.H,
+                                      a.d, a.st);
 }
 
 // ---- the backbone's feed-forward ResBlock (semicrf_ffn_residual) --------------------------------------------------------------------
@@ -1557,6 +1578,7 @@ STABLE_TORCH_LIBRARY(semicrf, m)
           "Tensor(b!) dW1, Tensor(c!) db1, Tensor(d!) dW2, Tensor(e!) db2, Tensor(f!) ws) -> ()");
     m.def("attribute_heads_dropout_mask(Tensor(a!) mask, int seed, int K, int Hv, int Ho, float pv, float po) -> ()");
     m.def("axial_attention(Tensor q, Tensor k, Tensor v, Tensor(a!) out, int H) -> ()");
+    m.def("axial_attention_bf16(Tensor q, Tensor k, Tensor v, Tensor(a!) out, int H) -> ()");
     m.def("axial_attention_bwd(Tensor q, Tensor k, Tensor v, Tensor out, Tensor dout, Tensor(a!)? dq, Tensor(b!)? dk, Tensor(c!)? dv, int H) -> ()");
     m.def("ffn_residual(Tensor x, Tensor W1, Tensor b1, Tensor W2, Tensor b2, Tensor scale, float eps, Tensor(a!) out) -> ()");
     m.def("log_mel(Tensor frames, Tensor windows, Tensor tw, Tensor fb_start, Tensor fb_len, Tensor fb_off, Tensor fb_val, int max_len, "
@@ -1601,6 +1623,7 @@ STABLE_TORCH_LIBRARY_IMPL(semicrf, CPU, m)
     m.impl("attribute_heads_bwd", TORCH_BOX(&attribute_heads_bwd_cpu));
     m.impl("attribute_heads_dropout_mask", TORCH_BOX(&attribute_heads_dropout_mask_cpu));
     m.impl("axial_attention", TORCH_BOX(&axial_attention_cpu));
+    m.impl("axial_attention_bf16", TORCH_BOX(&axial_attention_bf16_cpu));
     m.impl("axial_attention_bwd", TORCH_BOX(&axial_attention_bwd_cpu));
     m.impl("ffn_residual", TORCH_BOX(&ffn_residual_cpu));
     m.impl("log_mel", TORCH_BOX(&log_mel_cpu));
@@ -1651,6 +1674,7 @@ STABLE_TORCH_LIBRARY_IMPL(semicrf, CUDA, m)
     m.impl("attribute_heads_bwd", TORCH_BOX(&attribute_heads_bwd_op));
     m.impl("attribute_heads_dropout_mask", TORCH_BOX(&attribute_heads_dropout_mask_op));
     m.impl("axial_attention", TORCH_BOX(&axial_attention_op));
+    m.impl("axial_attention_bf16", TORCH_BOX(&axial_attention_bf16_op));
     m.impl("axial_attention_bwd", TORCH_BOX(&axial_attention_bwd_op));
     m.impl("ffn_residual", TORCH_BOX(&ffn_residual_op));
     m.impl("log_mel", TORCH_BOX(&log_mel_op));
