@@ -281,3 +281,27 @@ def test_no_register_copies_ahead_of_the_lds_waits(src):
     spec.loader.exec_module(mod)
     text = mod.compile_to_asm(os.path.join(root, "transkun_amd", "csrc", src), [])
     assert mod.check(text, src) == 0
+
+
+def test_documented_persist_variants_compile():
+    """tools/README.md tells people which variants of persist.hip to build (`python tools/mkvar.py NAME DEFINE ...`); a recipe
+    that no longer compiles is a rotten document (one did: a later static_assert ruled its geometry out and nobody noticed).  Every
+    recipe listed there goes through the compiler's front end -- host and device pass, static_asserts included -- with the release
+    flags; all of them at once.  The list is read from the README: it exists nowhere else."""
+    import subprocess
+    from transkun_amd import _build
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    with open(os.path.join(root, "tools", "README.md")) as f:
+        recipes = re.findall(r"^\* `python tools/mkvar\.py (\w+)((?: \w+=\w+)+)`", f.read(), re.M)
+    variants = {name: defs.split() for name, defs in recipes}
+    assert len(variants) == len(recipes) >= 5, recipes
+    for must in (["SEMICRF_DEBUG_BUILD=1"], ["SEMICRF_PANEL_PROBES=1", "SEMICRF_CT_DBG=16"], ["SEMICRF_PANEL_PROBES=1", "SEMICRF_PROBE_TASKS=1"],
+                 ["SEMICRF_PANEL_PROBES=1", "SEMICRF_PROBE_HIST=1"], ["SEMICRF_BANDX=0"]):
+        assert must in variants.values(), must
+    src = os.path.join(_build.CSRC, "persist.hip")
+    flags = ["--offload-arch=" + _build.ARCH, "-O3", "-std=c++17", "-fPIC", "-fno-fast-math", "-ffp-contract=off", "-Wall",
+             "-Wno-unused-function"] + _build.EXTRA_FLAGS["persist.hip"]
+    procs = {name: subprocess.Popen([_build._hipcc()] + flags + ["-D" + d for d in defs] + ["-fsyntax-only", src],
+                                    stdout=subprocess.PIPE, stderr=subprocess.STDOUT) for name, defs in variants.items()}
+    status = {name: (p.communicate(), p.returncode)[1] for name, p in procs.items()}
+    assert all(rc == 0 for rc in status.values()), status

@@ -1,6 +1,6 @@
 """Development helper: build a variant of libsemicrf_hip.so in which ONLY persist.hip (or the files named with --files) is
 recompiled with extra -D defines; every other object comes from the release build's csrc/_obj.
-   python tools/_mkvar.py NAME DEFINE[=V] ... [--files a.hip,b.hip]"""
+   python tools/mkvar.py NAME DEFINE[=V] ... [--files a.hip,b.hip]"""
 import os, shutil, subprocess, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from transkun_amd import _build
