@@ -165,6 +165,16 @@ int semicrf_debug_wg_ticket(int n_spine, int grid, int block);
  * automatic choice (the default).  The release library reads no environment variables. */
 void semicrf_debug_score_variant(int variant);
 
+/* Host-side view of interval_score_fwd's kernel choice (test hook, no device work, nothing is read from the process's state): the
+ * kernel that a call with C chains, T frames, contraction size D, row strides ldq / ldk, 16-byte aligned q and k (aligned != 0),
+ * precision prec (1 = SEMICRF_SCORE_BF16X3), the slot layout group / pitch, a row constant (rowc != 0), the forced variant
+ * (semicrf_debug_score_variant's argument) and the implementation impl (semicrf_set_impl's) would run.  The answer is in
+ * semicrf_debug_score_variant's numbering, extended: 0 register loads, 1 the plain kernel, 2 the 64 x 128 tiles, 3 the three-limb
+ * bf16 tiles, 32 streaming, 64 / 128 the reference tiles (debug library only), -1 the call is refused with SEMICRF_EINVAL.
+ * (A test hook: SEMICRF_ABI_VERSION stays 2, as for the entry points added since round 6.) */
+int semicrf_debug_score_route(int C, int T, int D, int64_t ldq, int64_t ldk, int aligned, int prec, int group, int pitch, int rowc,
+                              int forced, int impl);
+
 /*
  * Log-partition, forward (alpha) sweep.
  * Replaces: computeLogZ (NeuralSemiCRFInterval.py:207-246) and the un-flipped half of

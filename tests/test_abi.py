@@ -305,3 +305,144 @@ def test_documented_persist_variants_compile():
                                     stdout=subprocess.PIPE, stderr=subprocess.STDOUT) for name, defs in variants.items()}
     status = {name: (p.communicate(), p.returncode)[1] for name, p in procs.items()}
     assert all(rc == 0 for rc in status.values()), status
+
+
+def test_documented_scorer_variants_compile():
+    """The sibling of test_documented_persist_variants_compile for the scorer, projection and limb-split code: every recipe that
+    tools/README.md lists as `python tools/mkvar.py NAME --files a.hip[,b.hip] DEFINE=V ...` goes through the compiler's front
+    end (host and device pass, release flags), every named file of every recipe at once.  The probe builds that the scripts in
+    tools/ drive have to be among them."""
+    import subprocess
+    from transkun_amd import _build
+    with open(os.path.join(ROOT, "tools", "README.md")) as f:
+        recipes = re.findall(r"^\* `python tools/mkvar\.py (\w+) --files ([\w.,]+)((?: \w+=\w+)+)`", f.read(), re.M)
+    variants = {name: (files.split(","), defs.split()) for name, files, defs in recipes}
+    assert len(variants) == len(recipes) >= 5, recipes
+    for must in ((["scorer_mfma.hip"], ["SEMICRF_SCORE_PROBE=1"]), (["scorer_tiled.hip"], ["SEMICRF_TILED_PROBE=1"]),
+                 (["scorer_bwd_gemm.hip"], ["SEMICRF_G3_PROBE=1"]), (["proj_gemm3.hip"], ["SEMICRF_P3_PROBE=1"])):
+        assert must in variants.values(), must
+    assert any(files == ["scorer_bwd_gemm.hip"] and any(d.startswith("SEMICRF_G3_ABL=") for d in defs) for files, defs in variants.values())
+    flags = ["--offload-arch=" + _build.ARCH, "-O3", "-std=c++17", "-fPIC", "-fno-fast-math", "-ffp-contract=off", "-Wall",
+             "-Wno-unused-function"]
+    procs = {}
+    for name, (files, defs) in variants.items():
+        for base in files:
+            src = os.path.join(_build.CSRC, base)
+            assert os.path.exists(src), (name, base)
+            procs[name, base] = subprocess.Popen([_build._hipcc()] + flags + _build.EXTRA_FLAGS.get(base, []) + ["-D" + d for d in defs]
+                                                 + ["-fsyntax-only", src], stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
+    status = {key: (p.communicate(), p.returncode)[1] for key, p in procs.items()}
+    assert all(rc == 0 for rc in status.values()), status
+
+
+# interval_score_fwd's kernel choice, recorded from the commit before the route became one function (b09adaa): its launcher
+# compiled with the kernel launches stubbed to name the kernel, release and debug flags.  Key: (C, T, D, ldq = ldk, bases 16-byte
+# aligned, prec, group, pitch, row constant, forced variant, impl); value: (release library, debug library) in
+# semicrf_debug_score_route's numbering -- 0 register loads, 1 plain, 2 tiled, 3 three-limb, 32 streaming, 64 / 128 the reference
+# tiles, -1 refused.  ld = 2097160 at T = 256: T * ld * 4 >= 2^31 with ld % 4 == 0.
+_SCORE_ROUTES = {
+    (4, 256, 32, 32, 1, 0, 4, 4, 0, -1, 0): (1, 1),
+    (4, 256, 64, 64, 1, 0, 4, 4, 0, -1, 1): (1, 1),
+    (4, 256, 64, 129, 1, 0, 4, 4, 0, -1, 0): (0, 0),
+    (4, 256, 64, 2097160, 1, 0, 4, 4, 0, -1, 0): (0, 0),
+    (4, 256, 64, 64, 0, 0, 4, 4, 0, -1, 0): (0, 0),
+    (4, 100, 64, 64, 1, 0, 4, 4, 0, -1, 0): (32, 32),
+    (4, 100, 64, 64, 1, 1, 4, 4, 0, -1, 0): (32, 32),
+    (4, 128, 64, 64, 1, 0, 4, 4, 0, -1, 0): (32, 32),
+    (4, 128, 64, 64, 1, 1, 4, 4, 0, -1, 0): (3, 3),
+    (4, 128, 256, 256, 1, 0, 4, 4, 0, -1, 0): (32, 32),
+    (4, 128, 320, 320, 1, 0, 4, 4, 0, -1, 0): (32, 32),
+    (4, 128, 320, 320, 1, 1, 4, 4, 0, -1, 0): (3, 3),
+    (4, 255, 64, 64, 1, 0, 4, 4, 0, -1, 0): (32, 32),
+    (4, 255, 64, 64, 1, 1, 4, 4, 0, -1, 0): (3, 3),
+    (4, 255, 320, 320, 1, 0, 4, 4, 0, -1, 0): (32, 32),
+    (4, 255, 320, 320, 1, 1, 4, 4, 0, -1, 0): (3, 3),
+    (4, 256, 64, 64, 1, 0, 4, 4, 0, -1, 0): (2, 2),
+    (4, 256, 64, 64, 1, 1, 4, 4, 0, -1, 0): (3, 3),
+    (4, 256, 256, 256, 1, 0, 4, 4, 0, -1, 0): (2, 2),
+    (4, 256, 320, 320, 1, 0, 4, 4, 0, -1, 0): (0, 128),
+    (4, 256, 320, 320, 1, 1, 4, 4, 0, -1, 0): (3, 3),
+    (4, 691, 64, 64, 1, 0, 4, 4, 0, -1, 0): (2, 2),
+    (4, 691, 64, 64, 1, 1, 4, 4, 0, -1, 0): (3, 3),
+    (4, 691, 320, 320, 1, 0, 4, 4, 0, -1, 0): (0, 64),
+    (4, 691, 320, 320, 1, 1, 4, 4, 0, -1, 0): (3, 3),
+    (4, 1024, 64, 64, 1, 0, 4, 4, 0, -1, 0): (2, 2),
+    (4, 1024, 64, 64, 1, 1, 4, 4, 0, -1, 0): (3, 3),
+    (4, 1024, 256, 256, 1, 0, 4, 4, 0, -1, 0): (2, 2),
+    (4, 1024, 320, 320, 1, 0, 4, 4, 0, -1, 0): (0, 128),
+    (4, 1024, 320, 320, 1, 1, 4, 4, 0, -1, 0): (3, 3),
+    (16384, 1024, 64, 64, 1, 0, 16384, 16384, 0, -1, 0): (0, 128),
+    (4, 256, 32, 32, 1, 0, 2, 4, 0, -1, 0): (-1, -1),
+    (4, 256, 64, 64, 1, 0, 2, 4, 0, -1, 1): (-1, -1),
+    (4, 256, 64, 129, 1, 0, 2, 4, 0, -1, 0): (-1, -1),
+    (4, 256, 64, 2097160, 1, 0, 2, 4, 0, -1, 0): (-1, -1),
+    (4, 256, 64, 64, 0, 0, 2, 4, 0, -1, 0): (-1, -1),
+    (4, 100, 64, 64, 1, 0, 2, 4, 0, -1, 0): (-1, -1),
+    (4, 100, 64, 64, 1, 1, 2, 4, 0, -1, 0): (-1, -1),
+    (4, 128, 64, 64, 1, 0, 2, 4, 0, -1, 0): (2, 2),
+    (4, 128, 64, 64, 1, 1, 2, 4, 0, -1, 0): (3, 3),
+    (4, 128, 256, 256, 1, 0, 2, 4, 0, -1, 0): (2, 2),
+    (4, 128, 320, 320, 1, 0, 2, 4, 0, -1, 0): (-1, 128),
+    (4, 128, 320, 320, 1, 1, 2, 4, 0, -1, 0): (3, 3),
+    (4, 255, 64, 64, 1, 0, 2, 4, 0, -1, 0): (2, 2),
+    (4, 255, 64, 64, 1, 1, 2, 4, 0, -1, 0): (3, 3),
+    (4, 255, 320, 320, 1, 0, 2, 4, 0, -1, 0): (-1, 128),
+    (4, 255, 320, 320, 1, 1, 2, 4, 0, -1, 0): (3, 3),
+    (4, 256, 64, 64, 1, 0, 2, 4, 0, -1, 0): (2, 2),
+    (4, 256, 64, 64, 1, 1, 2, 4, 0, -1, 0): (3, 3),
+    (4, 256, 256, 256, 1, 0, 2, 4, 0, -1, 0): (2, 2),
+    (4, 256, 320, 320, 1, 0, 2, 4, 0, -1, 0): (-1, 128),
+    (4, 256, 320, 320, 1, 1, 2, 4, 0, -1, 0): (3, 3),
+    (4, 691, 64, 64, 1, 0, 2, 4, 0, -1, 0): (2, 2),
+    (4, 691, 64, 64, 1, 1, 2, 4, 0, -1, 0): (3, 3),
+    (4, 691, 320, 320, 1, 0, 2, 4, 0, -1, 0): (-1, 64),
+    (4, 691, 320, 320, 1, 1, 2, 4, 0, -1, 0): (3, 3),
+    (4, 1024, 64, 64, 1, 0, 2, 4, 0, -1, 0): (2, 2),
+    (4, 1024, 64, 64, 1, 1, 2, 4, 0, -1, 0): (3, 3),
+    (4, 1024, 256, 256, 1, 0, 2, 4, 0, -1, 0): (2, 2),
+    (4, 1024, 320, 320, 1, 0, 2, 4, 0, -1, 0): (-1, 128),
+    (4, 1024, 320, 320, 1, 1, 2, 4, 0, -1, 0): (3, 3),
+    (4, 100, 64, 64, 1, 0, 4, 4, 1, -1, 0): (-1, -1),
+    (4, 128, 64, 64, 1, 0, 4, 4, 1, -1, 0): (2, 2),
+    (4, 256, 64, 64, 1, 0, 4, 4, 1, -1, 0): (2, 2),
+    (4, 691, 320, 320, 1, 0, 4, 4, 1, -1, 0): (-1, 64),
+    (4, 100, 64, 64, 1, 0, 4, 4, 0, 0, 0): (0, 0),
+    (4, 128, 64, 64, 1, 0, 4, 4, 0, 0, 0): (0, 0),
+    (4, 256, 64, 64, 1, 0, 4, 4, 0, 0, 0): (0, 0),
+    (4, 1024, 64, 64, 1, 0, 4, 4, 0, 0, 0): (0, 0),
+    (4, 256, 64, 64, 1, 1, 4, 4, 0, 0, 0): (3, 3),
+    (4, 256, 64, 64, 1, 0, 2, 4, 0, 0, 0): (-1, 128),
+    (4, 1024, 320, 320, 1, 0, 4, 4, 0, 0, 0): (0, 0),
+    (4, 100, 64, 64, 1, 0, 4, 4, 0, 2, 0): (0, 128),
+    (4, 128, 64, 64, 1, 0, 4, 4, 0, 2, 0): (2, 2),
+    (4, 256, 64, 64, 1, 0, 4, 4, 0, 2, 0): (2, 2),
+    (4, 1024, 64, 64, 1, 0, 4, 4, 0, 2, 0): (2, 2),
+    (4, 256, 64, 64, 1, 1, 4, 4, 0, 2, 0): (3, 3),
+    (4, 256, 64, 64, 1, 0, 2, 4, 0, 2, 0): (2, 2),
+    (4, 1024, 320, 320, 1, 0, 4, 4, 0, 2, 0): (0, 128),
+    (4, 100, 64, 64, 1, 0, 4, 4, 0, 32, 0): (32, 32),
+    (4, 128, 64, 64, 1, 0, 4, 4, 0, 32, 0): (32, 32),
+    (4, 256, 64, 64, 1, 0, 4, 4, 0, 32, 0): (32, 32),
+    (4, 1024, 64, 64, 1, 0, 4, 4, 0, 32, 0): (32, 32),
+    (4, 256, 64, 64, 1, 1, 4, 4, 0, 32, 0): (3, 3),
+    (4, 256, 64, 64, 1, 0, 2, 4, 0, 32, 0): (-1, 128),
+    (4, 1024, 320, 320, 1, 0, 4, 4, 0, 32, 0): (32, 32),
+}
+
+
+def test_scorer_forward_routes_without_gpu():
+    """plan_score_route through semicrf_debug_score_route: one row per line of the route table (naive for D % 64 != 0 and impl != 0,
+    register loads for rows that are not addressable, streaming below 128 / 256 frames, the tiled kernel, the three-limb kernel,
+    what the release library refuses with a slot layout or a row constant and the debug library gives to its reference tiles, the
+    32 T Cs limit at C = 16384, every forced variant)."""
+    from transkun_amd import _lib
+    libs = (_lib.load(), _lib.load_debug())
+    assert set(v for pair in _SCORE_ROUTES.values() for v in pair) == {-1, 0, 1, 2, 3, 32, 64, 128}
+    for key, want in _SCORE_ROUTES.items():
+        C, T, D, ld, aligned, prec, group, pitch, rowc, forced, impl = key
+        got = tuple(lib.semicrf_debug_score_route(C, T, D, ld, ld, aligned, prec, group, pitch, rowc, forced, impl) for lib in libs)
+        assert got == want, (key, got, want)
+    # a shape the entry points would refuse before they ask: no crash, "refused"
+    assert libs[0].semicrf_debug_score_route(4, 256, 64, 64, 64, 1, 0, 3, 4, 0, -1, 0) == -1
+    # the forced variant is an argument: the query neither reads nor changes the process-wide hook
+    assert libs[0].semicrf_debug_score_route(4, 1024, 64, 64, 64, 1, 0, 4, 4, 0, -1, 0) == 2

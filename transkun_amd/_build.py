@@ -138,7 +138,7 @@ DEBUG_LIB = os.path.join(HERE, "libsemicrf_hip_debug.so")
 
 def build_debug(force: bool = False, verbose: bool = False) -> str:
     """libsemicrf_hip_debug.so: every source compiled with -DSEMICRF_DEBUG_BUILD=1 -- the reference tile kernels of the interval
-    scorer (scorer_mfma.hip: interval_score_tile_kernel<64|128>), all of semicrf_debug_score_variant's choices and the launch
+    scorer (csrc/scorer_fwd_tile_ref.h: interval_score_tile_kernel<64|128>), all of semicrf_debug_score_variant's choices and the launch
     geometry knobs of tools/ (read from the environment).  The parity tests load it explicitly (through ctypes, the same C ABI)
     as the bit-level reference of the default kernels; nothing under transkun_amd/ uses it."""
     deps = sources() + _headers()

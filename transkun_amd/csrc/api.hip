@@ -162,6 +162,13 @@ int semicrf_debug_device_status(void) { return read_and_clear_device_status(); }
 int semicrf_async_error(void) { return (int)take_async_error(); }
 int semicrf_debug_wg_ticket(int n_spine, int grid, int block) { return persist_wg_ticket(n_spine, grid, block); }
 void semicrf_debug_score_variant(int variant) { set_score_variant(variant); }
+int semicrf_debug_score_route(int C, int T, int D, int64_t ldq, int64_t ldk, int aligned, int prec, int group, int pitch, int rowc,
+                              int forced, int impl)
+{
+    if (C < 1 || T < 1 || D < 1 || group < 1 || pitch < group || C % group != 0) return SCORE_REFUSED;
+    if (pitch == group) group = pitch = C;                     // as the entry points normalise it
+    return plan_score_route(C, T, D, ldq, ldk, aligned != 0, prec, group, pitch, rowc != 0, forced, impl).kernel;
+}
 
 int semicrf_workspace_register(void* ws, size_t ws_bytes)
 {
@@ -671,24 +678,30 @@ int semicrf_eval_path_bwd(const float* gout, int T, int B, const int32_t* pairs,
     return SEMICRF_OK;
 }
 
-static int check_slots(int C, int group, int pitch)
+// ---- the interval scorer ---------------------------------------------------------------------------------------------------------
+// Every entry point comes in three forms: plain, _p (slot layout) and _pc (slot layout + the merged projection's row constant).
+// The _pc form is the implementation; the other two forward to it.
+
+// The argument checks the scorer's entry points start with, in the order in which a bad call's first error is reported.
+// operands: the non-NULL test of the pointers `names` lists; lds: the test of the leading dimensions.
+static int check_score_operands(int C, int T, int D, bool operands, const char* names, bool lds, int length_scaling)
+{
+    SEMICRF_CHECK_ARG(C >= 1 && T >= 1 && D >= 1, "C=%d T=%d D=%d must be >= 1", C, T, D);
+    SEMICRF_CHECK_ARG(operands, "%s must be non-NULL", names);
+    SEMICRF_CHECK_ARG(lds, "bad leading dimensions");
+    SEMICRF_CHECK_ARG(length_scaling >= 0 && length_scaling <= 2, "bad length_scaling %d", length_scaling);
+    return SEMICRF_OK;
+}
+
+// the slot layout, normalised: without ghosts it is ONE group (quads must not straddle a group's end).  Its own function because
+// the entry points report another error (full_square, the backward's D) between the operands' and this one.
+static int check_slots(int C, int& group, int& pitch)
 {
     SEMICRF_CHECK_ARG(group >= 1 && pitch >= group && C % group == 0, "bad slot layout: C=%d group=%d pitch=%d", C, group, pitch);
     SEMICRF_CHECK_ARG(pitch == group || pitch % 4 == 0, "a padded slot pitch must be a multiple of 4 (pitch=%d)", pitch);
     SEMICRF_CHECK_ARG((long long)(C / group) * pitch < (1ll << 31), "too many slots");
+    if (pitch == group) group = pitch = C;
     return SEMICRF_OK;
-}
-
-int interval_score_fwd_pc(const float* q, const float* k, const float* diag, const float* rowc, int C, int T, int D, int64_t ldq,
-                          int64_t ldk, int64_t ldd, int64_t ldrc, float qscale, int length_scaling, int full_square, int group,
-                          int pitch, float* S, float* noise_out, semicrf_stream_t stream);
-
-int interval_score_fwd_p(const float* q, const float* k, const float* diag, int C, int T, int D, int64_t ldq,
-                         int64_t ldk, int64_t ldd, float qscale, int length_scaling, int full_square, int group, int pitch,
-                         float* S, float* noise_out, semicrf_stream_t stream)
-{
-    return interval_score_fwd_pc(q, k, diag, nullptr, C, T, D, ldq, ldk, ldd, 1, qscale, length_scaling, full_square, group, pitch, S,
-                                 noise_out, stream);
 }
 
 int interval_score_fwd_pc(const float* q, const float* k, const float* diag, const float* rowc, int C, int T, int D, int64_t ldq,
@@ -696,38 +709,22 @@ int interval_score_fwd_pc(const float* q, const float* k, const float* diag, con
                           int pitch, float* S, float* noise_out, semicrf_stream_t stream)
 {
     SEMICRF_CHECK_ARG(!rowc || ldrc >= 1, "bad row-constant stride");
-    SEMICRF_CHECK_ARG(C >= 1 && T >= 1 && D >= 1, "C=%d T=%d D=%d must be >= 1", C, T, D);
-    SEMICRF_CHECK_ARG(q && k && diag && S, "q/k/diag/S must be non-NULL");
-    SEMICRF_CHECK_ARG(ldq >= D && ldk >= D && ldd >= 1, "bad leading dimensions");
-    SEMICRF_CHECK_ARG(length_scaling >= 0 && length_scaling <= 2, "bad length_scaling %d", length_scaling);
+    if (int rc = check_score_operands(C, T, D, q && k && diag && S, "q/k/diag/S", ldq >= D && ldk >= D && ldd >= 1, length_scaling)) return rc;
     SEMICRF_CHECK_ARG(full_square >= 0 && (full_square & 3) <= 2 && (full_square & ~7) == 0, "bad full_square %d", full_square);
     if (int rc = check_slots(C, group, pitch)) return rc;
-    if (pitch == group) group = pitch = C;                     // no ghosts: ONE group (quads must not straddle a group's end)
-    const bool slots = pitch != group || rowc != nullptr;
     const int Cs = (C / group) * pitch;
-    if (slots)
-        SEMICRF_CHECK_ARG(g_impl.load() == 0 && interval_score_slots_supported(C, T, D, q, k, ldq, ldk),
-                          "a padded slot layout / a row constant needs the shared-operand kernels: 16-byte aligned rows, D %% 64 == 0, T >= 128");
-    hipStream_t st = (hipStream_t)stream;
-    const int prec = (full_square & SEMICRF_SCORE_BF16X3) ? 1 : 0;   // opt-in: three-limb bf16 contraction (scorer_mfma.hip)
+    const int prec = (full_square & SEMICRF_SCORE_BF16X3) ? 1 : 0;   // opt-in: three-limb bf16 contraction (scorer_fwd_tile3.h)
     full_square &= 3;
+    const ScoreRoute route = plan_score_route(C, T, D, ldq, ldk, (((uintptr_t)q | (uintptr_t)k) & 15) == 0, prec, group, pitch, rowc != nullptr,
+                                              score_variant(), g_impl.load());
+    SEMICRF_CHECK_ARG(route.kernel != SCORE_REFUSED, "%s", route.why);
+    hipStream_t st = (hipStream_t)stream;
     if (full_square == 0) launch_zero_upper(S, T, Cs, st);     // begin > end: defined (zero), half the bytes of a full fill
     const int full_kernel = full_square == 1 ? 1 : 0;           // 2: lower triangle only, the rest of S is left as it is
-    if (g_impl.load() == 0 && interval_score_mfma_supported(C, T, D)) {
-        const int lrc = launch_interval_score_mfma(q, k, diag, C, T, D, ldq, ldk, ldd, qscale, length_scaling, full_kernel, S, st, prec, group,
-                                                   pitch, rowc, ldrc);
-        if (lrc == 2) {
-            set_error("interval_score_fwd: a padded slot layout / a row constant needs the tiled kernels (D <= 256, D %% 64 == 0, T >= 128, "
-                      "16-byte aligned rows, 32 T Cs floats within 32-bit offsets)");
-            return SEMICRF_EINVAL;
-        }
-        if (lrc != 0) {
-            set_error("interval_score_fwd: work list allocation failed");
-            return SEMICRF_ELAUNCH;
-        }
-    } else {
-        SEMICRF_CHECK_ARG(!slots, "a padded slot layout needs the shared-operand kernels");
-        launch_interval_score_naive(q, k, diag, C, T, D, ldq, ldk, ldd, qscale, length_scaling, full_kernel, S, st);
+    if (launch_interval_score_fwd(route.kernel, q, k, diag, C, T, D, ldq, ldk, ldd, qscale, length_scaling, full_kernel, S, st, group, pitch,
+                                  rowc, ldrc) != 0) {
+        set_error("interval_score_fwd: work list allocation failed");
+        return SEMICRF_ELAUNCH;
     }
     if (noise_out && T > 1) {
         if (hipMemsetAsync(noise_out, 0, (size_t)(T - 1) * Cs * sizeof(float), st) != hipSuccess) {
@@ -739,6 +736,14 @@ int interval_score_fwd_pc(const float* q, const float* k, const float* diag, con
     return SEMICRF_OK;
 }
 
+int interval_score_fwd_p(const float* q, const float* k, const float* diag, int C, int T, int D, int64_t ldq,
+                         int64_t ldk, int64_t ldd, float qscale, int length_scaling, int full_square, int group, int pitch,
+                         float* S, float* noise_out, semicrf_stream_t stream)
+{
+    return interval_score_fwd_pc(q, k, diag, nullptr, C, T, D, ldq, ldk, ldd, 1, qscale, length_scaling, full_square, group, pitch, S,
+                                 noise_out, stream);
+}
+
 int interval_score_fwd(const float* q, const float* k, const float* diag, int C, int T, int D, int64_t ldq,
                        int64_t ldk, int64_t ldd, float qscale, int length_scaling, int full_square, float* S,
                        float* noise_out, semicrf_stream_t stream)
@@ -747,15 +752,18 @@ int interval_score_fwd(const float* q, const float* k, const float* diag, int C,
                                 noise_out, stream);
 }
 
+// the leading dimensions of a backward call
+static bool bwd_lds_ok(int D, int64_t ldq, int64_t ldk, const float* dq, const float* dk, const float* ddiag, int64_t lddq, int64_t lddk,
+                       int64_t lddd)
+{
+    return ldq >= D && ldk >= D && (!dq || lddq >= D) && (!dk || lddk >= D) && (!ddiag || lddd >= 1);
+}
+
 int interval_score_bwd(const float* dS, const float* q, const float* k, int C, int T, int D, int64_t ldq, int64_t ldk,
                        float qscale, int length_scaling, float* dq, float* dk, float* ddiag, int64_t lddq,
                        int64_t lddk, int64_t lddd, semicrf_stream_t stream)
 {
-    SEMICRF_CHECK_ARG(C >= 1 && T >= 1 && D >= 1, "C=%d T=%d D=%d must be >= 1", C, T, D);
-    SEMICRF_CHECK_ARG(dS && q && k, "dS/q/k must be non-NULL");
-    SEMICRF_CHECK_ARG(ldq >= D && ldk >= D && (!dq || lddq >= D) && (!dk || lddk >= D) && (!ddiag || lddd >= 1),
-                      "bad leading dimensions");
-    SEMICRF_CHECK_ARG(length_scaling >= 0 && length_scaling <= 2, "bad length_scaling %d", length_scaling);
+    if (int rc = check_score_operands(C, T, D, dS && q && k, "dS/q/k", bwd_lds_ok(D, ldq, ldk, dq, dk, ddiag, lddq, lddk, lddd), length_scaling)) return rc;
     SEMICRF_CHECK_ARG(interval_score_bwd_supported(C, T, D), "interval_score_bwd needs D %% 32 == 0 and D <= 256 (D=%d)", D);
     launch_interval_score_bwd(dS, q, k, C, T, D, ldq, ldk, qscale, length_scaling, dq, dk, ddiag, lddq, lddk, lddd,
                               (hipStream_t)stream);
@@ -767,31 +775,14 @@ size_t interval_score_bwd_workspace_bytes(int C, int T, int D) { return interval
 
 int interval_score_bwd_ws_pc(const float* dS, const float* q, const float* k, int C, int T, int D, int64_t ldq, int64_t ldk,
                              float qscale, int length_scaling, int group, int pitch, float* dq, float* dk, float* ddiag, float* drowc,
-                             int64_t lddq, int64_t lddk, int64_t lddd, int64_t lddrc, void* ws, size_t ws_bytes, semicrf_stream_t stream);
-
-int interval_score_bwd_ws_p(const float* dS, const float* q, const float* k, int C, int T, int D, int64_t ldq, int64_t ldk,
-                            float qscale, int length_scaling, int group, int pitch, float* dq, float* dk, float* ddiag, int64_t lddq,
-                            int64_t lddk, int64_t lddd, void* ws, size_t ws_bytes, semicrf_stream_t stream)
-{
-    return interval_score_bwd_ws_pc(dS, q, k, C, T, D, ldq, ldk, qscale, length_scaling, group, pitch, dq, dk, ddiag, nullptr, lddq, lddk, lddd,
-                                    1, ws, ws_bytes, stream);
-}
-
-int interval_score_bwd_ws_pc(const float* dS, const float* q, const float* k, int C, int T, int D, int64_t ldq, int64_t ldk,
-                             float qscale, int length_scaling, int group, int pitch, float* dq, float* dk, float* ddiag, float* drowc,
                              int64_t lddq, int64_t lddk, int64_t lddd, int64_t lddrc, void* ws, size_t ws_bytes, semicrf_stream_t stream)
 {
     SEMICRF_CHECK_ARG(!drowc || lddrc >= 1, "bad row-constant stride");
-    SEMICRF_CHECK_ARG(C >= 1 && T >= 1 && D >= 1, "C=%d T=%d D=%d must be >= 1", C, T, D);
-    SEMICRF_CHECK_ARG(dS && q && k, "dS/q/k must be non-NULL");
-    SEMICRF_CHECK_ARG(ldq >= D && ldk >= D && (!dq || lddq >= D) && (!dk || lddk >= D) && (!ddiag || lddd >= 1),
-                      "bad leading dimensions");
-    const int prec = (length_scaling & SEMICRF_LEN_BF16X3) ? 1 : 0;   // opt-in: the two products on the three-limb bf16 kernels (scorer_bwd_gemm.hip)
+    const int prec = (length_scaling & SEMICRF_LEN_BF16X3) ? 1 : 0;   // opt-in: the two products on the three-limb bf16 kernels (scorer_bwd_gemm3.h)
     length_scaling &= ~SEMICRF_LEN_BF16X3;
-    SEMICRF_CHECK_ARG(length_scaling >= 0 && length_scaling <= 2, "bad length_scaling %d", length_scaling);
+    if (int rc = check_score_operands(C, T, D, dS && q && k, "dS/q/k", bwd_lds_ok(D, ldq, ldk, dq, dk, ddiag, lddq, lddk, lddd), length_scaling)) return rc;
     SEMICRF_CHECK_ARG(interval_score_bwd_supported(C, T, D), "interval_score_bwd needs D %% 32 == 0 and D <= 256 (D=%d)", D);
     if (int rc = check_slots(C, group, pitch)) return rc;
-    if (pitch == group) group = pitch = C;                     // no ghosts: ONE group (quads must not straddle a group's end)
     const bool slots = pitch != group;
     hipStream_t st = (hipStream_t)stream;
     if (g_impl.load() == 0 && (dq || dk) &&
@@ -807,6 +798,14 @@ int interval_score_bwd_ws_pc(const float* dS, const float* q, const float* k, in
     return SEMICRF_OK;
 }
 
+int interval_score_bwd_ws_p(const float* dS, const float* q, const float* k, int C, int T, int D, int64_t ldq, int64_t ldk,
+                            float qscale, int length_scaling, int group, int pitch, float* dq, float* dk, float* ddiag, int64_t lddq,
+                            int64_t lddk, int64_t lddd, void* ws, size_t ws_bytes, semicrf_stream_t stream)
+{
+    return interval_score_bwd_ws_pc(dS, q, k, C, T, D, ldq, ldk, qscale, length_scaling, group, pitch, dq, dk, ddiag, nullptr, lddq, lddk, lddd,
+                                    1, ws, ws_bytes, stream);
+}
+
 int interval_score_bwd_ws(const float* dS, const float* q, const float* k, int C, int T, int D, int64_t ldq, int64_t ldk,
                           float qscale, int length_scaling, float* dq, float* dk, float* ddiag, int64_t lddq,
                           int64_t lddk, int64_t lddd, void* ws, size_t ws_bytes, semicrf_stream_t stream)
@@ -820,11 +819,9 @@ int interval_score_bwd_fused(const float* S, const float* alpha, const float* be
                              int64_t ldk, float qscale, int length_scaling, float* dq, float* dk, float* ddiag,
                              int64_t lddq, int64_t lddk, int64_t lddd, semicrf_stream_t stream)
 {
-    SEMICRF_CHECK_ARG(C >= 1 && T >= 1 && D >= 1, "C=%d T=%d D=%d must be >= 1", C, T, D);
-    SEMICRF_CHECK_ARG(S && alpha && beta && logZ && gout && q && k, "S/alpha/beta/logZ/gout/q/k must be non-NULL");
-    SEMICRF_CHECK_ARG(ldq >= D && ldk >= D && (!dq || lddq >= D) && (!dk || lddk >= D) && (!ddiag || lddd >= 1),
-                      "bad leading dimensions");
-    SEMICRF_CHECK_ARG(length_scaling >= 0 && length_scaling <= 2, "bad length_scaling %d", length_scaling);
+    if (int rc = check_score_operands(C, T, D, S && alpha && beta && logZ && gout && q && k, "S/alpha/beta/logZ/gout/q/k", bwd_lds_ok(D, ldq, ldk, dq, dk, ddiag, lddq, lddk, lddd),
+                                      length_scaling))
+        return rc;
     SEMICRF_CHECK_ARG(interval_score_bwd_supported(C, T, D), "interval_score_bwd_fused needs D %% 32 == 0 and D <= 256 (D=%d)", D);
     launch_interval_score_bwd_fused(S, alpha, beta, logZ, gout, q, k, C, T, D, ldq, ldk, qscale, length_scaling, dq, dk,
                                     ddiag, lddq, lddk, lddd, (hipStream_t)stream);
@@ -836,34 +833,16 @@ int interval_score_bwd_fused_ws_pc(const float* S, const float* alpha, const flo
                                    const float* gout, const float* q, const float* k, int C, int T, int D, int64_t ldq,
                                    int64_t ldk, float qscale, int length_scaling, int group, int pitch, float* dq, float* dk, float* ddiag,
                                    float* drowc, int64_t lddq, int64_t lddk, int64_t lddd, int64_t lddrc, void* ws, size_t ws_bytes,
-                                   semicrf_stream_t stream);
-
-int interval_score_bwd_fused_ws_p(const float* S, const float* alpha, const float* beta, const float* logZ,
-                                  const float* gout, const float* q, const float* k, int C, int T, int D, int64_t ldq,
-                                  int64_t ldk, float qscale, int length_scaling, int group, int pitch, float* dq, float* dk, float* ddiag,
-                                  int64_t lddq, int64_t lddk, int64_t lddd, void* ws, size_t ws_bytes, semicrf_stream_t stream)
-{
-    return interval_score_bwd_fused_ws_pc(S, alpha, beta, logZ, gout, q, k, C, T, D, ldq, ldk, qscale, length_scaling, group, pitch, dq, dk,
-                                          ddiag, nullptr, lddq, lddk, lddd, 1, ws, ws_bytes, stream);
-}
-
-int interval_score_bwd_fused_ws_pc(const float* S, const float* alpha, const float* beta, const float* logZ,
-                                   const float* gout, const float* q, const float* k, int C, int T, int D, int64_t ldq,
-                                   int64_t ldk, float qscale, int length_scaling, int group, int pitch, float* dq, float* dk, float* ddiag,
-                                   float* drowc, int64_t lddq, int64_t lddk, int64_t lddd, int64_t lddrc, void* ws, size_t ws_bytes,
                                    semicrf_stream_t stream)
 {
     SEMICRF_CHECK_ARG(!drowc || lddrc >= 1, "bad row-constant stride");
-    SEMICRF_CHECK_ARG(C >= 1 && T >= 1 && D >= 1, "C=%d T=%d D=%d must be >= 1", C, T, D);
-    SEMICRF_CHECK_ARG(S && alpha && beta && logZ && gout && q && k, "S/alpha/beta/logZ/gout/q/k must be non-NULL");
-    SEMICRF_CHECK_ARG(ldq >= D && ldk >= D && (!dq || lddq >= D) && (!dk || lddk >= D) && (!ddiag || lddd >= 1),
-                      "bad leading dimensions");
-    const int prec = (length_scaling & SEMICRF_LEN_BF16X3) ? 1 : 0;   // opt-in: the two products on the three-limb bf16 kernels (scorer_bwd_gemm.hip)
+    const int prec = (length_scaling & SEMICRF_LEN_BF16X3) ? 1 : 0;   // opt-in: the two products on the three-limb bf16 kernels (scorer_bwd_gemm3.h)
     length_scaling &= ~SEMICRF_LEN_BF16X3;
-    SEMICRF_CHECK_ARG(length_scaling >= 0 && length_scaling <= 2, "bad length_scaling %d", length_scaling);
+    if (int rc = check_score_operands(C, T, D, S && alpha && beta && logZ && gout && q && k, "S/alpha/beta/logZ/gout/q/k", bwd_lds_ok(D, ldq, ldk, dq, dk, ddiag, lddq, lddk, lddd),
+                                      length_scaling))
+        return rc;
     SEMICRF_CHECK_ARG(interval_score_bwd_supported(C, T, D), "interval_score_bwd_fused needs D %% 32 == 0 and D <= 256 (D=%d)", D);
     if (int rc = check_slots(C, group, pitch)) return rc;
-    if (pitch == group) group = pitch = C;                     // no ghosts: ONE group (quads must not straddle a group's end)
     const bool slots = pitch != group;
     hipStream_t st = (hipStream_t)stream;
     const float* fused[4] = {alpha, beta, logZ, gout};
@@ -881,6 +860,15 @@ int interval_score_bwd_fused_ws_pc(const float* S, const float* alpha, const flo
     return SEMICRF_OK;
 }
 
+int interval_score_bwd_fused_ws_p(const float* S, const float* alpha, const float* beta, const float* logZ,
+                                  const float* gout, const float* q, const float* k, int C, int T, int D, int64_t ldq,
+                                  int64_t ldk, float qscale, int length_scaling, int group, int pitch, float* dq, float* dk, float* ddiag,
+                                  int64_t lddq, int64_t lddk, int64_t lddd, void* ws, size_t ws_bytes, semicrf_stream_t stream)
+{
+    return interval_score_bwd_fused_ws_pc(S, alpha, beta, logZ, gout, q, k, C, T, D, ldq, ldk, qscale, length_scaling, group, pitch, dq, dk,
+                                          ddiag, nullptr, lddq, lddk, lddd, 1, ws, ws_bytes, stream);
+}
+
 int interval_score_bwd_fused_ws(const float* S, const float* alpha, const float* beta, const float* logZ,
                                 const float* gout, const float* q, const float* k, int C, int T, int D, int64_t ldq,
                                 int64_t ldk, float qscale, int length_scaling, float* dq, float* dk, float* ddiag,
@@ -893,7 +881,21 @@ int interval_score_bwd_fused_ws(const float* S, const float* alpha, const float*
 int interval_score_path_bwd_pc(const float* gout, const int32_t* pairs, int64_t K, const int32_t* offsets, const float* q,
                                const float* k, int C, int T, int D, int64_t ldq, int64_t ldk, float qscale, int length_scaling,
                                int group, int pitch, float* dq, float* dk, float* ddiag, float* drowc, int64_t lddq, int64_t lddk,
-                               int64_t lddd, int64_t lddrc, semicrf_stream_t stream);
+                               int64_t lddd, int64_t lddrc, semicrf_stream_t stream)
+{
+    SEMICRF_CHECK_ARG(!drowc || lddrc >= 1, "bad row-constant stride");
+    // (its own sequence: the interval count is reported between the operands and the leading dimensions)
+    SEMICRF_CHECK_ARG(C >= 1 && T >= 1 && D >= 1, "C=%d T=%d D=%d must be >= 1", C, T, D);
+    SEMICRF_CHECK_ARG(gout && offsets && q && k, "gout/offsets/q/k must be non-NULL");
+    SEMICRF_CHECK_ARG(K >= 0 && K < (1ll << 31) && (K == 0 || pairs), "bad interval count");
+    SEMICRF_CHECK_ARG(bwd_lds_ok(D, ldq, ldk, dq, dk, ddiag, lddq, lddk, lddd), "bad leading dimensions");
+    SEMICRF_CHECK_ARG(length_scaling >= 0 && length_scaling <= 2, "bad length_scaling %d", length_scaling);
+    if (int rc = check_slots(C, group, pitch)) return rc;
+    launch_interval_score_path_bwd(gout, pairs, (int)K, offsets, q, k, C, T, D, ldq, ldk, qscale, length_scaling, dq, dk, ddiag,
+                                   lddq, lddk, lddd, (hipStream_t)stream, group, pitch, drowc, lddrc);
+    SEMICRF_CHECK_LAUNCH("interval_score_path_bwd");
+    return SEMICRF_OK;
+}
 
 int interval_score_path_bwd_p(const float* gout, const int32_t* pairs, int64_t K, const int32_t* offsets, const float* q,
                               const float* k, int C, int T, int D, int64_t ldq, int64_t ldk, float qscale, int length_scaling,
@@ -902,26 +904,6 @@ int interval_score_path_bwd_p(const float* gout, const int32_t* pairs, int64_t K
 {
     return interval_score_path_bwd_pc(gout, pairs, K, offsets, q, k, C, T, D, ldq, ldk, qscale, length_scaling, group, pitch, dq, dk, ddiag,
                                       nullptr, lddq, lddk, lddd, 1, stream);
-}
-
-int interval_score_path_bwd_pc(const float* gout, const int32_t* pairs, int64_t K, const int32_t* offsets, const float* q,
-                               const float* k, int C, int T, int D, int64_t ldq, int64_t ldk, float qscale, int length_scaling,
-                               int group, int pitch, float* dq, float* dk, float* ddiag, float* drowc, int64_t lddq, int64_t lddk,
-                               int64_t lddd, int64_t lddrc, semicrf_stream_t stream)
-{
-    SEMICRF_CHECK_ARG(!drowc || lddrc >= 1, "bad row-constant stride");
-    SEMICRF_CHECK_ARG(C >= 1 && T >= 1 && D >= 1, "C=%d T=%d D=%d must be >= 1", C, T, D);
-    SEMICRF_CHECK_ARG(gout && offsets && q && k, "gout/offsets/q/k must be non-NULL");
-    SEMICRF_CHECK_ARG(K >= 0 && K < (1ll << 31) && (K == 0 || pairs), "bad interval count");
-    SEMICRF_CHECK_ARG(ldq >= D && ldk >= D && (!dq || lddq >= D) && (!dk || lddk >= D) && (!ddiag || lddd >= 1),
-                      "bad leading dimensions");
-    SEMICRF_CHECK_ARG(length_scaling >= 0 && length_scaling <= 2, "bad length_scaling %d", length_scaling);
-    if (int rc = check_slots(C, group, pitch)) return rc;
-    if (pitch == group) group = pitch = C;
-    launch_interval_score_path_bwd(gout, pairs, (int)K, offsets, q, k, C, T, D, ldq, ldk, qscale, length_scaling, dq, dk, ddiag,
-                                   lddq, lddk, lddd, (hipStream_t)stream, group, pitch, drowc, lddrc);
-    SEMICRF_CHECK_LAUNCH("interval_score_path_bwd");
-    return SEMICRF_OK;
 }
 
 int interval_score_path_bwd(const float* gout, const int32_t* pairs, int64_t K, const int32_t* offsets, const float* q,

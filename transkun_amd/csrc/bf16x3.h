@@ -28,29 +28,18 @@ __device__ __forceinline__ unsigned cvt_pk_bf16(float a, float b)
     asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));      // (written out: from `(__bf16)x` the compiler converts
     return r;                                            // the first element a second time, alone, for the shift below)
 }
-#ifndef SEMICRF_SPLIT_SCALAR_SUB
-#define SEMICRF_SPLIT_SCALAR_SUB 1   // (0: `a - b`, i.e. v_pk_add_f32 -- measured 6-11 % slower kernels: backward 1.69 -> 1.58 ms, projection 0.238 -> 0.212)
-#endif
+// Two v_sub_f32, not the v_pk_add_f32 the compiler makes of `a - b`: packed fp32 next to matrix instructions is slow (measured
+// with `a - b`: 6-11 % slower kernels, backward 1.69 against 1.58 ms, projection 0.238 against 0.212).
 __device__ __forceinline__ f32x2 sub2(const f32x2 a, const f32x2 b)
 {
-#if SEMICRF_SPLIT_SCALAR_SUB
-    // two v_sub_f32 instead of the v_pk_add_f32 the compiler makes of `a - b` (packed fp32 next to matrix instructions is slow)
     f32x2 r;
     asm("v_sub_f32 %0, %1, %2" : "=v"(r.x) : "v"(a.x), "v"(b.x));
     asm("v_sub_f32 %0, %1, %2" : "=v"(r.y) : "v"(a.y), "v"(b.y));
     return r;
-#else
-    return a - b;
-#endif
 }
 // plain fp32 arithmetic of the staging lanes in the same spirit (the compiler would pair neighbouring operations into v_pk_*)
-#if SEMICRF_SPLIT_SCALAR_SUB
 __device__ __forceinline__ float fmac1(float a, float b, float c) { asm("v_fmac_f32 %0, %1, %2" : "+v"(c) : "v"(a), "v"(b)); return c; }
 __device__ __forceinline__ float add1(float a, float b) { float r; asm("v_add_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-#else
-__device__ __forceinline__ float fmac1(float a, float b, float c) { return fmaf(a, b, c); }
-__device__ __forceinline__ float add1(float a, float b) { return a + b; }
-#endif
 __device__ __forceinline__ void split_pair(float a, float b, unsigned& h, unsigned& m, unsigned& l)
 {
     const unsigned hu = cvt_pk_bf16(a, b);

@@ -46,6 +46,30 @@ struct PerDeviceOnce {
     }
 };
 
+// ---- launch helpers of the matrix-core kernels (scorer, projection) ----------------------------------------------
+// compute units of the current device (256 when the query fails)
+static inline int device_ncu()
+{
+    int ncu = 256, dev = 0, v = 0;
+    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ncu = v;
+    return ncu;
+}
+// grid of a persistent kernel: `wgs` workgroups fit the device; a whole number of `unit`s (slots per XCD and the like), at least
+// one unit, no more than the `need` the work asks for
+static inline int persistent_grid(long long wgs, int unit, long long need)
+{
+    long long grid = wgs / unit * unit;
+    if (grid < unit) grid = unit;
+    if (grid > need) grid = need;
+    return (int)grid;
+}
+// what `buffer_load ... lds` and 16-byte loads want of a [T][ld] block of floats: a 16-byte aligned base, rows a multiple of
+// 16 bytes, every byte offset inside the block below 2^31
+static inline bool rows_addressable(const void* p, long long ld, long long T)
+{
+    return ((uintptr_t)p & 15) == 0 && ld % 4 == 0 && T * ld * 4 < (1ll << 31);
+}
+
 // ---- slot layout of the chain axis (interval_score_*_p, include/semicrf_hip.h) ---------------------------------
 // The C chains come in groups of `group` (the symbols of one segment); every group owns `pitch` >= group slots of the
 // chain axis of S / dS / alpha / beta / logZ / gout / interval offsets; q, k, diag and their gradients are indexed by chain.

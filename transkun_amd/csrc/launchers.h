@@ -166,7 +166,6 @@ int launch_proj_nn(const float* A, long long lda, long long M, int K, const floa
 size_t proj_tn_workspace_bytes(long long M, int R, int N);
 int launch_proj_tn(const float* A, long long lda, long long M, int R, int extra_col0, int total_rows, const float* X, long long ldx, int N,
                    float* dW, long long lddw, float* db, void* ws, size_t ws_bytes, hipStream_t stream);
-int proj_ncu();
 bool proj_gemm_supported(long long M, int K, int N, const void* A, long long lda, const void* B, long long ldb, const void* out,
                          long long ldout);
 
@@ -211,21 +210,29 @@ void launch_interval_score_bwd_diag(const float* dS, const float* const* fused, 
                                     int group, int pitch, hipStream_t stream);
 
 // scorer_bwd_gemm.hip
+enum { SCORE_BWD_DIRECT = 0, SCORE_BWD_PACKED = 1, SCORE_BWD_PACKED3 = 2 };       // the direct kernels (scorer_bwd.hip) | packed, exact | packed, three-limb
+struct ScoreBwdPlan { int path; size_t ws_bytes; };                                // ws_bytes: what the packed path needs (0: it never applies to the shape)
+ScoreBwdPlan plan_score_bwd(int C, int T, int D, bool rows_ok, bool ws_ok, size_t ws_bytes, bool want_dq, bool want_drowc,
+                            long long lddq, long long lddk, int prec);
 size_t interval_score_bwd_ws_bytes(int C, int T, int D);
 bool launch_interval_score_bwd_packed(const float* dS, const float* q, const float* k, int C, int T, int D, long long ldq,
                                       long long ldk, float qscale, int mode, float* dq, float* dk, long long lddq,
                                       long long lddk, void* ws, size_t ws_bytes, hipStream_t stream,
-                                      const float* const* fused, int group, int pitch, float* drowc = nullptr, long long lddrc = 1,
-                                      int prec = 0);
+                                      const float* const* fused, int group, int pitch, float* drowc, long long lddrc, int prec);
 
 // scorer_mfma.hip
-bool interval_score_mfma_supported(int C, int T, int D);
-bool interval_score_slots_supported(int C, int T, int D, const float* q, const float* k, long long ldq, long long ldk);
-int launch_interval_score_mfma(const float* q, const float* k, const float* diag, int C, int T, int D,
-                                long long ldq, long long ldk, long long ldd, float qscale, int mode, int full,
-                                float* S, hipStream_t stream, int prec, int group, int pitch, const float* rowc = nullptr,
-                                long long ldrc = 1);
+// the forward kernels, in semicrf_debug_score_variant's numbering (0, 2, 32, 64, 128) extended by the plain kernel, the three-limb
+// kernel and "refused" (semicrf_debug_score_route returns these)
+enum { SCORE_REFUSED = -1, SCORE_REGLOAD = 0, SCORE_NAIVE = 1, SCORE_TILED = 2, SCORE_TILE3 = 3, SCORE_STREAM = 32, SCORE_TILE64 = 64,
+       SCORE_TILE128 = 128 };
+struct ScoreRoute { int kernel; const char* why; };       // why: the error text of a refusal
+ScoreRoute plan_score_route(int C, int T, int D, long long ldq, long long ldk, bool bases_aligned, int prec, int group, int pitch,
+                            bool rowc, int forced, int impl);
+int launch_interval_score_fwd(int kernel, const float* q, const float* k, const float* diag, int C, int T, int D, long long ldq,
+                              long long ldk, long long ldd, float qscale, int mode, int full, float* S, hipStream_t stream, int group,
+                              int pitch, const float* rowc, long long ldrc);
 void set_score_variant(int v);
+int score_variant();
 
 // scorer_tiled.hip
 void launch_interval_score_tiled(const float* q, const float* k, const float* diag, const float* rowc, int C, int T, int D,

@@ -557,13 +557,6 @@ __global__ __launch_bounds__(256) void proj_reduce_kernel(const float* __restric
 
 }  // namespace pj
 
-int proj_ncu()
-{
-    int ncu = 256, dev = 0, v = 0;
-    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ncu = v;
-    return ncu;
-}
-
 template <bool AT, int NW, bool EX>
 static void proj_launch(const pj::Args& P, long long nitems, int Kpad, hipStream_t stream)
 {
@@ -571,7 +564,7 @@ static void proj_launch(const pj::Args& P, long long nitems, int Kpad, hipStream
     static PerDeviceOnce attr_once;
     if (attr_once.first())
         (void)hipFuncSetAttribute((const void*)pj::proj_gemm_kernel<AT, NW, EX>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512);
-    const int ncu = proj_ncu();
+    const int ncu = device_ncu();
     const int grid = nitems < ncu ? (int)nitems : ncu;
     hipLaunchKernelGGL((pj::proj_gemm_kernel<AT, NW, EX>), dim3(grid), dim3(512), lds, stream, P);
 }
@@ -580,8 +573,7 @@ bool proj_gemm_supported(long long M, int K, int N, const void* A, long long lda
                          long long ldout)
 {
     if (!(N == 64 || N == 128 || N == 256) || K < 4 || K % 4 != 0 || K > 4096 || M < 1) return false;
-    if (((uintptr_t)A & 15) || ((uintptr_t)B & 15) || ((uintptr_t)out & 3) || lda % 4 || ldb % 4) return false;
-    if (M * lda * 4 >= (1ll << 31) || (long long)K * ldb * 4 >= (1ll << 31)) return false;          // 32-bit buffer offsets
+    if (!rows_addressable(A, lda, M) || !rows_addressable(B, ldb, K) || ((uintptr_t)out & 3)) return false;
     return true;
 }
 
@@ -611,7 +603,7 @@ static void proj_tn_geometry(long long M, int R, int* S, int* kslice, int* Mp)
 {
     const int nkt = (int)((M + pj::GK - 1) / pj::GK);
     const int nm = (R + pj::GM - 1) / pj::GM;
-    int s = proj_ncu() / (nm > 0 ? nm : 1);
+    int s = device_ncu() / (nm > 0 ? nm : 1);
     if (s < 1) s = 1;
     if (s > nkt) s = nkt;
     *kslice = (nkt + s - 1) / s;
@@ -634,7 +626,7 @@ int launch_proj_tn(const float* A, long long lda, long long M, int R, int extra_
     const int prec = (total_rows & SEMICRF_PROJ_TN_BF16X3) ? 1 : 0;        // opt-in: the matrix part on the three-limb bf16 kernel (N == 256)
     total_rows &= ~SEMICRF_PROJ_TN_BF16X3;
     if (!(N == 64 || N == 128 || N == 256) || R < 1 || M < 1) return 1;
-    if (((uintptr_t)A & 15) || ((uintptr_t)X & 15) || lda % 4 || ldx % 4 || M * lda * 4 >= (1ll << 31) || M * ldx * 4 >= (1ll << 31)) return 1;
+    if (!rows_addressable(A, lda, M) || !rows_addressable(X, ldx, M)) return 1;
     if (!ws || ws_bytes < proj_tn_workspace_bytes(M, R, N) || ((uintptr_t)ws & 15)) return 2;
     int S, ks, Mp;
     proj_tn_geometry(M, R, &S, &ks, &Mp);

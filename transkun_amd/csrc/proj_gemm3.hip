@@ -12,6 +12,7 @@
 #include "common.h"
 #include "launchers.h"
 #include "bf16x3.h"
+#include "scorer_tuning.h"
 
 #include <type_traits>
 
@@ -28,18 +29,9 @@ __device__ __forceinline__ void static_for(F&& f)
     }
 }
 
-#ifndef SEMICRF_P3_MMA_ORDER
-#define SEMICRF_P3_MMA_ORDER 0     // 1: a slab's limb products round-robin over the four accumulators (needs all four B operand sets)
-#endif
-#ifndef SEMICRF_MMA_PRIO
-#define SEMICRF_MMA_PRIO 0       // 1: raised wave priority while a wave issues its chunk's matrix instructions
-#endif
-#ifndef SEMICRF_P3_PHASED
-#define SEMICRF_P3_PHASED 1        // 0: all waves in the same order (multiply, then split): within 3 % of the opposite phases
-#endif
-#ifndef SEMICRF_P3_PROBE
-#define SEMICRF_P3_PROBE 0         // 1: per-wave cycle accounting in place of the first output rows (tools/bwd3_probe.py --proj-probe)
-#endif
+// Measured and removed (the code is in git history): a slab's limb products round-robin over the four accumulators (needs all
+// four B operand sets: no room in the register budget), raised wave priority while a wave issues its chunk's matrix instructions
+// (+-1 %), all waves in the same order -- multiply, then split -- instead of the two groups' opposite phases (within 3 %).
 constexpr int GM = 128;            // rows of an output tile
 constexpr int GK = 32;             // contraction values per chunk
 constexpr int N = 256;             // output columns through the matrix cores (the only width this kernel takes)
@@ -93,7 +85,7 @@ __global__ __launch_bounds__(512, 2) void proj_gemm3_kernel(Args P_)
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
     const int l31 = lane & 31, half = lane >> 5;
     const int wm = wave >> 1, wn = wave & 1;           // this wave: rows 32*wm.., columns 128*wn.. of the tile
-    const int grp = SEMICRF_P3_PHASED ? wave >> 2 : 0; // (waves w and w + 4 share a SIMD)
+    const int grp = wave >> 2;                          // (waves w and w + 4 share a SIMD)
     const int nm = (a_M + GM - 1) / GM;
     const int nk = a_nchunks;
     const int Kpad = nk * GK;
@@ -232,7 +224,6 @@ __global__ __launch_bounds__(512, 2) void proj_gemm3_kernel(Args P_)
     // issued before the instructions of group i (two operand sets, alternating: the register budget has no room for a whole slab's)
     auto multiply = [&](int stage) __attribute__((always_inline)) {
         const char* base = glds + stage * STAGE;
-#if SEMICRF_P3_MMA_ORDER == 0
         Limbs3 A, B[2];
         auto ldA = [&](Limbs3& L, int sl) __attribute__((always_inline)) {
             L.h = *(const bf16x8*)(base + rdA[sl]);
@@ -249,7 +240,7 @@ __global__ __launch_bounds__(512, 2) void proj_gemm3_kernel(Args P_)
         __builtin_amdgcn_sched_barrier(0);
         static_for<0, 2 * NW>([&](auto ic) __attribute__((always_inline)) {
             constexpr int i = decltype(ic)::value;
-            constexpr int sl = i / NW, t = i % NW;
+            constexpr int t = i % NW;
             if constexpr (i + 1 < 2 * NW) {
                 constexpr int sl2 = (i + 1) / NW, t2 = (i + 1) % NW;
                 if constexpr (t2 != 0) ldB(B[(i + 1) & 1], sl2, t2);
@@ -263,34 +254,6 @@ __global__ __launch_bounds__(512, 2) void proj_gemm3_kernel(Args P_)
                 __builtin_amdgcn_sched_barrier(0);
             }
         });
-#else
-        // a slab at a time: all its operands, then the six limb products round-robin over the accumulators (independent neighbours)
-        Limbs3 A, B[NW];
-#pragma unroll
-        for (int sl = 0; sl < 2; ++sl) {
-            A.h = *(const bf16x8*)(base + rdA[sl]);
-            A.m = *(const bf16x8*)(base + APL + rdA[sl]);
-            A.l = *(const bf16x8*)(base + 2 * APL + rdA[sl]);
-#pragma unroll
-            for (int t = 0; t < NW; ++t) {
-                B[t].h = *(const bf16x8*)(base + rdB[sl] + t * 2048);
-                B[t].m = *(const bf16x8*)(base + BPL + rdB[sl] + t * 2048);
-                B[t].l = *(const bf16x8*)(base + 2 * BPL + rdB[sl] + t * 2048);
-            }
-#pragma unroll
-            for (int t = 0; t < NW; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A.h, B[t].l, acc[t], 0, 0, 0);
-#pragma unroll
-            for (int t = 0; t < NW; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A.l, B[t].h, acc[t], 0, 0, 0);
-#pragma unroll
-            for (int t = 0; t < NW; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A.m, B[t].m, acc[t], 0, 0, 0);
-#pragma unroll
-            for (int t = 0; t < NW; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A.h, B[t].m, acc[t], 0, 0, 0);
-#pragma unroll
-            for (int t = 0; t < NW; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A.m, B[t].h, acc[t], 0, 0, 0);
-#pragma unroll
-            for (int t = 0; t < NW; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A.h, B[t].h, acc[t], 0, 0, 0);
-        }
-#endif
     };
 
     // the two extra weight rows (forward), zero-padded to whole chunks; the bias values of this lane's columns
@@ -377,9 +340,7 @@ __global__ __launch_bounds__(512, 2) void proj_gemm3_kernel(Args P_)
         sync();
         P3_STAMP(2);
         if (grp == 0) {
-            if (SEMICRF_MMA_PRIO) __builtin_amdgcn_s_setprio(1);
             multiply(Pst);
-            if (SEMICRF_MMA_PRIO) __builtin_amdgcn_s_setprio(0);
             P3_STAMP(0);
             more = finish();
             P3_STAMP(1);
@@ -391,9 +352,7 @@ __global__ __launch_bounds__(512, 2) void proj_gemm3_kernel(Args P_)
         fetch(gn, mn);
         P3_STAMP(5);
         if (grp != 0) {
-            if (SEMICRF_MMA_PRIO) __builtin_amdgcn_s_setprio(1);
             multiply(Pst);
-            if (SEMICRF_MMA_PRIO) __builtin_amdgcn_s_setprio(0);
             P3_STAMP(0);
             more = finish();
             P3_STAMP(1);
@@ -705,7 +664,7 @@ int launch_proj_nn3(const float* A, long long lda, long long M, int K, const flo
     P.accumulate = accumulate; P.bias = bias; P.w2 = w2; P.b2 = b2; P.zero_cols = zero_cols;
     static PerDeviceOnce attr_once[2];
     const long long nitems = (M + pj3::GM - 1) / pj3::GM;
-    const int ncu = proj_ncu();
+    const int ncu = device_ncu();
     const int grid = nitems < ncu ? (int)nitems : ncu;
     if (w2) {
         if (attr_once[0].first())
@@ -733,7 +692,7 @@ int launch_proj_tn3_core(const float* A, long long lda, long long M, int R, cons
     if (attr_once.first())
         (void)hipFuncSetAttribute((const void*)pj3::proj_tn3_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512);
     const long long nitems = (long long)(Mp / pj3::GM) * S;
-    const int ncu = proj_ncu();
+    const int ncu = device_ncu();
     const int grid = nitems < ncu ? (int)nitems : ncu;
     hipLaunchKernelGGL(pj3::proj_tn3_kernel, dim3(grid), dim3(512), lds, stream, P);
     return 0;

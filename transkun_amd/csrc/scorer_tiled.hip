@@ -15,16 +15,8 @@
 //               group g+1 read while group g multiplies;
 //   chunk     = [wait for the wave's pieces of the chunk (the next one stays in flight), s_barrier, request chunk + 2, the
 //               previous item's row(s) of this chunk, 32 matrix instructions].
-//   ping-pong (SEMICRF_TILED_PINGPONG=1, off): waves 0-3 and 4-7 (one of each on every SIMD) one phase apart -- one group in
-//               its memory phase (store + requests) while the other multiplies; three stages still suffice because group A
-//               loads the first halves of all rows and requests one chunk ahead, group B the second halves, two ahead.
-//               Correct (bit-identical) and SLOWER: 1.18 vs 1.11 ms at T=1024 x 352.  Cycle stamps (tools/tiled_probe.py) say
-//               why: the memory phase is not instruction-bound but bound by the CU's ONE vector-memory path -- every LDS-DMA
-//               piece (1 KB) and every scattered store costs its issuing wave ~100-400 cycles there, 56 of them per chunk --
-//               so the memory phase of four waves (~3000 cycles) is longer than the other four's contraction (2048) and the
-//               two phases add up to more than the in-step chunk.  64 x 128 tiles move 12 bytes of operands per matrix cycle
-//               and CU where the L1 delivers ~15; the 128 x 128 tiles of scorer_mfma.hip need 8 but
-//               cannot hold their results twice.
+//   (A ping-pong schedule -- waves 0-3 and 4-7 one phase apart, one group in its memory phase while the other multiplies -- was
+//   correct, bit-identical and SLOWER, 1.18 vs 1.11 ms at T=1024 x 352; DESIGN.md section 3 records why.  Removed.)
 //   item      = one tile x four adjacent chains: chain by chain, 4 D / 64 chunks; the 16 result rows of the PREVIOUS item are
 //               written during these chunks (16 / (4 D / 64) rows per chunk);
 //   order     = the 32 workgroups of an XCD work side by side on the 8 chain quads of one 128-byte line group (its L2
@@ -59,15 +51,6 @@ constexpr int YRING = 4;                     // row-constant buffers: item n's i
 constexpr int YRC = 2 * 4 * YTE * 4;         // [rowc | diag][chain][row] floats = 2 KB
 constexpr int YLDS = YNS * YSTAGE + YRING * YRC;     // 152 KB
 constexpr int YXCD = 8;
-#ifndef SEMICRF_TILED_SPREAD
-#define SEMICRF_TILED_SPREAD 0       // 1: a chunk's store and requests between its matrix instructions (in-step schedule), 0: in a block behind the barrier.
-                                     // Measured (round 5): 1: 1.131-1.134 ms, 0: 1.115-1.119 at T=1024 x 352 (0.669 / 0.661 at T=691 x 360) -- what gains 1 % in
-                                     // the backward GEMMs (SEMICRF_GEMM_SPREAD) loses 1.3 % here: the store's row constants come through the LDS
-                                     // and its wait sits in the middle of the operand reads
-#endif
-#ifndef SEMICRF_TILED_PINGPONG
-#define SEMICRF_TILED_PINGPONG 0     // 1: the two halves of the workgroup run one phase apart (measured slower, see the header)
-#endif
 
 __device__ __forceinline__ float y_len_scale(int len, int mode)
 {
@@ -192,8 +175,10 @@ __global__ __launch_bounds__(512, 2) void interval_score_tiled_kernel(
         }
     };
     // A chunk's requests: req(0 .. 5) (the wave's two q pieces and four k pieces, from the CURRENT request state), req_tail() (the row
-    // constants with a chain's first chunk; then the request state moves on).  issue_chunk() = all of them in a block;
-    // SEMICRF_TILED_SPREAD issues them one at a time between the chunk's matrix instructions instead (see the loop).
+    // constants with a chain's first chunk; then the request state moves on).  issue_chunk() = all of them in a block behind the
+    // barrier (one at a time between the chunk's matrix instructions, which gains 1 % in the backward GEMMs, measured 1.3 % slower
+    // here: 1.131-1.134 vs 1.115-1.119 ms at T=1024 x 352 -- the store's row constants come through the LDS and its wait sits in
+    // the middle of the operand reads).
     auto req = [&](int i) __attribute__((always_inline)) {
         char* st = ylds + nx_stage * YSTAGE;
         const int so = nx_ch * 256;                                          // 64 floats per chunk
@@ -348,21 +333,14 @@ __global__ __launch_bounds__(512, 2) void interval_score_tiled_kernel(
         for (int r = ci * 16 / NCI; r < (ci + 1) * 16 / NCI; ++r) store_row(r);
     };
 
-    // prologue: group A requests one chunk ahead, group B two (see the header); B's first phase is only the wait for its pieces
-    // of chunk 0
-    const bool grpB = SEMICRF_TILED_PINGPONG ? wave >= 4 : true;
-    int inflight = 0;                           // group B: chunks requested and not yet consumed
+    // prologue: two chunks requested
+    int inflight = 0;                           // chunks requested and not yet consumed
     if (nx_valid) { issue_chunk(); ++inflight; }
-    if (grpB && nx_valid) { issue_chunk(); ++inflight; }
+    if (nx_valid) { issue_chunk(); ++inflight; }
     int rd_stage = 0, cur_cnt = 0;
-    if (SEMICRF_TILED_PINGPONG && grpB) {
-        if (inflight >= 2) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-    }
 #ifdef SEMICRF_TILED_PROBE
-    // cycle accounting of one wave (tools/tiled_probe.py): 0 vmcnt wait, 1 stores, 2 requests, 3 barrier after the requests,
-    // 4 contraction, 5 barrier after the contraction, 7 the rest
+    // cycle accounting of one wave (tools/tiled_probe.py): 0 vmcnt wait + barrier, 1 stores, 2 requests, 4 contraction, 7 the rest
+    // (3 and 5 stay zero: they were the ping-pong schedule's barriers)
     unsigned long long pc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     unsigned long long pt = __builtin_readcyclecounter();
 #define TILED_PROBE(i) do { const unsigned long long n_ = __builtin_readcyclecounter(); pc[i] += n_ - pt; pt = n_; } while (0)
@@ -381,34 +359,24 @@ __global__ __launch_bounds__(512, 2) void interval_score_tiled_kernel(
         for (int j = 0; j < qi.nr; ++j) {
             for (int ch = 0; ch < NCH; ++ch) {
                 const int ci = j * NCH + ch;
-                // ---- phase S: this wave's memory instructions, while the SIMD's other wave multiplies ---------------------
+                // ---- the memory instructions: everybody waits for its pieces of this chunk (a younger request may stay in flight),
+                // one barrier, the previous item's rows of this chunk, the requests of chunk + 2 -----------------------------
                 TILED_PROBE(7);
-                // group A: its pieces of THIS chunk (requested one chunk ago; nothing younger is in flight) have landed
-                if (!grpB) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                if (!SEMICRF_TILED_PINGPONG) {
-                    // in step: everybody waits for its pieces of this chunk (a younger request may stay in flight), one barrier
-                    --inflight;
-                    if (inflight >= 1) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-                    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                    __builtin_amdgcn_s_barrier();
-                }
+                --inflight;
+                if (inflight >= 1) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+                else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                __builtin_amdgcn_s_barrier();
                 TILED_PROBE(0);
-                // SEMICRF_TILED_SPREAD (in-step schedule only): the store and the six requests do not go out in a block here -- where
-                // all eight waves queue for the CU's one vector-memory path at the same time and nobody multiplies -- but one behind
-                // each group of four matrix instructions, the two waves of a SIMD one group apart
-                const bool spread = SEMICRF_TILED_SPREAD && !SEMICRF_TILED_PINGPONG && on;
+                const bool spread = false; (void)spread;     // (left from the removed in-loop schedule, like the captures below)
                 const bool doreq = nx_valid;
-                if (!spread) store_chunk(ci);                               // the previous item's rows of this chunk
+                store_chunk(ci);
                 TILED_PROBE(1);
                 if (doreq) {
-                    if (!spread) issue_chunk();                             // A: chunk + 1, B: chunk + 2
+                    issue_chunk();
                     ++inflight;
                 }
                 TILED_PROBE(2);
-                if (SEMICRF_TILED_PINGPONG) __builtin_amdgcn_s_barrier();
-                TILED_PROBE(3);
-                // ---- phase M: the chunk's 32 matrix instructions; everybody's pieces of it were waited for before the barrier
-                // above (B's before the one in front of it) --------------------------------------------------------------
+                // ---- the chunk's 32 matrix instructions; everybody's pieces of it were waited for before the barrier above -----
                 const unsigned sb = lds0 + (unsigned)(rd_stage * YSTAGE);
                 rd_stage = rd_stage + 1 == YNS ? 0 : rd_stage + 1;
                 // eight groups of four contraction pairs (two halves x four segments); the operands of group g+1 are read
@@ -441,37 +409,16 @@ __global__ __launch_bounds__(512, 2) void interval_score_tiled_kernel(
                         }
                         mul_g(qa[g & 1], ka[g & 1]);
                         __builtin_amdgcn_sched_barrier(0);
-                        if (spread) {
-                            // slot = g (waves 0-3) or g - 1 (waves 4-7): slot 0 the store, slots 1 .. 6 the requests
-                            if (wer == 0) {
-                                if constexpr (g == 0) store_chunk(ci);
-                                if constexpr (g >= 1 && g <= 6) { if (doreq) req(g - 1); }
-                            } else {
-                                if constexpr (g == 1) store_chunk(ci);
-                                if constexpr (g >= 2) { if (doreq) req(g - 2); }
-                            }
-                            __builtin_amdgcn_sched_barrier(0);
-                        }
+                        // (captures left from the removed in-loop schedule: without them the closure's layout and with it one SGPR spill change)
+                        (void)store_chunk; (void)req; (void)doreq; (void)ci; (void)wer;
                         if constexpr (g < 7) {
                             wait_g(qa[(g + 1) & 1], ka[(g + 1) & 1]);
                             __builtin_amdgcn_sched_barrier(0);
                         }
                     });
                     asm volatile("" : "+v"(acc));                            // (the matrix instructions stay in front of the barrier)
-                    if (spread && doreq) req_tail();
                 }
                 TILED_PROBE(4);
-                // group B: its pieces of the NEXT chunk (requested one chunk ago; the requests of this chunk's phase S may stay
-                // in flight, its store has had the whole contraction to retire) have landed before group A reads them
-                if (SEMICRF_TILED_PINGPONG) {
-                    if (grpB) {
-                        --inflight;
-                        if (inflight >= 2) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-                        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                    }
-                    __builtin_amdgcn_s_barrier();
-                }
-                TILED_PROBE(5);
             }
             // the chain's block waits in registers for the quad's other chains (the last one stays in acc)
             if (j == qi.nr - 1) {
@@ -513,20 +460,12 @@ __global__ __launch_bounds__(512, 2) void interval_score_tiled_kernel(
         QuadInfo q2;
         if (!item_of(cur_u, e2, b2, q2)) break;
     }
-    if (SEMICRF_TILED_PINGPONG && !grpB) __builtin_amdgcn_s_barrier();     // (group B's last contraction phase)
     for (int ci = 0; ci < NCI; ++ci) store_chunk(ci);
 #ifdef SEMICRF_TILED_PROBE
     if (lane == 0 && !full)
         for (int i = 0; i < 8; ++i) S[(size_t)Cs + (size_t)((blockIdx.x * 8 + wave) * 8 + i)] = (float)pc[i];
 #endif
 #undef TILED_PROBE
-}
-
-bool interval_score_tiled_supported(int C, int T, int D, const float* q, const float* k, long long ldq, long long ldk)
-{
-    const bool aligned = ((uintptr_t)q % 16 == 0) && ((uintptr_t)k % 16 == 0) && ldq % 4 == 0 && ldk % 4 == 0;
-    return aligned && D % 64 == 0 && D <= 256 && T >= 128 && C >= 1 && (long long)T * ldq * 4 < (1ll << 31) &&
-           (long long)T * ldk * 4 < (1ll << 31);      // (+ interval_score_tiled_fits for the slot count: 32-bit offsets inside a block of S)
 }
 
 template <int NCH>
@@ -541,7 +480,7 @@ static void launch_tiled(const float* q, const float* k, const float* diag, cons
                        qscale, mode, full, S, Cs, G, TG);
 }
 
-// rowc may be NULL; group / pitch: the slot layout (scorer_tiles.h).  The caller checked interval_score_tiled_supported.
+// rowc may be NULL; group / pitch: the slot layout (scorer_tiles.h).  The caller asked plan_score_route (scorer_mfma.hip).
 void launch_interval_score_tiled(const float* q, const float* k, const float* diag, const float* rowc, int C, int T, int D,
                                  long long ldq, long long ldk, long long ldd, long long ldrc, float qscale, int mode, int full,
                                  float* S, hipStream_t stream, int group, int pitch)
@@ -559,15 +498,9 @@ void launch_interval_score_tiled(const float* q, const float* k, const float* di
     }
     TG.ntg = (TG.ntiles + 3) / 4;
     TG.nlg = (G.nrq + 7) / 8;
-    int ncu = 256, dev = 0, v = 0;
-    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0)
-        ncu = v;
     // persistent workgroups, one per CU; per XCD a multiple of 32 slots (one super item at a time)
-    int grid = ncu / (32 * YXCD) * (32 * YXCD);
-    if (grid < 32 * YXCD) grid = 32 * YXCD;
     const long long supers = (long long)TG.nlg * TG.ntg;
-    const long long need = (supers + YXCD - 1) / YXCD * 32 * YXCD;
-    if (grid > need) grid = (int)need;
+    const int grid = persistent_grid(device_ncu(), 32 * YXCD, (supers + YXCD - 1) / YXCD * 32 * YXCD);
     switch (D / 64) {
     case 1: launch_tiled<1>(q, k, diag, rowc, C, T, ldq, ldk, ldd, ldrc, qscale, mode, full, S, Cs, G, TG, grid, stream); break;
     case 2: launch_tiled<2>(q, k, diag, rowc, C, T, ldq, ldk, ldd, ldrc, qscale, mode, full, S, Cs, G, TG, grid, stream); break;

@@ -42,5 +42,27 @@ __device__ __forceinline__ QuadInfo quad_info(const SlotGeom& g, int rq)
     return o;
 }
 
+// Tile t of the walk over the 128-column tiles that the 64- / 128-row tile kernels share (scorer_fwd_tile_ref.h, _tile3.h): the
+// full square row by row, or the lower triangle.  SQUARE: 128-row tiles (row et holds et+1 tiles); else 64-row tiles (rows 2p
+// and 2p+1 hold p+1 tiles each; p(p+1) tiles lie before the pair).
+template <bool SQUARE>
+__device__ __forceinline__ void tile_of_index(int t, int nbt, int full, int& et, int& bt)
+{
+    if (full) {
+        et = t / nbt; bt = t % nbt;
+    } else if (SQUARE) {
+        et = (int)((sqrtf(8.0f * (float)t + 1.0f) - 1.0f) * 0.5f);
+        while (et * (et + 1) / 2 > t) --et;
+        while ((et + 1) * (et + 2) / 2 <= t) ++et;
+        bt = t - et * (et + 1) / 2;
+    } else {
+        int pp = (int)((sqrtf(4.0f * (float)t + 1.0f) - 1.0f) * 0.5f);
+        while (pp * (pp + 1) > t) --pp;
+        while ((pp + 1) * (pp + 2) <= t) ++pp;
+        const int r = t - pp * (pp + 1);
+        et = r < pp + 1 ? 2 * pp : 2 * pp + 1;
+        bt = r < pp + 1 ? r : r - (pp + 1);
+    }
+}
 
 }  // namespace semicrf

@@ -107,6 +107,15 @@ def bwd_workspace(C: int, T: int, D: int, device) -> torch.Tensor:
     return torch.empty(n, dtype=torch.uint8, device=device)
 
 
+def proj_tn_workspace(M: int, R: int, K: int, device) -> torch.Tensor:
+    """Workspace of scorer_proj_tn (the geometry depends on that device's compute-unit count, hence the device in the key)."""
+    key = ("tn", M, R, K, device.index)
+    n = _BWD_WS.get(key)
+    if n is None:
+        n = _BWD_WS[key] = int(_lib.load().scorer_proj_tn_workspace_bytes(M, R, K))
+    return torch.empty(n, dtype=torch.uint8, device=device)
+
+
 BF16X3 = _lib.SCORE_BF16X3      # OR into full_square
 LEN_BF16X3 = _lib.LEN_BF16X3    # OR into the backward's length-scaling mode (the two products on the three-limb bf16 kernels)
 BWD_BF16X3 = 8  # this package's autograd nodes only (never handed to the library): "the backward of this forward uses LEN_BF16X3"
@@ -311,11 +320,7 @@ def proj_weight_grad(dy2: torch.Tensor, x2: torch.Tensor, n_main: int, prec: int
         return _tn_splitk(dy2, x2), dy2.sum(0)
     dW = torch.empty(Nout, K, dtype=torch.float32, device=dy2.device)
     db = torch.empty(Nout, dtype=torch.float32, device=dy2.device)
-    key = ("tn", M, n_main, K, dy2.device.index)
-    n = _BWD_WS.get(key)
-    if n is None:
-        n = _BWD_WS[key] = int(_lib.load().scorer_proj_tn_workspace_bytes(M, n_main, K))
-    ws = torch.empty(n, dtype=torch.uint8, device=dy2.device)
+    ws = proj_tn_workspace(M, n_main, K, dy2.device)
     _lib.ops().proj_tn(dy2, Nout, M, n_main, n_main if Nout > n_main else -1, Nout | (PROJ_TN_BF16X3 if prec else 0), x2, K, K, dW, K, db, ws)
     return dW, db
 
@@ -453,22 +458,14 @@ class _ScorerLinearPacked(torch.autograd.Function):
             dW = torch.zeros(rows, K, dtype=torch.float32, device=dev) if (g1 is None or g2 is None) else torch.empty(rows, K, dtype=torch.float32, device=dev)
             db = torch.zeros(rows, dtype=torch.float32, device=dev) if (g1 is None or g2 is None) else torch.empty(rows, dtype=torch.float32, device=dev)
             if g1 is not None:
-                key = ("tn", M, D, K, dev.index)              # (the geometry depends on that device's compute-unit count)
-                n = _BWD_WS.get(key)
-                if n is None:
-                    n = _BWD_WS[key] = int(_lib.load().scorer_proj_tn_workspace_bytes(M, D, K))
-                ws = torch.empty(n, dtype=torch.uint8, device=dev)
+                ws = proj_tn_workspace(M, D, K, dev)
                 ops.proj_tn(g1, D + QPAD, M, D, D, (D + QPAD) | (PROJ_TN_BF16X3 if ctx.prec else 0), x2, K, K, dW, K, db, ws)
                 dW[2 * D].copy_(dW[D])
                 db[2 * D:2 * D + 1].copy_(db[D:D + 1])
                 if g2 is None:
                     dW[D:2 * D].zero_(); db[D:2 * D].zero_()
             if g2 is not None:
-                key = ("tn", M, D, K, dev.index)              # (the geometry depends on that device's compute-unit count)
-                n = _BWD_WS.get(key)
-                if n is None:
-                    n = _BWD_WS[key] = int(_lib.load().scorer_proj_tn_workspace_bytes(M, D, K))
-                ws = torch.empty(n, dtype=torch.uint8, device=dev)
+                ws = proj_tn_workspace(M, D, K, dev)
                 ops.proj_tn(g2, D, M, D, -1, D | (PROJ_TN_BF16X3 if ctx.prec else 0), x2, K, K, dW.view(-1)[D * K:], K, db[D:], ws)
             dW, db = dW[:2 * D + 1], db[:2 * D + 1]
         return dx, dW if need[1] else None, db if need[2] else None, None, None
