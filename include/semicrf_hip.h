@@ -1118,6 +1118,53 @@ int semicrf_axial_attention_bf16(const uint16_t* q, const uint16_t* k, const uin
                                  int64_t out_stride_s0, int64_t out_stride_s1, int64_t out_stride_l, semicrf_stream_t stream);
 
 /*
+ * The backward of semicrf_axial_attention_bf16: dq, dk, dv from q, k, v and the cotangent dout, every element one bf16 value.  It is
+ * the contract of semicrf_axial_attention_bwd with bf16 elements and WITHOUT `out`: TOKEN-MAJOR, head h the slice [h d, (h + 1) d);
+ * two sequence dimensions and three ELEMENT strides for each of the seven tensors (q, dout, dq: Lq tokens; k, v, dk, dv: Lk tokens), so
+ * the gradient of the time-axis call lands in the [N][T'][F'][H d] buffer without a transposed copy.  Strides of q, k, v are >= 0 (0
+ * repeats); dout, dq, dk, dv are real, non-overlapping tensors.  A token stride stays below 2^28 elements; all offsets are 64-bit.  Any
+ * of dq, dk, dv may be NULL: nothing is computed or written for it.
+ *
+ * Supported (semicrf_axial_attention_bf16_bwd_supported returns 1): exactly the forward's set -- 1 <= Lq, Lk <= SEMICRF_ATTENTION_MAX_L;
+ * d a multiple of 8 in [8, SEMICRF_ATTENTION_MAX_D]; H >= 1.  n0 n1 H < 2^31.  n0 n1 == 0 launches nothing.
+ *
+ * The chain (csrc/attention_bf16_math.h), per sequence and head; s, m, p, ph = bf16_rne(p) and sum are recomputed exactly as the bf16
+ * forward forms them (the forward saves nothing), scale = (float)(1 / sqrt(d)):
+ *   P[i][j]  = (float)ph[i][j] / sum_i                          one fp32 division
+ *   dP[i][j] = sum over c of dout[i][c] v[j][c]                 exact products, fp32 accumulation
+ *   D_i      = sum over j of P[i][j] dP[i][j]                   fp32, in the fixed order of `sum`: the keys whose ((j >> 2) & 1) is 0
+ *                                                               ascending, then those whose bit is 1, then the two partial sums added
+ *   dS[i][j] = P[i][j] (dP[i][j] - D_i)                         fp32
+ *   dSh = bf16_rne(dS), Ph = bf16_rne(P)                        what the three gradient products consume
+ *   dq[i][c] = bf16_rne(scale * sum over j of dSh[i][j] k[j][c])   fp32 accumulation, one multiplication by scale, one rounding
+ *   dk[j][c] = bf16_rne(scale * sum over i of dSh[i][j] q[i][c])
+ *   dv[j][c] = bf16_rne(sum over i of Ph[i][j] dout[i][c])
+ * D_i is the softmax form, not dout_i . out_i: it is up to 3.4 x closer to float64 on sharp softmaxes, gives dq = dk = 0 exactly at
+ * Lk = 1, and needs no `out`.
+ * On the device all five products run on v_mfma_f32_32x32x16_bf16.  Keys from Lk to the tile edge are masked to -inf before the maximum
+ * and have P = dS = 0 exactly; rows past Lq / Lk are never read and never written; a padded query has dout = 0 in registers and adds
+ * exact zeros to dk and dv; the head dimension is padded with zeros in registers and LDS only.  One workgroup per (sequence, head) forms
+ * all of its dk and dv: no atomics, no workspace, one launch on `stream`, and a sequence's gradients are bit-identical from run to run,
+ * whatever n0, n1, its position in the batch, the strides and the alignment are.
+ * The device and the host mirror (the CPU key of torch.ops.semicrf.axial_attention_bf16_bwd) are NOT bit-identical to each other: the
+ * matrix instruction's internal summation is not the mirror's ascending fp32 chain, and expf differs.  Both answer to the same
+ * accuracy gates and give the same exact answers wherever every partial sum is exact.
+ * Pointers need 2-byte alignment only.  Q, K, V and dout rows are read with 16-byte loads when q, k, v, dout are 16-byte aligned and all
+ * their strides are multiples of 8, with 2-byte loads otherwise; each of dq, dk, dv is written with 8-byte stores when it is 8-byte
+ * aligned and its strides are multiples of 4, with 2-byte stores otherwise: the same bits either way.
+ * SEMICRF_EINVAL, with nothing launched and dq / dk / dv untouched: a shape outside the supported set, a NULL q / k / v / dout, a
+ * misaligned (odd) pointer, a negative count or stride, a token stride >= 2^28, n0 n1 H >= 2^31.
+ */
+int semicrf_axial_attention_bf16_bwd_supported(int Lq, int Lk, int H, int d);
+int semicrf_axial_attention_bf16_bwd(const uint16_t* q, const uint16_t* k, const uint16_t* v, const uint16_t* dout, uint16_t* dq, uint16_t* dk,
+                                     uint16_t* dv, int64_t n0, int64_t n1, int Lq, int Lk, int H, int d, int64_t q_stride_s0, int64_t q_stride_s1,
+                                     int64_t q_stride_l, int64_t k_stride_s0, int64_t k_stride_s1, int64_t k_stride_l, int64_t v_stride_s0,
+                                     int64_t v_stride_s1, int64_t v_stride_l, int64_t dout_stride_s0, int64_t dout_stride_s1,
+                                     int64_t dout_stride_l, int64_t dq_stride_s0, int64_t dq_stride_s1, int64_t dq_stride_l, int64_t dk_stride_s0,
+                                     int64_t dk_stride_s1, int64_t dk_stride_l, int64_t dv_stride_s0, int64_t dv_stride_s1, int64_t dv_stride_l,
+                                     semicrf_stream_t stream);
+
+/*
  * The feed-forward ResBlock of the backbone's transformer layers in eval mode, as one launch.  Replaces: RMSNorm, Linear, GELU,
  * Linear, the multiplication by the LayerScale and the residual addition of ResBlock around the feed-forward module
  * (LayersTransformer.py), about ten launches and three round trips of the [tokens, hidden] activation.  For every token t = (i0, i1),

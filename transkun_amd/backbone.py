@@ -32,6 +32,14 @@ always have.  "fused" sends bf16 calls to the op wherever the fp32 op would appl
 shape, no broadcasting keys, token strides within the limit); it is forward only, so under autograd both "fused" and "fused-train"
 answer by the stock route for bf16.  `ATTENTION_BF16_ROUTES` counts the bf16 calls made with the knob at "fused".
 
+Training in bf16 has a third knob, `attentionBf16Train = "torch" | "fused"` (default "torch": everything above, unchanged).  With
+`attention = "fused-train"`, `attentionBf16 = "fused"` AND `attentionBf16Train = "fused"`, a bf16 call under autograd is a
+`torch.autograd.Function` around the same bf16 forward op whose backward is `torch.ops.semicrf.axial_attention_bf16_bwd`
+(csrc/attention_bf16_bwd.hip: all five products on the bf16 matrix instruction; the host mirror on the CPU).  It saves the q, k, v views
+only -- the backward recomputes the softmax and needs no `out` -- writes dq, dk, dv by strides in the layouts of q, k, v, and is once
+differentiable.  `ATTENTION_BF16_TRAIN_ROUTES` counts the bf16 calls under autograd made with the knob at "fused", and the launches
+of the backward.
+
 The feed-forward half of a layer has a fused route too.  `feedForward = "fused" | "torch"` on a `ResBlock`, and on `BasicBlock` and
 `Backbone` for all of their feed-forward blocks, picks it; the default is "torch", the stock expression.  "fused" runs a block whose
 module is the `Linear, GELU, Dropout, Linear` sequence through `feed_forward_residual`: RMSNorm, both Linears, the GELU, the LayerScale
@@ -63,6 +71,11 @@ BF16_KINDS = ("torch", "fused")
 DEFAULT_ATTENTION_BF16 = "torch"
 # calls of axial_attention on bfloat16 tensors with bf16 = "fused", by the way they went; tests read it
 ATTENTION_BF16_ROUTES = {"fused": 0, "torch": 0}
+BF16_TRAIN_KINDS = ("torch", "fused")
+DEFAULT_ATTENTION_BF16_TRAIN = "torch"
+# calls of axial_attention on bfloat16 tensors under autograd with bf16_train = "fused", by the way they went ("fused": the autograd
+# Function around the bf16 op; "torch": the stock call) and, under "bwd", the launches of the bf16 HIP backward; tests read it
+ATTENTION_BF16_TRAIN_ROUTES = {"fused": 0, "torch": 0, "bwd": 0}
 
 
 # ---- the attention ------------------------------------------------------------------------------------------------------------------
@@ -74,6 +87,11 @@ def attention_supported(Lq: int, Lk: int, num_heads: int, head_dim: int) -> bool
 def attention_bf16_supported(Lq: int, Lk: int, num_heads: int, head_dim: int) -> bool:
     """semicrf_axial_attention_bf16_supported: the fp32 op's set."""
     return bool(_lib.load().semicrf_axial_attention_bf16_supported(int(Lq), int(Lk), int(num_heads), int(head_dim)))
+
+
+def attention_bf16_bwd_supported(Lq: int, Lk: int, num_heads: int, head_dim: int) -> bool:
+    """semicrf_axial_attention_bf16_bwd_supported: the forward's set."""
+    return bool(_lib.load().semicrf_axial_attention_bf16_bwd_supported(int(Lq), int(Lk), int(num_heads), int(head_dim)))
 
 
 def attention_bwd_supported(Lq: int, Lk: int, num_heads: int, head_dim: int) -> bool:
@@ -138,7 +156,7 @@ def _fused_applies(q, k, v, num_heads, train=False, dtype=torch.float32) -> bool
         return False                                            # tokens 2^28 elements apart or more: outside the device op's addressing
     dims = (q.shape[-2], k.shape[-2], num_heads, q.shape[-1] // num_heads)
     if dtype == torch.bfloat16:
-        return not train and attention_bf16_supported(*dims)    # forward only
+        return attention_bf16_supported(*dims) and (not train or attention_bf16_bwd_supported(*dims))
     return attention_supported(*dims) and (not train or attention_bwd_supported(*dims))
 
 
@@ -178,6 +196,28 @@ def _real_strides(x4) -> bool:
     return all(n == 1 or s > 0 for n, s in zip(x4.shape[:3], x4.stride()[:3]))
 
 
+def _backward_views(ctx, dout):
+    """What a backward op is handed -> (dout's 4-d view, the gradients, their 4-d views): dout by its strides under the forward's
+    split (made contiguous only where that cannot be said), the gradients allocated in the layouts of q, k, v; None for an input
+    that needs none."""
+    split = ctx.split
+    g4 = _as_sequences(dout, split)
+    if g4 is None or not _real_strides(g4) or (dout.device.type == "cuda" and not _token_strides_fit(g4)):
+        g4 = _as_sequences(dout.contiguous(), split)
+    grads, grads4 = [], []
+    for need, (shape, strides) in zip(ctx.needs_input_grad[:3], ctx.layouts):
+        g = x4 = None
+        if need:
+            g = torch.empty_strided(shape, strides, dtype=dout.dtype, device=dout.device)
+            x4 = _as_sequences(g, split)
+            if x4 is None:
+                g = torch.empty(shape, dtype=dout.dtype, device=dout.device)
+                x4 = _as_sequences(g, split)
+        grads.append(g)
+        grads4.append(x4)
+    return g4, grads, grads4
+
+
 class _AxialAttentionTrain(torch.autograd.Function):
     """The forward op, and axial_attention_bwd as its backward (route "fused-train")."""
 
@@ -193,29 +233,36 @@ class _AxialAttentionTrain(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, dout):
         q4, k4, v4, out = ctx.saved_tensors
-        split = ctx.split
-        o4 = _as_sequences(out, split)
-        g4 = _as_sequences(dout, split)                         # by its strides, under the forward's split
-        if g4 is None or not _real_strides(g4) or (dout.device.type == "cuda" and not _token_strides_fit(g4)):
-            g4 = _as_sequences(dout.contiguous(), split)
-        grads, grads4 = [], []
-        for need, (shape, strides) in zip(ctx.needs_input_grad[:3], ctx.layouts):
-            g = x4 = None
-            if need:
-                g = torch.empty_strided(shape, strides, dtype=dout.dtype, device=dout.device)
-                x4 = _as_sequences(g, split)
-                if x4 is None:
-                    g = torch.empty(shape, dtype=dout.dtype, device=dout.device)
-                    x4 = _as_sequences(g, split)
-            grads.append(g)
-            grads4.append(x4)
+        o4 = _as_sequences(out, ctx.split)
+        g4, grads, grads4 = _backward_views(ctx, dout)
         _lib.ops().axial_attention_bwd(q4, k4, v4, o4, g4, grads4[0], grads4[1], grads4[2], ctx.num_heads)
         ATTENTION_ROUTES["bwd"] += 1
         return grads[0], grads[1], grads[2], None
 
 
+class _AxialAttentionBf16Train(torch.autograd.Function):
+    """The bf16 forward op, and axial_attention_bf16_bwd as its backward (bf16_train = "fused").  Only the q, k, v views are saved."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, num_heads):
+        out, split, views = _fused_forward(q, k, v, num_heads)
+        ctx.save_for_backward(*views)
+        ctx.split, ctx.num_heads = split, num_heads
+        ctx.layouts = [_layout_of(t) for t in (q, k, v)]
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout):
+        q4, k4, v4 = ctx.saved_tensors
+        g4, grads, grads4 = _backward_views(ctx, dout)
+        _lib.ops().axial_attention_bf16_bwd(q4, k4, v4, g4, grads4[0], grads4[1], grads4[2], ctx.num_heads)
+        ATTENTION_BF16_TRAIN_ROUTES["bwd"] += 1
+        return grads[0], grads[1], grads[2], None
+
+
 def axial_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, num_heads: int, route: str = "fused",
-                    bf16: str = "torch") -> torch.Tensor:
+                    bf16: str = "torch", bf16_train: str = "torch") -> torch.Tensor:
     """softmax(q k^T / sqrt(d)) v per head and sequence.  q [..., Lq, H d], k and v [..., Lk, H d], arbitrary strided views whose last
     dimension is contiguous: the leading dimensions are handed to the op as its two sequence dimensions by strides alone (a tensor
     whose leading dimensions cannot be expressed that way is made contiguous first, that tensor only).  Returns [..., Lq, H d], laid
@@ -233,11 +280,26 @@ def axial_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, num_heads
     q, k and v are all bfloat16, route is not "torch" and no gradient is wanted, the call is the HIP op axial_attention_bf16 (the host
     kernel for CPU tensors) under the same conditions as the fp32 op -- same device, no broadcasting keys, a supported shape, token
     strides within the limit -- and returns bf16 laid out like q; in every other case, under autograd with either fused route
-    included, the call is what it is with bf16 = "torch"."""
+    included, the call is what it is with bf16 = "torch".
+
+    bf16_train = "torch" (the default): all of the above.  bf16_train = "fused" has an effect only when q, k and v are all bfloat16,
+    route is "fused-train", bf16 is "fused", a gradient is wanted, the bf16 op applies to the call and
+    semicrf_axial_attention_bf16_bwd_supported holds: the call is then an autograd Function around the bf16 forward op whose backward
+    is the HIP op axial_attention_bf16_bwd (once differentiable; only the q, k, v views are saved; bf16 gradients laid out like q, k,
+    v; None for an input that needs none).  In every other case the call is exactly what it is with bf16_train = "torch"."""
     if route not in ROUTES:
         raise ValueError(f"route must be one of {ROUTES}, not {route!r}")
     if bf16 not in BF16_KINDS:
         raise ValueError(f"bf16 must be one of {BF16_KINDS}, not {bf16!r}")
+    if bf16_train not in BF16_TRAIN_KINDS:
+        raise ValueError(f"bf16_train must be one of {BF16_TRAIN_KINDS}, not {bf16_train!r}")
+    if bf16_train == "fused" and q.dtype == k.dtype == v.dtype == torch.bfloat16 and _wants_grad(q, k, v):
+        if route == "fused-train" and bf16 == "fused" and _fused_applies(q, k, v, num_heads, True, torch.bfloat16):
+            ATTENTION_BF16_TRAIN_ROUTES["fused"] += 1
+            ATTENTION_BF16_ROUTES["fused"] += 1
+            ATTENTION_ROUTES["fused-train"] += 1
+            return _AxialAttentionBf16Train.apply(q, k, v, num_heads)
+        ATTENTION_BF16_TRAIN_ROUTES["torch"] += 1
     if bf16 == "fused" and q.dtype == k.dtype == v.dtype == torch.bfloat16:
         if route != "torch" and _fused_applies(q, k, v, num_heads, dtype=torch.bfloat16):
             ATTENTION_BF16_ROUTES["fused"] += 1
@@ -445,7 +507,9 @@ class MultiHeadAttentionKernel(nn.Module):
     attention: "fused" (axial_attention's HIP op where it applies; the stock route under autograd), "fused-train" (the HIP op and its
     HIP backward under autograd) or "torch" (the stock route).
     attentionBf16: "torch" (bfloat16 tensors take the stock route: the default) or "fused" (axial_attention's bf16 HIP op where it
-    applies, forward only)."""
+    applies, forward only).
+    attentionBf16Train: "torch" (the default) or "fused": with attention = "fused-train" and attentionBf16 = "fused", bfloat16 calls
+    under autograd run the bf16 HIP op and its HIP backward."""
 
     def __init__(self, embed_dim, num_heads, dropout=0., k_dim=None, v_dim=None, fourierSize=32, kernel="fourier", hiddenFactor=1):
         super().__init__()
@@ -464,6 +528,7 @@ class MultiHeadAttentionKernel(nn.Module):
             self.norm = RMSNorm()
         self.attention = DEFAULT_ATTENTION
         self.attentionBf16 = DEFAULT_ATTENTION_BF16
+        self.attentionBf16Train = DEFAULT_ATTENTION_BF16_TRAIN
         self._reset_parameters()
 
     def _reset_parameters(self):
@@ -485,7 +550,8 @@ class MultiHeadAttentionKernel(nn.Module):
         q, k, v = query @ self.q_proj_weight, key @ self.k_proj_weight, value @ self.v_proj_weight
         if seq_dim == -3:
             q, k, v = q.transpose(-3, -2), k.transpose(-3, -2), v.transpose(-3, -2)
-        fetched = axial_attention(q, k, v, self.num_heads, route=self.attention, bf16=self.attentionBf16)
+        fetched = axial_attention(q, k, v, self.num_heads, route=self.attention, bf16=self.attentionBf16,
+                                  bf16_train=self.attentionBf16Train)
         if seq_dim == -3:
             fetched = fetched.transpose(-3, -2)
         return self.out_proj(fetched)
@@ -503,7 +569,8 @@ class BasicBlock(nn.Module):
     With attention = "fused" or "fused-train" the "F" and "T" halves run on the [N, T, F, D] buffer as it is: everything but the
     attention is per token, and the two halves differ only in which dimension the attention is told is the sequence.  With "torch"
     the block follows the reference's order of operations, `transpose(-3, -2)` around the time-axis half included.
-    attentionBf16 = "torch" | "fused" sets the bfloat16 knob of all its attention modules."""
+    attentionBf16 = "torch" | "fused" sets the bfloat16 knob of all its attention modules, attentionBf16Train = "torch" | "fused"
+    their bfloat16 training knob."""
 
     def __init__(self, inputSize, num_heads, fourierSize, hiddenFactor=2, hiddenFactorAttn=1, approxKernels=[None, None, None, None],
                  enabled=["F", "T", "All0", "0All"], dropoutProb=0.0):
@@ -554,6 +621,19 @@ class BasicBlock(nn.Module):
         for m in self.modules():
             if isinstance(m, MultiHeadAttentionKernel):
                 m.attentionBf16 = kind
+
+    @property
+    def attentionBf16Train(self):
+        kinds = {m.attentionBf16Train for m in self.modules() if isinstance(m, MultiHeadAttentionKernel)}
+        return kinds.pop() if len(kinds) == 1 else "mixed"
+
+    @attentionBf16Train.setter
+    def attentionBf16Train(self, kind):
+        if kind not in BF16_TRAIN_KINDS:
+            raise ValueError(f"attentionBf16Train must be one of {BF16_TRAIN_KINDS}, not {kind!r}")
+        for m in self.modules():
+            if isinstance(m, MultiHeadAttentionKernel):
+                m.attentionBf16Train = kind
 
     def feed_forward_blocks(self):
         return [m for m in self.modules() if isinstance(m, ResBlock) and m.is_feed_forward()]
@@ -616,6 +696,7 @@ class Backbone(nn.Module):
 
     attention: "fused" | "fused-train" | "torch" for all layers (the property reads "mixed" when they differ).
     attentionBf16: "torch" | "fused" for the bfloat16 calls of all layers, likewise.
+    attentionBf16Train: "torch" | "fused" for the bfloat16 calls of all layers under autograd, likewise.
     feedForward: "torch" | "fused" for the feed-forward blocks of all layers, likewise."""
 
     def __init__(self, inputSize, baseSize, posEmbedInitGamma, nHead, fourierSize=16, hiddenFactor=2, hiddenFactorAttn=1,
@@ -675,6 +756,19 @@ class Backbone(nn.Module):
         for m in self.modules():
             if isinstance(m, MultiHeadAttentionKernel):
                 m.attentionBf16 = kind
+
+    @property
+    def attentionBf16Train(self):
+        kinds = {m.attentionBf16Train for m in self.modules() if isinstance(m, MultiHeadAttentionKernel)}
+        return kinds.pop() if len(kinds) == 1 else "mixed"
+
+    @attentionBf16Train.setter
+    def attentionBf16Train(self, kind):
+        if kind not in BF16_TRAIN_KINDS:
+            raise ValueError(f"attentionBf16Train must be one of {BF16_TRAIN_KINDS}, not {kind!r}")
+        for m in self.modules():
+            if isinstance(m, MultiHeadAttentionKernel):
+                m.attentionBf16Train = kind
 
     def feed_forward_blocks(self):
         return [m for m in self.modules() if isinstance(m, ResBlock) and m.is_feed_forward()]

@@ -1312,6 +1312,39 @@ int semicrf_axial_attention_bf16(const uint16_t* q, const uint16_t* k, const uin
     return SEMICRF_OK;
 }
 
+int semicrf_axial_attention_bf16_bwd_supported(int Lq, int Lk, int H, int d) { return attention::supported(Lq, Lk, H, d) ? 1 : 0; }
+
+int semicrf_axial_attention_bf16_bwd(const uint16_t* q, const uint16_t* k, const uint16_t* v, const uint16_t* dout, uint16_t* dq, uint16_t* dk,
+                                     uint16_t* dv, int64_t n0, int64_t n1, int Lq, int Lk, int H, int d, int64_t q_stride_s0, int64_t q_stride_s1,
+                                     int64_t q_stride_l, int64_t k_stride_s0, int64_t k_stride_s1, int64_t k_stride_l, int64_t v_stride_s0,
+                                     int64_t v_stride_s1, int64_t v_stride_l, int64_t dout_stride_s0, int64_t dout_stride_s1,
+                                     int64_t dout_stride_l, int64_t dq_stride_s0, int64_t dq_stride_s1, int64_t dq_stride_l, int64_t dk_stride_s0,
+                                     int64_t dk_stride_s1, int64_t dk_stride_l, int64_t dv_stride_s0, int64_t dv_stride_s1, int64_t dv_stride_l,
+                                     semicrf_stream_t stream)
+{
+    SEMICRF_CHECK_ARG(attention::supported(Lq, Lk, H, d),
+                      "axial_attention_bf16_bwd: Lq=%d Lk=%d H=%d d=%d is outside the supported set (1 <= Lq, Lk <= %d; d a multiple of 8 in "
+                      "[%d, %d]; H >= 1): see semicrf_axial_attention_bf16_bwd_supported", Lq, Lk, H, d, attention::ATT_MAX_L,
+                      attention::ATT_MIN_D, attention::ATT_MAX_D);
+    SEMICRF_CHECK_ARG(n0 >= 0 && n1 >= 0, "axial_attention_bf16_bwd: n0=%lld n1=%lld must be >= 0", (long long)n0, (long long)n1);
+    if (n0 == 0 || n1 == 0) return SEMICRF_OK;
+    SEMICRF_CHECK_ARG(n0 < (1ll << 31) && n1 < (1ll << 31) && n0 * n1 * H < (1ll << 31),
+                      "axial_attention_bf16_bwd: n0 * n1 * H = %lld * %lld * %d must stay below 2^31", (long long)n0, (long long)n1, H);
+    SEMICRF_CHECK_ARG(q && k && v && dout, "axial_attention_bf16_bwd: q/k/v/dout must be non-NULL");
+    SEMICRF_CHECK_ARG((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)dout | (uintptr_t)dq | (uintptr_t)dk | (uintptr_t)dv) & 1) == 0,
+                      "axial_attention_bf16_bwd: every pointer must be 2-byte aligned");
+    const long long strides[21] = {q_stride_s0, q_stride_s1, q_stride_l, k_stride_s0, k_stride_s1, k_stride_l, v_stride_s0, v_stride_s1,
+                                   v_stride_l, dout_stride_s0, dout_stride_s1, dout_stride_l, dq_stride_s0, dq_stride_s1, dq_stride_l,
+                                   dk_stride_s0, dk_stride_s1, dk_stride_l, dv_stride_s0, dv_stride_s1, dv_stride_l};
+    for (int i = 0; i < 21; ++i) SEMICRF_CHECK_ARG(strides[i] >= 0, "axial_attention_bf16_bwd: stride %d is negative (%lld)", i, strides[i]);
+    for (int i = 2; i < 21; i += 3)
+        SEMICRF_CHECK_ARG(strides[i] < (1ll << 28), "axial_attention_bf16_bwd: token stride %lld must stay below 2^28 elements", strides[i]);
+    if (!dq && !dk && !dv) return SEMICRF_OK;
+    launch_axial_attention_bf16_bwd(q, k, v, dout, dq, dk, dv, n0, n1, Lq, Lk, H, d, strides, (hipStream_t)stream);
+    SEMICRF_CHECK_LAUNCH("semicrf_axial_attention_bf16_bwd");
+    return SEMICRF_OK;
+}
+
 int semicrf_axial_attention_bwd_supported(int Lq, int Lk, int H, int d) { return attention::supported(Lq, Lk, H, d) ? 1 : 0; }
 
 int semicrf_axial_attention_bwd(const float* q, const float* k, const float* v, const float* out, const float* dout, float* dq, float* dk,

@@ -1,5 +1,6 @@
-// attention_bf16_math.h -- what the HIP kernel of the bf16 axial attention (attention_bf16.hip) and its host mirror (cpu_ops.cpp) share:
-// the chain of operations, the bf16 conversions and the order of the keys inside a matrix instruction's k-step.
+// attention_bf16_math.h -- what the HIP kernels of the bf16 axial attention (attention_bf16.hip, attention_bf16_bwd.hip) and their host
+// mirrors (cpu_ops.cpp) share: the chains of operations, the bf16 conversions and the order of the keys inside a matrix instruction's
+// k-step.  The forward first, the backward at the end.
 //
 // Per sequence s, head h and query i (q, k, v, out token-major bf16, head h the slice [h d, (h + 1) d)):
 //   s[j]   = (sum over c < d of q[i][c] * k[j][c]) * scale     every product exact in fp32, fp32 accumulation; scale = (float)(1 / sqrt(d))
@@ -50,6 +51,31 @@ ATTENTION_HD size_t lds_bytes_bf16(int Lk, int d)
 {
     const int nkt = key_tiles(Lk);
     return 2 * ((size_t)nkt * ATT_TILE * (16 * dim_steps(d) + ATT16_KPAD) + (size_t)32 * col_blocks(d) * (nkt * ATT_TILE + ATT16_VPAD));
+}
+
+// ---- the backward (attention_bf16_bwd.hip, semicrf_cpu::axial_attention_bf16_bwd) -----------------------------------------------------
+// s, m, p, ph and sum are the forward's, recomputed by its chain (nothing is saved; the products commute, so the pass that holds a key
+// per lane forms the scores of the pass that holds a query per lane).  Then, per sequence and head, dout the bf16 cotangent:
+//   P[i][j]  = (float)ph[i][j] / sum[i]                            one fp32 division
+//   dP[i][j] = sum over c < d of dout[i][c] * v[j][c]              exact products, fp32 accumulation
+//   D[i]     = D0 + D1,  D_b = the sum of P[i][j] * dP[i][j] over the keys with sum_half(j) == b, ascending in j from +0: the order
+//              of `sum`.  The softmax form, not dout . out: `out` is not an input, and at Lk = 1 dS is an exact zero
+//   dS[i][j] = P[i][j] * (dP[i][j] - D[i])                         fp32
+//   dSh = bf16_rne(dS), Ph = bf16_rne(P)                           what the three gradient products consume
+//   dq[i][c] = bf16_rne(scale * sum over j of dSh[i][j] k[j][c])   fp32 accumulation, one multiplication by scale, one rounding
+//   dk[j][c] = bf16_rne(scale * sum over i of dSh[i][j] q[i][c])
+//   dv[j][c] = bf16_rne(        sum over i of Ph[i][j] dout[i][c])
+// A key from Lk to the tile edge has P = dS = 0 exactly; a padded query has dout = 0, so D = dS = 0 and it adds exact zeros.
+// On the device the five products are v_mfma_f32_32x32x16_bf16's; the mirror accumulates in fp32 ascending.
+
+// LDS of one workgroup of the backward, nt = the tiles of the longer of the two sequences: two token-major images [32 nt][16 ks +
+// KPAD] and two transposed ones [32 db][32 nt + VPAD] in bf16 (pass A: K, V, K^T; pass B: Q, dout, Q^T, dout^T), and m, sum, D of
+// every query row as fp32
+ATTENTION_HD size_t lds_bytes_bf16_bwd(int Lq, int Lk, int d)
+{
+    const int nt = key_tiles(Lq > Lk ? Lq : Lk);
+    return 2 * (2 * (size_t)nt * ATT_TILE * (16 * dim_steps(d) + ATT16_KPAD) + 2 * (size_t)32 * col_blocks(d) * (nt * ATT_TILE + ATT16_VPAD)) +
+           3 * (size_t)nt * ATT_TILE * sizeof(float);
 }
 
 }  // namespace attention

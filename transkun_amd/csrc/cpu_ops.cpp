@@ -1597,6 +1597,95 @@ void axial_attention_bwd(const float* q, const float* k, const float* v, const f
     }
 }
 
+// semicrf_axial_attention_bf16_bwd: the backward chain of attention_bf16_math.h.  s, m, ph and sum as axial_attention_bf16 forms them;
+// P = ph / sum; dP and the three gradient sums plain fp32 additions of exact products ascending from +0; D as the two half-wave
+// chains of `sum`; dS and P rounded to bf16 before they meet k, q and dout.  P and dS of one (sequence, head) are kept [Lq][Lk] in
+// their rounded form.  st: q, k, v, dout, dq, dk, dv.
+void axial_attention_bf16_bwd(const uint16_t* q, const uint16_t* k, const uint16_t* v, const uint16_t* dout, uint16_t* dq, uint16_t* dk, uint16_t* dv,
+                              int64_t n0, int64_t n1, int Lq, int Lk, int H, int d, const int64_t* st)
+{
+    using namespace semicrf::attention;
+    const float scale = scale_of(d);
+    const int64_t nwork = n0 * n1 * H;
+#pragma omp parallel
+    {
+        std::vector<float> Ph((size_t)Lq * Lk), dSh((size_t)Lq * Lk), p((size_t)Lk), dp((size_t)Lk), acc((size_t)d), acc2((size_t)d), qf((size_t)d),
+            gf((size_t)d);
+#pragma omp for schedule(static)
+        for (int64_t w = 0; w < nwork; ++w) {
+            const int h = (int)(w % H);
+            const int64_t s = w / H, s0 = s / n1, s1 = s % n1, hd = (int64_t)h * d;
+            auto base = [&](auto* x, int t) { return x + s0 * st[3 * t] + s1 * st[3 * t + 1] + hd; };
+            const uint16_t *qb = base(q, 0), *kb = base(k, 1), *vb = base(v, 2), *gb = base(dout, 3);
+            for (int i = 0; i < Lq; ++i) {
+                const uint16_t* qi = qb + (int64_t)i * st[2];
+                const uint16_t* gi = gb + (int64_t)i * st[11];
+                for (int c = 0; c < d; ++c) { qf[c] = bf16_to_float(qi[c]); gf[c] = bf16_to_float(gi[c]); }
+                float mx = -std::numeric_limits<float>::infinity();
+                for (int j = 0; j < Lk; ++j) {
+                    const uint16_t* kj = kb + (int64_t)j * st[5];
+                    float t = 0.0f;
+                    for (int c = 0; c < d; ++c) t += bf16_to_float(kj[c]) * qf[c];
+                    p[j] = t * scale;
+                    mx = fmaxf(mx, p[j]);
+                }
+                float half[2] = {0.0f, 0.0f};
+                for (int j = 0; j < Lk; ++j) {
+                    p[j] = bf16_to_float(bf16_rne(expf(p[j] - mx)));
+                    half[sum_half(j)] += p[j];
+                }
+                const float sum = half[0] + half[1];
+                float dhalf[2] = {0.0f, 0.0f};
+                for (int j = 0; j < Lk; ++j) {
+                    const uint16_t* vj = vb + (int64_t)j * st[8];
+                    float t = 0.0f;
+                    for (int c = 0; c < d; ++c) t += bf16_to_float(vj[c]) * gf[c];
+                    dp[j] = t;
+                    p[j] = p[j] / sum;
+                    dhalf[sum_half(j)] += p[j] * t;
+                }
+                const float D = dhalf[0] + dhalf[1];
+                for (int j = 0; j < Lk; ++j) {
+                    Ph[(size_t)i * Lk + j] = bf16_to_float(bf16_rne(p[j]));
+                    dSh[(size_t)i * Lk + j] = bf16_to_float(bf16_rne(p[j] * (dp[j] - D)));
+                }
+                if (dq) {
+                    std::fill(acc.begin(), acc.end(), 0.0f);
+                    for (int j = 0; j < Lk; ++j) {
+                        const uint16_t* kj = kb + (int64_t)j * st[5];
+                        const float ds = dSh[(size_t)i * Lk + j];
+                        for (int c = 0; c < d; ++c) acc[c] += ds * bf16_to_float(kj[c]);
+                    }
+                    uint16_t* dqi = base(dq, 4) + (int64_t)i * st[14];
+                    for (int c = 0; c < d; ++c) dqi[c] = bf16_rne(acc[c] * scale);
+                }
+            }
+            if (!dk && !dv) continue;
+            for (int j = 0; j < Lk; ++j) {
+                std::fill(acc.begin(), acc.end(), 0.0f);
+                std::fill(acc2.begin(), acc2.end(), 0.0f);
+                for (int i = 0; i < Lq; ++i) {
+                    const uint16_t* qi = qb + (int64_t)i * st[2];
+                    const uint16_t* gi = gb + (int64_t)i * st[11];
+                    const float ds = dSh[(size_t)i * Lk + j], ph = Ph[(size_t)i * Lk + j];
+                    for (int c = 0; c < d; ++c) {
+                        acc[c] += ds * bf16_to_float(qi[c]);
+                        acc2[c] += ph * bf16_to_float(gi[c]);
+                    }
+                }
+                if (dk) {
+                    uint16_t* dkj = base(dk, 5) + (int64_t)j * st[17];
+                    for (int c = 0; c < d; ++c) dkj[c] = bf16_rne(acc[c] * scale);
+                }
+                if (dv) {
+                    uint16_t* dvj = base(dv, 6) + (int64_t)j * st[20];
+                    for (int c = 0; c < d; ++c) dvj[c] = bf16_rne(acc2[c]);
+                }
+            }
+        }
+    }
+}
+
 // ---- the backbone's feed-forward ResBlock (semicrf_ffn_residual) --------------------------------------------------------------------
 // The order of operations of ffn.hip per output element, in fp32 (ffn_math.h): the sum of squares as four strided chains added pairwise,
 // rs = 1 / sqrt(ss / D + eps), xn = x rs, the chain of W1 xn over k ascending from +0 (fmaf), + b1, gelu, per hidden chunk the chain of

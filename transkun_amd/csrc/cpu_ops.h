@@ -82,6 +82,10 @@ void axial_attention_bf16(const uint16_t* q, const uint16_t* k, const uint16_t* 
 // element strides q, k, v, out, dout, dq, dk, dv x (s0, s1, l)
 void axial_attention_bwd(const float* q, const float* k, const float* v, const float* out, const float* dout, float* dq, float* dk, float* dv,
                          int64_t n0, int64_t n1, int Lq, int Lk, int H, int d, const int64_t* strides);
+// the backward of the bf16 attention (semicrf_axial_attention_bf16_bwd): the backward chain of attention_bf16_math.h, fp32 accumulation
+// ascending; any of dq, dk, dv may be null; strides: the twenty-one element strides q, k, v, dout, dq, dk, dv x (s0, s1, l)
+void axial_attention_bf16_bwd(const uint16_t* q, const uint16_t* k, const uint16_t* v, const uint16_t* dout, uint16_t* dq, uint16_t* dk, uint16_t* dv,
+                              int64_t n0, int64_t n1, int Lq, int Lk, int H, int d, const int64_t* strides);
 // the backbone's feed-forward ResBlock (semicrf_ffn_residual): the device kernel's order of operations per output element, in fp32
 // (ffn_math.h); x and out [n0, n1, D] with their two element row strides; the caller has checked the supported set
 void ffn_residual(const float* x, float* out, int64_t n0, int64_t n1, int64_t xs0, int64_t xs1, int64_t os0, int64_t os1, int D, int H,

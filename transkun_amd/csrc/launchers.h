@@ -17,6 +17,11 @@ void launch_axial_attention(const float* q, const float* k, const float* v, floa
 void launch_axial_attention_bf16(const uint16_t* q, const uint16_t* k, const uint16_t* v, uint16_t* out, long long n0, long long n1, int Lq, int Lk, int H,
                                  int d, const long long* strides, hipStream_t stream);
 
+// attention_bf16_bwd.hip
+void launch_axial_attention_bf16_bwd(const uint16_t* q, const uint16_t* k, const uint16_t* v, const uint16_t* dout, uint16_t* dq, uint16_t* dk,
+                                     uint16_t* dv, long long n0, long long n1, int Lq, int Lk, int H, int d, const long long* strides,
+                                     hipStream_t stream);
+
 // attention_bwd.hip
 void launch_axial_attention_bwd(const float* q, const float* k, const float* v, const float* out, const float* dout, float* dq, float* dk, float* dv,
                                 long long n0, long long n1, int Lq, int Lk, int H, int d, const long long* strides, hipStream_t stream);

@@ -1373,6 +1373,74 @@ void axial_attention_bwd_cpu(Tensor q, Tensor k, Tensor v, Tensor out, Tensor do
     semicrf_cpu::axial_attention_bwd(a.q, a.k, a.v, a.out, a.dout, a.dq, a.dk, a.dv, a.n0, a.n1, a.Lq, a.Lk, a.H, a.d, a.st);
 }
 
+// the backward of the bf16 op (semicrf_axial_attention_bf16_bwd): the views and checks of axial_attention_bwd with bfloat16 tensors and
+// without `out` -- q, dout, dq [n0, n1, Lq, H d]; k, v, dk, dv [n0, n1, Lk, H d]
+struct AttentionBf16BwdArgs { const uint16_t *q, *k, *v, *dout; uint16_t *dq, *dk, *dv; int64_t n0, n1; int Lq, Lk, H, d; int64_t st[21]; };
+inline AttentionBf16BwdArgs attention_bf16_bwd_args(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& dout,
+                                                    const std::optional<Tensor>& dq, const std::optional<Tensor>& dk,
+                                                    const std::optional<Tensor>& dv, int64_t H)
+{
+    const Tensor* ts[7] = {&q, &k, &v, &dout, dq ? &*dq : nullptr, dk ? &*dk : nullptr, dv ? &*dv : nullptr};
+    const char* names[7] = {"q", "k", "v", "dout", "dq", "dk", "dv"};
+    const bool on_q[7] = {true, false, false, true, true, false, false};
+    AttentionBf16BwdArgs a{};
+    STD_TORCH_CHECK(q.defined() && q.dim() == 4, "semicrf: `q` must be [n0, n1, Lq, H * d]");
+    a.n0 = q.size(0); a.n1 = q.size(1);
+    const int64_t Lq = q.size(2), Lk = k.defined() && k.dim() == 4 ? k.size(2) : -1, HD = q.size(3);
+    STD_TORCH_CHECK(H >= 1 && H < (1 << 20) && HD % H == 0, "semicrf: the last dimension must be H * d");
+    const void* ptrs[7] = {};
+    for (int i = 0; i < 7; ++i) {
+        if (!ts[i]) continue;
+        const Tensor& t = *ts[i];
+        STD_TORCH_CHECK(t.defined() && t.scalar_type() == ScalarType::BFloat16 && t.dim() == 4, "semicrf: `", names[i],
+                        "` must be a 4-d bfloat16 tensor");
+        STD_TORCH_CHECK(t.size(0) == a.n0 && t.size(1) == a.n1 && t.size(3) == HD && t.size(2) == (on_q[i] ? Lq : Lk),
+                        "semicrf: `", names[i], "` does not have the shape of the call");
+        STD_TORCH_CHECK(HD == 1 || t.stride(3) == 1, "semicrf: `", names[i], "` must have a contiguous last dimension");
+        for (int j = 0; j < 3; ++j) {
+            const int64_t s = t.size(j) > 1 ? t.stride(j) : 0;
+            STD_TORCH_CHECK(s >= 0, "semicrf: negative stride");
+            STD_TORCH_CHECK(i < 3 || t.size(j) == 1 || s > 0, "semicrf: `", names[i], "` must not repeat over a dimension");
+            a.st[3 * i + j] = s;
+        }
+        ptrs[i] = t.numel() > 0 ? t.data_ptr() : nullptr;
+    }
+    STD_TORCH_CHECK(Lq < (1 << 20) && Lk < (1 << 20), "semicrf: sequence too long");
+    a.Lq = (int)Lq; a.Lk = (int)Lk; a.H = (int)H; a.d = (int)(HD / H);
+    STD_TORCH_CHECK(semicrf_axial_attention_bf16_bwd_supported(a.Lq, a.Lk, a.H, a.d),
+                    "semicrf: axial_attention_bf16_bwd does not support Lq=", Lq, " Lk=", Lk, " H=", H, " d=", HD / H,
+                    " (semicrf_axial_attention_bf16_bwd_supported)");
+    a.q = (const uint16_t*)ptrs[0]; a.k = (const uint16_t*)ptrs[1]; a.v = (const uint16_t*)ptrs[2]; a.dout = (const uint16_t*)ptrs[3];
+    a.dq = (uint16_t*)ptrs[4]; a.dk = (uint16_t*)ptrs[5]; a.dv = (uint16_t*)ptrs[6];
+    return a;
+}
+void axial_attention_bf16_bwd_op(Tensor q, Tensor k, Tensor v, Tensor dout, std::optional<Tensor> dq, std::optional<Tensor> dk,
+                                 std::optional<Tensor> dv, int64_t H)
+{
+    Ctx c(q); c.same(q, k, v, dout);
+    if (dq) c.same(q, *dq);
+    if (dk) c.same(q, *dk);
+    if (dv) c.same(q, *dv);
+    const AttentionBf16BwdArgs a = attention_bf16_bwd_args(q, k, v, dout, dq, dk, dv, H);
+    if (a.n0 == 0 || a.n1 == 0) return;
+    const int64_t* s = a.st;
+    check(semicrf_axial_attention_bf16_bwd(a.q, a.k, a.v, a.dout, a.dq, a.dk, a.dv, a.n0, a.n1, a.Lq, a.Lk, a.H, a.d, s[0], s[1], s[2], s[3], s[4],
+                                           s[5], s[6], s[7], s[8], s[9], s[10], s[11], s[12], s[13], s[14], s[15], s[16], s[17], s[18], s[19],
+                                           s[20], c.stream),
+          "semicrf_axial_attention_bf16_bwd");
+}
+void axial_attention_bf16_bwd_cpu(Tensor q, Tensor k, Tensor v, Tensor dout, std::optional<Tensor> dq, std::optional<Tensor> dk,
+                                  std::optional<Tensor> dv, int64_t H)
+{
+    all_cpu(q, k, v, dout);
+    if (dq) all_cpu(*dq);
+    if (dk) all_cpu(*dk);
+    if (dv) all_cpu(*dv);
+    const AttentionBf16BwdArgs a = attention_bf16_bwd_args(q, k, v, dout, dq, dk, dv, H);
+    if (a.n0 == 0 || a.n1 == 0) return;
+    semicrf_cpu::axial_attention_bf16_bwd(a.q, a.k, a.v, a.dout, a.dq, a.dk, a.dv, a.n0, a.n1, a.Lq, a.Lk, a.H, a.d, a.st);
+}
+
 // ---- the attribute heads in training (semicrf_attribute_heads_train_fwd / _bwd / _dropout_mask) -------------------------------------
 // seed: the 64 bits of an int; z [K, Hv + Ho] and the gradients are dense and checked for their element counts
 void attribute_heads_train_fwd_op(Tensor ctx, int64_t C, int64_t T, int64_t D, int64_t ldc, Tensor pairs, int64_t K, Tensor offsets, int64_t nSym,
@@ -1580,6 +1648,7 @@ STABLE_TORCH_LIBRARY(semicrf, m)
     m.def("axial_attention(Tensor q, Tensor k, Tensor v, Tensor(a!) out, int H) -> ()");
     m.def("axial_attention_bf16(Tensor q, Tensor k, Tensor v, Tensor(a!) out, int H) -> ()");
     m.def("axial_attention_bwd(Tensor q, Tensor k, Tensor v, Tensor out, Tensor dout, Tensor(a!)? dq, Tensor(b!)? dk, Tensor(c!)? dv, int H) -> ()");
+    m.def("axial_attention_bf16_bwd(Tensor q, Tensor k, Tensor v, Tensor dout, Tensor(a!)? dq, Tensor(b!)? dk, Tensor(c!)? dv, int H) -> ()");
     m.def("ffn_residual(Tensor x, Tensor W1, Tensor b1, Tensor W2, Tensor b2, Tensor scale, float eps, Tensor(a!) out) -> ()");
     m.def("log_mel(Tensor frames, Tensor windows, Tensor tw, Tensor fb_start, Tensor fb_len, Tensor fb_off, Tensor fb_val, int max_len, "
           "Tensor shift, Tensor denom, bool has_gain, bool log_flag, float eps, bool to_mono, Tensor(a!) out) -> ()");
@@ -1625,6 +1694,7 @@ STABLE_TORCH_LIBRARY_IMPL(semicrf, CPU, m)
     m.impl("axial_attention", TORCH_BOX(&axial_attention_cpu));
     m.impl("axial_attention_bf16", TORCH_BOX(&axial_attention_bf16_cpu));
     m.impl("axial_attention_bwd", TORCH_BOX(&axial_attention_bwd_cpu));
+    m.impl("axial_attention_bf16_bwd", TORCH_BOX(&axial_attention_bf16_bwd_cpu));
     m.impl("ffn_residual", TORCH_BOX(&ffn_residual_cpu));
     m.impl("log_mel", TORCH_BOX(&log_mel_cpu));
     m.impl("grad_sqnorm", TORCH_BOX(&grad_sqnorm_cpu));
@@ -1676,6 +1746,7 @@ STABLE_TORCH_LIBRARY_IMPL(semicrf, CUDA, m)
     m.impl("axial_attention", TORCH_BOX(&axial_attention_op));
     m.impl("axial_attention_bf16", TORCH_BOX(&axial_attention_bf16_op));
     m.impl("axial_attention_bwd", TORCH_BOX(&axial_attention_bwd_op));
+    m.impl("axial_attention_bf16_bwd", TORCH_BOX(&axial_attention_bf16_bwd_op));
     m.impl("ffn_residual", TORCH_BOX(&ffn_residual_op));
     m.impl("log_mel", TORCH_BOX(&log_mel_op));
     m.impl("grad_sqnorm", TORCH_BOX(&grad_sqnorm_op));
