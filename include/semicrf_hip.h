@@ -43,6 +43,69 @@
  *     Everything else of an output is written by every call: logZ [B], v / beta / q_out [T][B], dScore / C [T][T][B] (zeros
  *     included, without the flag), dNoise / Cn / noiseP [T-1][B], offsets (all B+1, nSample*B+1, k*B+1 entries), scores [k][B],
  *     npaths [B], node / begin / end / single [T][B], entropy / E / H / out / logProb [B].
+ *
+ * Memory contract of the scorer entry points (interval_score_*, scorer_*; tests/test_scorer_contract.py pins every sentence, S1 .. S12;
+ * the test behind each is named in brackets).  Throughout: nothing outside the elements named as written is written, nothing outside the
+ * elements named as read reaches a result, an output passed as NULL is not touched, SEMICRF_EINVAL / SEMICRF_EWORKSPACE write nothing;
+ * a leading dimension's pad columns (D .. ld-1 of q / k / dq / dk, N .. of the GEMMs' operands and outputs) are neither read nor written.
+ *   S1  interval_score_fwd[_p|_pc] READS the D used columns of the C * T rows of q and k, diag[c][t] at stride ldd and rowc[c][t] at
+ *       stride ldrc -- no row past T (the tile kernels round T up to 64 or 128 rows and CLAMP the rows they ask for to T - 1), no chain
+ *       past C.  diag, rowc, ldd, ldrc and noise_out take any 4-byte alignment.  [test_forward]
+ *   S2  It WRITES S[e][b][slot] for e >= b (full_square 2: the cells e < b keep their bits), the exact +0.0f above the diagonal on top
+ *       (full_square 0), or the full square (1); every slot of a written cell is written, the ghost slots of a padded pitch with
+ *       +0.0f; noise_out [T-1][Cs] is zero-filled when non-NULL (T == 1: it has no elements).  [test_forward]
+ *   S3  Alignment is a matter of the ROUTE, never of correctness (semicrf_debug_score_route states it): with q, k and S 16-byte aligned,
+ *       ldq % 4 == 0, ldk % 4 == 0 and T * ld * 4 < 2^31 the LDS-staged kernels run (16-byte loads of the rows, 16-byte stores of S's
+ *       chain axis); anything else -- rows of a packed [C][T][2D+1] tensor, an S off 16 bytes -- runs the register-load kernel
+ *       (D % 64 == 0: dword loads and stores) or the plain kernel: the same scores to the bound below, not bit for bit (the streaming
+ *       kernel sums two accumulators, the register-load kernel one).  A padded pitch or a row constant exists in the
+ *       tiled kernels only: D % 64 == 0, T >= 128 and that alignment, else SEMICRF_EINVAL; so are a pitch that is no multiple of 4 and
+ *       ldq / ldk < D.  [test_forward_route_table, test_forward_refused, test_forward_S_off_16_bytes_takes_the_register_load_kernel]
+ *   S4  interval_score_bwd_ws and _ws_p are _ws_pc with drowc == NULL (and group == pitch == C): the same bits; interval_score_bwd is
+ *       the direct kernels.  [test_backward_entry_point_forms]
+ *   S5  The backward READS dS[e][b][slot] for e >= b in the slots of real chains only -- the cells e < b and the ghost slots of a
+ *       padded pitch may hold anything (the CRF's gradient there is not zero) -- and the D used columns of q and k.  dS takes any 4-byte
+ *       alignment (16-byte loads where C % 4 == 0 and it is 16-byte aligned).  [test_backward_direct_kernels,
+ *       test_backward_packed_gemms, test_backward_slot_layout]
+ *   S6  It WRITES (never adds to) the D used columns of dq[c][t] and dk[c][t], ddiag[c][t] at stride lddd (bit-equal to dS[t][t][c])
+ *       and drowc[c][t] at stride lddrc; each output only when its pointer is non-NULL, and with the bits of the call that asks for
+ *       all of them.  Outputs take any 4-byte alignment and any leading dimension >= D.  [test_backward_output_subsets]
+ *   S7  The packed path runs when D is 64, 128 or 256, T >= 64, q and k are 16-byte aligned with ldq % 4 == 0 and ldk % 4 == 0, ws is
+ *       non-NULL, 16-byte aligned and holds interval_score_bwd_workspace_bytes(C, T, D) bytes, dq or dk is wanted, and drowc is not
+ *       wanted without dq (its row sums come out of the dq product).  Otherwise the call runs exactly interval_score_bwd (+ a row-sum
+ *       kernel for drowc): the same bits as that entry point; with a padded pitch, which only the packed path knows,
+ *       SEMICRF_EINVAL.  [test_backward_falls_back_to_the_direct_kernels, test_backward_slot_layout]
+ *   S8  ws of the backward: exactly interval_score_bwd_workspace_bytes(C, T, D) bytes (the 4096 bytes of slack for the transposed walk
+ *       of the last tile are part of that figure), 16-byte aligned; nothing past ws + ws_bytes is read or written and what it held
+ *       before the call does not matter.  [test_backward_workspace_contents_do_not_matter, test_backward_packed_gemms]
+ *   S9  interval_score_bwd_fused[_ws[_p|_pc]] read S for e >= b (real slots), alpha and beta [T][Cs], logZ and gout [Cs] instead of dS;
+ *       any 4-byte alignment (16-byte loads where Cs % 4 == 0 and S, alpha and beta are 16-byte aligned); outputs, workspace and
+ *       fallback as S6 - S8.  [test_backward_fused]
+ *   S10 interval_score_path_bwd[_p|_pc] ADDS (4-byte atomics): w k[c][b][:] to dq[c][e][:D], w q[c][e][:] to dk[c][b][:D], w to
+ *       drowc[c][e], gout to ddiag[c][e] when b == e, for every interval; every other row and entry keeps its bits; K == 0 launches
+ *       nothing.  It reads gout [Cs], offsets [Cs + 1], pairs [K][2] and the rows of q and k that paths name.  [test_path_backward]
+ *   S11 scorer_proj_nn / _nn3 READ the K used columns of A's M rows (rows past M and contraction values past K are clamped back into
+ *       the matrix), B's Kpad = ceil(K / 32) * 32 rows of N columns -- the caller keeps the rows K .. Kpad-1 ZERO in memory --, bias [N]
+ *       (NOT with accumulate: an accumulating call adds the product alone), w2 [2][K], b2 [2]; they WRITE out[m][0 .. N-1] (accumulate:
+ *       add to it) and with w2 the two extra columns and zero_cols exact zeros behind them (written, not added).  A, B: 16-byte aligned,
+ *       lda % 4 == 0, ldb % 4 == 0, M * lda * 4 < 2^31; N in {64, 128, 256}, K % 4 == 0, ldout >= N (+ 2 + zero_cols): enforced,
+ *       SEMICRF_EINVAL before anything is launched.  out, bias, w2, b2, ldout: any 4-byte alignment.  scorer_proj_nn3's ws: exactly
+ *       scorer_proj_nn3_workspace_bytes(K, N) bytes, 16-byte aligned, earlier contents do not matter; without it (NULL, short, off 16
+ *       bytes, N != 256) the call is scorer_proj_nn, bit for bit.  scorer_proj_tn READS the R main columns of dy's M rows, the columns
+ *       extra_col0 and extra_col0 + 1 (>= R; or -1) and the N used columns of x; it WRITES dW[r][0 .. N-1] and db[r] for r <
+ *       total_rows, exact zeros from R + 2 (R without extra columns) on.  dy, x: 16-byte aligned with lddy % 4 == 0, ldx % 4 == 0
+ *       (enforced); dW, db, lddw: any 4-byte alignment.  Its ws: exactly scorer_proj_tn_workspace_bytes(M, R, N) bytes, 16-byte aligned,
+ *       earlier contents do not matter; NULL, short or misaligned: SEMICRF_EWORKSPACE.  With SEMICRF_PROJ_TN_BF16X3 the two extra rows
+ *       and db are the exact call's bits.  [test_proj_nn_every_width, test_proj_nn_every_row_count, test_proj_nn3, test_proj_tn,
+ *       test_projection_rejections_host, test_projection_rejections_device]
+ *   S12 scorer_stage_linear, scorer_merge_weights_fwd / _bwd: contiguous operands and outputs at any 4-byte alignment.  They write every
+ *       element of BT [size][2 D], Wqd [rows_pad][size], w2 [2][size], b2 [2]; of Wm [rows][size], bm [rows] and (when non-NULL) WmT
+ *       [size][size]; of dW [2 D + 1][size] and dbias [2 D + 1] -- the rows behind the diagonal row exact zeros; _bwd reads the first
+ *       size + 2 rows of dWm / entries of dbm.  _bwd's ws: exactly scorer_merge_weights_bwd_workspace_bytes(size) bytes, 4-byte
+ *       aligned, earlier contents do not matter; NULL or short: SEMICRF_EWORKSPACE.  [test_stage_linear, test_merge_weights]
+ *   Accuracy, per element against float64 (u = 2^-24; derivations: tests/scorer_contract_common.py): forward (D + 8) u (qscale len
+ *   (sum_d |q k| + |rowc|) + |diag|); dq / dk (n + 8) u sum |G k| over the n terms of the row; scorer_proj_nn (K + 4) u (sum_k |a b| +
+ *   |bias|); scorer_proj_tn (M + 8) u sum_m |dy x|; the three-limb forms add 2^-21 of the same sum.
  */
 #ifndef SEMICRF_HIP_H
 #define SEMICRF_HIP_H
@@ -161,12 +224,13 @@ int semicrf_debug_wg_ticket(int n_spine, int grid, int block);
 /* Test hook, process-wide: force one of interval_score_fwd's kernels where it applies (0 = register loads, 32 = streaming,
  * 2 = the 64 x 128 tiles with the epilogue inside the contraction loop; 64 / 128 = the earlier shared-operand tiles, compiled into
  * the DEBUG library only -- libsemicrf_hip_debug.so, the same ABI built with -DSEMICRF_DEBUG_BUILD=1, which the parity tests load
- * through ctypes as the bit-level reference; the release library ignores 64 / 128 -- all give bit-identical scores); -1 =
+ * through ctypes as the bit-level reference of 2; the release library ignores 64 / 128.  The kernels agree to fp32 rounding, not all bit
+ * for bit: the register-load kernel sums one accumulator, the streaming kernel two -- tests/test_scorer_contract.py); -1 =
  * automatic choice (the default).  The release library reads no environment variables. */
 void semicrf_debug_score_variant(int variant);
 
 /* Host-side view of interval_score_fwd's kernel choice (test hook, no device work, nothing is read from the process's state): the
- * kernel that a call with C chains, T frames, contraction size D, row strides ldq / ldk, 16-byte aligned q and k (aligned != 0),
+ * kernel that a call with C chains, T frames, contraction size D, row strides ldq / ldk, 16-byte aligned q, k and S (aligned != 0),
  * precision prec (1 = SEMICRF_SCORE_BF16X3), the slot layout group / pitch, a row constant (rowc != 0), the forced variant
  * (semicrf_debug_score_variant's argument) and the implementation impl (semicrf_set_impl's) would run.  The answer is in
  * semicrf_debug_score_variant's numbering, extended: 0 register loads, 1 the plain kernel, 2 the 64 x 128 tiles, 3 the three-limb

@@ -715,8 +715,9 @@ int interval_score_fwd_pc(const float* q, const float* k, const float* diag, con
     const int Cs = (C / group) * pitch;
     const int prec = (full_square & SEMICRF_SCORE_BF16X3) ? 1 : 0;   // opt-in: three-limb bf16 contraction (scorer_fwd_tile3.h)
     full_square &= 3;
-    const ScoreRoute route = plan_score_route(C, T, D, ldq, ldk, (((uintptr_t)q | (uintptr_t)k) & 15) == 0, prec, group, pitch, rowc != nullptr,
-                                              score_variant(), g_impl.load());
+    // (S too: the LDS-staged kernels write 16-byte pieces of the chain axis; the register-load and plain kernels store dword by dword)
+    const ScoreRoute route = plan_score_route(C, T, D, ldq, ldk, (((uintptr_t)q | (uintptr_t)k | (uintptr_t)S) & 15) == 0, prec, group, pitch,
+                                              rowc != nullptr, score_variant(), g_impl.load());
     SEMICRF_CHECK_ARG(route.kernel != SCORE_REFUSED, "%s", route.why);
     hipStream_t st = (hipStream_t)stream;
     if (full_square == 0) launch_zero_upper(S, T, Cs, st);     // begin > end: defined (zero), half the bytes of a full fill

@@ -68,7 +68,8 @@ __global__ __launch_bounds__(64 * BC) void interval_score_bwd_kernel(
     auto tile_of = [&](int s) { return ROWS_E ? s : rt + s; };
 
     // stage the (e-tile, b-tile) block of dS for 8 chains: 1024 cells x 32 bytes, two float4 per cell
-    const bool vec = (C % 4 == 0) && (((uintptr_t)dS & 15) == 0);      // uniform: 16-byte loads are aligned
+    const bool vec = (C % 4 == 0) && (((uintptr_t)dS & 15) == 0) &&
+                     (!FUSED || ((((uintptr_t)F.alpha | (uintptr_t)F.beta) & 15) == 0));      // uniform: 16-byte loads are aligned
     auto stage = [&](int buf, int ct) __attribute__((always_inline)) {
         const int e0 = (ROWS_E ? rt : ct) * BT, b0 = (ROWS_E ? ct : rt) * BT;
         constexpr int NS = (BT * BT * 2) / (64 * BC);

@@ -34,7 +34,7 @@ int score_variant() { return g_score_variant.load(std::memory_order_relaxed); }
 
 // Which forward kernel runs.  group / pitch: the slot layout of S's chain axis (SlotGeom; group == pitch == C is the contiguous
 // layout), rowc: a row constant is present (the merged projection) -- both live in the tile kernels only ("slots" below).
-// bases_aligned: q and k are 16-byte aligned.  forced: the test hook's variant, impl: semicrf_set_impl's.
+// bases_aligned: q, k and S are 16-byte aligned (the LDS-staged kernels load q / k rows and store S's chain axis in 16-byte pieces).  forced: the test hook's variant, impl: semicrf_set_impl's.
 ScoreRoute plan_score_route(int C, int T, int D, long long ldq, long long ldk, bool bases_aligned, int prec, int group, int pitch,
                             bool rowc, int forced, int impl)
 {
