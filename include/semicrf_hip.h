@@ -44,6 +44,32 @@
  *     included, without the flag), dNoise / Cn / noiseP [T-1][B], offsets (all B+1, nSample*B+1, k*B+1 entries), scores [k][B],
  *     npaths [B], node / begin / end / single [T][B], entropy / E / H / out / logProb [B].
  *
+ *   Accuracy of the sweeps, per element (tests/test_sweep_accuracy.py asserts every sentence against float64 of the same fp32 inputs;
+ *   tests/sweep_accuracy_common.py counts the constants operation by operation).  u = 2^-24, natural-log units.  For chain c let A_c
+ *   be the largest magnitude among its alpha, beta, logZ, the scores end >= begin and the noise, and P_c its largest
+ *   softplus(score[t][t]).  An element of v / alpha, beta / q_out or logZ with n recurrence steps behind it (alpha[t]: t + 1,
+ *   beta[t]: T - t, logZ: T) is within
+ *       L(n) = u ((a n + b) A_c + s n P_c + c0 n + c1 n^2 / 2)
+ *   of the float64 value: a, b count a step's (an output's) roundings at the size of alpha, s those inside softplus, c0 those at
+ *   magnitude one (exp2 / log2 at 1 ulp, the linear-domain sums), c1 the serial part of a row's sum.
+ *       persistent sweep (implementation 0, T >= 2, NBatch >= 2, T <= 2048): a = 6.25, b = 1.1, s = 3.25, c1 = 0, c0 = 257 for
+ *                                  the steps at positions below 64 (no far field) and 655 for the others (c0 n is their sum)
+ *       row-sequential kernels and the host kernels:                         a = 3,    b = 0,   s = 4,    c0 = 114, c1 = 0.275
+ *   A marginal -- dScore[e][b], e >= b, off the target path; out[i] of semicrf_interval_marginals -- has the sign of its float64
+ *   value gout gscale m and |ln|got| - ln|value|| <= L_alpha(b + 1) + L_beta(T - e) + L_logZ(T) + E, with E = u (11 A_c + 6.5 P_c +
+ *   |ln m| + 256) in the persistent sweep and u (5 A_c + 8 P_c + 3 |ln m| + 8) elsewhere (semicrf_interval_marginals: the latter,
+ *   on top of the L of whatever produced its v, q, logZ).  A path cell of semicrf_logprob_bwd holds gout (1 - m) to within
+ *   |gout| (m (e^bound - 1) + 2u); dNoise[t] is ONE term, the marginal of the skip over gap t, to within |g| (m (e^bound - 1) + 3u)
+ *   with the bound of alpha[t], beta[t + 1], logZ and E.  Cells begin > end are +0.0f.  Below 2^-100 |gout gscale| a value is only
+ *   finite, of the right sign or zero, and below 2^-99 |gout gscale| (fp32 exp2 returns 0 near 2^-126).  One exception: the
+ *   persistent gradient sweep forms a far-field marginal (row block k >= 4 of the descending sweep, column tile m <= k - 4) as
+ *   (gz 2^(M + arow)) 2^(t - M) around the reference M of its accumulator, which an earlier cell of the same row, chain and column
+ *   part (12 tiles) set to 96 above its own term, and v_exp_f32 returns 0 below -126.  Such a cell may be exactly 0 if one of those
+ *   earlier cells has a marginal below 2^-220 (the common factor is then 0), or if its own marginal is below 2^-28 of the largest
+ *   of them (its own factor is).  Where it is not 0 it is within the bound.  No cell of the `balanced` test inputs qualifies at
+ *   any length; on an MI355X the rule was needed for marginals between 2^-100 and 2^-75 of the `model` inputs only.  These are
+ *   worst-case bounds: measured errors are 4 to 5000 times smaller ("Accuracy of the sweeps, per element").
+ *
  * Memory contract of the scorer entry points (interval_score_*, scorer_*; tests/test_scorer_contract.py pins every sentence, S1 .. S12;
  * the test behind each is named in brackets).  Throughout: nothing outside the elements named as written is written, nothing outside the
  * elements named as read reaches a result, an output passed as NULL is not touched, SEMICRF_EINVAL / SEMICRF_EWORKSPACE write nothing;

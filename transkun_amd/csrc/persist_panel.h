@@ -414,7 +414,12 @@ __device__ __forceinline__ void panel_role(const SweepParams& P, char* lds, int 
                     // and the ring's block period in the head of the sweep IS that task's time per tile.  M + arow <= ~97: M sits
                     // RESC_LIFT above the largest term when it is set and 2^(term + arow) is a marginal; a cell whose term
                     // lies 2^-30 below that one underflows -- as it does in the sum -- where the reference holds a marginal below
-                    // 1e-9.)  The beta values are bit-identical to the plain beta sweep's.
+                    // 1e-9.  The factor underflows too: M + arow is 96 above log2 of the marginal of the cell that set M, and M
+                    // stays where it is until a term of the wave passes M + RESC_HI.  After a cell with a marginal below 2^-221
+                    // v_exp_f32 returns 0 for the factor, and every later cell of that row and chain is stored as 0 until the next
+                    // lift, marginals up to 2^-18 among them; measured, it took ones below 2^-75 (tests/test_sweep_accuracy.py,
+                    // DESIGN.md "Accuracy of the sweeps, per element").)  The beta values are bit-identical to the plain beta
+                    // sweep's.
                     typedef float v2f __attribute__((ext_vector_type(2)));
                     const v2f l2e = {LOG2E, LOG2E};
                     const v2f u2[2][2] = {{{uv[0][0], uv[0][1]}, {uv[0][2], uv[0][3]}}, {{uv[1][0], uv[1][1]}, {uv[1][2], uv[1][3]}}};
