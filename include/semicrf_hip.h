@@ -1291,6 +1291,39 @@ int semicrf_ffn_residual(const float* x, float* out, int64_t n0, int64_t n1, int
                          const float* scale, float eps, semicrf_stream_t stream);
 
 /*
+ * The same block with both products on the bf16 matrix instruction (v_mfma_f32_32x32x16_bf16), eval mode, forward only, one launch, no
+ * workspace, no atomics: what a bf16 backbone, or an fp32 one under bf16 autocast, runs in place of about ten stock launches.  Two
+ * entry points share one kernel body (csrc/ffn_bf16.hip) and one chain of operations (csrc/ffn_bf16_math.h):
+ *   semicrf_ffn_residual_bf16        x, out, W1, b1, W2, b2 and scale are bfloat16 in memory (raw 16-bit patterns)
+ *   semicrf_ffn_residual_bf16_mixed  all seven are fp32 in memory, as the module holds them.  W1 and W2 are rounded to bf16 (nearest
+ *                                    even) while they are staged, on every call: no bf16 copy of the weights exists that could go
+ *                                    stale.  b1, b2 and scale are used AS FP32 -- unlike autocast's nn.Linear, which rounds its
+ *                                    bias (and its output) to bf16 too -- and `out` is not rounded.
+ * Chain: x to fp32; the sum of squares and rs exactly as semicrf_ffn_residual; x rs rounded to bf16; h = W1 xh with exact products
+ * and fp32 accumulation, + b1; gelu in fp32 (exact erf form), rounded to bf16; acc = W2 gh on ONE running fp32 accumulator over all
+ * of hidden; out = x + (acc + b2) * scale in fp32, rounded ONCE to the output type.  The device sums 16 products inside a matrix
+ * instruction and the host mirror one by one: they agree wherever every partial sum is exact, and to rounding elsewhere.
+ * Views, strides, the supported set, padding and determinism are semicrf_ffn_residual's: [n0, n1, D] views with two ELEMENT row
+ * strides each; D a multiple of 8 in [8, SEMICRF_FFN_MAX_D], hidden a multiple of 8 in [8, SEMICRF_FFN_MAX_HIDDEN], 1 <= n0, n1,
+ * n0 n1 < 2^37; a workgroup owns SEMICRF_FFN_BF16_ROW_TILE rows and walks hidden in chunks of SEMICRF_FFN_BF16_HIDDEN_CHUNK columns;
+ * rows past the last token, columns past D and past hidden are zeros formed in registers, never read as data and never stored; a
+ * token's result is bit-identical whatever the other tokens, n0, n1, the strides and the alignment are.  Pointers need the alignment
+ * of an element (2 bytes, 4 bytes for _mixed); 16-byte loads when x, W1 and W2 are 16-byte aligned and x's strides multiples of 16
+ * bytes, element loads otherwise (the same bits).  One launch on `stream`; no synchronisation, no allocation.
+ * SEMICRF_EINVAL, with nothing launched and `out` untouched: the cases of semicrf_ffn_residual.
+ */
+#define SEMICRF_FFN_BF16_ROW_TILE 64
+#define SEMICRF_FFN_BF16_HIDDEN_CHUNK 64
+int semicrf_ffn_residual_bf16_supported(int D, int hidden);
+int semicrf_ffn_residual_bf16_mixed_supported(int D, int hidden);
+int semicrf_ffn_residual_bf16(const uint16_t* x, uint16_t* out, int64_t n0, int64_t n1, int64_t x_stride_0, int64_t x_stride_1, int64_t out_stride_0,
+                              int64_t out_stride_1, int D, int hidden, const uint16_t* W1, const uint16_t* b1, const uint16_t* W2,
+                              const uint16_t* b2, const uint16_t* scale, float eps, semicrf_stream_t stream);
+int semicrf_ffn_residual_bf16_mixed(const float* x, float* out, int64_t n0, int64_t n1, int64_t x_stride_0, int64_t x_stride_1, int64_t out_stride_0,
+                                    int64_t out_stride_1, int D, int hidden, const float* W1, const float* b1, const float* W2, const float* b2,
+                                    const float* scale, float eps, semicrf_stream_t stream);
+
+/*
  * The audio front end (Util.py:78-170 behind the gain of ModelTransformer.py:159-164) as one launch.  Replaces: the gain normalisation,
  * the product of the frames with the analysis windows, the orthonormal real transform, |.|^2, the channel mean, the matrix product with
  * the mel filterbank and the log compression -- a dozen launches and two round trips of a [N, C, nFrame, nWin, W] tensor.  For every

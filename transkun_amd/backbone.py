@@ -48,6 +48,15 @@ hidden state as it lies in memory -- the [tokens, hidden] activation is never wr
 autograd, with an active dropout, for dtypes other than float32, for shapes outside the op's supported set, for any other module and
 for extra arguments the block runs the stock expression.  `FEED_FORWARD_ROUTES` counts which way the calls went.
 
+bfloat16 has a knob of its own beside it, as the attention has: `feedForwardBf16 = "torch" | "fused"` on `ResBlock`, `BasicBlock` and
+`Backbone` (default "torch": everything above, unchanged).  It takes effect only where `feedForward = "fused"` and the conditions above
+hold.  Then a block whose input and five parameters are all bfloat16 is `torch.ops.semicrf.ffn_residual_bf16` (csrc/ffn_bf16.hip: both
+products on the bf16 matrix instruction), and a float32 block called under `torch.autocast(dtype=torch.bfloat16)` is
+`torch.ops.semicrf.ffn_residual_bf16_mixed`: the same kernel on the float32 tensors as the module holds them, the weights rounded to
+bf16 inside the launch, the biases and the LayerScale used as float32, a float32 result.  A float32 call outside autocast stays the
+float32 op; any other mix of dtypes, and autocast to any other dtype, takes the stock expression.  `FEED_FORWARD_BF16_ROUTES` counts the
+calls made with the knob at "fused" that were bfloat16 or under bfloat16 autocast; a fused answer counts in `FEED_FORWARD_ROUTES` too.
+
 Hidden size and head dimension come from the constructor as in the reference: head_dim = ceil(ceil(hiddenFactor * embed_dim) /
 num_heads), hidden size = head_dim * num_heads (the model: embed_dim 160, 4 heads, hiddenFactorAttn 1 -> d = 40).
 """
@@ -324,11 +333,24 @@ DEFAULT_FEED_FORWARD = "torch"
 FEED_FORWARD_ROUTES = {"fused": 0, "torch": 0}
 FEED_FORWARD_ROW_TILE = _lib.FFN_ROW_TILE                       # token rows per workgroup of the op
 FEED_FORWARD_HIDDEN_CHUNK = _lib.FFN_HIDDEN_CHUNK               # hidden columns per step of its walk
+FEED_FORWARD_BF16_KINDS = ("torch", "fused")
+DEFAULT_FEED_FORWARD_BF16 = "torch"
+# calls made with bf16 = "fused" on bfloat16 tensors or under bfloat16 autocast, by the way they went; tests read it
+FEED_FORWARD_BF16_ROUTES = {"fused": 0, "torch": 0}
+FEED_FORWARD_BF16_ROW_TILE = _lib.FFN_BF16_ROW_TILE             # token rows per workgroup of the bf16 op
+FEED_FORWARD_BF16_HIDDEN_CHUNK = _lib.FFN_BF16_HIDDEN_CHUNK     # hidden columns per step of its walk
 
 
 def feed_forward_supported(D: int, hidden: int) -> bool:
     """semicrf_ffn_residual_supported: D a multiple of 8 in [8, 256], hidden a multiple of 8 in [8, 4096]."""
     return bool(_lib.load().semicrf_ffn_residual_supported(int(D), int(hidden)))
+
+
+def feed_forward_bf16_supported(D: int, hidden: int) -> bool:
+    """semicrf_ffn_residual_bf16_supported (both forms): the set of feed_forward_supported."""
+    lib = _lib.load()
+    return bool(lib.semicrf_ffn_residual_bf16_supported(int(D), int(hidden))
+                and lib.semicrf_ffn_residual_bf16_mixed_supported(int(D), int(hidden)))
 
 
 def feed_forward_torch(x, w1, b1, w2, b2, scale, eps=1e-6):
@@ -354,9 +376,9 @@ def _as_rows(t: torch.Tensor, order):
     return torch.as_strided(t, (n0, n1, t.shape[-1]), (s0, s1, 1), t.storage_offset())
 
 
-def _ffn_applies(x, w1, b1, w2, b2, scale) -> bool:
+def _ffn_applies(x, w1, b1, w2, b2, scale, dtype=torch.float32) -> bool:
     ts = (x, w1, b1, w2, b2, scale)
-    if any(t.dtype != torch.float32 for t in ts) or any(t.device != x.device for t in ts):
+    if any(t.dtype != dtype for t in ts) or any(t.device != x.device for t in ts):
         return False
     if x.device.type not in ("cuda", "cpu") or x.dim() < 1 or x.numel() == 0 or w1.dim() != 2 or w2.dim() != 2:
         return False
@@ -365,10 +387,38 @@ def _ffn_applies(x, w1, b1, w2, b2, scale) -> bool:
         return False
     if torch.is_grad_enabled() and any(t.requires_grad for t in ts):
         return False                                            # forward only
-    return feed_forward_supported(D, hidden)
+    return feed_forward_supported(D, hidden) if dtype == torch.float32 else feed_forward_bf16_supported(D, hidden)
 
 
-def _ffn_fused(x, w1, b1, w2, b2, scale, eps):
+def _ffn_pick(ts, bf16):
+    """(op, is16): the torch op that answers the call -- "ffn_residual", "ffn_residual_bf16" (form A), "ffn_residual_bf16_mixed"
+    (form B) or None for the stock expression -- and whether FEED_FORWARD_BF16_ROUTES counts it (the knob at "fused", and x
+    bfloat16 or bfloat16 autocast on for x's device type)."""
+    if bf16 != "fused":
+        return ("ffn_residual" if _ffn_applies(*ts) else None), False
+    x = ts[0]
+    kind = x.device.type
+    ac = torch.get_autocast_dtype(kind) if kind in ("cuda", "cpu") and torch.is_autocast_enabled(kind) else None
+    is16 = x.dtype == torch.bfloat16 or ac == torch.bfloat16
+    op = None
+    if x.dtype == torch.bfloat16:
+        if ac in (None, torch.bfloat16) and _ffn_applies(*ts, dtype=torch.bfloat16):
+            op = "ffn_residual_bf16"
+    elif ac is None:
+        if _ffn_applies(*ts):
+            op = "ffn_residual"
+    elif ac == torch.bfloat16 and _ffn_applies(*ts):
+        op = "ffn_residual_bf16_mixed"
+    return op, is16
+
+
+def _ffn_count(op, is16):
+    FEED_FORWARD_ROUTES["torch" if op is None else "fused"] += 1
+    if is16:
+        FEED_FORWARD_BF16_ROUTES["torch" if op is None else "fused"] += 1
+
+
+def _ffn_fused(x, w1, b1, w2, b2, scale, eps, op="ffn_residual"):
     if x.shape[-1] != 1 and x.stride(-1) != 1:
         x = x.contiguous()
     order = sorted(range(x.dim() - 1), key=lambda i: -x.stride(i))          # the tokens in the order of their addresses
@@ -379,11 +429,11 @@ def _ffn_fused(x, w1, b1, w2, b2, scale, eps):
         out = torch.empty_like(x)
         order = list(range(x.dim() - 1))
         x3, o3 = _as_rows(x, order), _as_rows(out, order)
-    _lib.ops().ffn_residual(x3, w1.contiguous(), b1.contiguous(), w2.contiguous(), b2.contiguous(), scale.contiguous(), float(eps), o3)
+    getattr(_lib.ops(), op)(x3, w1.contiguous(), b1.contiguous(), w2.contiguous(), b2.contiguous(), scale.contiguous(), float(eps), o3)
     return out
 
 
-def feed_forward_residual(x, w1, b1, w2, b2, scale, eps=1e-6, route="fused"):
+def feed_forward_residual(x, w1, b1, w2, b2, scale, eps=1e-6, route="fused", bf16=DEFAULT_FEED_FORWARD_BF16):
     """x + (W2 gelu(W1 rmsnorm(x) + b1) + b2) * scale per token: the feed-forward ResBlock in eval mode.  x [..., D] with a contiguous
     last dimension, any strides in front (a tensor whose rows cannot be handed over as two strides is made contiguous first); w1
     [hidden, D], b1 [hidden], w2 [D, hidden], b2 [D], scale [D] as nn.Linear and ResBlock hold them.  Returns [..., D], laid out in
@@ -391,14 +441,24 @@ def feed_forward_residual(x, w1, b1, w2, b2, scale, eps=1e-6, route="fused"):
 
     route = "fused": the HIP op (the host kernel for CPU tensors) whenever it applies; the stock route (feed_forward_torch) when a
     dtype is not float32, the shape is outside the supported set (feed_forward_supported), or gradients are enabled and an input or
-    a parameter requires grad.  route = "torch": always the stock route.  Always usable, always differentiable."""
+    a parameter requires grad.  route = "torch": always the stock route.  Always usable, always differentiable.
+
+    bf16 = "torch" (the default): the above.  bf16 = "fused", with route = "fused": bfloat16 x and parameters take the bf16 HIP op
+    (form A); float32 x and parameters under torch.autocast(dtype=torch.bfloat16) take the same kernel on the float32 tensors
+    (form B: bf16 operands, float32 biases, LayerScale and result); float32 outside autocast stays the float32 op; any other mix of
+    dtypes, and autocast to another dtype, is the stock route."""
     if route not in FEED_FORWARD_KINDS:
         raise ValueError(f"route must be one of {FEED_FORWARD_KINDS}, not {route!r}")
-    if route == "torch" or not _ffn_applies(x, w1, b1, w2, b2, scale):
+    if bf16 not in FEED_FORWARD_BF16_KINDS:
+        raise ValueError(f"bf16 must be one of {FEED_FORWARD_BF16_KINDS}, not {bf16!r}")
+    if route == "torch":
         FEED_FORWARD_ROUTES["torch"] += 1
         return feed_forward_torch(x, w1, b1, w2, b2, scale, eps)
-    FEED_FORWARD_ROUTES["fused"] += 1
-    return _ffn_fused(x, w1, b1, w2, b2, scale, eps)
+    op, is16 = _ffn_pick((x, w1, b1, w2, b2, scale), bf16)
+    _ffn_count(op, is16)
+    if op is None:
+        return feed_forward_torch(x, w1, b1, w2, b2, scale, eps)
+    return _ffn_fused(x, w1, b1, w2, b2, scale, eps, op)
 
 
 # ---- the modules --------------------------------------------------------------------------------------------------------------------
@@ -461,7 +521,10 @@ class ResBlock(nn.Module):
     feedForward: "torch" (the default: the expression above as it stands) or "fused": when the module is the `Linear, GELU, Dropout,
     Linear` sequence of a feed-forward block, no extra arguments are passed and no dropout is active (eval mode or p = 0), the block
     is feed_forward_residual's one op wherever that applies (float32, a supported shape, no gradient wanted); the expression above
-    in every other case."""
+    in every other case.
+    feedForwardBf16: "torch" (the default: the above) or "fused": where feedForward = "fused" and its conditions hold, a block whose
+    input and parameters are all bfloat16 is the bf16 HIP op, and a float32 block under bfloat16 autocast is the same kernel on its
+    float32 tensors (feed_forward_residual's bf16 = "fused")."""
 
     def __init__(self, module, size, prenorm=True, dropoutProb=0.0):
         super().__init__()
@@ -470,6 +533,7 @@ class ResBlock(nn.Module):
         self.scale = nn.Parameter(torch.ones(size) * 1e-2)
         self.dropout = nn.Dropout(dropoutProb)
         self.feedForward = DEFAULT_FEED_FORWARD
+        self.feedForwardBf16 = DEFAULT_FEED_FORWARD_BF16
 
     def is_feed_forward(self) -> bool:
         """The module is the Linear, GELU (exact), Dropout, Linear sequence of _feed_forward."""
@@ -479,23 +543,24 @@ class ResBlock(nn.Module):
                 and m[0].bias is not None and m[3].bias is not None and type(self.norm) is RMSNorm)
 
     def _fused_feed_forward(self, x, args):
-        if self.feedForward != "fused" or args or not self.is_feed_forward():
-            return None
-        m = self.module
-        if self.training and (self.dropout.p > 0 or m[2].p > 0):
-            return None
-        params = (m[0].weight, m[0].bias, m[3].weight, m[3].bias, self.scale)
-        if not _ffn_applies(x, *params):
-            return None
-        FEED_FORWARD_ROUTES["fused"] += 1
-        return _ffn_fused(x, *params, self.norm.eps)
+        """The fused op's answer, or None for the stock expression; counts the call either way."""
+        if self.feedForwardBf16 not in FEED_FORWARD_BF16_KINDS:
+            raise ValueError(f"feedForwardBf16 must be one of {FEED_FORWARD_BF16_KINDS}, not {self.feedForwardBf16!r}")
+        op, is16 = None, False
+        if self.feedForward == "fused" and self.is_feed_forward():
+            m = self.module
+            params = (m[0].weight, m[0].bias, m[3].weight, m[3].bias, self.scale)
+            op, is16 = _ffn_pick((x, *params), self.feedForwardBf16)
+            if args or (self.training and (self.dropout.p > 0 or m[2].p > 0)):
+                op = None
+        _ffn_count(op, is16)
+        return None if op is None else _ffn_fused(x, *params, self.norm.eps, op)
 
     def forward(self, x, *args):
         if self.feedForward != DEFAULT_FEED_FORWARD:             # a block left at "torch" touches nothing, the counters included
             out = self._fused_feed_forward(x, args)
             if out is not None:
                 return out
-            FEED_FORWARD_ROUTES["torch"] += 1
         return x + self.dropout(self.module(self.norm(x), *args)) * self.scale
 
 
@@ -570,7 +635,8 @@ class BasicBlock(nn.Module):
     attention is per token, and the two halves differ only in which dimension the attention is told is the sequence.  With "torch"
     the block follows the reference's order of operations, `transpose(-3, -2)` around the time-axis half included.
     attentionBf16 = "torch" | "fused" sets the bfloat16 knob of all its attention modules, attentionBf16Train = "torch" | "fused"
-    their bfloat16 training knob."""
+    their bfloat16 training knob; feedForward = "torch" | "fused" and feedForwardBf16 = "torch" | "fused" set the two knobs of all
+    its feed-forward blocks (ResBlock)."""
 
     def __init__(self, inputSize, num_heads, fourierSize, hiddenFactor=2, hiddenFactorAttn=1, approxKernels=[None, None, None, None],
                  enabled=["F", "T", "All0", "0All"], dropoutProb=0.0):
@@ -650,6 +716,18 @@ class BasicBlock(nn.Module):
         for m in self.feed_forward_blocks():
             m.feedForward = kind
 
+    @property
+    def feedForwardBf16(self):
+        kinds = {m.feedForwardBf16 for m in self.feed_forward_blocks()}
+        return kinds.pop() if len(kinds) == 1 else "mixed"
+
+    @feedForwardBf16.setter
+    def feedForwardBf16(self, kind):
+        if kind not in FEED_FORWARD_BF16_KINDS:
+            raise ValueError(f"feedForwardBf16 must be one of {FEED_FORWARD_BF16_KINDS}, not {kind!r}")
+        for m in self.feed_forward_blocks():
+            m.feedForwardBf16 = kind
+
     def forward(self, x, mem=None, crossAttn=False):
         nT, nF = x.shape[-3], x.shape[-2]
         if mem is None:
@@ -697,7 +775,8 @@ class Backbone(nn.Module):
     attention: "fused" | "fused-train" | "torch" for all layers (the property reads "mixed" when they differ).
     attentionBf16: "torch" | "fused" for the bfloat16 calls of all layers, likewise.
     attentionBf16Train: "torch" | "fused" for the bfloat16 calls of all layers under autograd, likewise.
-    feedForward: "torch" | "fused" for the feed-forward blocks of all layers, likewise."""
+    feedForward: "torch" | "fused" for the feed-forward blocks of all layers, likewise.
+    feedForwardBf16: "torch" | "fused" for their bfloat16 and bfloat16-autocast calls, likewise."""
 
     def __init__(self, inputSize, baseSize, posEmbedInitGamma, nHead, fourierSize=16, hiddenFactor=2, hiddenFactorAttn=1,
                  expansionFactor=1, dropoutProb=0.0, nLayers=4, enabledAttn=["F", "T"], useGradientCheckpoint=True, downsampleF=True,
@@ -784,6 +863,18 @@ class Backbone(nn.Module):
             raise ValueError(f"feedForward must be one of {FEED_FORWARD_KINDS}, not {kind!r}")
         for m in self.feed_forward_blocks():
             m.feedForward = kind
+
+    @property
+    def feedForwardBf16(self):
+        kinds = {m.feedForwardBf16 for m in self.feed_forward_blocks()}
+        return kinds.pop() if len(kinds) == 1 else "mixed"
+
+    @feedForwardBf16.setter
+    def feedForwardBf16(self, kind):
+        if kind not in FEED_FORWARD_BF16_KINDS:
+            raise ValueError(f"feedForwardBf16 must be one of {FEED_FORWARD_BF16_KINDS}, not {kind!r}")
+        for m in self.feed_forward_blocks():
+            m.feedForwardBf16 = kind
 
     def tokens(self, x, outputIndices):
         """The input of the first layer: [N, T', F' + P, 4 baseSize], the spectrogram tokens followed by the target tokens."""

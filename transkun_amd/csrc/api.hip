@@ -148,6 +148,32 @@ static void lease_failed(void* ws)
     if (it != g_leases.end()) it->second.clean = false;
 }
 
+// The argument checks of the two bf16 feed-forward entry points: semicrf_ffn_residual's cases in its words, on elements of T.  The
+// strides of the dimensions that count come back in st.
+template <typename T>
+static int ffn_bf16_check(const char* op, const T* x, T* out, int64_t n0, int64_t n1, int64_t xs0, int64_t xs1, int64_t os0, int64_t os1, int D,
+                          int hidden, const T* W1, const T* b1, const T* W2, const T* b2, const T* scale, long long* st)
+{
+    SEMICRF_CHECK_ARG(ffn::supported(D, hidden),
+                      "%s: D=%d hidden=%d is outside the supported set (D a multiple of 8 in [%d, %d]; hidden a multiple of 8 in "
+                      "[%d, %d]): see semicrf_%s_supported", op, D, hidden, ffn::FFN_MIN_D, ffn::FFN_MAX_D, ffn::FFN_MIN_H, ffn::FFN_MAX_H, op);
+    SEMICRF_CHECK_ARG(n0 >= 1 && n1 >= 1, "%s: n0=%lld n1=%lld must be >= 1", op, (long long)n0, (long long)n1);
+    SEMICRF_CHECK_ARG(n0 < (1ll << 37) && n1 < (1ll << 37) && n0 * n1 < (1ll << 37), "%s: n0 * n1 = %lld * %lld must stay below 2^37", op,
+                      (long long)n0, (long long)n1);
+    SEMICRF_CHECK_ARG(x && out && W1 && b1 && W2 && b2 && scale, "%s: x/out/W1/b1/W2/b2/scale must be non-NULL", op);
+    SEMICRF_CHECK_ARG((((uintptr_t)x | (uintptr_t)out | (uintptr_t)W1 | (uintptr_t)b1 | (uintptr_t)W2 | (uintptr_t)b2 | (uintptr_t)scale) &
+                       (sizeof(T) - 1)) == 0,
+                      "%s: every pointer must be %d-byte aligned", op, (int)sizeof(T));
+    st[0] = n0 > 1 ? xs0 : 0; st[1] = n1 > 1 ? xs1 : 0; st[2] = n0 > 1 ? os0 : 0; st[3] = n1 > 1 ? os1 : 0;
+    for (int i = 0; i < 4; ++i) SEMICRF_CHECK_ARG(st[i] >= 0 && st[i] < (1ll << 40), "%s: stride %d = %lld must be in [0, 2^40)", op, i, st[i]);
+    SEMICRF_CHECK_ARG((n0 == 1 || st[2] >= D) && (n1 == 1 || st[3] >= D), "%s: a row stride of `out` (%lld, %lld) is below D=%d", op, st[2], st[3], D);
+    // the element ranges the two views span (strides below 2^40, counts below 2^37: no overflow)
+    const long long xext = (n0 - 1) * st[0] + (n1 - 1) * st[1] + D, oext = (n0 - 1) * st[2] + (n1 - 1) * st[3] + D;
+    const uintptr_t xb = (uintptr_t)x, ob = (uintptr_t)out;
+    SEMICRF_CHECK_ARG(xb + (uintptr_t)xext * sizeof(T) <= ob || ob + (uintptr_t)oext * sizeof(T) <= xb, "%s: `out` overlaps `x`", op);
+    return SEMICRF_OK;
+}
+
 }  // namespace semicrf
 
 using namespace semicrf;
@@ -1406,6 +1432,35 @@ int semicrf_ffn_residual(const float* x, float* out, int64_t n0, int64_t n1, int
     SEMICRF_CHECK_ARG(xb + (uintptr_t)xext * 4 <= ob || ob + (uintptr_t)oext * 4 <= xb, "ffn_residual: `out` overlaps `x`");
     launch_ffn_residual(x, out, n0, n1, st[0], st[1], st[2], st[3], D, hidden, W1, b1, W2, b2, scale, eps, (hipStream_t)stream);
     SEMICRF_CHECK_LAUNCH("semicrf_ffn_residual");
+    return SEMICRF_OK;
+}
+
+int semicrf_ffn_residual_bf16_supported(int D, int hidden) { return ffn::supported(D, hidden) ? 1 : 0; }
+int semicrf_ffn_residual_bf16_mixed_supported(int D, int hidden) { return ffn::supported(D, hidden) ? 1 : 0; }
+
+int semicrf_ffn_residual_bf16(const uint16_t* x, uint16_t* out, int64_t n0, int64_t n1, int64_t x_stride_0, int64_t x_stride_1, int64_t out_stride_0,
+                              int64_t out_stride_1, int D, int hidden, const uint16_t* W1, const uint16_t* b1, const uint16_t* W2,
+                              const uint16_t* b2, const uint16_t* scale, float eps, semicrf_stream_t stream)
+{
+    long long st[4];
+    const int rc = ffn_bf16_check<uint16_t>("ffn_residual_bf16", x, out, n0, n1, x_stride_0, x_stride_1, out_stride_0, out_stride_1, D, hidden, W1,
+                                            b1, W2, b2, scale, st);
+    if (rc != SEMICRF_OK) return rc;
+    launch_ffn_residual_bf16(x, out, n0, n1, st[0], st[1], st[2], st[3], D, hidden, W1, b1, W2, b2, scale, eps, (hipStream_t)stream);
+    SEMICRF_CHECK_LAUNCH("semicrf_ffn_residual_bf16");
+    return SEMICRF_OK;
+}
+
+int semicrf_ffn_residual_bf16_mixed(const float* x, float* out, int64_t n0, int64_t n1, int64_t x_stride_0, int64_t x_stride_1, int64_t out_stride_0,
+                                    int64_t out_stride_1, int D, int hidden, const float* W1, const float* b1, const float* W2, const float* b2,
+                                    const float* scale, float eps, semicrf_stream_t stream)
+{
+    long long st[4];
+    const int rc = ffn_bf16_check<float>("ffn_residual_bf16_mixed", x, out, n0, n1, x_stride_0, x_stride_1, out_stride_0, out_stride_1, D, hidden,
+                                         W1, b1, W2, b2, scale, st);
+    if (rc != SEMICRF_OK) return rc;
+    launch_ffn_residual_bf16_mixed(x, out, n0, n1, st[0], st[1], st[2], st[3], D, hidden, W1, b1, W2, b2, scale, eps, (hipStream_t)stream);
+    SEMICRF_CHECK_LAUNCH("semicrf_ffn_residual_bf16_mixed");
     return SEMICRF_OK;
 }
 

@@ -23,6 +23,7 @@
 #include "attention_math.h"
 #include "attention_bf16_math.h"
 #include "ffn_math.h"
+#include "ffn_bf16_math.h"
 #include "logmel_math.h"
 #include "cpu_ops.h"
 
@@ -1728,6 +1729,57 @@ void ffn_residual(const float* x, float* out, int64_t n0, int64_t n1, int64_t xs
             for (int n = 0; n < D; ++n) ot[n] = epilogue(xt[n], acc[n], b2[n], scale[n]);
         }
     }
+}
+
+// ---- the bf16 feed-forward ResBlock (semicrf_ffn_residual_bf16, semicrf_ffn_residual_bf16_mixed) ----------------------------------------
+// The chain of ffn_bf16_math.h per output element, T = uint16_t (bf16 tensors) or float (fp32 tensors, bf16 operands): the products of
+// two bf16 values are exact in fp32, so each fmaf below is the exact product added with one rounding; both sums ascend one term at a
+// time where the device adds 16 products per matrix instruction.  Only that and erf / erfc differ from the device's.
+template <typename T>
+static void ffn_residual_bf16_any(const T* x, T* out, int64_t n0, int64_t n1, int64_t xs0, int64_t xs1, int64_t os0, int64_t os1, int D, int H,
+                                  const T* W1, const T* b1, const T* W2, const T* b2, const T* scale, float eps)
+{
+    using namespace semicrf::ffn;
+    const int64_t ntok = n0 * n1;
+    std::vector<float> w1h((size_t)H * D), w2h((size_t)D * H);           // the operands as fp32 values, rounded once per call
+    for (size_t i = 0; i < w1h.size(); ++i) w1h[i] = bf16_to_float(operand_of(W1[i]));
+    for (size_t i = 0; i < w2h.size(); ++i) w2h[i] = bf16_to_float(operand_of(W2[i]));
+#pragma omp parallel
+    {
+        std::vector<float> xh((size_t)D), gh((size_t)H);
+#pragma omp for schedule(static)
+        for (int64_t t = 0; t < ntok; ++t) {
+            const int64_t i0 = t / n1, i1 = t % n1;
+            const T* xt = x + i0 * xs0 + i1 * xs1;
+            T* ot = out + i0 * os0 + i1 * os1;
+            float s[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+            for (int k = 0; k < D; ++k) s[k & 3] = fmaf(to_f32(xt[k]), to_f32(xt[k]), s[k & 3]);
+            const float rs = rs_of(sumsq_combine(s[0], s[1], s[2], s[3]), D, eps);
+            for (int k = 0; k < D; ++k) xh[k] = bf16_to_float(bf16_rne(to_f32(xt[k]) * rs));
+            for (int j = 0; j < H; ++j) {
+                const float* w = w1h.data() + (size_t)j * D;
+                float h = 0.0f;
+                for (int k = 0; k < D; ++k) h = fmaf(xh[k], w[k], h);
+                gh[j] = bf16_to_float(bf16_rne(semicrf::attr_heads::gelu<float>(h + to_f32(b1[j]))));
+            }
+            for (int n = 0; n < D; ++n) {
+                const float* w = w2h.data() + (size_t)n * H;
+                float a = 0.0f;                              // one running accumulator over all of hidden
+                for (int j = 0; j < H; ++j) a = fmaf(gh[j], w[j], a);
+                store_as(ot + n, epilogue(to_f32(xt[n]), a, to_f32(b2[n]), to_f32(scale[n])));
+            }
+        }
+    }
+}
+void ffn_residual_bf16(const uint16_t* x, uint16_t* out, int64_t n0, int64_t n1, int64_t xs0, int64_t xs1, int64_t os0, int64_t os1, int D, int H,
+                       const uint16_t* W1, const uint16_t* b1, const uint16_t* W2, const uint16_t* b2, const uint16_t* scale, float eps)
+{
+    ffn_residual_bf16_any<uint16_t>(x, out, n0, n1, xs0, xs1, os0, os1, D, H, W1, b1, W2, b2, scale, eps);
+}
+void ffn_residual_bf16_mixed(const float* x, float* out, int64_t n0, int64_t n1, int64_t xs0, int64_t xs1, int64_t os0, int64_t os1, int D, int H,
+                             const float* W1, const float* b1, const float* W2, const float* b2, const float* scale, float eps)
+{
+    ffn_residual_bf16_any<float>(x, out, n0, n1, xs0, xs1, os0, os1, D, H, W1, b1, W2, b2, scale, eps);
 }
 
 // ---- the audio front end (semicrf_log_mel) -------------------------------------------------------------------------------------------

@@ -90,6 +90,12 @@ void axial_attention_bf16_bwd(const uint16_t* q, const uint16_t* k, const uint16
 // (ffn_math.h); x and out [n0, n1, D] with their two element row strides; the caller has checked the supported set
 void ffn_residual(const float* x, float* out, int64_t n0, int64_t n1, int64_t xs0, int64_t xs1, int64_t os0, int64_t os1, int D, int H,
                   const float* W1, const float* b1, const float* W2, const float* b2, const float* scale, float eps);
+// the bf16 feed-forward ResBlock (semicrf_ffn_residual_bf16 on bf16 tensors, semicrf_ffn_residual_bf16_mixed on fp32 tensors): the
+// chain of ffn_bf16_math.h per output element, both sums in fp32 ascending; the caller has checked the supported set
+void ffn_residual_bf16(const uint16_t* x, uint16_t* out, int64_t n0, int64_t n1, int64_t xs0, int64_t xs1, int64_t os0, int64_t os1, int D, int H,
+                       const uint16_t* W1, const uint16_t* b1, const uint16_t* W2, const uint16_t* b2, const uint16_t* scale, float eps);
+void ffn_residual_bf16_mixed(const float* x, float* out, int64_t n0, int64_t n1, int64_t xs0, int64_t xs1, int64_t os0, int64_t os1, int D, int H,
+                             const float* W1, const float* b1, const float* W2, const float* b2, const float* scale, float eps);
 // the audio front end (semicrf_log_mel): the device kernel's order of operations per output element, in fp32 (logmel_math.h); frames
 // by its three element strides, out contiguous [N][to_mono ? 1 : C][nFrame][nMel][nWin]; the caller has checked the supported set
 void log_mel(const float* frames, int64_t sn, int64_t sc, int64_t sf, int N, int C, int nFrame, int W, const float* windows, int nWin,

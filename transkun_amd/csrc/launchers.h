@@ -84,6 +84,14 @@ void launch_ffn_residual(const float* x, float* out, long long n0, long long n1,
                          int D, int H, const float* W1, const float* b1, const float* W2, const float* b2, const float* scale, float eps,
                          hipStream_t stream);
 
+// ffn_bf16.hip
+void launch_ffn_residual_bf16(const uint16_t* x, uint16_t* out, long long n0, long long n1, long long xs0, long long xs1, long long os0, long long os1,
+                              int D, int H, const uint16_t* W1, const uint16_t* b1, const uint16_t* W2, const uint16_t* b2, const uint16_t* scale,
+                              float eps, hipStream_t stream);
+void launch_ffn_residual_bf16_mixed(const float* x, float* out, long long n0, long long n1, long long xs0, long long xs1, long long os0, long long os1,
+                                    int D, int H, const float* W1, const float* b1, const float* W2, const float* b2, const float* scale, float eps,
+                                    hipStream_t stream);
+
 // logmel.hip
 void launch_log_mel(const float* frames, long long sn, long long sc, long long sf, int N, int C, int nFrame, int W, const float* windows, int nWin,
                     const float* tw, const int* fb_start, const int* fb_len, const int* fb_off, const float* fb_val, int nMel, int total,

@@ -1191,13 +1191,15 @@ void axial_attention_bf16_cpu(Tensor q, Tensor k, Tensor v, Tensor out, int64_t 
 // ---- the backbone's feed-forward ResBlock (semicrf_ffn_residual) --------------------------------------------------------------------
 // x, out: [n0, n1, D] VIEWS with a contiguous last dimension (their two row strides are read from the tensors); W1 [hidden, D],
 // b1 [hidden], W2 [D, hidden], b2 [D], scale [D] contiguous, as nn.Linear and ResBlock store them
-struct FfnArgs { const float *x, *W1, *b1, *W2, *b2, *scale; float* out; int64_t n0, n1, st[4]; int D, H; };
+struct FfnArgs { const void *x, *W1, *b1, *W2, *b2, *scale; void* out; int64_t n0, n1, st[4]; int D, H; };   // elements of `dtype`
 inline FfnArgs ffn_args(const Tensor& x, const Tensor& W1, const Tensor& b1, const Tensor& W2, const Tensor& b2, const Tensor& scale,
-                        const Tensor& out)
+                        const Tensor& out, ScalarType dtype = ScalarType::Float)
 {
+    const char* const dname = dtype == ScalarType::Float ? "float32" : "bfloat16";
+    auto ptr = [&](const Tensor& t, int64_t n, const char* name) -> const void* { want(t, dtype, n, name); return t.data_ptr(); };
     FfnArgs a{};
     STD_TORCH_CHECK(x.defined() && x.dim() == 3 && out.defined() && out.dim() == 3, "semicrf: `x` and `out` must be [n0, n1, D]");
-    STD_TORCH_CHECK(x.scalar_type() == ScalarType::Float && out.scalar_type() == ScalarType::Float, "semicrf: `x` and `out` must be float32");
+    STD_TORCH_CHECK(x.scalar_type() == dtype && out.scalar_type() == dtype, "semicrf: `x` and `out` must be ", dname);
     STD_TORCH_CHECK(W1.defined() && W1.dim() == 2 && W2.defined() && W2.dim() == 2, "semicrf: `W1` must be [hidden, D], `W2` [D, hidden]");
     const int64_t D = x.size(2), H = W1.size(0);
     a.n0 = x.size(0); a.n1 = x.size(1);
@@ -1214,29 +1216,71 @@ inline FfnArgs ffn_args(const Tensor& x, const Tensor& W1, const Tensor& b1, con
         STD_TORCH_CHECK(out.size(j) == 1 || a.st[2 + j] >= D, "semicrf: `out` must not repeat or interleave its rows");
     }
     a.D = (int)D; a.H = (int)H;
-    a.W1 = f32(W1, H * D, "W1"); a.b1 = f32(b1, H, "b1"); a.W2 = f32(W2, D * H, "W2"); a.b2 = f32(b2, D, "b2"); a.scale = f32(scale, D, "scale");
+    a.W1 = ptr(W1, H * D, "W1"); a.b1 = ptr(b1, H, "b1"); a.W2 = ptr(W2, D * H, "W2"); a.b2 = ptr(b2, D, "b2"); a.scale = ptr(scale, D, "scale");
     STD_TORCH_CHECK(b1.numel() == H && b2.numel() == D && scale.numel() == D, "semicrf: `b1` / `b2` / `scale` do not have the shape of the call");
-    a.x = x.numel() > 0 ? (const float*)x.data_ptr() : nullptr;
-    a.out = out.numel() > 0 ? (float*)out.data_ptr() : nullptr;
+    a.x = x.numel() > 0 ? x.data_ptr() : nullptr;
+    a.out = out.numel() > 0 ? out.data_ptr() : nullptr;
     return a;
+}
+// one body per entry point: E the element type of the C ABI, `overlap` the element ranges of the two views
+template <typename E, typename F>
+void ffn_on_device(const FfnArgs& a, double eps, semicrf_stream_t stream, F entry, const char* name)
+{
+    check(entry((const E*)a.x, (E*)a.out, a.n0, a.n1, a.st[0], a.st[1], a.st[2], a.st[3], a.D, a.H, (const E*)a.W1, (const E*)a.b1, (const E*)a.W2,
+                (const E*)a.b2, (const E*)a.scale, (float)eps, stream),
+          name);
+}
+template <typename E, typename F>
+void ffn_on_host(const FfnArgs& a, double eps, F mirror, const char* name)
+{
+    const int64_t xext = (a.n0 - 1) * a.st[0] + (a.n1 - 1) * a.st[1] + a.D, oext = (a.n0 - 1) * a.st[2] + (a.n1 - 1) * a.st[3] + a.D;
+    const E *x = (const E*)a.x, *o = (const E*)a.out;
+    STD_TORCH_CHECK(x + xext <= o || o + oext <= x, "semicrf: ", name, ": `out` overlaps `x`");
+    mirror(x, (E*)a.out, a.n0, a.n1, a.st[0], a.st[1], a.st[2], a.st[3], a.D, a.H, (const E*)a.W1, (const E*)a.b1, (const E*)a.W2, (const E*)a.b2,
+           (const E*)a.scale, (float)eps);
 }
 void ffn_residual_op(Tensor x, Tensor W1, Tensor b1, Tensor W2, Tensor b2, Tensor scale, double eps, Tensor out)
 {
     Ctx c(x); c.same(x, W1, b1, W2, b2, scale, out);
     const FfnArgs a = ffn_args(x, W1, b1, W2, b2, scale, out);
     if (a.n0 == 0 || a.n1 == 0) return;
-    check(semicrf_ffn_residual(a.x, a.out, a.n0, a.n1, a.st[0], a.st[1], a.st[2], a.st[3], a.D, a.H, a.W1, a.b1, a.W2, a.b2, a.scale, (float)eps,
-                               c.stream),
-          "semicrf_ffn_residual");
+    ffn_on_device<float>(a, eps, c.stream, &semicrf_ffn_residual, "semicrf_ffn_residual");
 }
 void ffn_residual_cpu(Tensor x, Tensor W1, Tensor b1, Tensor W2, Tensor b2, Tensor scale, double eps, Tensor out)
 {
     all_cpu(x, W1, b1, W2, b2, scale, out);
     const FfnArgs a = ffn_args(x, W1, b1, W2, b2, scale, out);
     if (a.n0 == 0 || a.n1 == 0) return;
-    const int64_t xext = (a.n0 - 1) * a.st[0] + (a.n1 - 1) * a.st[1] + a.D, oext = (a.n0 - 1) * a.st[2] + (a.n1 - 1) * a.st[3] + a.D;
-    STD_TORCH_CHECK(a.x + xext <= a.out || a.out + oext <= a.x, "semicrf: ffn_residual: `out` overlaps `x`");
-    semicrf_cpu::ffn_residual(a.x, a.out, a.n0, a.n1, a.st[0], a.st[1], a.st[2], a.st[3], a.D, a.H, a.W1, a.b1, a.W2, a.b2, a.scale, (float)eps);
+    ffn_on_host<float>(a, eps, &semicrf_cpu::ffn_residual, "ffn_residual");
+}
+// the bf16 forms: `ffn_residual_bf16` on bfloat16 tensors, `ffn_residual_bf16_mixed` on float32 tensors (bf16 operands inside)
+void ffn_residual_bf16_op(Tensor x, Tensor W1, Tensor b1, Tensor W2, Tensor b2, Tensor scale, double eps, Tensor out)
+{
+    Ctx c(x); c.same(x, W1, b1, W2, b2, scale, out);
+    const FfnArgs a = ffn_args(x, W1, b1, W2, b2, scale, out, ScalarType::BFloat16);
+    if (a.n0 == 0 || a.n1 == 0) return;
+    ffn_on_device<uint16_t>(a, eps, c.stream, &semicrf_ffn_residual_bf16, "semicrf_ffn_residual_bf16");
+}
+void ffn_residual_bf16_cpu(Tensor x, Tensor W1, Tensor b1, Tensor W2, Tensor b2, Tensor scale, double eps, Tensor out)
+{
+    all_cpu(x, W1, b1, W2, b2, scale, out);
+    const FfnArgs a = ffn_args(x, W1, b1, W2, b2, scale, out, ScalarType::BFloat16);
+    if (a.n0 == 0 || a.n1 == 0) return;
+    ffn_on_host<uint16_t>(a, eps, &semicrf_cpu::ffn_residual_bf16, "ffn_residual_bf16");
+}
+void ffn_residual_bf16_mixed_op(Tensor x, Tensor W1, Tensor b1, Tensor W2, Tensor b2, Tensor scale, double eps, Tensor out)
+{
+    Ctx c(x); c.same(x, W1, b1, W2, b2, scale, out);
+    const FfnArgs a = ffn_args(x, W1, b1, W2, b2, scale, out);
+    if (a.n0 == 0 || a.n1 == 0) return;
+    ffn_on_device<float>(a, eps, c.stream, &semicrf_ffn_residual_bf16_mixed, "semicrf_ffn_residual_bf16_mixed");
+}
+void ffn_residual_bf16_mixed_cpu(Tensor x, Tensor W1, Tensor b1, Tensor W2, Tensor b2, Tensor scale, double eps, Tensor out)
+{
+    all_cpu(x, W1, b1, W2, b2, scale, out);
+    const FfnArgs a = ffn_args(x, W1, b1, W2, b2, scale, out);
+    if (a.n0 == 0 || a.n1 == 0) return;
+    ffn_on_host<float>(a, eps, &semicrf_cpu::ffn_residual_bf16_mixed, "ffn_residual_bf16_mixed");
 }
 
 // ---- the audio front end (semicrf_log_mel) -------------------------------------------------------------------------------------------
@@ -1650,6 +1694,8 @@ STABLE_TORCH_LIBRARY(semicrf, m)
     m.def("axial_attention_bwd(Tensor q, Tensor k, Tensor v, Tensor out, Tensor dout, Tensor(a!)? dq, Tensor(b!)? dk, Tensor(c!)? dv, int H) -> ()");
     m.def("axial_attention_bf16_bwd(Tensor q, Tensor k, Tensor v, Tensor dout, Tensor(a!)? dq, Tensor(b!)? dk, Tensor(c!)? dv, int H) -> ()");
     m.def("ffn_residual(Tensor x, Tensor W1, Tensor b1, Tensor W2, Tensor b2, Tensor scale, float eps, Tensor(a!) out) -> ()");
+    m.def("ffn_residual_bf16(Tensor x, Tensor W1, Tensor b1, Tensor W2, Tensor b2, Tensor scale, float eps, Tensor(a!) out) -> ()");
+    m.def("ffn_residual_bf16_mixed(Tensor x, Tensor W1, Tensor b1, Tensor W2, Tensor b2, Tensor scale, float eps, Tensor(a!) out) -> ()");
     m.def("log_mel(Tensor frames, Tensor windows, Tensor tw, Tensor fb_start, Tensor fb_len, Tensor fb_off, Tensor fb_val, int max_len, "
           "Tensor shift, Tensor denom, bool has_gain, bool log_flag, float eps, bool to_mono, Tensor(a!) out) -> ()");
     m.def("grad_sqnorm(Tensor flat, int numel, Tensor(a!) partials) -> ()");
@@ -1696,6 +1742,8 @@ STABLE_TORCH_LIBRARY_IMPL(semicrf, CPU, m)
     m.impl("axial_attention_bwd", TORCH_BOX(&axial_attention_bwd_cpu));
     m.impl("axial_attention_bf16_bwd", TORCH_BOX(&axial_attention_bf16_bwd_cpu));
     m.impl("ffn_residual", TORCH_BOX(&ffn_residual_cpu));
+    m.impl("ffn_residual_bf16", TORCH_BOX(&ffn_residual_bf16_cpu));
+    m.impl("ffn_residual_bf16_mixed", TORCH_BOX(&ffn_residual_bf16_mixed_cpu));
     m.impl("log_mel", TORCH_BOX(&log_mel_cpu));
     m.impl("grad_sqnorm", TORCH_BOX(&grad_sqnorm_cpu));
     m.impl("clip_from_history", TORCH_BOX(&clip_from_history_cpu));
@@ -1748,6 +1796,8 @@ STABLE_TORCH_LIBRARY_IMPL(semicrf, CUDA, m)
     m.impl("axial_attention_bwd", TORCH_BOX(&axial_attention_bwd_op));
     m.impl("axial_attention_bf16_bwd", TORCH_BOX(&axial_attention_bf16_bwd_op));
     m.impl("ffn_residual", TORCH_BOX(&ffn_residual_op));
+    m.impl("ffn_residual_bf16", TORCH_BOX(&ffn_residual_bf16_op));
+    m.impl("ffn_residual_bf16_mixed", TORCH_BOX(&ffn_residual_bf16_mixed_op));
     m.impl("log_mel", TORCH_BOX(&log_mel_op));
     m.impl("grad_sqnorm", TORCH_BOX(&grad_sqnorm_op));
     m.impl("clip_from_history", TORCH_BOX(&clip_from_history_op));
