@@ -172,6 +172,7 @@ extern "C" {
 #define SEMICRF_OP_MARGINAL_DECODE_TOL 11   /* semicrf_marginal_decode_tol */
 #define SEMICRF_OP_ATTRIBUTE_HEADS 12       /* semicrf_attribute_heads: T = rows K, B = Hv + Ho (see there) */
 #define SEMICRF_OP_ATTRIBUTE_HEADS_BWD 13   /* semicrf_attribute_heads_bwd: T = rows K, B = Hv + Ho (see there) */
+#define SEMICRF_OP_FFN_RESIDUAL_BWD 14      /* semicrf_ffn_residual_bwd: T = tokens n0 n1, B = hidden (see there) */
 
 #define SEMICRF_WS_ALIGN 256           /* required alignment of every `ws` of the semicrf_* entry points (enforced: SEMICRF_EINVAL) */
 
@@ -1289,6 +1290,57 @@ int semicrf_ffn_residual_supported(int D, int hidden);
 int semicrf_ffn_residual(const float* x, float* out, int64_t n0, int64_t n1, int64_t x_stride_0, int64_t x_stride_1, int64_t out_stride_0,
                          int64_t out_stride_1, int D, int hidden, const float* W1, const float* b1, const float* W2, const float* b2,
                          const float* scale, float eps, semicrf_stream_t stream);
+
+/*
+ * The same block in TRAINING: both dropouts in the forward, and its backward (once differentiable).  fp32, exact on the matrix pipe.
+ * With i = i0 n1 + i1 the token's index in the [n0, n1, D] view that is handed over (so: the tokens in the order the caller lists
+ * them; the Python wrapper lists them in the order of their addresses), M1 = keep(seed, 0, i, j) / (1 - p_hidden) on the hidden
+ * activation and M2 = keep(seed, 1, i, n) / (1 - p_out) on the module's output (a dropout with p = 0 neither masks nor scales):
+ *   rs  = 1 / sqrt(mean(x^2) + eps)      xn = x * rs
+ *   z   = W1 xn + b1                     a  = gelu(z) * M1
+ *   y   = W2 a + b2                      out = x + (y * M2) * scale
+ *   dscale = sum_tok g * (y * M2)        dy  = (g * scale) * M2   db2 = sum_tok dy                      g = dout
+ *   dW2    = sum_tok dy (x) a            da  = W2^T dy            dz  = (da * M1) * gelu'(z)
+ *   db1    = sum_tok dz                  dW1 = sum_tok dz (x) xn  dxn = W1^T dz
+ *   dx     = g + rs * (dxn - xn * mean(dxn * xn))
+ * keep(seed, stream, i, j): Philox-4x32-10 (Salmon et al., SC'11) with counter ((i >> 2) mod 2^32, j, stream, i >> 34) and key (seed mod
+ * 2^32, seed >> 32); element i takes output word i & 3 and is KEPT iff that word >= floor(p * 2^32).  stream 0: the hidden dropout
+ * (j a hidden column), stream 1: the output dropout (j a column of D).  A stateless function of (seed, stream, i, j): a token's mask
+ * does not depend on the number of tokens.  semicrf_ffn_dropout_mask writes both masks as bytes (1 = kept), [rows][hidden] and
+ * [rows][D]; a dropout with p = 0 is all ones.
+ *
+ * semicrf_ffn_residual_train_fwd: semicrf_ffn_residual's kernel in its training mode, the same chain per element; it also stores
+ * z [n0 n1][hidden] and y [n0 n1][D] (dense, row i = the token's index) for the backward.  With p_hidden = p_out = 0 `out` has the
+ * bits of semicrf_ffn_residual.  One launch, no workspace.
+ *
+ * semicrf_ffn_residual_bwd: dout, x and dx are [n0, n1, D] views with two ELEMENT row strides each and a contiguous last dimension
+ * (dx is laid out by its own strides, e.g. like x); z and y are the forward's; W1, W2, scale as the forward read them; dW1 [hidden][D],
+ * db1 [hidden], dW2 [D][hidden], db2 [D], dscale [D] are contiguous and written whole.  Seven launches on `stream`, no atomics, no
+ * allocation: the order of operations of every gradient is fixed (csrc/ffn_math.h) -- fmaf chains in sub-chains of 64 contraction
+ * values (da, dxn) or 128 tokens (dW1, dW2), one partial plane of all parameter gradients per chunk of SEMICRF_FFN_BWD_ROW_CHUNK tokens
+ * (whatever n0 n1 is), the column sums db1, db2, dscale per chunk in double and rounded once, the planes added in ascending order --
+ * so every gradient is bit-identical from run to run and a token's dx does not depend on the other tokens.
+ * Workspace: semicrf_ffn_residual_bwd_workspace_bytes(n0 n1, D, hidden): rs [tokens], dy [tokens][D], dz [tokens][hidden] and
+ * ceil(tokens / chunk) planes of 2 D hidden + hidden + 2 D floats; semicrf_workspace_bytes(SEMICRF_OP_FFN_RESIDUAL_BWD, tokens,
+ * hidden) is an upper bound of it for every supported D.  Nothing is written past the size the function names, nor outside dx and the
+ * five gradients.  Supported: semicrf_ffn_residual_bwd_supported = the set of semicrf_ffn_residual; n0 n1 <= 65535 chunks.
+ * SEMICRF_EINVAL, with nothing launched and nothing written: the cases of semicrf_ffn_residual (dx in the place of out), p outside
+ * [0, 1), dx overlapping dout, x, z or y; SEMICRF_EWORKSPACE: a workspace smaller than the function says.
+ */
+#define SEMICRF_FFN_BWD_ROW_CHUNK 512
+int semicrf_ffn_residual_train_fwd(const float* x, float* out, float* z, float* y, int64_t n0, int64_t n1, int64_t x_stride_0,
+                                   int64_t x_stride_1, int64_t out_stride_0, int64_t out_stride_1, int D, int hidden, const float* W1,
+                                   const float* b1, const float* W2, const float* b2, const float* scale, float eps, uint64_t seed,
+                                   double p_hidden, double p_out, semicrf_stream_t stream);
+int semicrf_ffn_residual_bwd_supported(int D, int hidden);
+size_t semicrf_ffn_residual_bwd_workspace_bytes(int64_t tokens, int D, int hidden);
+int semicrf_ffn_residual_bwd(const float* dout, const float* x, const float* z, const float* y, int64_t n0, int64_t n1, int64_t dout_stride_0,
+                             int64_t dout_stride_1, int64_t x_stride_0, int64_t x_stride_1, int64_t dx_stride_0, int64_t dx_stride_1, int D,
+                             int hidden, const float* W1, const float* W2, const float* scale, float eps, uint64_t seed, double p_hidden,
+                             double p_out, float* dx, float* dW1, float* db1, float* dW2, float* db2, float* dscale, void* ws, size_t ws_bytes,
+                             semicrf_stream_t stream);
+int semicrf_ffn_dropout_mask(uint64_t seed, int64_t rows, int D, int hidden, double p_hidden, double p_out, unsigned char* mask_hidden,
+                             unsigned char* mask_out, semicrf_stream_t stream);
 
 /*
  * The same block with both products on the bf16 matrix instruction (v_mfma_f32_32x32x16_bf16), eval mode, forward only, one launch, no

@@ -57,6 +57,14 @@ bf16 inside the launch, the biases and the LayerScale used as float32, a float32
 float32 op; any other mix of dtypes, and autocast to any other dtype, takes the stock expression.  `FEED_FORWARD_BF16_ROUTES` counts the
 calls made with the knob at "fused" that were bfloat16 or under bfloat16 autocast; a fused answer counts in `FEED_FORWARD_ROUTES` too.
 
+Training in float32 has a third knob, `feedForwardTrain = "torch" | "fused"` (default "torch": everything above, unchanged, counters
+included).  With `feedForward = "fused"` AND `feedForwardTrain = "fused"`, a float32 call outside autocast that wants a gradient -- its
+two dropouts active or not -- is `torch.ops.semicrf.ffn_residual_train_fwd` (csrc/ffn.hip in its training mode: both dropouts from a
+stateless Philox mask, z and y saved) with `torch.ops.semicrf.ffn_residual_bwd` (csrc/ffn_bwd.hip) as its backward, once
+differentiable, every gradient bit-identical from run to run.  bfloat16, autocast, extra arguments and an unsupported shape take the
+stock expression.  `FEED_FORWARD_TRAIN_ROUTES` counts the gradient-wanting calls made with the knob at "fused" (and, under "bwd", the
+launches of the HIP backward); a fused answer counts in `FEED_FORWARD_ROUTES` too.
+
 Hidden size and head dimension come from the constructor as in the reference: head_dim = ceil(ceil(hiddenFactor * embed_dim) /
 num_heads), hidden size = head_dim * num_heads (the model: embed_dim 160, 4 heads, hiddenFactorAttn 1 -> d = 40).
 """
@@ -339,6 +347,13 @@ DEFAULT_FEED_FORWARD_BF16 = "torch"
 FEED_FORWARD_BF16_ROUTES = {"fused": 0, "torch": 0}
 FEED_FORWARD_BF16_ROW_TILE = _lib.FFN_BF16_ROW_TILE             # token rows per workgroup of the bf16 op
 FEED_FORWARD_BF16_HIDDEN_CHUNK = _lib.FFN_BF16_HIDDEN_CHUNK     # hidden columns per step of its walk
+FEED_FORWARD_TRAIN_KINDS = ("torch", "fused")
+DEFAULT_FEED_FORWARD_TRAIN = "torch"
+# gradient-wanting calls made with train = "fused", by the way they went ("bwd": launches of the HIP backward); tests read it
+FEED_FORWARD_TRAIN_ROUTES = {"fused": 0, "torch": 0, "bwd": 0}
+FEED_FORWARD_BWD_ROW_CHUNK = _lib.FFN_BWD_ROW_CHUNK             # tokens per partial plane of the backward's sums over tokens
+# what the last fused training forward / backward handed to the op: (data_ptr, shape, strides) of its x view; tests read it
+FEED_FORWARD_TRAIN_LAST = {"fwd": None, "bwd": None}
 
 
 def feed_forward_supported(D: int, hidden: int) -> bool:
@@ -433,7 +448,130 @@ def _ffn_fused(x, w1, b1, w2, b2, scale, eps, op="ffn_residual"):
     return out
 
 
-def feed_forward_residual(x, w1, b1, w2, b2, scale, eps=1e-6, route="fused", bf16=DEFAULT_FEED_FORWARD_BF16):
+def _seed_arg(seed) -> int:
+    """A seed (any int; its low 64 bits count) as the signed 64-bit value the torch ops carry."""
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    return seed - (1 << 64) if seed >= (1 << 63) else seed
+
+
+def feed_forward_dropout_mask(seed: int, rows: int, D: int, hidden: int, p_hidden: float, p_out: float, device="cpu"):
+    """The two dropout masks of the fused training route as tensors: (bool [rows, hidden], bool [rows, D]), True = kept; the first
+    belongs to the hidden activation (probability p_hidden), the second to the module's output (p_out); p = 0 keeps everything.  Row
+    i is token i of the [n0, n1, D] view the wrapper hands to the op: the tokens in the order of their addresses (for a contiguous
+    x: x.reshape(-1, D)'s rows).  A stateless function of (seed, stream, i, column) (Philox-4x32-10, include/semicrf_hip.h): the
+    first rows of a larger `rows` are the same rows.  On a GPU by semicrf_ffn_dropout_mask, on the CPU by the host mirror: the same
+    bits."""
+    dev = torch.device(device)
+    mh = torch.empty(int(rows), int(hidden), dtype=torch.uint8, device=dev)
+    mo = torch.empty(int(rows), int(D), dtype=torch.uint8, device=dev)
+    _lib.ops().ffn_dropout_mask(mh, mo, _seed_arg(seed), int(rows), int(D), int(hidden), float(p_hidden), float(p_out))
+    return mh.view(torch.bool), mo.view(torch.bool)
+
+
+def _rows_views(ts, order):
+    """Tensors of one shape [..., D] as [n0, n1, D] views with one (n0, n1) that list the tokens in the same order (the leading
+    dimensions taken in `order`), or None."""
+    lead = [(ts[0].shape[i], [t.stride(i) for t in ts]) for i in order if ts[0].shape[i] != 1]
+    merged = []
+    for n, ss in lead:                                          # merge what lies evenly spaced in every tensor
+        if merged and all(p == s * n for p, s in zip(merged[-1][1], ss)):
+            merged[-1] = (merged[-1][0] * n, ss)
+        else:
+            merged.append((n, ss))
+    if len(merged) > 2:
+        return None
+    while len(merged) < 2:
+        merged.insert(0, (1, [0] * len(ts)))
+    (n0, s0), (n1, s1) = merged
+    return [torch.as_strided(t, (n0, n1, t.shape[-1]), (s0[k], s1[k], 1), t.storage_offset()) for k, t in enumerate(ts)]
+
+
+def _ffn_train_applies(x, w1, b1, w2, b2, scale, p_hidden=0.0, p_out=0.0) -> bool:
+    """The fused training route answers: float32 everywhere, one device, no autocast for it, a supported shape, p < 1."""
+    ts = (x, w1, b1, w2, b2, scale)
+    if any(t.dtype != torch.float32 for t in ts) or any(t.device != x.device for t in ts):
+        return False
+    kind = x.device.type
+    if kind not in ("cuda", "cpu") or torch.is_autocast_enabled(kind) or x.dim() < 1 or x.numel() == 0 or w1.dim() != 2 or w2.dim() != 2:
+        return False
+    D, hidden = x.shape[-1], w1.shape[0]
+    if w1.shape != (hidden, D) or w2.shape != (D, hidden) or b1.shape != (hidden,) or b2.shape != (D,) or scale.shape != (D,):
+        return False
+    if not (0.0 <= p_hidden < 1.0 and 0.0 <= p_out < 1.0):
+        return False
+    return bool(_lib.load().semicrf_ffn_residual_bwd_supported(int(D), int(hidden)))
+
+
+class _FeedForwardTrain(torch.autograd.Function):
+    """The op behind train = "fused": semicrf_ffn_residual_train_fwd and semicrf_ffn_residual_bwd."""
+
+    @staticmethod
+    def forward(ctx, x, w1, b1, w2, b2, scale, eps, seed, p1, p2):
+        xd = x.detach()
+        if xd.shape[-1] != 1 and xd.stride(-1) != 1:
+            xd = xd.contiguous()
+        order = sorted(range(xd.dim() - 1), key=lambda i: -xd.stride(i))       # the tokens in the order of their addresses
+        out = torch.empty_like(xd)
+        views = _rows_views((xd, out), order)
+        if views is None:
+            xd = xd.contiguous()
+            out = torch.empty_like(xd)
+            order = list(range(xd.dim() - 1))
+            views = _rows_views((xd, out), order)
+        x3, o3 = views
+        ntok, D, hidden = x3.shape[0] * x3.shape[1], x3.shape[2], w1.shape[0]
+        z = torch.empty(ntok, hidden, dtype=torch.float32, device=xd.device)
+        y = torch.empty(ntok, D, dtype=torch.float32, device=xd.device)
+        w1, b1, w2, b2, scale = (t.detach().contiguous() for t in (w1, b1, w2, b2, scale))
+        FEED_FORWARD_TRAIN_LAST["fwd"] = (x3.data_ptr(), tuple(x3.shape), tuple(x3.stride()))
+        _lib.ops().ffn_residual_train_fwd(x3, w1, b1, w2, b2, scale, float(eps), seed, p1, p2, o3, z, y)
+        ctx.save_for_backward(xd, z, y, w1, w2, scale)
+        ctx.geom = (order, float(eps), seed, p1, p2)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout):
+        xd, z, y, w1, w2, scale = ctx.saved_tensors
+        order, eps, seed, p1, p2 = ctx.geom
+        dev = xd.device
+        hidden, D = w1.shape
+        dx = torch.empty_like(xd)
+        views = None
+        if dout.dtype == torch.float32 and (dout.shape[-1] == 1 or dout.stride(-1) == 1):
+            views = _rows_views((xd, dout, dx), order)
+        if views is None:                                       # dout laid out like dx: then the three merge as x and out did
+            dout = torch.empty_like(xd).copy_(dout)
+            views = _rows_views((xd, dout, dx), order)
+        x3, g3, d3 = views
+        ntok = x3.shape[0] * x3.shape[1]
+        flat = torch.empty(2 * hidden * D + hidden + 2 * D, dtype=torch.float32, device=dev)
+        e1, e2, e3, e4 = hidden * D, hidden * D + hidden, 2 * hidden * D + hidden, 2 * hidden * D + hidden + D
+        dW1, db1, dW2, db2, dscale = flat[:e1].view(hidden, D), flat[e1:e2], flat[e2:e3].view(D, hidden), flat[e3:e4], flat[e4:]
+        if dev.type == "cpu":
+            ws = torch.empty(0, dtype=torch.uint8)
+        else:
+            ws = torch.empty(int(_lib.load().semicrf_ffn_residual_bwd_workspace_bytes(ntok, D, hidden)), dtype=torch.uint8, device=dev)
+        FEED_FORWARD_TRAIN_ROUTES["bwd"] += 1
+        FEED_FORWARD_TRAIN_LAST["bwd"] = (x3.data_ptr(), tuple(x3.shape), tuple(x3.stride()), g3.data_ptr(), tuple(g3.stride()))
+        _lib.ops().ffn_residual_bwd(g3, x3, z, y, w1, w2, scale, eps, seed, p1, p2, d3, dW1, db1, dW2, db2, dscale, ws)
+        need = ctx.needs_input_grad
+        grads = (dx, dW1, db1, dW2, db2, dscale)
+        return tuple(g if need[i] else None for i, g in enumerate(grads)) + (None, None, None, None)
+
+
+def _ffn_train(x, w1, b1, w2, b2, scale, eps, p_hidden, p_out, seed):
+    if seed is None:
+        if p_hidden > 0 or p_out > 0:
+            lo, hi = torch.randint(0, 1 << 32, (2,), dtype=torch.int64).tolist()       # the CPU default generator: no device sync
+            seed = (hi << 32) | lo
+        else:
+            seed = 0
+    return _FeedForwardTrain.apply(x, w1, b1, w2, b2, scale, float(eps), _seed_arg(seed), float(p_hidden), float(p_out))
+
+
+def feed_forward_residual(x, w1, b1, w2, b2, scale, eps=1e-6, route="fused", bf16=DEFAULT_FEED_FORWARD_BF16,
+                          train=DEFAULT_FEED_FORWARD_TRAIN, p_hidden=0.0, p_out=0.0, seed=None):
     """x + (W2 gelu(W1 rmsnorm(x) + b1) + b2) * scale per token: the feed-forward ResBlock in eval mode.  x [..., D] with a contiguous
     last dimension, any strides in front (a tensor whose rows cannot be handed over as two strides is made contiguous first); w1
     [hidden, D], b1 [hidden], w2 [D, hidden], b2 [D], scale [D] as nn.Linear and ResBlock hold them.  Returns [..., D], laid out in
@@ -446,18 +584,51 @@ def feed_forward_residual(x, w1, b1, w2, b2, scale, eps=1e-6, route="fused", bf1
     bf16 = "torch" (the default): the above.  bf16 = "fused", with route = "fused": bfloat16 x and parameters take the bf16 HIP op
     (form A); float32 x and parameters under torch.autocast(dtype=torch.bfloat16) take the same kernel on the float32 tensors
     (form B: bf16 operands, float32 biases, LayerScale and result); float32 outside autocast stays the float32 op; any other mix of
-    dtypes, and autocast to another dtype, is the stock route."""
+    dtypes, and autocast to another dtype, is the stock route.
+
+    train = "torch" (the default): the above.  train = "fused", with route = "fused": a call that wants a gradient (grad mode on, x or
+    a parameter requires grad) on float32 tensors of one device, outside autocast, with a supported shape is the HIP op in its training
+    mode and its HIP backward (semicrf_ffn_residual_train_fwd / _bwd; the host mirrors on the CPU): once differentiable (a second
+    differentiation raises) w.r.t. x, w1, b1, w2, b2 and scale, every gradient bit-identical from run to run.  FEED_FORWARD_TRAIN_ROUTES
+    counts the gradient-wanting calls made with train = "fused".
+
+    p_hidden, p_out (default 0): the block in TRAINING mode, out = x + dropout(W2 dropout(gelu(..)) + b2) * scale.  On the fused
+    training route element (token i, column j) is kept iff feed_forward_dropout_mask(seed, ...)[.][i, j]: a stateless function of
+    (seed, i, j), so a token's output does not depend on the other tokens.  seed = None draws one value per call from torch's CPU
+    default generator when something drops (torch.manual_seed makes runs reproducible, and torch.utils.checkpoint's RNG preservation
+    reproduces the mask on recomputation; nothing waits for the device); an explicit seed makes the call reproducible.  The seed is a
+    HOST value: a call captured in a HIP graph replays one and the same mask.  On every other route the two dropouts are
+    F.dropout's."""
     if route not in FEED_FORWARD_KINDS:
         raise ValueError(f"route must be one of {FEED_FORWARD_KINDS}, not {route!r}")
     if bf16 not in FEED_FORWARD_BF16_KINDS:
         raise ValueError(f"bf16 must be one of {FEED_FORWARD_BF16_KINDS}, not {bf16!r}")
+    if train not in FEED_FORWARD_TRAIN_KINDS:
+        raise ValueError(f"train must be one of {FEED_FORWARD_TRAIN_KINDS}, not {train!r}")
+    drops = p_hidden > 0 or p_out > 0
+
+    def stock():
+        if not drops:
+            return feed_forward_torch(x, w1, b1, w2, b2, scale, eps)
+        xn = x * torch.rsqrt(x.pow(2).mean(dim=-1, keepdim=True) + eps)
+        return x + F.dropout(F.linear(F.dropout(F.gelu(F.linear(xn, w1, b1)), p_hidden), w2, b2), p_out) * scale
+
     if route == "torch":
         FEED_FORWARD_ROUTES["torch"] += 1
-        return feed_forward_torch(x, w1, b1, w2, b2, scale, eps)
-    op, is16 = _ffn_pick((x, w1, b1, w2, b2, scale), bf16)
+        return stock()
+    ts = (x, w1, b1, w2, b2, scale)
+    if train == "fused" and torch.is_grad_enabled() and any(t.requires_grad for t in ts):
+        if _ffn_train_applies(*ts, p_hidden, p_out):
+            FEED_FORWARD_TRAIN_ROUTES["fused"] += 1
+            FEED_FORWARD_ROUTES["fused"] += 1
+            return _ffn_train(*ts, eps, p_hidden, p_out, seed)
+        FEED_FORWARD_TRAIN_ROUTES["torch"] += 1
+    op, is16 = _ffn_pick(ts, bf16)
+    if drops:
+        op = None
     _ffn_count(op, is16)
     if op is None:
-        return feed_forward_torch(x, w1, b1, w2, b2, scale, eps)
+        return stock()
     return _ffn_fused(x, w1, b1, w2, b2, scale, eps, op)
 
 
@@ -524,7 +695,12 @@ class ResBlock(nn.Module):
     in every other case.
     feedForwardBf16: "torch" (the default: the above) or "fused": where feedForward = "fused" and its conditions hold, a block whose
     input and parameters are all bfloat16 is the bf16 HIP op, and a float32 block under bfloat16 autocast is the same kernel on its
-    float32 tensors (feed_forward_residual's bf16 = "fused")."""
+    float32 tensors (feed_forward_residual's bf16 = "fused").
+    feedForwardTrain: "torch" (the default: the above) or "fused": where feedForward = "fused" and the module is the feed-forward
+    sequence, a call that wants a gradient -- with its dropouts active or not -- is feed_forward_residual's train = "fused" route
+    (the HIP op in training mode and its HIP backward) on float32 tensors outside autocast with a supported shape and no extra
+    arguments; p comes from module[2] and self.dropout where they are in training mode, else 0.  bfloat16, autocast, extra
+    arguments and an unsupported shape take the stock expression."""
 
     def __init__(self, module, size, prenorm=True, dropoutProb=0.0):
         super().__init__()
@@ -534,6 +710,7 @@ class ResBlock(nn.Module):
         self.dropout = nn.Dropout(dropoutProb)
         self.feedForward = DEFAULT_FEED_FORWARD
         self.feedForwardBf16 = DEFAULT_FEED_FORWARD_BF16
+        self.feedForwardTrain = DEFAULT_FEED_FORWARD_TRAIN
 
     def is_feed_forward(self) -> bool:
         """The module is the Linear, GELU (exact), Dropout, Linear sequence of _feed_forward."""
@@ -546,10 +723,21 @@ class ResBlock(nn.Module):
         """The fused op's answer, or None for the stock expression; counts the call either way."""
         if self.feedForwardBf16 not in FEED_FORWARD_BF16_KINDS:
             raise ValueError(f"feedForwardBf16 must be one of {FEED_FORWARD_BF16_KINDS}, not {self.feedForwardBf16!r}")
+        kind = getattr(self, "feedForwardTrain", DEFAULT_FEED_FORWARD_TRAIN)
+        if kind not in FEED_FORWARD_TRAIN_KINDS:
+            raise ValueError(f"feedForwardTrain must be one of {FEED_FORWARD_TRAIN_KINDS}, not {kind!r}")
         op, is16 = None, False
         if self.feedForward == "fused" and self.is_feed_forward():
             m = self.module
             params = (m[0].weight, m[0].bias, m[3].weight, m[3].bias, self.scale)
+            if kind == "fused" and torch.is_grad_enabled() and any(t.requires_grad for t in (x, *params)):
+                p1 = float(m[2].p) if m[2].training else 0.0
+                p2 = float(self.dropout.p) if self.dropout.training else 0.0
+                if not args and _ffn_train_applies(x, *params, p1, p2):
+                    FEED_FORWARD_TRAIN_ROUTES["fused"] += 1
+                    FEED_FORWARD_ROUTES["fused"] += 1
+                    return _ffn_train(x, *params, self.norm.eps, p1, p2, None)
+                FEED_FORWARD_TRAIN_ROUTES["torch"] += 1
             op, is16 = _ffn_pick((x, *params), self.feedForwardBf16)
             if args or (self.training and (self.dropout.p > 0 or m[2].p > 0)):
                 op = None
@@ -728,6 +916,18 @@ class BasicBlock(nn.Module):
         for m in self.feed_forward_blocks():
             m.feedForwardBf16 = kind
 
+    @property
+    def feedForwardTrain(self):
+        kinds = {getattr(m, "feedForwardTrain", DEFAULT_FEED_FORWARD_TRAIN) for m in self.feed_forward_blocks()}
+        return kinds.pop() if len(kinds) == 1 else ("mixed" if kinds else DEFAULT_FEED_FORWARD_TRAIN)
+
+    @feedForwardTrain.setter
+    def feedForwardTrain(self, kind):
+        if kind not in FEED_FORWARD_TRAIN_KINDS:
+            raise ValueError(f"feedForwardTrain must be one of {FEED_FORWARD_TRAIN_KINDS}, not {kind!r}")
+        for m in self.feed_forward_blocks():
+            m.feedForwardTrain = kind
+
     def forward(self, x, mem=None, crossAttn=False):
         nT, nF = x.shape[-3], x.shape[-2]
         if mem is None:
@@ -875,6 +1075,18 @@ class Backbone(nn.Module):
             raise ValueError(f"feedForwardBf16 must be one of {FEED_FORWARD_BF16_KINDS}, not {kind!r}")
         for m in self.feed_forward_blocks():
             m.feedForwardBf16 = kind
+
+    @property
+    def feedForwardTrain(self):
+        kinds = {getattr(m, "feedForwardTrain", DEFAULT_FEED_FORWARD_TRAIN) for m in self.feed_forward_blocks()}
+        return kinds.pop() if len(kinds) == 1 else ("mixed" if kinds else DEFAULT_FEED_FORWARD_TRAIN)
+
+    @feedForwardTrain.setter
+    def feedForwardTrain(self, kind):
+        if kind not in FEED_FORWARD_TRAIN_KINDS:
+            raise ValueError(f"feedForwardTrain must be one of {FEED_FORWARD_TRAIN_KINDS}, not {kind!r}")
+        for m in self.feed_forward_blocks():
+            m.feedForwardTrain = kind
 
     def tokens(self, x, outputIndices):
         """The input of the first layer: [N, T', F' + P, 4 baseSize], the spectrogram tokens followed by the target tokens."""

@@ -235,6 +235,8 @@ size_t semicrf_workspace_bytes(int op, int T, int B)
         case SEMICRF_OP_ATTRIBUTE_HEADS: return attr_heads_workspace_bytes(T, 64 * ((B + 63) / 64 + 1), 1, 128, 1);
         // T = rows, B = Hv + Ho: a bound for 3 D <= B and at most 128 outputs a head (every term grows with D, the hidden sizes, the outputs)
         case SEMICRF_OP_ATTRIBUTE_HEADS_BWD: return attr_heads_bwd_workspace_bytes(T, (B + 2) / 3, B, 1, 128, 128);
+        // T = tokens, B = hidden: a bound for every supported D (every term grows with D)
+        case SEMICRF_OP_FFN_RESIDUAL_BWD: return ffn_bwd_workspace_bytes(T, ffn::FFN_MAX_D, B);
         default: return 0;
     }
 }
@@ -1432,6 +1434,115 @@ int semicrf_ffn_residual(const float* x, float* out, int64_t n0, int64_t n1, int
     SEMICRF_CHECK_ARG(xb + (uintptr_t)xext * 4 <= ob || ob + (uintptr_t)oext * 4 <= xb, "ffn_residual: `out` overlaps `x`");
     launch_ffn_residual(x, out, n0, n1, st[0], st[1], st[2], st[3], D, hidden, W1, b1, W2, b2, scale, eps, (hipStream_t)stream);
     SEMICRF_CHECK_LAUNCH("semicrf_ffn_residual");
+    return SEMICRF_OK;
+}
+
+// the checks the fp32 entry points share: sizes, pointers, the two views `in` (read) and `out` (written) -- `what` names the call
+static int ffn_f32_check(const char* what, int64_t n0, int64_t n1, int D, int hidden, const long long st_in[2], const long long st_out[2])
+{
+    SEMICRF_CHECK_ARG(ffn::supported(D, hidden),
+                      "%s: D=%d hidden=%d is outside the supported set (D a multiple of 8 in [%d, %d]; hidden a multiple of 8 in "
+                      "[%d, %d]): see semicrf_ffn_residual_supported", what, D, hidden, ffn::FFN_MIN_D, ffn::FFN_MAX_D, ffn::FFN_MIN_H,
+                      ffn::FFN_MAX_H);
+    SEMICRF_CHECK_ARG(n0 >= 1 && n1 >= 1, "%s: n0=%lld n1=%lld must be >= 1", what, (long long)n0, (long long)n1);
+    SEMICRF_CHECK_ARG(n0 < (1ll << 37) && n1 < (1ll << 37) && n0 * n1 < (1ll << 37), "%s: n0 * n1 = %lld * %lld must stay below 2^37", what,
+                      (long long)n0, (long long)n1);
+    for (int i = 0; i < 2; ++i)
+        SEMICRF_CHECK_ARG(st_in[i] >= 0 && st_in[i] < (1ll << 40) && st_out[i] >= 0 && st_out[i] < (1ll << 40),
+                          "%s: stride %lld / %lld must be in [0, 2^40)", what, st_in[i], st_out[i]);
+    SEMICRF_CHECK_ARG((n0 == 1 || st_out[0] >= D) && (n1 == 1 || st_out[1] >= D), "%s: a row stride of the output view (%lld, %lld) is below D=%d",
+                      what, st_out[0], st_out[1], D);
+    return SEMICRF_OK;
+}
+static bool ffn_ranges_overlap(const void* a, long long na, const void* b, long long nb)     // element counts of fp32
+{
+    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+    return !(pa + (uintptr_t)na * 4 <= pb || pb + (uintptr_t)nb * 4 <= pa);
+}
+static int ffn_p_check(const char* what, double p1, double p2)
+{
+    SEMICRF_CHECK_ARG(p1 >= 0.0 && p1 < 1.0 && p2 >= 0.0 && p2 < 1.0, "%s: dropout probabilities p_hidden=%g p_out=%g must lie in [0, 1)", what, p1,
+                      p2);
+    return SEMICRF_OK;
+}
+
+int semicrf_ffn_residual_train_fwd(const float* x, float* out, float* z, float* y, int64_t n0, int64_t n1, int64_t x_stride_0,
+                                   int64_t x_stride_1, int64_t out_stride_0, int64_t out_stride_1, int D, int hidden, const float* W1,
+                                   const float* b1, const float* W2, const float* b2, const float* scale, float eps, uint64_t seed,
+                                   double p_hidden, double p_out, semicrf_stream_t stream)
+{
+    const long long si[2] = {n0 > 1 ? x_stride_0 : 0, n1 > 1 ? x_stride_1 : 0}, so[2] = {n0 > 1 ? out_stride_0 : 0, n1 > 1 ? out_stride_1 : 0};
+    if (const int rc = ffn_f32_check("ffn_residual_train_fwd", n0, n1, D, hidden, si, so)) return rc;
+    if (const int rc = ffn_p_check("ffn_residual_train_fwd", p_hidden, p_out)) return rc;
+    SEMICRF_CHECK_ARG(x && out && z && y && W1 && b1 && W2 && b2 && scale, "ffn_residual_train_fwd: x/out/z/y/W1/b1/W2/b2/scale must be non-NULL");
+    SEMICRF_CHECK_ARG((((uintptr_t)x | (uintptr_t)out | (uintptr_t)z | (uintptr_t)y | (uintptr_t)W1 | (uintptr_t)b1 | (uintptr_t)W2 | (uintptr_t)b2 |
+                        (uintptr_t)scale) & 3) == 0, "ffn_residual_train_fwd: every pointer must be 4-byte aligned");
+    const long long ntok = n0 * n1;
+    const long long xext = (n0 - 1) * si[0] + (n1 - 1) * si[1] + D, oext = (n0 - 1) * so[0] + (n1 - 1) * so[1] + D;
+    SEMICRF_CHECK_ARG(!ffn_ranges_overlap(x, xext, out, oext) && !ffn_ranges_overlap(x, xext, z, ntok * hidden) &&
+                      !ffn_ranges_overlap(x, xext, y, ntok * D) && !ffn_ranges_overlap(out, oext, z, ntok * hidden) &&
+                      !ffn_ranges_overlap(out, oext, y, ntok * D) && !ffn_ranges_overlap(z, ntok * hidden, y, ntok * D),
+                      "ffn_residual_train_fwd: x, out, z and y must not overlap");
+    launch_ffn_residual_train(x, out, n0, n1, si[0], si[1], so[0], so[1], D, hidden, W1, b1, W2, b2, scale, eps, seed, p_hidden, p_out, z, y,
+                              (hipStream_t)stream);
+    SEMICRF_CHECK_LAUNCH("semicrf_ffn_residual_train_fwd");
+    return SEMICRF_OK;
+}
+
+int semicrf_ffn_residual_bwd_supported(int D, int hidden) { return ffn::supported(D, hidden) ? 1 : 0; }
+
+size_t semicrf_ffn_residual_bwd_workspace_bytes(int64_t tokens, int D, int hidden)
+{
+    if (tokens < 1 || tokens >= (1ll << 37) || !ffn::supported(D, hidden)) return 0;
+    return ffn_bwd_workspace_bytes(tokens, D, hidden);
+}
+
+int semicrf_ffn_residual_bwd(const float* dout, const float* x, const float* z, const float* y, int64_t n0, int64_t n1, int64_t dout_stride_0,
+                             int64_t dout_stride_1, int64_t x_stride_0, int64_t x_stride_1, int64_t dx_stride_0, int64_t dx_stride_1, int D,
+                             int hidden, const float* W1, const float* W2, const float* scale, float eps, uint64_t seed, double p_hidden,
+                             double p_out, float* dx, float* dW1, float* db1, float* dW2, float* db2, float* dscale, void* ws, size_t ws_bytes,
+                             semicrf_stream_t stream)
+{
+    const long long sg[2] = {n0 > 1 ? dout_stride_0 : 0, n1 > 1 ? dout_stride_1 : 0}, sx[2] = {n0 > 1 ? x_stride_0 : 0, n1 > 1 ? x_stride_1 : 0};
+    const long long sd[2] = {n0 > 1 ? dx_stride_0 : 0, n1 > 1 ? dx_stride_1 : 0};
+    if (const int rc = ffn_f32_check("ffn_residual_bwd", n0, n1, D, hidden, sg, sd)) return rc;
+    if (const int rc = ffn_f32_check("ffn_residual_bwd", n0, n1, D, hidden, sx, sd)) return rc;
+    if (const int rc = ffn_p_check("ffn_residual_bwd", p_hidden, p_out)) return rc;
+    const long long ntok = n0 * n1;
+    SEMICRF_CHECK_ARG(ntok <= 65535ll * SEMICRF_FFN_BWD_ROW_CHUNK, "ffn_residual_bwd: n0 * n1 = %lld: more than 65535 row chunks", ntok);
+    SEMICRF_CHECK_ARG(dout && x && z && y && W1 && W2 && scale, "ffn_residual_bwd: dout/x/z/y/W1/W2/scale must be non-NULL");
+    SEMICRF_CHECK_ARG(dx && dW1 && db1 && dW2 && db2 && dscale, "ffn_residual_bwd: dx/dW1/db1/dW2/db2/dscale must be non-NULL");
+    SEMICRF_CHECK_ARG((((uintptr_t)dout | (uintptr_t)x | (uintptr_t)z | (uintptr_t)y | (uintptr_t)W1 | (uintptr_t)W2 | (uintptr_t)scale | (uintptr_t)dx |
+                        (uintptr_t)dW1 | (uintptr_t)db1 | (uintptr_t)dW2 | (uintptr_t)db2 | (uintptr_t)dscale) & 3) == 0,
+                      "ffn_residual_bwd: every pointer must be 4-byte aligned");
+    const long long gext = (n0 - 1) * sg[0] + (n1 - 1) * sg[1] + D, xext = (n0 - 1) * sx[0] + (n1 - 1) * sx[1] + D;
+    const long long dext = (n0 - 1) * sd[0] + (n1 - 1) * sd[1] + D;
+    SEMICRF_CHECK_ARG(!ffn_ranges_overlap(dx, dext, dout, gext) && !ffn_ranges_overlap(dx, dext, x, xext) &&
+                      !ffn_ranges_overlap(dx, dext, z, ntok * hidden) && !ffn_ranges_overlap(dx, dext, y, ntok * D),
+                      "ffn_residual_bwd: `dx` overlaps dout, x, z or y");
+    const size_t need = ffn_bwd_workspace_bytes(ntok, D, hidden);
+    SEMICRF_CHECK_ARG(ws && ((uintptr_t)ws & 3) == 0, "ffn_residual_bwd: ws must be non-NULL and 4-byte aligned");
+    if (ws_bytes < need) {
+        set_error("workspace too small for ffn_residual_bwd: %zu bytes given, semicrf_ffn_residual_bwd_workspace_bytes says %zu", ws_bytes, need);
+        return SEMICRF_EWORKSPACE;
+    }
+    launch_ffn_residual_bwd(dout, x, z, y, n0, n1, sg[0], sg[1], sx[0], sx[1], sd[0], sd[1], D, hidden, W1, W2, scale, eps, seed, p_hidden, p_out, dx,
+                            dW1, db1, dW2, db2, dscale, (float*)ws, (hipStream_t)stream);
+    SEMICRF_CHECK_LAUNCH("semicrf_ffn_residual_bwd");
+    return SEMICRF_OK;
+}
+
+int semicrf_ffn_dropout_mask(uint64_t seed, int64_t rows, int D, int hidden, double p_hidden, double p_out, unsigned char* mask_hidden,
+                             unsigned char* mask_out, semicrf_stream_t stream)
+{
+    SEMICRF_CHECK_ARG(D >= 1 && D < (1 << 20) && hidden >= 1 && hidden < (1 << 20), "ffn_dropout_mask: D=%d hidden=%d out of range", D, hidden);
+    SEMICRF_CHECK_ARG(rows >= 0 && rows < (1ll << 37) && (rows + 3) / 4 * ((long long)D + hidden) < (1ll << 38),
+                      "ffn_dropout_mask: rows=%lld too large", (long long)rows);
+    if (const int rc = ffn_p_check("ffn_dropout_mask", p_hidden, p_out)) return rc;
+    if (rows == 0) return SEMICRF_OK;
+    SEMICRF_CHECK_ARG(mask_hidden && mask_out, "ffn_dropout_mask: mask_hidden/mask_out must be non-NULL");
+    launch_ffn_mask(seed, rows, D, hidden, p_hidden, p_out, mask_hidden, mask_out, (hipStream_t)stream);
+    SEMICRF_CHECK_LAUNCH("semicrf_ffn_dropout_mask");
     return SEMICRF_OK;
 }
 

@@ -1692,8 +1692,10 @@ void axial_attention_bf16_bwd(const uint16_t* q, const uint16_t* k, const uint16
 // rs = 1 / sqrt(ss / D + eps), xn = x rs, the chain of W1 xn over k ascending from +0 (fmaf), + b1, gelu, per hidden chunk the chain of
 // W2 g over its columns ascending from +0 (on over the zero padding of the last chunk), the chunks' sums added in ascending order from
 // +0, (+ b2) * scale, + x.  Only erf and erfc differ from the device's.
-void ffn_residual(const float* x, float* out, int64_t n0, int64_t n1, int64_t xs0, int64_t xs1, int64_t os0, int64_t os1, int D, int H,
-                  const float* W1, const float* b1, const float* W2, const float* b2, const float* scale, float eps)
+// drop / zs / ys: the training mode (z and y saved, both dropouts), NULL in eval mode
+static void ffn_residual_any(const float* x, float* out, int64_t n0, int64_t n1, int64_t xs0, int64_t xs1, int64_t os0, int64_t os1, int D, int H,
+                             const float* W1, const float* b1, const float* W2, const float* b2, const float* scale, float eps,
+                             const semicrf::ffn::DropoutParams* drop, float* zs, float* ys)
 {
     using namespace semicrf::ffn;
     const int64_t ntok = n0 * n1;
@@ -1716,7 +1718,14 @@ void ffn_residual(const float* x, float* out, int64_t n0, int64_t n1, int64_t xs
                     const float* w = W1 + (int64_t)(j0 + j) * D;
                     float h = 0.0f;
                     for (int k = 0; k < D; ++k) h = fmaf(xn[k], w[k], h);
-                    g[j] = semicrf::attr_heads::gelu<float>(h + b1[j0 + j]);
+                    if (drop) {
+                        const float zz = h + b1[j0 + j];
+                        zs[t * H + j0 + j] = zz;
+                        const float a = semicrf::attr_heads::gelu<float>(zz);
+                        g[j] = keep(*drop, 0, t, j0 + j) ? (drop->on[0] ? a * drop->scale[0] : a) : 0.0f;
+                    } else {
+                        g[j] = semicrf::attr_heads::gelu<float>(h + b1[j0 + j]);
+                    }
                 }
                 for (int n = 0; n < D; ++n) {
                     const float* w = W2 + (int64_t)n * H + j0;
@@ -1726,9 +1735,161 @@ void ffn_residual(const float* x, float* out, int64_t n0, int64_t n1, int64_t xs
                     acc[n] += a;                             // chunks ascending
                 }
             }
-            for (int n = 0; n < D; ++n) ot[n] = epilogue(xt[n], acc[n], b2[n], scale[n]);
+            if (drop) {
+                for (int n = 0; n < D; ++n) {
+                    const float yy = acc[n] + b2[n];
+                    ys[t * D + n] = yy;
+                    ot[n] = xt[n] + (keep(*drop, 1, t, n) ? (drop->on[1] ? yy * drop->scale[1] : yy) : 0.0f) * scale[n];
+                }
+            } else {
+                for (int n = 0; n < D; ++n) ot[n] = epilogue(xt[n], acc[n], b2[n], scale[n]);
+            }
         }
     }
+}
+
+void ffn_residual(const float* x, float* out, int64_t n0, int64_t n1, int64_t xs0, int64_t xs1, int64_t os0, int64_t os1, int D, int H,
+                  const float* W1, const float* b1, const float* W2, const float* b2, const float* scale, float eps)
+{
+    ffn_residual_any(x, out, n0, n1, xs0, xs1, os0, os1, D, H, W1, b1, W2, b2, scale, eps, nullptr, nullptr, nullptr);
+}
+
+// ---- the block in training (semicrf_ffn_residual_train_fwd / _bwd / semicrf_ffn_dropout_mask) ----------------------------------------------
+void ffn_residual_train_fwd(const float* x, float* out, float* z, float* y, int64_t n0, int64_t n1, int64_t xs0, int64_t xs1, int64_t os0,
+                            int64_t os1, int D, int H, const float* W1, const float* b1, const float* W2, const float* b2, const float* scale,
+                            float eps, uint64_t seed, double p1, double p2)
+{
+    const semicrf::ffn::DropoutParams drop = semicrf::attr_heads::dropout_params(seed, p1, p2);
+    ffn_residual_any(x, out, n0, n1, xs0, xs1, os0, os1, D, H, W1, b1, W2, b2, scale, eps, &drop, z, y);
+}
+
+void ffn_dropout_mask(uint64_t seed, int64_t rows, int D, int H, double p1, double p2, unsigned char* mask_hidden, unsigned char* mask_out)
+{
+    using namespace semicrf::ffn;
+    const DropoutParams drop = semicrf::attr_heads::dropout_params(seed, p1, p2);
+#pragma omp parallel for schedule(static)
+    for (int64_t i = 0; i < rows; ++i) {
+        for (int j = 0; j < H; ++j) mask_hidden[i * H + j] = keep(drop, 0, i, j) ? 1 : 0;
+        for (int n = 0; n < D; ++n) mask_out[i * D + n] = keep(drop, 1, i, n) ? 1 : 0;
+    }
+}
+
+// The backward in the order of operations of ffn_bwd.hip (ffn_math.h), in fp32; only erf, erfc and exp differ from the device's.
+void ffn_residual_bwd(const float* dout, const float* x, const float* z, const float* y, int64_t n0, int64_t n1, int64_t gs0, int64_t gs1,
+                      int64_t xs0, int64_t xs1, int64_t ds0, int64_t ds1, int D, int H, const float* W1, const float* W2, const float* scale,
+                      float eps, uint64_t seed, double p1, double p2, float* dx, float* dW1, float* db1, float* dW2, float* db2, float* dscale)
+{
+    using namespace semicrf::ffn;
+    using semicrf::attr_heads::gelu;
+    using semicrf::attr_heads::gelu_grad;
+    const DropoutParams drop = semicrf::attr_heads::dropout_params(seed, p1, p2);
+    const int64_t ntok = n0 * n1;
+    auto off = [&](int64_t i, int64_t s0, int64_t s1) { return (i / n1) * s0 + (i % n1) * s1; };
+    auto m1 = [&](int64_t i, int j, float v) { return keep(drop, 0, i, j) ? (drop.on[0] ? v * drop.scale[0] : v) : 0.0f; };
+    auto m2 = [&](int64_t i, int n, float v) { return keep(drop, 1, i, n) ? (drop.on[1] ? v * drop.scale[1] : v) : 0.0f; };
+    std::vector<float> rs((size_t)ntok), dy((size_t)ntok * D), dz((size_t)ntok * H), xn((size_t)ntok * D), av((size_t)ntok * H);
+    // a chain over the contraction values k of `term`, in sub-chains of FFN_BWD_KSUB, padded with 0 * 0 up to a multiple of FFN_BWD_KSTEP
+    auto chain = [&](int K, auto term) {
+        float acc = 0.0f;
+        for (int k0 = 0; k0 < K; k0 += FFN_BWD_KSUB) {
+            const int k1 = std::min(K, k0 + FFN_BWD_KSUB);
+            float part = 0.0f;
+            for (int k = k0; k < k1; ++k) part = term(k, part);
+            if (k1 == K && K % FFN_BWD_KSTEP) part = fmaf(0.0f, 0.0f, part);
+            acc += part;
+        }
+        return acc;
+    };
+#pragma omp parallel for schedule(static)
+    for (int64_t i = 0; i < ntok; ++i) {
+        const float* xt = x + off(i, xs0, xs1);
+        const float* gt = dout + off(i, gs0, gs1);
+        float s[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        for (int k = 0; k < D; ++k) s[k & 3] = fmaf(xt[k], xt[k], s[k & 3]);
+        rs[i] = rs_of(sumsq_combine(s[0], s[1], s[2], s[3]), D, eps);
+        for (int k = 0; k < D; ++k) xn[i * D + k] = xt[k] * rs[i];
+        for (int n = 0; n < D; ++n) dy[i * D + n] = m2(i, n, gt[n] * scale[n]);
+        for (int j = 0; j < H; ++j) {
+            const float da = chain(D, [&](int n, float p) { return fmaf(dy[i * D + n], W2[(int64_t)n * H + j], p); });
+            dz[i * H + j] = m1(i, j, da) * gelu_grad<float>(z[i * H + j]);
+            av[i * H + j] = m1(i, j, gelu<float>(z[i * H + j]));
+        }
+        // dx
+        std::vector<float> dxn((size_t)D);
+        for (int k = 0; k < D; ++k) dxn[k] = chain(H, [&](int j, float p) { return fmaf(dz[i * H + j], W1[(int64_t)j * D + k], p); });
+        const int NB = (D + 63) / 64;
+        float T[2];
+        for (int cw = 0; cw < 2; ++cw) {
+            float v[32], w[32];
+            for (int c = 0; c < 32; ++c) {
+                float p = 0.0f;
+                for (int b = 0; b < NB; ++b) {
+                    const int col = (cw + 2 * b) * 32 + c;
+                    p = col < D ? fmaf(dxn[col], xn[i * D + col], p) : fmaf(0.0f, 0.0f, p);
+                }
+                v[c] = p;
+            }
+            for (int st = 1; st < 32; st <<= 1) {
+                for (int c = 0; c < 32; ++c) w[c] = v[c] + v[c ^ st];
+                for (int c = 0; c < 32; ++c) v[c] = w[c];
+            }
+            T[cw] = v[0];
+        }
+        const float t = T[0] + T[1];
+        float* dt = dx + off(i, ds0, ds1);
+        for (int k = 0; k < D; ++k) dt[k] = dx_of(gt[k], rs[i], dxn[k], xn[i * D + k], t, D);
+    }
+    // the sums over tokens: per chunk a plane, the planes added in ascending order starting from plane 0
+    const int64_t nch = (ntok + FFN_BWD_ROWS - 1) / FFN_BWD_ROWS;
+    // C[m][n] = sum_i A[i][m] B[i][n] into out [Md][Nd]
+    auto colgemm = [&](const float* A, int Md, const float* B, int Nd, float* out) {
+#pragma omp parallel for schedule(static)
+        for (int m = 0; m < Md; ++m) {
+            std::vector<float> acc((size_t)Nd), part((size_t)Nd);
+            for (int64_t ch = 0; ch < nch; ++ch) {
+                const int64_t r0 = ch * FFN_BWD_ROWS, r1 = std::min(ntok, r0 + FFN_BWD_ROWS);
+                std::fill(acc.begin(), acc.end(), 0.0f);
+                for (int64_t s0 = r0; s0 < r1; s0 += FFN_BWD_RSUB) {
+                    const int64_t s1 = std::min(r1, s0 + FFN_BWD_RSUB);
+                    std::fill(part.begin(), part.end(), 0.0f);
+                    for (int64_t i = s0; i < s1; ++i) {
+                        const float a = A[i * Md + m];
+                        const float* b = B + i * Nd;
+                        for (int n = 0; n < Nd; ++n) part[n] = fmaf(a, b[n], part[n]);
+                    }
+                    const bool pad = (s1 - r0) % FFN_BWD_RSTEP != 0;
+                    for (int n = 0; n < Nd; ++n) acc[n] += pad ? fmaf(0.0f, 0.0f, part[n]) : part[n];
+                }
+                float* o = out + (int64_t)m * Nd;
+                if (ch == 0) for (int n = 0; n < Nd; ++n) o[n] = acc[n];
+                else for (int n = 0; n < Nd; ++n) o[n] += acc[n];
+            }
+        }
+    };
+    colgemm(dy.data(), D, av.data(), H, dW2);
+    colgemm(dz.data(), H, xn.data(), D, dW1);
+    auto colsum = [&](int ncol, float* out, auto value) {
+#pragma omp parallel for schedule(static)
+        for (int c = 0; c < ncol; ++c) {
+            float total = 0.0f;
+            for (int64_t ch = 0; ch < nch; ++ch) {
+                const int64_t r0 = ch * FFN_BWD_ROWS, r1 = std::min(ntok, r0 + FFN_BWD_ROWS);
+                double sub[FFN_BWD_SUBSUMS];
+                for (int q = 0; q < FFN_BWD_SUBSUMS; ++q) {
+                    double t = 0.0;
+                    for (int64_t i = r0 + q; i < r1; i += FFN_BWD_SUBSUMS) t += (double)value(i, c);
+                    sub[q] = t;
+                }
+                double s = sub[0];
+                for (int q = 1; q < FFN_BWD_SUBSUMS; ++q) s += sub[q];
+                total = ch == 0 ? (float)s : total + (float)s;
+            }
+            out[c] = total;
+        }
+    };
+    colsum(H, db1, [&](int64_t i, int j) { return dz[i * H + j]; });
+    colsum(D, db2, [&](int64_t i, int n) { return dy[i * D + n]; });
+    colsum(D, dscale, [&](int64_t i, int n) { return dout[off(i, gs0, gs1) + n] * m2(i, n, y[i * D + n]); });
 }
 
 // ---- the bf16 feed-forward ResBlock (semicrf_ffn_residual_bf16, semicrf_ffn_residual_bf16_mixed) ----------------------------------------

@@ -90,6 +90,14 @@ void axial_attention_bf16_bwd(const uint16_t* q, const uint16_t* k, const uint16
 // (ffn_math.h); x and out [n0, n1, D] with their two element row strides; the caller has checked the supported set
 void ffn_residual(const float* x, float* out, int64_t n0, int64_t n1, int64_t xs0, int64_t xs1, int64_t os0, int64_t os1, int D, int H,
                   const float* W1, const float* b1, const float* W2, const float* b2, const float* scale, float eps);
+// the block in training (semicrf_ffn_residual_train_fwd / _bwd / semicrf_ffn_dropout_mask): the device's order of operations (ffn_math.h)
+void ffn_residual_train_fwd(const float* x, float* out, float* z, float* y, int64_t n0, int64_t n1, int64_t xs0, int64_t xs1, int64_t os0,
+                            int64_t os1, int D, int H, const float* W1, const float* b1, const float* W2, const float* b2, const float* scale,
+                            float eps, uint64_t seed, double p1, double p2);
+void ffn_residual_bwd(const float* dout, const float* x, const float* z, const float* y, int64_t n0, int64_t n1, int64_t gs0, int64_t gs1,
+                      int64_t xs0, int64_t xs1, int64_t ds0, int64_t ds1, int D, int H, const float* W1, const float* W2, const float* scale,
+                      float eps, uint64_t seed, double p1, double p2, float* dx, float* dW1, float* db1, float* dW2, float* db2, float* dscale);
+void ffn_dropout_mask(uint64_t seed, int64_t rows, int D, int H, double p1, double p2, unsigned char* mask_hidden, unsigned char* mask_out);
 // the bf16 feed-forward ResBlock (semicrf_ffn_residual_bf16 on bf16 tensors, semicrf_ffn_residual_bf16_mixed on fp32 tensors): the
 // chain of ffn_bf16_math.h per output element, both sums in fp32 ascending; the caller has checked the supported set
 void ffn_residual_bf16(const uint16_t* x, uint16_t* out, int64_t n0, int64_t n1, int64_t xs0, int64_t xs1, int64_t os0, int64_t os1, int D, int H,

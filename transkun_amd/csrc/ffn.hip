@@ -21,9 +21,15 @@
 //   both sets stay in registers for the whole walk
 // Epilogue: x + (acc + b2) * scale from Xs, stored by rows.  Ragged edges (rows past the last token, the last chunk of hidden, the
 // last column block of D) are exact zeros formed in registers.
+//
+// TRAIN (semicrf_ffn_residual_train_fwd): the same walk; z = h + b1 is stored [tokens][H] as it leaves the accumulators, a = gelu(z) * M1
+// goes to Gs in gelu's place, and the epilogue stores y = acc + b2 [tokens][D] and out = x + (y * M2) * scale.  One Philox call serves
+// the four accumulator rows r & 3 of a lane (tokens 4 q .. 4 q + 3 at one column).  The eval instantiations carry none of it.
 #include "common.h"
 #include "launchers.h"
 #include "ffn_math.h"
+
+#include <type_traits>
 
 namespace semicrf {
 
@@ -74,13 +80,15 @@ __device__ __forceinline__ float4 ffn_load4(const float* p, bool ok)
 
 // DB: column blocks of 32 that cover D (D in (32 (DB - 1), 32 DB]); up to D = 160 two workgroups share a CU
 // VEC: 16-byte loads (every base 16-byte aligned, every stride a multiple of four floats)
-template <int DB, bool VEC>
-__global__ __launch_bounds__(256, DB <= 5 ? 2 : 1) void ffn_residual_kernel(const float* __restrict__ x, float* __restrict__ out,
-                                                                          long long ntok, long long n1, long long xs0, long long xs1,
-                                                                          long long os0, long long os1, int D, int H,
-                                                                          const float* __restrict__ W1, const float* __restrict__ b1,
-                                                                          const float* __restrict__ W2, const float* __restrict__ b2,
-                                                                          const float* __restrict__ scale, float eps)
+struct FfnTrainArgs { float* z; float* y; DropoutParams drop; };
+struct FfnNoArgs {};
+
+// TRAIN at DB = 5 does not fit two workgroups' registers without scratch: one workgroup per CU there
+template <int DB, bool VEC, bool TRAIN>
+__global__ __launch_bounds__(256, DB <= (TRAIN ? 4 : 5) ? 2 : 1) void ffn_residual_kernel(
+    const float* __restrict__ x, float* __restrict__ out, long long ntok, long long n1, long long xs0, long long xs1, long long os0,
+    long long os1, int D, int H, const float* __restrict__ W1, const float* __restrict__ b1, const float* __restrict__ W2,
+    const float* __restrict__ b2, const float* __restrict__ scale, float eps, std::conditional_t<TRAIN, FfnTrainArgs, FfnNoArgs> tr)
 {
     constexpr int NB = (DB + 1) / 2;                         // column blocks per wave
     constexpr int NW = DB;                                   // float4 of a half tile per thread (64 (D / 2) / 4 / 256 = D / 32 <= DB)
@@ -280,9 +288,24 @@ __global__ __launch_bounds__(256, DB <= 5 ? 2 : 1) void ffn_residual_kernel(cons
         {
             float* const gw = Gs + lds_pos(col);
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = rt * 32 + ffn_acc_row(r, hh);
-                gw[row * FFN_LDG] = real ? gelu<float>(h[r] + bias) : 0.0f;
+            for (int g4 = 0; g4 < 4; ++g4) {
+                uint32_t draw[4] = {0u, 0u, 0u, 0u};
+                if constexpr (TRAIN) {
+                    const long long ib = row0 + rt * 32 + 8 * g4 + 4 * hh;          // a multiple of 4: rows ib .. ib + 3 are r & 3
+                    if (tr.drop.on[0] && real) dropout_draws(tr.drop.seed, 0u, (unsigned long long)ib >> 2, (uint32_t)(j0 + col), draw);
+                }
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const int r = 4 * g4 + u;
+                    const int row = rt * 32 + ffn_acc_row(r, hh);
+                    if constexpr (TRAIN) {
+                        const float zz = h[r] + bias;
+                        if (real && row0 + row < ntok) tr.z[(size_t)(row0 + row) * H + j0 + col] = zz;
+                        gw[row * FFN_LDG] = real ? masked(tr.drop, 0, draw[u], gelu<float>(zz)) : 0.0f;
+                    } else {
+                        gw[row * FFN_LDG] = real ? gelu<float>(h[r] + bias) : 0.0f;
+                    }
+                }
             }
         }
         __syncthreads();                                     // Gs is written, Ws (W1) is read
@@ -315,25 +338,63 @@ __global__ __launch_bounds__(256, DB <= 5 ? 2 : 1) void ffn_residual_kernel(cons
             const float bb = b2[n], sc = scale[n];
             const int xp = lds_pos(n);
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = rt * 32 + ffn_acc_row(r, hh);
-                const long long oo = roff[row];
-                if (oo >= 0) out[oo + n] = epilogue(Xs[row * ldx + xp], acc[i][r], bb, sc);
+            for (int g4 = 0; g4 < 4; ++g4) {
+                uint32_t draw[4] = {0u, 0u, 0u, 0u};
+                if constexpr (TRAIN) {
+                    const long long ib = row0 + rt * 32 + 8 * g4 + 4 * hh;
+                    if (tr.drop.on[1]) dropout_draws(tr.drop.seed, 1u, (unsigned long long)ib >> 2, (uint32_t)n, draw);
+                }
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const int r = 4 * g4 + u;
+                    const int row = rt * 32 + ffn_acc_row(r, hh);
+                    const long long oo = roff[row];
+                    if constexpr (TRAIN) {
+                        if (oo >= 0) {
+                            const float yy = acc[i][r] + bb;
+                            tr.y[(size_t)(row0 + row) * D + n] = yy;
+                            out[oo + n] = Xs[row * ldx + xp] + masked(tr.drop, 1, draw[u], yy) * sc;
+                        }
+                    } else {
+                        if (oo >= 0) out[oo + n] = epilogue(Xs[row * ldx + xp], acc[i][r], bb, sc);
+                    }
+                }
             }
         }
     }
 }
 
-template <int DB, bool VEC>
+template <int DB, bool VEC, bool TRAIN>
 static void ffn_launch_one(const float* x, float* out, long long ntok, long long n1, long long xs0, long long xs1, long long os0, long long os1,
                            int D, int H, const float* W1, const float* b1, const float* W2, const float* b2, const float* scale, float eps,
-                           hipStream_t stream)
+                           hipStream_t stream, std::conditional_t<TRAIN, FfnTrainArgs, FfnNoArgs> tr)
 {
     static PerDeviceOnce once;
     if (once.first())
-        (void)hipFuncSetAttribute((const void*)ffn_residual_kernel<DB, VEC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ffn_lds_bytes(DB * 32));
-    hipLaunchKernelGGL((ffn_residual_kernel<DB, VEC>), dim3((unsigned)((ntok + FFN_ROWS - 1) / FFN_ROWS)), dim3(256), ffn_lds_bytes(D), stream, x, out,
-                       ntok, n1, xs0, xs1, os0, os1, D, H, W1, b1, W2, b2, scale, eps);
+        (void)hipFuncSetAttribute((const void*)ffn_residual_kernel<DB, VEC, TRAIN>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)ffn_lds_bytes(DB * 32));
+    hipLaunchKernelGGL((ffn_residual_kernel<DB, VEC, TRAIN>), dim3((unsigned)((ntok + FFN_ROWS - 1) / FFN_ROWS)), dim3(256), ffn_lds_bytes(D), stream,
+                       x, out, ntok, n1, xs0, xs1, os0, os1, D, H, W1, b1, W2, b2, scale, eps, tr);
+}
+
+template <bool TRAIN>
+static void ffn_launch_any(const float* x, float* out, long long n0, long long n1, long long xs0, long long xs1, long long os0, long long os1,
+                           int D, int H, const float* W1, const float* b1, const float* W2, const float* b2, const float* scale, float eps,
+                           hipStream_t stream, std::conditional_t<TRAIN, FfnTrainArgs, FfnNoArgs> tr)
+{
+    // 16-byte loads: every base and every stride a multiple of four floats (D and H are multiples of 8)
+    const bool vec = ((((uintptr_t)x | (uintptr_t)W1 | (uintptr_t)W2) & 15) == 0) && ((xs0 | xs1) & 3) == 0;
+    const long long ntok = n0 * n1;
+#define SEMICRF_FFN_CASE(N)                                                                                                        \
+    case N:                                                                                                                        \
+        if (vec) ffn_launch_one<N, true, TRAIN>(x, out, ntok, n1, xs0, xs1, os0, os1, D, H, W1, b1, W2, b2, scale, eps, stream, tr);  \
+        else ffn_launch_one<N, false, TRAIN>(x, out, ntok, n1, xs0, xs1, os0, os1, D, H, W1, b1, W2, b2, scale, eps, stream, tr);     \
+        break
+    switch ((D + 31) / 32) {
+        SEMICRF_FFN_CASE(1); SEMICRF_FFN_CASE(2); SEMICRF_FFN_CASE(3); SEMICRF_FFN_CASE(4);
+        SEMICRF_FFN_CASE(5); SEMICRF_FFN_CASE(6); SEMICRF_FFN_CASE(7); SEMICRF_FFN_CASE(8);
+    }
+#undef SEMICRF_FFN_CASE
 }
 
 // the caller (api.hip) has checked the supported set, the pointers, the strides and n0 n1 < 2^37
@@ -341,19 +402,17 @@ void launch_ffn_residual(const float* x, float* out, long long n0, long long n1,
                          int D, int H, const float* W1, const float* b1, const float* W2, const float* b2, const float* scale, float eps,
                          hipStream_t stream)
 {
-    // 16-byte loads: every base and every stride a multiple of four floats (D and H are multiples of 8)
-    const bool vec = ((((uintptr_t)x | (uintptr_t)W1 | (uintptr_t)W2) & 15) == 0) && ((xs0 | xs1) & 3) == 0;
-    const long long ntok = n0 * n1;
-#define SEMICRF_FFN_CASE(N)                                                                                                        \
-    case N:                                                                                                                        \
-        if (vec) ffn_launch_one<N, true>(x, out, ntok, n1, xs0, xs1, os0, os1, D, H, W1, b1, W2, b2, scale, eps, stream);         \
-        else ffn_launch_one<N, false>(x, out, ntok, n1, xs0, xs1, os0, os1, D, H, W1, b1, W2, b2, scale, eps, stream);            \
-        break
-    switch ((D + 31) / 32) {
-        SEMICRF_FFN_CASE(1); SEMICRF_FFN_CASE(2); SEMICRF_FFN_CASE(3); SEMICRF_FFN_CASE(4);
-        SEMICRF_FFN_CASE(5); SEMICRF_FFN_CASE(6); SEMICRF_FFN_CASE(7); SEMICRF_FFN_CASE(8);
-    }
-#undef SEMICRF_FFN_CASE
+    ffn_launch_any<false>(x, out, n0, n1, xs0, xs1, os0, os1, D, H, W1, b1, W2, b2, scale, eps, stream, FfnNoArgs{});
+}
+
+// the training mode: also z [n0 n1][H] and y [n0 n1][D], dense, and the two dropouts of (seed, p1, p2)
+void launch_ffn_residual_train(const float* x, float* out, long long n0, long long n1, long long xs0, long long xs1, long long os0,
+                               long long os1, int D, int H, const float* W1, const float* b1, const float* W2, const float* b2,
+                               const float* scale, float eps, unsigned long long seed, double p1, double p2, float* z, float* y,
+                               hipStream_t stream)
+{
+    ffn_launch_any<true>(x, out, n0, n1, xs0, xs1, os0, os1, D, H, W1, b1, W2, b2, scale, eps, stream,
+                         FfnTrainArgs{z, y, attr_heads::dropout_params(seed, p1, p2)});
 }
 
 }  // namespace semicrf

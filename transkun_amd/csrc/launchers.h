@@ -84,6 +84,20 @@ void launch_ffn_residual(const float* x, float* out, long long n0, long long n1,
                          int D, int H, const float* W1, const float* b1, const float* W2, const float* b2, const float* scale, float eps,
                          hipStream_t stream);
 
+void launch_ffn_residual_train(const float* x, float* out, long long n0, long long n1, long long xs0, long long xs1, long long os0,
+                               long long os1, int D, int H, const float* W1, const float* b1, const float* W2, const float* b2,
+                               const float* scale, float eps, unsigned long long seed, double p1, double p2, float* z, float* y,
+                               hipStream_t stream);
+
+// ffn_bwd.hip
+size_t ffn_bwd_workspace_bytes(long long ntok, int D, int H);
+void launch_ffn_residual_bwd(const float* dout, const float* x, const float* z, const float* y, long long n0, long long n1, long long gs0,
+                             long long gs1, long long xs0, long long xs1, long long ds0, long long ds1, int D, int H, const float* W1,
+                             const float* W2, const float* scale, float eps, unsigned long long seed, double p1, double p2, float* dx,
+                             float* dW1, float* db1, float* dW2, float* db2, float* dscale, float* ws, hipStream_t stream);
+void launch_ffn_mask(unsigned long long seed, long long rows, int D, int H, double p1, double p2, unsigned char* mask_hidden,
+                     unsigned char* mask_out, hipStream_t stream);
+
 // ffn_bf16.hip
 void launch_ffn_residual_bf16(const uint16_t* x, uint16_t* out, long long n0, long long n1, long long xs0, long long xs1, long long os0, long long os1,
                               int D, int H, const uint16_t* W1, const uint16_t* b1, const uint16_t* W2, const uint16_t* b2, const uint16_t* scale,

@@ -1253,6 +1253,131 @@ void ffn_residual_cpu(Tensor x, Tensor W1, Tensor b1, Tensor W2, Tensor b2, Tens
     if (a.n0 == 0 || a.n1 == 0) return;
     ffn_on_host<float>(a, eps, &semicrf_cpu::ffn_residual, "ffn_residual");
 }
+// ---- the block in training (semicrf_ffn_residual_train_fwd / _bwd / semicrf_ffn_dropout_mask) -------------------------------------------
+// z [n0 n1, hidden], y [n0 n1, D] dense; seed: the 64 bits of an int
+void ffn_residual_train_fwd_op(Tensor x, Tensor W1, Tensor b1, Tensor W2, Tensor b2, Tensor scale, double eps, int64_t seed, double p_hidden,
+                               double p_out, Tensor out, Tensor z, Tensor y)
+{
+    Ctx c(x); c.same(x, W1, b1, W2, b2, scale, out, z, y);
+    const FfnArgs a = ffn_args(x, W1, b1, W2, b2, scale, out);
+    float* zp = f32w(z, a.n0 * a.n1 * a.H, "z");
+    float* yp = f32w(y, a.n0 * a.n1 * a.D, "y");
+    if (a.n0 == 0 || a.n1 == 0) return;
+    check(semicrf_ffn_residual_train_fwd((const float*)a.x, (float*)a.out, zp, yp, a.n0, a.n1, a.st[0], a.st[1], a.st[2], a.st[3], a.D, a.H,
+                                         (const float*)a.W1, (const float*)a.b1, (const float*)a.W2, (const float*)a.b2, (const float*)a.scale,
+                                         (float)eps, (uint64_t)seed, p_hidden, p_out, c.stream),
+          "semicrf_ffn_residual_train_fwd");
+}
+void ffn_residual_train_fwd_cpu(Tensor x, Tensor W1, Tensor b1, Tensor W2, Tensor b2, Tensor scale, double eps, int64_t seed, double p_hidden,
+                                double p_out, Tensor out, Tensor z, Tensor y)
+{
+    all_cpu(x, W1, b1, W2, b2, scale, out, z, y);
+    const FfnArgs a = ffn_args(x, W1, b1, W2, b2, scale, out);
+    float* zp = f32w(z, a.n0 * a.n1 * a.H, "z");
+    float* yp = f32w(y, a.n0 * a.n1 * a.D, "y");
+    STD_TORCH_CHECK(p_hidden >= 0.0 && p_hidden < 1.0 && p_out >= 0.0 && p_out < 1.0, "semicrf: dropout probabilities must lie in [0, 1)");
+    if (a.n0 == 0 || a.n1 == 0) return;
+    const int64_t xext = (a.n0 - 1) * a.st[0] + (a.n1 - 1) * a.st[1] + a.D, oext = (a.n0 - 1) * a.st[2] + (a.n1 - 1) * a.st[3] + a.D;
+    const float *xp = (const float*)a.x, *op = (const float*)a.out;
+    STD_TORCH_CHECK(xp + xext <= op || op + oext <= xp, "semicrf: ffn_residual_train_fwd: `out` overlaps `x`");
+    semicrf_cpu::ffn_residual_train_fwd(xp, (float*)a.out, zp, yp, a.n0, a.n1, a.st[0], a.st[1], a.st[2], a.st[3], a.D, a.H, (const float*)a.W1,
+                                        (const float*)a.b1, (const float*)a.W2, (const float*)a.b2, (const float*)a.scale, (float)eps,
+                                        (uint64_t)seed, p_hidden, p_out);
+}
+
+struct FfnBwdArgs {
+    const float *g, *x, *z, *y, *W1, *W2, *scale;
+    float *dx, *dW1, *db1, *dW2, *db2, *dscale;
+    int64_t n0, n1, st[6];           // dout, x, dx: two element row strides each
+    int D, H;
+};
+inline FfnBwdArgs ffn_bwd_args(const Tensor& dout, const Tensor& x, const Tensor& z, const Tensor& y, const Tensor& W1, const Tensor& W2,
+                               const Tensor& scale, double p_hidden, double p_out, const Tensor& dx, const Tensor& dW1, const Tensor& db1,
+                               const Tensor& dW2, const Tensor& db2, const Tensor& dscale)
+{
+    FfnBwdArgs a{};
+    const Tensor* views[3] = {&dout, &x, &dx};
+    STD_TORCH_CHECK(x.defined() && x.dim() == 3, "semicrf: `x` must be [n0, n1, D]");
+    STD_TORCH_CHECK(W1.defined() && W1.dim() == 2 && W2.defined() && W2.dim() == 2, "semicrf: `W1` must be [hidden, D], `W2` [D, hidden]");
+    const int64_t D = x.size(2), H = W1.size(0);
+    a.n0 = x.size(0); a.n1 = x.size(1);
+    STD_TORCH_CHECK(D >= 1 && D < (1 << 20) && H >= 1 && H < (1 << 20) && W1.size(1) == D && W2.size(0) == D && W2.size(1) == H,
+                    "semicrf: `W1` / `W2` do not have the shape of the call");
+    STD_TORCH_CHECK(semicrf_ffn_residual_bwd_supported((int)D, (int)H), "semicrf: ffn_residual_bwd does not support D=", D, " hidden=", H,
+                    " (semicrf_ffn_residual_bwd_supported)");
+    STD_TORCH_CHECK(p_hidden >= 0.0 && p_hidden < 1.0 && p_out >= 0.0 && p_out < 1.0, "semicrf: dropout probabilities must lie in [0, 1)");
+    for (int v = 0; v < 3; ++v) {
+        const Tensor& t = *views[v];
+        STD_TORCH_CHECK(t.defined() && t.dim() == 3 && t.scalar_type() == ScalarType::Float, "semicrf: `dout`, `x` and `dx` must be float32 [n0, n1, D]");
+        STD_TORCH_CHECK(t.size(0) == a.n0 && t.size(1) == a.n1 && t.size(2) == D && t.stride(2) == 1,
+                        "semicrf: `dout`, `x` and `dx` must share one shape and have a contiguous last dimension");
+        for (int j = 0; j < 2; ++j) {
+            a.st[2 * v + j] = t.size(j) > 1 ? t.stride(j) : 0;
+            STD_TORCH_CHECK(a.st[2 * v + j] >= 0, "semicrf: negative stride");
+        }
+    }
+    STD_TORCH_CHECK((a.n0 <= 1 || a.st[4] >= D) && (a.n1 <= 1 || a.st[5] >= D), "semicrf: `dx` must not repeat or interleave its rows");
+    a.D = (int)D; a.H = (int)H;
+    const int64_t ntok = a.n0 * a.n1;
+    a.z = f32(z, ntok * H, "z"); a.y = f32(y, ntok * D, "y");
+    a.W1 = f32(W1, H * D, "W1"); a.W2 = f32(W2, D * H, "W2"); a.scale = f32(scale, D, "scale");
+    a.dW1 = f32w(dW1, H * D, "dW1"); a.db1 = f32w(db1, H, "db1"); a.dW2 = f32w(dW2, D * H, "dW2"); a.db2 = f32w(db2, D, "db2");
+    a.dscale = f32w(dscale, D, "dscale");
+    a.g = ntok > 0 ? (const float*)dout.data_ptr() : nullptr;
+    a.x = ntok > 0 ? (const float*)x.data_ptr() : nullptr;
+    a.dx = ntok > 0 ? (float*)dx.data_ptr() : nullptr;
+    return a;
+}
+void ffn_residual_bwd_op(Tensor dout, Tensor x, Tensor z, Tensor y, Tensor W1, Tensor W2, Tensor scale, double eps, int64_t seed, double p_hidden,
+                         double p_out, Tensor dx, Tensor dW1, Tensor db1, Tensor dW2, Tensor db2, Tensor dscale, Tensor ws)
+{
+    Ctx c(x); c.same(x, dout, z, y, W1, W2, scale, dx, dW1, db1, dW2, db2, dscale, ws);
+    const FfnBwdArgs a = ffn_bwd_args(dout, x, z, y, W1, W2, scale, p_hidden, p_out, dx, dW1, db1, dW2, db2, dscale);
+    if (a.n0 == 0 || a.n1 == 0) return;
+    check(semicrf_ffn_residual_bwd(a.g, a.x, a.z, a.y, a.n0, a.n1, a.st[0], a.st[1], a.st[2], a.st[3], a.st[4], a.st[5], a.D, a.H, a.W1, a.W2,
+                                   a.scale, (float)eps, (uint64_t)seed, p_hidden, p_out, a.dx, a.dW1, a.db1, a.dW2, a.db2, a.dscale,
+                                   bytes(ws, "ws"), (size_t)ws.numel(), c.stream),
+          "semicrf_ffn_residual_bwd");
+}
+void ffn_residual_bwd_cpu(Tensor dout, Tensor x, Tensor z, Tensor y, Tensor W1, Tensor W2, Tensor scale, double eps, int64_t seed, double p_hidden,
+                          double p_out, Tensor dx, Tensor dW1, Tensor db1, Tensor dW2, Tensor db2, Tensor dscale, Tensor ws)
+{
+    all_cpu(x, dout, z, y, W1, W2, scale, dx, dW1, db1, dW2, db2, dscale, ws);
+    const FfnBwdArgs a = ffn_bwd_args(dout, x, z, y, W1, W2, scale, p_hidden, p_out, dx, dW1, db1, dW2, db2, dscale);
+    if (a.n0 == 0 || a.n1 == 0) return;
+    auto ext = [&](int v) { return (a.n0 - 1) * a.st[2 * v] + (a.n1 - 1) * a.st[2 * v + 1] + a.D; };
+    auto apart = [](const float* p, int64_t np, const float* q, int64_t nq) { return p + np <= q || q + nq <= p; };
+    const int64_t ntok = a.n0 * a.n1;
+    STD_TORCH_CHECK(apart(a.dx, ext(2), a.g, ext(0)) && apart(a.dx, ext(2), a.x, ext(1)) && apart(a.dx, ext(2), a.z, ntok * a.H) &&
+                    apart(a.dx, ext(2), a.y, ntok * a.D), "semicrf: ffn_residual_bwd: `dx` overlaps dout, x, z or y");
+    semicrf_cpu::ffn_residual_bwd(a.g, a.x, a.z, a.y, a.n0, a.n1, a.st[0], a.st[1], a.st[2], a.st[3], a.st[4], a.st[5], a.D, a.H, a.W1, a.W2,
+                                  a.scale, (float)eps, (uint64_t)seed, p_hidden, p_out, a.dx, a.dW1, a.db1, a.dW2, a.db2, a.dscale);
+}
+
+inline void ffn_mask_args(const Tensor& mh, const Tensor& mo, int64_t rows, int64_t D, int64_t H, double p_hidden, double p_out)
+{
+    STD_TORCH_CHECK(rows >= 0 && rows < (1ll << 37) && D >= 1 && D < (1 << 20) && H >= 1 && H < (1 << 20), "semicrf: bad mask shape");
+    STD_TORCH_CHECK(p_hidden >= 0.0 && p_hidden < 1.0 && p_out >= 0.0 && p_out < 1.0, "semicrf: dropout probabilities must lie in [0, 1)");
+    want(mh, ScalarType::Byte, rows * H, "mask_hidden");
+    want(mo, ScalarType::Byte, rows * D, "mask_out");
+}
+void ffn_dropout_mask_op(Tensor mh, Tensor mo, int64_t seed, int64_t rows, int64_t D, int64_t H, double p_hidden, double p_out)
+{
+    Ctx c(mh); c.same(mh, mo);
+    ffn_mask_args(mh, mo, rows, D, H, p_hidden, p_out);
+    if (rows == 0) return;
+    check(semicrf_ffn_dropout_mask((uint64_t)seed, rows, (int)D, (int)H, p_hidden, p_out, (unsigned char*)mh.data_ptr(),
+                                   (unsigned char*)mo.data_ptr(), c.stream),
+          "semicrf_ffn_dropout_mask");
+}
+void ffn_dropout_mask_cpu(Tensor mh, Tensor mo, int64_t seed, int64_t rows, int64_t D, int64_t H, double p_hidden, double p_out)
+{
+    all_cpu(mh, mo);
+    ffn_mask_args(mh, mo, rows, D, H, p_hidden, p_out);
+    if (rows == 0) return;
+    semicrf_cpu::ffn_dropout_mask((uint64_t)seed, rows, (int)D, (int)H, p_hidden, p_out, (unsigned char*)mh.data_ptr(), (unsigned char*)mo.data_ptr());
+}
+
 // the bf16 forms: `ffn_residual_bf16` on bfloat16 tensors, `ffn_residual_bf16_mixed` on float32 tensors (bf16 operands inside)
 void ffn_residual_bf16_op(Tensor x, Tensor W1, Tensor b1, Tensor W2, Tensor b2, Tensor scale, double eps, Tensor out)
 {
@@ -1694,6 +1819,12 @@ STABLE_TORCH_LIBRARY(semicrf, m)
     m.def("axial_attention_bwd(Tensor q, Tensor k, Tensor v, Tensor out, Tensor dout, Tensor(a!)? dq, Tensor(b!)? dk, Tensor(c!)? dv, int H) -> ()");
     m.def("axial_attention_bf16_bwd(Tensor q, Tensor k, Tensor v, Tensor dout, Tensor(a!)? dq, Tensor(b!)? dk, Tensor(c!)? dv, int H) -> ()");
     m.def("ffn_residual(Tensor x, Tensor W1, Tensor b1, Tensor W2, Tensor b2, Tensor scale, float eps, Tensor(a!) out) -> ()");
+    m.def("ffn_residual_train_fwd(Tensor x, Tensor W1, Tensor b1, Tensor W2, Tensor b2, Tensor scale, float eps, int seed, float p_hidden, "
+          "float p_out, Tensor(a!) out, Tensor(b!) z, Tensor(c!) y) -> ()");
+    m.def("ffn_residual_bwd(Tensor dout, Tensor x, Tensor z, Tensor y, Tensor W1, Tensor W2, Tensor scale, float eps, int seed, float p_hidden, "
+          "float p_out, Tensor(a!) dx, Tensor(b!) dW1, Tensor(c!) db1, Tensor(d!) dW2, Tensor(e!) db2, Tensor(f!) dscale, Tensor ws) -> ()");
+    m.def("ffn_dropout_mask(Tensor(a!) mask_hidden, Tensor(b!) mask_out, int seed, int rows, int D, int hidden, float p_hidden, float p_out) "
+          "-> ()");
     m.def("ffn_residual_bf16(Tensor x, Tensor W1, Tensor b1, Tensor W2, Tensor b2, Tensor scale, float eps, Tensor(a!) out) -> ()");
     m.def("ffn_residual_bf16_mixed(Tensor x, Tensor W1, Tensor b1, Tensor W2, Tensor b2, Tensor scale, float eps, Tensor(a!) out) -> ()");
     m.def("log_mel(Tensor frames, Tensor windows, Tensor tw, Tensor fb_start, Tensor fb_len, Tensor fb_off, Tensor fb_val, int max_len, "
@@ -1742,6 +1873,9 @@ STABLE_TORCH_LIBRARY_IMPL(semicrf, CPU, m)
     m.impl("axial_attention_bwd", TORCH_BOX(&axial_attention_bwd_cpu));
     m.impl("axial_attention_bf16_bwd", TORCH_BOX(&axial_attention_bf16_bwd_cpu));
     m.impl("ffn_residual", TORCH_BOX(&ffn_residual_cpu));
+    m.impl("ffn_residual_train_fwd", TORCH_BOX(&ffn_residual_train_fwd_cpu));
+    m.impl("ffn_residual_bwd", TORCH_BOX(&ffn_residual_bwd_cpu));
+    m.impl("ffn_dropout_mask", TORCH_BOX(&ffn_dropout_mask_cpu));
     m.impl("ffn_residual_bf16", TORCH_BOX(&ffn_residual_bf16_cpu));
     m.impl("ffn_residual_bf16_mixed", TORCH_BOX(&ffn_residual_bf16_mixed_cpu));
     m.impl("log_mel", TORCH_BOX(&log_mel_cpu));
@@ -1796,6 +1930,9 @@ STABLE_TORCH_LIBRARY_IMPL(semicrf, CUDA, m)
     m.impl("axial_attention_bwd", TORCH_BOX(&axial_attention_bwd_op));
     m.impl("axial_attention_bf16_bwd", TORCH_BOX(&axial_attention_bf16_bwd_op));
     m.impl("ffn_residual", TORCH_BOX(&ffn_residual_op));
+    m.impl("ffn_residual_train_fwd", TORCH_BOX(&ffn_residual_train_fwd_op));
+    m.impl("ffn_residual_bwd", TORCH_BOX(&ffn_residual_bwd_op));
+    m.impl("ffn_dropout_mask", TORCH_BOX(&ffn_dropout_mask_op));
     m.impl("ffn_residual_bf16", TORCH_BOX(&ffn_residual_bf16_op));
     m.impl("ffn_residual_bf16_mixed", TORCH_BOX(&ffn_residual_bf16_mixed_op));
     m.impl("log_mel", TORCH_BOX(&log_mel_op));
