@@ -1376,6 +1376,53 @@ int semicrf_ffn_residual_bf16_mixed(const float* x, float* out, int64_t n0, int6
                                     const float* scale, float eps, semicrf_stream_t stream);
 
 /*
+ * Training through the bf16 block: the forward kernel in a training mode and one backward on the same matrix instruction, in both
+ * forms (every tensor bfloat16; every tensor fp32 with bf16 operands inside: _mixed).  The chain of every element, the order of every
+ * sum and the layout of the saved buffer are stated in csrc/ffn_bf16_train_math.h; the host mirrors follow it one product at a time.
+ *   out = x + ((W2 (gelu(W1 rmsnorm(x) + b1) * M1) + b2) * M2) * scale
+ * M1, M2: the masks of semicrf_ffn_dropout_mask (the same seed gives the same masks on the fp32 and the bf16 routes), as factors
+ * keep / (1 - p).  With p_hidden = p_out = 0 `out` has the bits of semicrf_ffn_residual_bf16 / _mixed.
+ *
+ * semicrf_ffn_residual_bf16_train_fwd / _mixed_train_fwd: the eval entry points' contract (views, strides, supported set, rejected
+ * calls), one launch, no workspace.  `saved` (16-byte aligned, semicrf_ffn_residual_bf16_train_saved_bytes(n0 n1, D, hidden) bytes) is an
+ * opaque buffer for the backward: zs = bf16(h) [tokens][hidden], then ys = y rounded to the form's element [tokens][D].
+ *
+ * semicrf_ffn_residual_bf16_bwd / _mixed_bwd: dout, x and dx are [n0, n1, D] views with two ELEMENT row strides each; W1, W2, scale and
+ * the five gradients lie as nn.Linear and ResBlock store them, in the form's element type.  Five launches on `stream` (the weights as
+ * transposed bf16 operands; the per-token part dy, da, dz, dxn, dx in the forward's geometry; dW2 and dW1 per chunk of
+ * SEMICRF_FFN_BWD_ROW_CHUNK tokens; the column sums in double; the planes added in ascending order with one rounding), no atomics, no
+ * memset, no synchronisation, no allocation: every gradient is bit-identical from run to run, and a token's dx depends on its own row,
+ * its index, the seed and the weights only.  ah = bf16(gelu(zs) * M1) is recomputed from zs (the forward's operand saw the unrounded h).
+ * Workspace (16-byte aligned): semicrf_ffn_residual_bf16_bwd_workspace_bytes(n0 n1, D, hidden); nothing in it is read before it is
+ * written.  16-byte loads of x and dout when both are 16-byte aligned with strides multiples of 16 bytes, element loads otherwise: the
+ * same bits.  Supported: semicrf_ffn_residual_bf16_bwd_supported = the set of semicrf_ffn_residual_bf16; n0 n1 <= 65535 chunks.
+ * SEMICRF_EINVAL, with nothing launched and nothing written: the cases of semicrf_ffn_residual_bf16 (dx in the place of out, dout and x
+ * each in the place of x), p outside [0, 1), a saved buffer that is too small, misaligned or overlaps a view; SEMICRF_EWORKSPACE: a
+ * workspace that is too small.
+ */
+int semicrf_ffn_residual_bf16_bwd_supported(int D, int hidden);
+size_t semicrf_ffn_residual_bf16_train_saved_bytes(int64_t tokens, int D, int hidden);
+size_t semicrf_ffn_residual_bf16_bwd_workspace_bytes(int64_t tokens, int D, int hidden);
+int semicrf_ffn_residual_bf16_train_fwd(const uint16_t* x, uint16_t* out, void* saved, size_t saved_bytes, int64_t n0, int64_t n1, int64_t x_stride_0,
+                                        int64_t x_stride_1, int64_t out_stride_0, int64_t out_stride_1, int D, int hidden, const uint16_t* W1,
+                                        const uint16_t* b1, const uint16_t* W2, const uint16_t* b2, const uint16_t* scale, float eps, uint64_t seed,
+                                        double p_hidden, double p_out, semicrf_stream_t stream);
+int semicrf_ffn_residual_bf16_mixed_train_fwd(const float* x, float* out, void* saved, size_t saved_bytes, int64_t n0, int64_t n1, int64_t x_stride_0,
+                                              int64_t x_stride_1, int64_t out_stride_0, int64_t out_stride_1, int D, int hidden, const float* W1,
+                                              const float* b1, const float* W2, const float* b2, const float* scale, float eps, uint64_t seed,
+                                              double p_hidden, double p_out, semicrf_stream_t stream);
+int semicrf_ffn_residual_bf16_bwd(const uint16_t* dout, const uint16_t* x, const void* saved, size_t saved_bytes, int64_t n0, int64_t n1,
+                                  int64_t dout_stride_0, int64_t dout_stride_1, int64_t x_stride_0, int64_t x_stride_1, int64_t dx_stride_0,
+                                  int64_t dx_stride_1, int D, int hidden, const uint16_t* W1, const uint16_t* W2, const uint16_t* scale, float eps,
+                                  uint64_t seed, double p_hidden, double p_out, uint16_t* dx, uint16_t* dW1, uint16_t* db1, uint16_t* dW2, uint16_t* db2,
+                                  uint16_t* dscale, void* ws, size_t ws_bytes, semicrf_stream_t stream);
+int semicrf_ffn_residual_bf16_mixed_bwd(const float* dout, const float* x, const void* saved, size_t saved_bytes, int64_t n0, int64_t n1,
+                                        int64_t dout_stride_0, int64_t dout_stride_1, int64_t x_stride_0, int64_t x_stride_1, int64_t dx_stride_0,
+                                        int64_t dx_stride_1, int D, int hidden, const float* W1, const float* W2, const float* scale, float eps,
+                                        uint64_t seed, double p_hidden, double p_out, float* dx, float* dW1, float* db1, float* dW2, float* db2,
+                                        float* dscale, void* ws, size_t ws_bytes, semicrf_stream_t stream);
+
+/*
  * The audio front end (Util.py:78-170 behind the gain of ModelTransformer.py:159-164) as one launch.  Replaces: the gain normalisation,
  * the product of the frames with the analysis windows, the orthonormal real transform, |.|^2, the channel mean, the matrix product with
  * the mel filterbank and the log compression -- a dozen launches and two round trips of a [N, C, nFrame, nWin, W] tensor.  For every

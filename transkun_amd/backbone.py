@@ -65,6 +65,15 @@ differentiable, every gradient bit-identical from run to run.  bfloat16, autocas
 stock expression.  `FEED_FORWARD_TRAIN_ROUTES` counts the gradient-wanting calls made with the knob at "fused" (and, under "bwd", the
 launches of the HIP backward); a fused answer counts in `FEED_FORWARD_ROUTES` too.
 
+Training in bfloat16 has a fourth knob, `feedForwardBf16Train = "torch" | "fused"` (default "torch": everything above, unchanged,
+counters included).  With `feedForward`, `feedForwardTrain`, `feedForwardBf16` AND `feedForwardBf16Train` at "fused", a gradient-wanting
+call on bfloat16 tensors (form A), or on float32 tensors under bfloat16 autocast (form B: float32 parameters and gradients, which is what
+FusedAdaBelief and FlatGradBucket work on), is `torch.ops.semicrf.ffn_residual_bf16_train_fwd` / `_mixed_train_fwd` (csrc/ffn_bf16.hip
+in its training mode: the fp32 route's masks, bf16(h) and y saved in one opaque buffer) with `torch.ops.semicrf.ffn_residual_bf16_bwd` /
+`_mixed_bwd` (csrc/ffn_bf16_bwd.hip: five launches, every product on the bf16 matrix instruction) as its backward, once differentiable,
+every gradient bit-identical from run to run.  `FEED_FORWARD_BF16_TRAIN_ROUTES` counts the gradient-wanting bfloat16 / bfloat16-autocast
+calls made with all four at "fused"; a fused answer counts in the three other dicts too.
+
 Hidden size and head dimension come from the constructor as in the reference: head_dim = ceil(ceil(hiddenFactor * embed_dim) /
 num_heads), hidden size = head_dim * num_heads (the model: embed_dim 160, 4 heads, hiddenFactorAttn 1 -> d = 40).
 """
@@ -354,6 +363,13 @@ FEED_FORWARD_TRAIN_ROUTES = {"fused": 0, "torch": 0, "bwd": 0}
 FEED_FORWARD_BWD_ROW_CHUNK = _lib.FFN_BWD_ROW_CHUNK             # tokens per partial plane of the backward's sums over tokens
 # what the last fused training forward / backward handed to the op: (data_ptr, shape, strides) of its x view; tests read it
 FEED_FORWARD_TRAIN_LAST = {"fwd": None, "bwd": None}
+FEED_FORWARD_BF16_TRAIN_KINDS = ("torch", "fused")
+DEFAULT_FEED_FORWARD_BF16_TRAIN = "torch"
+# gradient-wanting calls on bfloat16 tensors or under bfloat16 autocast made with route, train, bf16 AND bf16_train = "fused", by the way
+# they went ("bwd": launches of the bf16 HIP backward); tests read it
+FEED_FORWARD_BF16_TRAIN_ROUTES = {"fused": 0, "torch": 0, "bwd": 0}
+# what the last fused bf16 training forward / backward handed to the op, as FEED_FORWARD_TRAIN_LAST
+FEED_FORWARD_BF16_TRAIN_LAST = {"fwd": None, "bwd": None}
 
 
 def feed_forward_supported(D: int, hidden: int) -> bool:
@@ -570,8 +586,117 @@ def _ffn_train(x, w1, b1, w2, b2, scale, eps, p_hidden, p_out, seed):
     return _FeedForwardTrain.apply(x, w1, b1, w2, b2, scale, float(eps), _seed_arg(seed), float(p_hidden), float(p_out))
 
 
+def _autocast_dtype(kind):
+    return torch.get_autocast_dtype(kind) if kind in ("cuda", "cpu") and torch.is_autocast_enabled(kind) else None
+
+
+def _ffn_bf16_train_form(x, w1, b1, w2, b2, scale, p_hidden=0.0, p_out=0.0):
+    """(form, is16): "A" (bfloat16 tensors, outside autocast or under bfloat16 autocast), "B" (float32 tensors under bfloat16 autocast)
+    or None where the fused bf16 training route does not answer; is16: x bfloat16 or bfloat16 autocast on (what the counter counts)."""
+    ts = (x, w1, b1, w2, b2, scale)
+    kind = x.device.type
+    ac = _autocast_dtype(kind)
+    is16 = x.dtype == torch.bfloat16 or ac == torch.bfloat16
+    if any(t.device != x.device for t in ts) or kind not in ("cuda", "cpu"):
+        return None, is16
+    if all(t.dtype == torch.bfloat16 for t in ts) and ac in (None, torch.bfloat16):
+        form = "A"
+    elif all(t.dtype == torch.float32 for t in ts) and ac == torch.bfloat16:
+        form = "B"
+    else:
+        return None, is16
+    if x.dim() < 1 or x.numel() == 0 or w1.dim() != 2 or w2.dim() != 2:
+        return None, is16
+    D, hidden = x.shape[-1], w1.shape[0]
+    if w1.shape != (hidden, D) or w2.shape != (D, hidden) or b1.shape != (hidden,) or b2.shape != (D,) or scale.shape != (D,):
+        return None, is16
+    if not (0.0 <= p_hidden < 1.0 and 0.0 <= p_out < 1.0):
+        return None, is16
+    if not _lib.load().semicrf_ffn_residual_bf16_bwd_supported(int(D), int(hidden)):
+        return None, is16
+    return form, is16
+
+
+class _FeedForwardBf16Train(torch.autograd.Function):
+    """The op behind bf16_train = "fused": semicrf_ffn_residual_bf16_train_fwd / _bwd (form A) and their _mixed forms (form B)."""
+
+    @staticmethod
+    def forward(ctx, x, w1, b1, w2, b2, scale, eps, seed, p1, p2, form):
+        xd = x.detach()
+        if xd.shape[-1] != 1 and xd.stride(-1) != 1:
+            xd = xd.contiguous()
+        order = sorted(range(xd.dim() - 1), key=lambda i: -xd.stride(i))       # the tokens in the order of their addresses
+        out = torch.empty_like(xd)
+        views = _rows_views((xd, out), order)
+        if views is None:
+            xd = xd.contiguous()
+            out = torch.empty_like(xd)
+            order = list(range(xd.dim() - 1))
+            views = _rows_views((xd, out), order)
+        x3, o3 = views
+        ntok, D, hidden = x3.shape[0] * x3.shape[1], x3.shape[2], w1.shape[0]
+        saved = torch.empty(int(_lib.load().semicrf_ffn_residual_bf16_train_saved_bytes(ntok, D, hidden)), dtype=torch.uint8, device=xd.device)
+        w1, b1, w2, b2, scale = (t.detach().contiguous() for t in (w1, b1, w2, b2, scale))
+        FEED_FORWARD_BF16_TRAIN_LAST["fwd"] = (x3.data_ptr(), tuple(x3.shape), tuple(x3.stride()))
+        ops = _lib.ops()
+        (ops.ffn_residual_bf16_train_fwd if form == "A" else ops.ffn_residual_bf16_mixed_train_fwd)(
+            x3, w1, b1, w2, b2, scale, float(eps), seed, p1, p2, o3, saved)
+        ctx.save_for_backward(xd, saved, w1, w2, scale)
+        ctx.geom = (order, float(eps), seed, p1, p2, form)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout):
+        xd, saved, w1, w2, scale = ctx.saved_tensors
+        order, eps, seed, p1, p2, form = ctx.geom
+        dev = xd.device
+        hidden, D = w1.shape
+        dx = torch.empty_like(xd)
+        views = None
+        if dout.dtype == xd.dtype and (dout.shape[-1] == 1 or dout.stride(-1) == 1):
+            views = _rows_views((xd, dout, dx), order)
+        if views is None:                                       # dout laid out like dx: then the three merge as x and out did
+            dout = torch.empty_like(xd).copy_(dout)
+            views = _rows_views((xd, dout, dx), order)
+        x3, g3, d3 = views
+        ntok = x3.shape[0] * x3.shape[1]
+        flat = torch.empty(2 * hidden * D + hidden + 2 * D, dtype=xd.dtype, device=dev)
+        e1, e2, e3, e4 = hidden * D, hidden * D + hidden, 2 * hidden * D + hidden, 2 * hidden * D + hidden + D
+        dW1, db1, dW2, db2, dscale = flat[:e1].view(hidden, D), flat[e1:e2], flat[e2:e3].view(D, hidden), flat[e3:e4], flat[e4:]
+        if dev.type == "cpu":
+            ws = torch.empty(0, dtype=torch.uint8)
+        else:
+            ws = torch.empty(int(_lib.load().semicrf_ffn_residual_bf16_bwd_workspace_bytes(ntok, D, hidden)), dtype=torch.uint8, device=dev)
+        FEED_FORWARD_BF16_TRAIN_ROUTES["bwd"] += 1
+        FEED_FORWARD_TRAIN_ROUTES["bwd"] += 1
+        FEED_FORWARD_BF16_TRAIN_LAST["bwd"] = (x3.data_ptr(), tuple(x3.shape), tuple(x3.stride()), g3.data_ptr(), tuple(g3.stride()))
+        ops = _lib.ops()
+        (ops.ffn_residual_bf16_bwd if form == "A" else ops.ffn_residual_bf16_mixed_bwd)(
+            g3, x3, saved, w1, w2, scale, eps, seed, p1, p2, d3, dW1, db1, dW2, db2, dscale, ws)
+        need = ctx.needs_input_grad
+        grads = (dx, dW1, db1, dW2, db2, dscale)
+        return tuple(g if need[i] else None for i, g in enumerate(grads)) + (None, None, None, None, None)
+
+
+def _ffn_bf16_train(form, x, w1, b1, w2, b2, scale, eps, p_hidden, p_out, seed):
+    """The fused bf16 training call, counted: the seed rule of _ffn_train (a host value from the CPU generator)."""
+    FEED_FORWARD_BF16_TRAIN_ROUTES["fused"] += 1
+    FEED_FORWARD_TRAIN_ROUTES["fused"] += 1
+    FEED_FORWARD_ROUTES["fused"] += 1
+    FEED_FORWARD_BF16_ROUTES["fused"] += 1
+    if seed is None:
+        if p_hidden > 0 or p_out > 0:
+            lo, hi = torch.randint(0, 1 << 32, (2,), dtype=torch.int64).tolist()       # the CPU default generator: no device sync
+            seed = (hi << 32) | lo
+        else:
+            seed = 0
+    return _FeedForwardBf16Train.apply(x, w1, b1, w2, b2, scale, float(eps), _seed_arg(seed), float(p_hidden), float(p_out), form)
+
+
 def feed_forward_residual(x, w1, b1, w2, b2, scale, eps=1e-6, route="fused", bf16=DEFAULT_FEED_FORWARD_BF16,
-                          train=DEFAULT_FEED_FORWARD_TRAIN, p_hidden=0.0, p_out=0.0, seed=None):
+                          train=DEFAULT_FEED_FORWARD_TRAIN, p_hidden=0.0, p_out=0.0, seed=None,
+                          bf16_train=DEFAULT_FEED_FORWARD_BF16_TRAIN):
     """x + (W2 gelu(W1 rmsnorm(x) + b1) + b2) * scale per token: the feed-forward ResBlock in eval mode.  x [..., D] with a contiguous
     last dimension, any strides in front (a tensor whose rows cannot be handed over as two strides is made contiguous first); w1
     [hidden, D], b1 [hidden], w2 [D, hidden], b2 [D], scale [D] as nn.Linear and ResBlock hold them.  Returns [..., D], laid out in
@@ -598,13 +723,24 @@ def feed_forward_residual(x, w1, b1, w2, b2, scale, eps=1e-6, route="fused", bf1
     default generator when something drops (torch.manual_seed makes runs reproducible, and torch.utils.checkpoint's RNG preservation
     reproduces the mask on recomputation; nothing waits for the device); an explicit seed makes the call reproducible.  The seed is a
     HOST value: a call captured in a HIP graph replays one and the same mask.  On every other route the two dropouts are
-    F.dropout's."""
+    F.dropout's.
+
+    bf16_train = "torch" (the default): the above.  bf16_train = "fused", with route, train AND bf16 = "fused": a call that wants a
+    gradient on bfloat16 x and parameters (outside autocast or under bfloat16 autocast: form A) or on float32 x and parameters under
+    bfloat16 autocast (form B: float32 parameters and gradients, bf16 operands inside the launch) is the bf16 HIP op in its training
+    mode and its HIP backward (semicrf_ffn_residual_bf16_train_fwd / _bwd and their _mixed forms; the host mirrors on the CPU): once
+    differentiable, the same masks and the same seed rule as train = "fused", every gradient bit-identical from run to run.  float32
+    outside autocast stays the float32 training route; every other case is what it was.  FEED_FORWARD_BF16_TRAIN_ROUTES counts the
+    gradient-wanting bfloat16 / bfloat16-autocast calls made with all four at "fused"; a fused answer counts in
+    FEED_FORWARD_TRAIN_ROUTES, FEED_FORWARD_ROUTES and FEED_FORWARD_BF16_ROUTES too."""
     if route not in FEED_FORWARD_KINDS:
         raise ValueError(f"route must be one of {FEED_FORWARD_KINDS}, not {route!r}")
     if bf16 not in FEED_FORWARD_BF16_KINDS:
         raise ValueError(f"bf16 must be one of {FEED_FORWARD_BF16_KINDS}, not {bf16!r}")
     if train not in FEED_FORWARD_TRAIN_KINDS:
         raise ValueError(f"train must be one of {FEED_FORWARD_TRAIN_KINDS}, not {train!r}")
+    if bf16_train not in FEED_FORWARD_BF16_TRAIN_KINDS:
+        raise ValueError(f"bf16_train must be one of {FEED_FORWARD_BF16_TRAIN_KINDS}, not {bf16_train!r}")
     drops = p_hidden > 0 or p_out > 0
 
     def stock():
@@ -622,6 +758,12 @@ def feed_forward_residual(x, w1, b1, w2, b2, scale, eps=1e-6, route="fused", bf1
             FEED_FORWARD_TRAIN_ROUTES["fused"] += 1
             FEED_FORWARD_ROUTES["fused"] += 1
             return _ffn_train(*ts, eps, p_hidden, p_out, seed)
+        if bf16_train == "fused" and bf16 == "fused":
+            form, is16 = _ffn_bf16_train_form(*ts, p_hidden, p_out)
+            if form is not None:
+                return _ffn_bf16_train(form, *ts, eps, p_hidden, p_out, seed)
+            if is16:
+                FEED_FORWARD_BF16_TRAIN_ROUTES["torch"] += 1
         FEED_FORWARD_TRAIN_ROUTES["torch"] += 1
     op, is16 = _ffn_pick(ts, bf16)
     if drops:
@@ -700,7 +842,10 @@ class ResBlock(nn.Module):
     sequence, a call that wants a gradient -- with its dropouts active or not -- is feed_forward_residual's train = "fused" route
     (the HIP op in training mode and its HIP backward) on float32 tensors outside autocast with a supported shape and no extra
     arguments; p comes from module[2] and self.dropout where they are in training mode, else 0.  bfloat16, autocast, extra
-    arguments and an unsupported shape take the stock expression."""
+    arguments and an unsupported shape take the stock expression.
+    feedForwardBf16Train: "torch" (the default: the above) or "fused": where feedForward, feedForwardTrain AND feedForwardBf16 are
+    "fused", a gradient-wanting call of a bfloat16 block, or of a float32 block under bfloat16 autocast, is feed_forward_residual's
+    bf16_train = "fused" route (the bf16 HIP op in training mode and its HIP backward; float32 parameters keep float32 gradients)."""
 
     def __init__(self, module, size, prenorm=True, dropoutProb=0.0):
         super().__init__()
@@ -711,6 +856,7 @@ class ResBlock(nn.Module):
         self.feedForward = DEFAULT_FEED_FORWARD
         self.feedForwardBf16 = DEFAULT_FEED_FORWARD_BF16
         self.feedForwardTrain = DEFAULT_FEED_FORWARD_TRAIN
+        self.feedForwardBf16Train = DEFAULT_FEED_FORWARD_BF16_TRAIN
 
     def is_feed_forward(self) -> bool:
         """The module is the Linear, GELU (exact), Dropout, Linear sequence of _feed_forward."""
@@ -726,6 +872,9 @@ class ResBlock(nn.Module):
         kind = getattr(self, "feedForwardTrain", DEFAULT_FEED_FORWARD_TRAIN)
         if kind not in FEED_FORWARD_TRAIN_KINDS:
             raise ValueError(f"feedForwardTrain must be one of {FEED_FORWARD_TRAIN_KINDS}, not {kind!r}")
+        kind16 = getattr(self, "feedForwardBf16Train", DEFAULT_FEED_FORWARD_BF16_TRAIN)
+        if kind16 not in FEED_FORWARD_BF16_TRAIN_KINDS:
+            raise ValueError(f"feedForwardBf16Train must be one of {FEED_FORWARD_BF16_TRAIN_KINDS}, not {kind16!r}")
         op, is16 = None, False
         if self.feedForward == "fused" and self.is_feed_forward():
             m = self.module
@@ -737,6 +886,12 @@ class ResBlock(nn.Module):
                     FEED_FORWARD_TRAIN_ROUTES["fused"] += 1
                     FEED_FORWARD_ROUTES["fused"] += 1
                     return _ffn_train(x, *params, self.norm.eps, p1, p2, None)
+                if kind16 == "fused" and self.feedForwardBf16 == "fused":
+                    form, is16t = _ffn_bf16_train_form(x, *params, p1, p2)
+                    if form is not None and not args:
+                        return _ffn_bf16_train(form, x, *params, self.norm.eps, p1, p2, None)
+                    if is16t:
+                        FEED_FORWARD_BF16_TRAIN_ROUTES["torch"] += 1
                 FEED_FORWARD_TRAIN_ROUTES["torch"] += 1
             op, is16 = _ffn_pick((x, *params), self.feedForwardBf16)
             if args or (self.training and (self.dropout.p > 0 or m[2].p > 0)):
@@ -928,6 +1083,18 @@ class BasicBlock(nn.Module):
         for m in self.feed_forward_blocks():
             m.feedForwardTrain = kind
 
+    @property
+    def feedForwardBf16Train(self):
+        kinds = {getattr(m, "feedForwardBf16Train", DEFAULT_FEED_FORWARD_BF16_TRAIN) for m in self.feed_forward_blocks()}
+        return kinds.pop() if len(kinds) == 1 else ("mixed" if kinds else DEFAULT_FEED_FORWARD_BF16_TRAIN)
+
+    @feedForwardBf16Train.setter
+    def feedForwardBf16Train(self, kind):
+        if kind not in FEED_FORWARD_BF16_TRAIN_KINDS:
+            raise ValueError(f"feedForwardBf16Train must be one of {FEED_FORWARD_BF16_TRAIN_KINDS}, not {kind!r}")
+        for m in self.feed_forward_blocks():
+            m.feedForwardBf16Train = kind
+
     def forward(self, x, mem=None, crossAttn=False):
         nT, nF = x.shape[-3], x.shape[-2]
         if mem is None:
@@ -1087,6 +1254,18 @@ class Backbone(nn.Module):
             raise ValueError(f"feedForwardTrain must be one of {FEED_FORWARD_TRAIN_KINDS}, not {kind!r}")
         for m in self.feed_forward_blocks():
             m.feedForwardTrain = kind
+
+    @property
+    def feedForwardBf16Train(self):
+        kinds = {getattr(m, "feedForwardBf16Train", DEFAULT_FEED_FORWARD_BF16_TRAIN) for m in self.feed_forward_blocks()}
+        return kinds.pop() if len(kinds) == 1 else ("mixed" if kinds else DEFAULT_FEED_FORWARD_BF16_TRAIN)
+
+    @feedForwardBf16Train.setter
+    def feedForwardBf16Train(self, kind):
+        if kind not in FEED_FORWARD_BF16_TRAIN_KINDS:
+            raise ValueError(f"feedForwardBf16Train must be one of {FEED_FORWARD_BF16_TRAIN_KINDS}, not {kind!r}")
+        for m in self.feed_forward_blocks():
+            m.feedForwardBf16Train = kind
 
     def tokens(self, x, outputIndices):
         """The input of the first layer: [N, T', F' + P, 4 baseSize], the spectrogram tokens followed by the target tokens."""

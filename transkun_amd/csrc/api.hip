@@ -10,6 +10,7 @@
 #include "launchers.h"
 #include "attention_math.h"
 #include "ffn_math.h"
+#include "ffn_bf16_train_math.h"
 #include "logmel_math.h"
 
 namespace semicrf {
@@ -152,11 +153,12 @@ static void lease_failed(void* ws)
 // strides of the dimensions that count come back in st.
 template <typename T>
 static int ffn_bf16_check(const char* op, const T* x, T* out, int64_t n0, int64_t n1, int64_t xs0, int64_t xs1, int64_t os0, int64_t os1, int D,
-                          int hidden, const T* W1, const T* b1, const T* W2, const T* b2, const T* scale, long long* st)
+                          int hidden, const T* W1, const T* b1, const T* W2, const T* b2, const T* scale, long long* st, const char* sup = nullptr)
 {
     SEMICRF_CHECK_ARG(ffn::supported(D, hidden),
                       "%s: D=%d hidden=%d is outside the supported set (D a multiple of 8 in [%d, %d]; hidden a multiple of 8 in "
-                      "[%d, %d]): see semicrf_%s_supported", op, D, hidden, ffn::FFN_MIN_D, ffn::FFN_MAX_D, ffn::FFN_MIN_H, ffn::FFN_MAX_H, op);
+                      "[%d, %d]): see semicrf_%s_supported", op, D, hidden, ffn::FFN_MIN_D, ffn::FFN_MAX_D, ffn::FFN_MIN_H, ffn::FFN_MAX_H,
+                      sup ? sup : op);
     SEMICRF_CHECK_ARG(n0 >= 1 && n1 >= 1, "%s: n0=%lld n1=%lld must be >= 1", op, (long long)n0, (long long)n1);
     SEMICRF_CHECK_ARG(n0 < (1ll << 37) && n1 < (1ll << 37) && n0 * n1 < (1ll << 37), "%s: n0 * n1 = %lld * %lld must stay below 2^37", op,
                       (long long)n0, (long long)n1);
@@ -171,6 +173,71 @@ static int ffn_bf16_check(const char* op, const T* x, T* out, int64_t n0, int64_
     const long long xext = (n0 - 1) * st[0] + (n1 - 1) * st[1] + D, oext = (n0 - 1) * st[2] + (n1 - 1) * st[3] + D;
     const uintptr_t xb = (uintptr_t)x, ob = (uintptr_t)out;
     SEMICRF_CHECK_ARG(xb + (uintptr_t)xext * sizeof(T) <= ob || ob + (uintptr_t)oext * sizeof(T) <= xb, "%s: `out` overlaps `x`", op);
+    return SEMICRF_OK;
+}
+
+// ---- the training route of the bf16 feed-forward op: one body per call, both forms (T = uint16_t | float) -------------------------------
+static bool ffn16_bytes_overlap(const void* a, size_t na, const void* b, size_t nb)
+{
+    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+    return !(pa + na <= pb || pb + nb <= pa);
+}
+
+template <typename T, typename L>
+static int ffn_bf16_train_fwd_any(const char* op, L launch, const T* x, T* out, void* saved, size_t saved_bytes, int64_t n0, int64_t n1, int64_t xs0,
+                                  int64_t xs1, int64_t os0, int64_t os1, int D, int hidden, const T* W1, const T* b1, const T* W2, const T* b2,
+                                  const T* scale, float eps, uint64_t seed, double p1, double p2, semicrf_stream_t stream)
+{
+    long long st[4];
+    const int rc = ffn_bf16_check<T>(op, x, out, n0, n1, xs0, xs1, os0, os1, D, hidden, W1, b1, W2, b2, scale, st, "ffn_residual_bf16_bwd");
+    if (rc != SEMICRF_OK) return rc;
+    SEMICRF_CHECK_ARG(p1 >= 0.0 && p1 < 1.0 && p2 >= 0.0 && p2 < 1.0, "%s: dropout probabilities p_hidden=%g p_out=%g must lie in [0, 1)", op, p1, p2);
+    const long long ntok = n0 * n1;
+    const size_t need = ffn::train_saved_bytes(ntok, D, hidden);
+    SEMICRF_CHECK_ARG(saved && ((uintptr_t)saved & 15) == 0, "%s: saved must be non-NULL and 16-byte aligned", op);
+    SEMICRF_CHECK_ARG(saved_bytes >= need, "%s: saved buffer too small: %zu bytes given, semicrf_ffn_residual_bf16_train_saved_bytes says %zu", op,
+                      saved_bytes, need);
+    const long long xext = (n0 - 1) * st[0] + (n1 - 1) * st[1] + D, oext = (n0 - 1) * st[2] + (n1 - 1) * st[3] + D;
+    SEMICRF_CHECK_ARG(!ffn16_bytes_overlap(saved, need, x, (size_t)xext * sizeof(T)) && !ffn16_bytes_overlap(saved, need, out, (size_t)oext * sizeof(T)),
+                      "%s: saved overlaps x or out", op);
+    launch(x, out, n0, n1, st[0], st[1], st[2], st[3], D, hidden, W1, b1, W2, b2, scale, eps, seed, p1, p2, saved, (hipStream_t)stream);
+    SEMICRF_CHECK_LAUNCH(op);
+    return SEMICRF_OK;
+}
+
+template <typename T, typename L>
+static int ffn_bf16_bwd_any(const char* op, L launch, const T* dout, const T* x, const void* saved, size_t saved_bytes, int64_t n0, int64_t n1,
+                            int64_t gs0, int64_t gs1, int64_t xs0, int64_t xs1, int64_t ds0, int64_t ds1, int D, int hidden, const T* W1, const T* W2,
+                            const T* scale, float eps, uint64_t seed, double p1, double p2, T* dx, T* dW1, T* db1, T* dW2, T* db2, T* dscale, void* ws,
+                            size_t ws_bytes, semicrf_stream_t stream)
+{
+    // the cases of the eval op, in its words: once with dout, once with x in the place of `x`, dx in the place of `out`
+    long long sg[4], sx[4];
+    int rc = ffn_bf16_check<T>(op, dout, dx, n0, n1, gs0, gs1, ds0, ds1, D, hidden, W1, W1, W2, W2, scale, sg, "ffn_residual_bf16_bwd");
+    if (rc != SEMICRF_OK) return rc;
+    rc = ffn_bf16_check<T>(op, x, dx, n0, n1, xs0, xs1, ds0, ds1, D, hidden, W1, W1, W2, W2, scale, sx, "ffn_residual_bf16_bwd");
+    if (rc != SEMICRF_OK) return rc;
+    SEMICRF_CHECK_ARG(p1 >= 0.0 && p1 < 1.0 && p2 >= 0.0 && p2 < 1.0, "%s: dropout probabilities p_hidden=%g p_out=%g must lie in [0, 1)", op, p1, p2);
+    const long long ntok = n0 * n1;
+    SEMICRF_CHECK_ARG(ntok <= 65535ll * SEMICRF_FFN_BWD_ROW_CHUNK, "%s: n0 * n1 = %lld: more than 65535 row chunks", op, ntok);
+    SEMICRF_CHECK_ARG(dW1 && db1 && dW2 && db2 && dscale, "%s: dW1/db1/dW2/db2/dscale must be non-NULL", op);
+    SEMICRF_CHECK_ARG((((uintptr_t)dW1 | (uintptr_t)db1 | (uintptr_t)dW2 | (uintptr_t)db2 | (uintptr_t)dscale) & (sizeof(T) - 1)) == 0,
+                      "%s: every pointer must be %d-byte aligned", op, (int)sizeof(T));
+    const size_t need_saved = ffn::train_saved_bytes(ntok, D, hidden);
+    SEMICRF_CHECK_ARG(saved && ((uintptr_t)saved & 15) == 0, "%s: saved must be non-NULL and 16-byte aligned", op);
+    SEMICRF_CHECK_ARG(saved_bytes >= need_saved, "%s: saved buffer too small: %zu bytes given, semicrf_ffn_residual_bf16_train_saved_bytes says %zu",
+                      op, saved_bytes, need_saved);
+    const size_t dext = (size_t)((n0 - 1) * sg[2] + (n1 - 1) * sg[3] + D) * sizeof(T);
+    SEMICRF_CHECK_ARG(!ffn16_bytes_overlap(dx, dext, saved, need_saved), "%s: `dx` overlaps saved", op);
+    const size_t need = ffn_bf16_bwd_workspace_bytes(ntok, D, hidden);
+    SEMICRF_CHECK_ARG(ws && ((uintptr_t)ws & 15) == 0, "%s: ws must be non-NULL and 16-byte aligned", op);
+    if (ws_bytes < need) {
+        set_error("workspace too small for %s: %zu bytes given, semicrf_ffn_residual_bf16_bwd_workspace_bytes says %zu", op, ws_bytes, need);
+        return SEMICRF_EWORKSPACE;
+    }
+    launch(dout, x, saved, n0, n1, sg[0], sg[1], sx[0], sx[1], sg[2], sg[3], D, hidden, W1, W2, scale, eps, seed, p1, p2, dx, dW1, db1, dW2, db2,
+           dscale, ws, (hipStream_t)stream);
+    SEMICRF_CHECK_LAUNCH(op);
     return SEMICRF_OK;
 }
 
@@ -1573,6 +1640,62 @@ int semicrf_ffn_residual_bf16_mixed(const float* x, float* out, int64_t n0, int6
     launch_ffn_residual_bf16_mixed(x, out, n0, n1, st[0], st[1], st[2], st[3], D, hidden, W1, b1, W2, b2, scale, eps, (hipStream_t)stream);
     SEMICRF_CHECK_LAUNCH("semicrf_ffn_residual_bf16_mixed");
     return SEMICRF_OK;
+}
+
+int semicrf_ffn_residual_bf16_bwd_supported(int D, int hidden) { return ffn::supported(D, hidden) ? 1 : 0; }
+
+size_t semicrf_ffn_residual_bf16_train_saved_bytes(int64_t tokens, int D, int hidden)
+{
+    if (tokens < 1 || tokens >= (1ll << 37) || !ffn::supported(D, hidden)) return 0;
+    return ffn::train_saved_bytes(tokens, D, hidden);
+}
+
+size_t semicrf_ffn_residual_bf16_bwd_workspace_bytes(int64_t tokens, int D, int hidden)
+{
+    if (tokens < 1 || tokens >= (1ll << 37) || !ffn::supported(D, hidden)) return 0;
+    return ffn_bf16_bwd_workspace_bytes(tokens, D, hidden);
+}
+
+int semicrf_ffn_residual_bf16_train_fwd(const uint16_t* x, uint16_t* out, void* saved, size_t saved_bytes, int64_t n0, int64_t n1, int64_t x_stride_0,
+                                        int64_t x_stride_1, int64_t out_stride_0, int64_t out_stride_1, int D, int hidden, const uint16_t* W1,
+                                        const uint16_t* b1, const uint16_t* W2, const uint16_t* b2, const uint16_t* scale, float eps, uint64_t seed,
+                                        double p_hidden, double p_out, semicrf_stream_t stream)
+{
+    return ffn_bf16_train_fwd_any<uint16_t>("ffn_residual_bf16_train_fwd", &launch_ffn_residual_bf16_train, x, out, saved, saved_bytes, n0, n1,
+                                            x_stride_0, x_stride_1, out_stride_0, out_stride_1, D, hidden, W1, b1, W2, b2, scale, eps, seed, p_hidden,
+                                            p_out, stream);
+}
+
+int semicrf_ffn_residual_bf16_mixed_train_fwd(const float* x, float* out, void* saved, size_t saved_bytes, int64_t n0, int64_t n1, int64_t x_stride_0,
+                                              int64_t x_stride_1, int64_t out_stride_0, int64_t out_stride_1, int D, int hidden, const float* W1,
+                                              const float* b1, const float* W2, const float* b2, const float* scale, float eps, uint64_t seed,
+                                              double p_hidden, double p_out, semicrf_stream_t stream)
+{
+    return ffn_bf16_train_fwd_any<float>("ffn_residual_bf16_mixed_train_fwd", &launch_ffn_residual_bf16_mixed_train, x, out, saved, saved_bytes, n0, n1,
+                                         x_stride_0, x_stride_1, out_stride_0, out_stride_1, D, hidden, W1, b1, W2, b2, scale, eps, seed, p_hidden, p_out,
+                                         stream);
+}
+
+int semicrf_ffn_residual_bf16_bwd(const uint16_t* dout, const uint16_t* x, const void* saved, size_t saved_bytes, int64_t n0, int64_t n1,
+                                  int64_t dout_stride_0, int64_t dout_stride_1, int64_t x_stride_0, int64_t x_stride_1, int64_t dx_stride_0,
+                                  int64_t dx_stride_1, int D, int hidden, const uint16_t* W1, const uint16_t* W2, const uint16_t* scale, float eps,
+                                  uint64_t seed, double p_hidden, double p_out, uint16_t* dx, uint16_t* dW1, uint16_t* db1, uint16_t* dW2, uint16_t* db2,
+                                  uint16_t* dscale, void* ws, size_t ws_bytes, semicrf_stream_t stream)
+{
+    return ffn_bf16_bwd_any<uint16_t>("ffn_residual_bf16_bwd", &launch_ffn_residual_bf16_bwd, dout, x, saved, saved_bytes, n0, n1, dout_stride_0,
+                                      dout_stride_1, x_stride_0, x_stride_1, dx_stride_0, dx_stride_1, D, hidden, W1, W2, scale, eps, seed, p_hidden,
+                                      p_out, dx, dW1, db1, dW2, db2, dscale, ws, ws_bytes, stream);
+}
+
+int semicrf_ffn_residual_bf16_mixed_bwd(const float* dout, const float* x, const void* saved, size_t saved_bytes, int64_t n0, int64_t n1,
+                                        int64_t dout_stride_0, int64_t dout_stride_1, int64_t x_stride_0, int64_t x_stride_1, int64_t dx_stride_0,
+                                        int64_t dx_stride_1, int D, int hidden, const float* W1, const float* W2, const float* scale, float eps,
+                                        uint64_t seed, double p_hidden, double p_out, float* dx, float* dW1, float* db1, float* dW2, float* db2,
+                                        float* dscale, void* ws, size_t ws_bytes, semicrf_stream_t stream)
+{
+    return ffn_bf16_bwd_any<float>("ffn_residual_bf16_mixed_bwd", &launch_ffn_residual_bf16_mixed_bwd, dout, x, saved, saved_bytes, n0, n1, dout_stride_0,
+                                   dout_stride_1, x_stride_0, x_stride_1, dx_stride_0, dx_stride_1, D, hidden, W1, W2, scale, eps, seed, p_hidden, p_out,
+                                   dx, dW1, db1, dW2, db2, dscale, ws, ws_bytes, stream);
 }
 
 int semicrf_log_mel_supported(int W, int nWin, int C, int nMel, int max_len, int total)

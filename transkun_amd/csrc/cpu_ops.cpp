@@ -24,6 +24,7 @@
 #include "attention_bf16_math.h"
 #include "ffn_math.h"
 #include "ffn_bf16_math.h"
+#include "ffn_bf16_train_math.h"
 #include "logmel_math.h"
 #include "cpu_ops.h"
 
@@ -1941,6 +1942,187 @@ void ffn_residual_bf16_mixed(const float* x, float* out, int64_t n0, int64_t n1,
                              const float* W1, const float* b1, const float* W2, const float* b2, const float* scale, float eps)
 {
     ffn_residual_bf16_any<float>(x, out, n0, n1, xs0, xs1, os0, os1, D, H, W1, b1, W2, b2, scale, eps);
+}
+
+// ---- the bf16 block in training (semicrf_ffn_residual_bf16_train_fwd / _bwd and their _mixed forms) -------------------------------------
+// The chain of ffn_bf16_train_math.h, one product at a time in ascending order; `saved` is laid out as the header says.
+template <typename T>
+static void ffn_residual_bf16_train_fwd_any(const T* x, T* out, void* saved, int64_t n0, int64_t n1, int64_t xs0, int64_t xs1, int64_t os0,
+                                            int64_t os1, int D, int H, const T* W1, const T* b1, const T* W2, const T* b2, const T* scale, float eps,
+                                            uint64_t seed, double p1, double p2)
+{
+    using namespace semicrf::ffn;
+    const DropoutParams drop = semicrf::attr_heads::dropout_params(seed, p1, p2);
+    const int64_t ntok = n0 * n1;
+    uint16_t* const zs = (uint16_t*)saved;
+    T* const ys = (T*)((unsigned char*)saved + train_saved_ys_offset(ntok, H));
+    auto mk = [&](int stream, int64_t i, int j, float v) { return keep(drop, stream, i, j) ? (drop.on[stream] ? v * drop.scale[stream] : v) : 0.0f; };
+    std::vector<float> w1h((size_t)H * D), w2h((size_t)D * H);
+    for (size_t i = 0; i < w1h.size(); ++i) w1h[i] = bf16_to_float(operand_of(W1[i]));
+    for (size_t i = 0; i < w2h.size(); ++i) w2h[i] = bf16_to_float(operand_of(W2[i]));
+#pragma omp parallel
+    {
+        std::vector<float> xh((size_t)D), ah((size_t)H);
+#pragma omp for schedule(static)
+        for (int64_t t = 0; t < ntok; ++t) {
+            const int64_t i0 = t / n1, i1 = t % n1;
+            const T* xt = x + i0 * xs0 + i1 * xs1;
+            T* ot = out + i0 * os0 + i1 * os1;
+            float s[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+            for (int k = 0; k < D; ++k) s[k & 3] = fmaf(to_f32(xt[k]), to_f32(xt[k]), s[k & 3]);
+            const float rs = rs_of(sumsq_combine(s[0], s[1], s[2], s[3]), D, eps);
+            for (int k = 0; k < D; ++k) xh[k] = bf16_to_float(bf16_rne(to_f32(xt[k]) * rs));
+            for (int j = 0; j < H; ++j) {
+                const float* w = w1h.data() + (size_t)j * D;
+                float h = 0.0f;
+                for (int k = 0; k < D; ++k) h = fmaf(xh[k], w[k], h);
+                h += to_f32(b1[j]);
+                zs[t * H + j] = bf16_rne(h);
+                ah[j] = bf16_to_float(bf16_rne(mk(0, t, j, semicrf::attr_heads::gelu<float>(h))));
+            }
+            for (int n = 0; n < D; ++n) {
+                const float* w = w2h.data() + (size_t)n * H;
+                float a = 0.0f;
+                for (int j = 0; j < H; ++j) a = fmaf(ah[j], w[j], a);
+                const float y = a + to_f32(b2[n]);
+                store_as(ys + t * D + n, y);
+                store_as(ot + n, to_f32(xt[n]) + mk(1, t, n, y) * to_f32(scale[n]));
+            }
+        }
+    }
+}
+
+template <typename T>
+static void ffn_residual_bf16_bwd_any(const T* dout, const T* x, const void* saved, int64_t n0, int64_t n1, int64_t gs0, int64_t gs1, int64_t xs0,
+                                      int64_t xs1, int64_t ds0, int64_t ds1, int D, int H, const T* W1, const T* W2, const T* scale, float eps,
+                                      uint64_t seed, double p1, double p2, T* dx, T* dW1, T* db1, T* dW2, T* db2, T* dscale)
+{
+    using namespace semicrf::ffn;
+    using semicrf::attr_heads::gelu;
+    using semicrf::attr_heads::gelu_grad;
+    const DropoutParams drop = semicrf::attr_heads::dropout_params(seed, p1, p2);
+    const int64_t ntok = n0 * n1;
+    const uint16_t* const zs = (const uint16_t*)saved;
+    const T* const ys = (const T*)((const unsigned char*)saved + train_saved_ys_offset(ntok, H));
+    auto off = [&](int64_t i, int64_t s0, int64_t s1) { return (i / n1) * s0 + (i % n1) * s1; };
+    auto mk = [&](int stream, int64_t i, int j, float v) { return keep(drop, stream, i, j) ? (drop.on[stream] ? v * drop.scale[stream] : v) : 0.0f; };
+    auto r16 = [](float v) { return bf16_to_float(bf16_rne(v)); };
+    std::vector<float> w1h((size_t)H * D), w2t((size_t)H * D);           // Wh1 [H][D]; Wh2 transposed [H][D]
+    for (int j = 0; j < H; ++j)
+        for (int k = 0; k < D; ++k) {
+            w1h[(size_t)j * D + k] = bf16_to_float(operand_of(W1[(size_t)j * D + k]));
+            w2t[(size_t)j * D + k] = bf16_to_float(operand_of(W2[(size_t)k * H + j]));
+        }
+    std::vector<float> dyf((size_t)ntok * D), dyh((size_t)ntok * D), xh((size_t)ntok * D), dzh((size_t)ntok * H), ah((size_t)ntok * H);
+#pragma omp parallel
+    {
+        std::vector<float> xn((size_t)D), dxn((size_t)D);
+#pragma omp for schedule(static)
+        for (int64_t i = 0; i < ntok; ++i) {
+            const T* xt = x + off(i, xs0, xs1);
+            const T* gt = dout + off(i, gs0, gs1);
+            float s[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+            for (int k = 0; k < D; ++k) s[k & 3] = fmaf(to_f32(xt[k]), to_f32(xt[k]), s[k & 3]);
+            const float rs = rs_of(sumsq_combine(s[0], s[1], s[2], s[3]), D, eps);
+            for (int k = 0; k < D; ++k) {
+                xn[k] = to_f32(xt[k]) * rs;
+                xh[i * D + k] = r16(xn[k]);
+                dyf[i * D + k] = mk(1, i, k, to_f32(gt[k]) * to_f32(scale[k]));
+                dyh[i * D + k] = r16(dyf[i * D + k]);
+            }
+            for (int j = 0; j < H; ++j) {
+                const float* w = w2t.data() + (size_t)j * D;
+                float da = 0.0f;
+                for (int n = 0; n < D; ++n) da = fmaf(dyh[i * D + n], w[n], da);
+                const float zf = bf16_to_float(zs[i * H + j]);
+                dzh[i * H + j] = r16(mk(0, i, j, da) * gelu_grad<float>(zf));
+                ah[i * H + j] = r16(mk(0, i, j, gelu<float>(zf)));
+            }
+            std::fill(dxn.begin(), dxn.end(), 0.0f);
+            for (int j = 0; j < H; ++j) {                    // every dxn[k] is its own chain over j ascending
+                const float d = dzh[i * H + j];
+                const float* w = w1h.data() + (size_t)j * D;
+                for (int k = 0; k < D; ++k) dxn[k] = fmaf(d, w[k], dxn[k]);
+            }
+            float P[2][2] = {{0.0f, 0.0f}, {0.0f, 0.0f}};
+            for (int k = 0; k < D; ++k) P[(k >> 5) & 1][(k >> 2) & 1] = fmaf(dxn[k], xn[k], P[(k >> 5) & 1][(k >> 2) & 1]);
+            const float t = (P[0][0] + P[0][1]) + (P[1][0] + P[1][1]);
+            T* dt = dx + off(i, ds0, ds1);
+            for (int k = 0; k < D; ++k) store_as(dt + k, dx_of(to_f32(gt[k]), rs, dxn[k], xn[k], t, D));
+        }
+    }
+    // the sums over tokens: per chunk a plane from +0 with the tokens ascending, the planes added in ascending order, one rounding to T
+    const int64_t nch = (ntok + FFN_BWD_ROWS - 1) / FFN_BWD_ROWS;
+    auto colgemm = [&](const float* A, int Md, const float* B, int Nd, T* o) {
+#pragma omp parallel for schedule(static)
+        for (int m = 0; m < Md; ++m) {
+            std::vector<float> acc((size_t)Nd), total((size_t)Nd);
+            for (int64_t ch = 0; ch < nch; ++ch) {
+                const int64_t r0 = ch * FFN_BWD_ROWS, r1 = std::min(ntok, r0 + FFN_BWD_ROWS);
+                std::fill(acc.begin(), acc.end(), 0.0f);
+                for (int64_t i = r0; i < r1; ++i) {
+                    const float a = A[i * Md + m];
+                    const float* b = B + i * Nd;
+                    for (int n = 0; n < Nd; ++n) acc[n] = fmaf(a, b[n], acc[n]);
+                }
+                if (ch == 0) total = acc;
+                else for (int n = 0; n < Nd; ++n) total[n] += acc[n];
+            }
+            for (int n = 0; n < Nd; ++n) store_as(o + (int64_t)m * Nd + n, total[n]);
+        }
+    };
+    colgemm(dyh.data(), D, ah.data(), H, dW2);
+    colgemm(dzh.data(), H, xh.data(), D, dW1);
+    auto colsum = [&](int ncol, T* o, auto value) {
+#pragma omp parallel for schedule(static)
+        for (int c = 0; c < ncol; ++c) {
+            float total = 0.0f;
+            for (int64_t ch = 0; ch < nch; ++ch) {
+                const int64_t r0 = ch * FFN_BWD_ROWS, r1 = std::min(ntok, r0 + FFN_BWD_ROWS);
+                double sub[FFN_BWD_SUBSUMS];
+                for (int q = 0; q < FFN_BWD_SUBSUMS; ++q) {
+                    double t = 0.0;
+                    for (int64_t i = r0 + q; i < r1; i += FFN_BWD_SUBSUMS) t += (double)value(i, c);
+                    sub[q] = t;
+                }
+                double sacc = sub[0];
+                for (int q = 1; q < FFN_BWD_SUBSUMS; ++q) sacc += sub[q];
+                total = ch == 0 ? (float)sacc : total + (float)sacc;
+            }
+            store_as(o + c, total);
+        }
+    };
+    colsum(H, db1, [&](int64_t i, int j) { return dzh[i * H + j]; });
+    colsum(D, db2, [&](int64_t i, int n) { return dyf[i * D + n]; });
+    colsum(D, dscale, [&](int64_t i, int n) { return to_f32(dout[off(i, gs0, gs1) + n]) * mk(1, i, n, to_f32(ys[i * D + n])); });
+}
+
+void ffn_residual_bf16_train_fwd(const uint16_t* x, uint16_t* out, void* saved, int64_t n0, int64_t n1, int64_t xs0, int64_t xs1, int64_t os0,
+                                 int64_t os1, int D, int H, const uint16_t* W1, const uint16_t* b1, const uint16_t* W2, const uint16_t* b2,
+                                 const uint16_t* scale, float eps, uint64_t seed, double p1, double p2)
+{
+    ffn_residual_bf16_train_fwd_any<uint16_t>(x, out, saved, n0, n1, xs0, xs1, os0, os1, D, H, W1, b1, W2, b2, scale, eps, seed, p1, p2);
+}
+void ffn_residual_bf16_mixed_train_fwd(const float* x, float* out, void* saved, int64_t n0, int64_t n1, int64_t xs0, int64_t xs1, int64_t os0,
+                                       int64_t os1, int D, int H, const float* W1, const float* b1, const float* W2, const float* b2,
+                                       const float* scale, float eps, uint64_t seed, double p1, double p2)
+{
+    ffn_residual_bf16_train_fwd_any<float>(x, out, saved, n0, n1, xs0, xs1, os0, os1, D, H, W1, b1, W2, b2, scale, eps, seed, p1, p2);
+}
+void ffn_residual_bf16_bwd(const uint16_t* dout, const uint16_t* x, const void* saved, int64_t n0, int64_t n1, int64_t gs0, int64_t gs1, int64_t xs0,
+                           int64_t xs1, int64_t ds0, int64_t ds1, int D, int H, const uint16_t* W1, const uint16_t* W2, const uint16_t* scale,
+                           float eps, uint64_t seed, double p1, double p2, uint16_t* dx, uint16_t* dW1, uint16_t* db1, uint16_t* dW2, uint16_t* db2,
+                           uint16_t* dscale)
+{
+    ffn_residual_bf16_bwd_any<uint16_t>(dout, x, saved, n0, n1, gs0, gs1, xs0, xs1, ds0, ds1, D, H, W1, W2, scale, eps, seed, p1, p2, dx, dW1, db1,
+                                        dW2, db2, dscale);
+}
+void ffn_residual_bf16_mixed_bwd(const float* dout, const float* x, const void* saved, int64_t n0, int64_t n1, int64_t gs0, int64_t gs1, int64_t xs0,
+                                 int64_t xs1, int64_t ds0, int64_t ds1, int D, int H, const float* W1, const float* W2, const float* scale, float eps,
+                                 uint64_t seed, double p1, double p2, float* dx, float* dW1, float* db1, float* dW2, float* db2, float* dscale)
+{
+    ffn_residual_bf16_bwd_any<float>(dout, x, saved, n0, n1, gs0, gs1, xs0, xs1, ds0, ds1, D, H, W1, W2, scale, eps, seed, p1, p2, dx, dW1, db1, dW2,
+                                     db2, dscale);
 }
 
 // ---- the audio front end (semicrf_log_mel) -------------------------------------------------------------------------------------------

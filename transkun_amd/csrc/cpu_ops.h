@@ -104,6 +104,21 @@ void ffn_residual_bf16(const uint16_t* x, uint16_t* out, int64_t n0, int64_t n1,
                        const uint16_t* W1, const uint16_t* b1, const uint16_t* W2, const uint16_t* b2, const uint16_t* scale, float eps);
 void ffn_residual_bf16_mixed(const float* x, float* out, int64_t n0, int64_t n1, int64_t xs0, int64_t xs1, int64_t os0, int64_t os1, int D, int H,
                              const float* W1, const float* b1, const float* W2, const float* b2, const float* scale, float eps);
+// the bf16 block in training (semicrf_ffn_residual_bf16_train_fwd / _bwd and their _mixed forms): the chain of ffn_bf16_train_math.h one
+// product at a time in ascending order; `saved` as that header lays it out (semicrf_ffn_residual_bf16_train_saved_bytes bytes)
+void ffn_residual_bf16_train_fwd(const uint16_t* x, uint16_t* out, void* saved, int64_t n0, int64_t n1, int64_t xs0, int64_t xs1, int64_t os0,
+                                 int64_t os1, int D, int H, const uint16_t* W1, const uint16_t* b1, const uint16_t* W2, const uint16_t* b2,
+                                 const uint16_t* scale, float eps, uint64_t seed, double p1, double p2);
+void ffn_residual_bf16_mixed_train_fwd(const float* x, float* out, void* saved, int64_t n0, int64_t n1, int64_t xs0, int64_t xs1, int64_t os0,
+                                       int64_t os1, int D, int H, const float* W1, const float* b1, const float* W2, const float* b2,
+                                       const float* scale, float eps, uint64_t seed, double p1, double p2);
+void ffn_residual_bf16_bwd(const uint16_t* dout, const uint16_t* x, const void* saved, int64_t n0, int64_t n1, int64_t gs0, int64_t gs1, int64_t xs0,
+                           int64_t xs1, int64_t ds0, int64_t ds1, int D, int H, const uint16_t* W1, const uint16_t* W2, const uint16_t* scale,
+                           float eps, uint64_t seed, double p1, double p2, uint16_t* dx, uint16_t* dW1, uint16_t* db1, uint16_t* dW2, uint16_t* db2,
+                           uint16_t* dscale);
+void ffn_residual_bf16_mixed_bwd(const float* dout, const float* x, const void* saved, int64_t n0, int64_t n1, int64_t gs0, int64_t gs1, int64_t xs0,
+                                 int64_t xs1, int64_t ds0, int64_t ds1, int D, int H, const float* W1, const float* W2, const float* scale, float eps,
+                                 uint64_t seed, double p1, double p2, float* dx, float* dW1, float* db1, float* dW2, float* db2, float* dscale);
 // the audio front end (semicrf_log_mel): the device kernel's order of operations per output element, in fp32 (logmel_math.h); frames
 // by its three element strides, out contiguous [N][to_mono ? 1 : C][nFrame][nMel][nWin]; the caller has checked the supported set
 void log_mel(const float* frames, int64_t sn, int64_t sc, int64_t sf, int N, int C, int nFrame, int W, const float* windows, int nWin,

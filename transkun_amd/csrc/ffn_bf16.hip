@@ -26,133 +26,38 @@
 // stored); hidden columns past the last chunk and columns past D are zeros formed in registers; the loads behind them are clamped
 // onto real elements and their values dropped.  Tile sizes depend on nothing and every sum has one order: a token's result is
 // bit-identical whatever the other tokens, n0, n1, the strides and the alignment are.
+//
+// Training mode (template parameter TRAIN; semicrf_ffn_residual_bf16_train_fwd / _mixed_train_fwd; the chain: ffn_bf16_train_math.h): the
+// same walk with both dropouts from the fp32 route's stateless mask (one Philox call per lane and register group: the four lanes of a
+// quad share their draws), zs = bf16(h) written through one more LDS tile [64][64 + 8] as whole 128-byte lines, ys = y rounded to T
+// beside `out`.  The eval instantiations compile to the registers they had; with p = 0 the training mode gives their bits.
 #include "common.h"
 #include "launchers.h"
 #include "bf16x3.h"
-#include "ffn_bf16_math.h"
+#include "ffn_bf16_dev.h"
+
+#include <type_traits>
 
 namespace semicrf {
 
 using namespace ffn;
 using attr_heads::gelu;
 
-static_assert(FFN16_ROWS == 64 && FFN16_CHUNK == 64, "the lane maps below are written for 64 x 64");
-constexpr int FFN16_LDG = FFN16_CHUNK + FFN16_PAD;          // bf16 per row of Gs and of the W2 tile
-
-struct Ffn16F8 { float v[8]; };
-
-// 8 consecutive elements as fp32 (exact): 16-byte loads, or element loads put together -- the same bits
+struct Ffn16Eval {};
 template <typename T>
-__device__ __forceinline__ Ffn16F8 ffn16_load8f(const T* p, bool vec);
-template <>
-__device__ __forceinline__ Ffn16F8 ffn16_load8f<uint16_t>(const uint16_t* p, bool vec)
-{
-    u32x4 x;
-    if (vec) {
-        x = *(const u32x4*)p;
-    } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) x[e] = (unsigned)p[2 * e] | ((unsigned)p[2 * e + 1] << 16);
-    }
-    Ffn16F8 r;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        r.v[2 * e] = __uint_as_float(x[e] << 16);
-        r.v[2 * e + 1] = __uint_as_float(x[e] & 0xffff0000u);
-    }
-    return r;
-}
-template <>
-__device__ __forceinline__ Ffn16F8 ffn16_load8f<float>(const float* p, bool vec)
-{
-    Ffn16F8 r;
-    if (vec) {
-        const float4 a = *(const float4*)p, b = *(const float4*)(p + 4);
-        r.v[0] = a.x; r.v[1] = a.y; r.v[2] = a.z; r.v[3] = a.w;
-        r.v[4] = b.x; r.v[5] = b.y; r.v[6] = b.z; r.v[7] = b.w;
-    } else {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) r.v[e] = p[e];
-    }
-    return r;
-}
-
-// 8 consecutive weights as the bf16 operand of a product: as they are (form A), rounded to nearest even (form B)
-template <typename T>
-__device__ __forceinline__ u32x4 ffn16_load8h(const T* p, bool vec);
-template <>
-__device__ __forceinline__ u32x4 ffn16_load8h<uint16_t>(const uint16_t* p, bool vec)
-{
-    u32x4 x;
-    if (vec) {
-        x = *(const u32x4*)p;
-    } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) x[e] = (unsigned)p[2 * e] | ((unsigned)p[2 * e + 1] << 16);
-    }
-    return x;
-}
-template <>
-__device__ __forceinline__ u32x4 ffn16_load8h<float>(const float* p, bool vec)
-{
-    const Ffn16F8 f = ffn16_load8f<float>(p, vec);
-    u32x4 x;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) x[e] = cvt_pk_bf16(f.v[2 * e], f.v[2 * e + 1]);
-    return x;
-}
-
-// four consecutive elements as fp32, and four results rounded once to T
-__device__ __forceinline__ void ffn16_load4f(const uint16_t* p, bool vec, float* v)
-{
-    if (vec) {
-        const uint2 u = *(const uint2*)p;
-        v[0] = __uint_as_float(u.x << 16); v[1] = __uint_as_float(u.x & 0xffff0000u);
-        v[2] = __uint_as_float(u.y << 16); v[3] = __uint_as_float(u.y & 0xffff0000u);
-    } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = __uint_as_float((unsigned)p[e] << 16);
-    }
-}
-__device__ __forceinline__ void ffn16_load4f(const float* p, bool vec, float* v)
-{
-    if (vec) {
-        const float4 a = *(const float4*)p;
-        v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
-    } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = p[e];
-    }
-}
-__device__ __forceinline__ void ffn16_store4(uint16_t* p, bool vec, const float* v)
-{
-    const unsigned a = cvt_pk_bf16(v[0], v[1]), b = cvt_pk_bf16(v[2], v[3]);
-    if (vec) {
-        *(uint2*)p = make_uint2(a, b);
-    } else {
-        p[0] = (uint16_t)a; p[1] = (uint16_t)(a >> 16);
-        p[2] = (uint16_t)b; p[3] = (uint16_t)(b >> 16);
-    }
-}
-__device__ __forceinline__ void ffn16_store4(float* p, bool vec, const float* v)
-{
-    if (vec) {
-        *(float4*)p = make_float4(v[0], v[1], v[2], v[3]);
-    } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) p[e] = v[e];
-    }
-}
+struct Ffn16Train { DropoutParams drop; uint16_t* zs; T* ys; };
 
 // T: uint16_t (bf16 tensors) or float (fp32 tensors, bf16 operands)
+// TRAIN: the training mode: both dropouts, zs and ys saved (tr); the eval instantiations compile to what they were
 // DB: column blocks of 32 that cover D (D in (32 (DB - 1), 32 DB]); up to D = 160 two workgroups share a CU
 // vec: 16-byte loads of x, W1 and W2 (launch_ffn_residual_bf16 decides); ovec: the epilogue's four-column reads of x and stores of out
-template <typename T, int DB>
+template <typename T, int DB, bool TRAIN = false>
 __global__ __launch_bounds__(256, DB <= 5 ? 2 : 1) void ffn_residual_bf16_kernel(const T* x, T* out, long long ntok, long long n1, long long xs0,
                                                                                long long xs1, long long os0, long long os1, int D, int H,
                                                                                const T* __restrict__ W1, const T* __restrict__ b1,
                                                                                const T* __restrict__ W2, const T* __restrict__ b2,
-                                                                               const T* __restrict__ scale, float eps, int vec, int ovec)
+                                                                               const T* __restrict__ scale, float eps, int vec, int ovec,
+                                                                               std::conditional_t<TRAIN, Ffn16Train<T>, Ffn16Eval> tr = {})
 {
     constexpr int NB = (DB + 1) / 2;                         // column blocks per wave
     constexpr int KS = 2 * DB;                               // k-steps of layer 1 an instantiation can have
@@ -163,6 +68,7 @@ __global__ __launch_bounds__(256, DB <= 5 ? 2 : 1) void ffn_residual_bf16_kernel
     uint16_t* const W2s = W1s + FFN16_CHUNK * ldw1;                     // [D][FFN16_LDG]
     uint16_t* const Gs = W2s + D * FFN16_LDG;                           // [64][FFN16_LDG]
     float* const Rs = (float*)(Gs + FFN16_ROWS * FFN16_LDG);            // [64]
+    uint16_t* const Zs = (uint16_t*)(Rs + FFN16_ROWS);                  // [64][FFN16_LDZ]: the chunk's zs tile (TRAIN)
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l31 = lane & 31, hh = lane >> 5;
@@ -287,7 +193,7 @@ __global__ __launch_bounds__(256, DB <= 5 ? 2 : 1) void ffn_residual_bf16_kernel
         for (int r = 0; r < 16; ++r) {
             const int j = j0 + cw * 32 + 8 * (r >> 2) + 4 * hh + (r & 3);
             real[r] = j < H;
-            bias[r] = to_f32(b1[min(j, H - 1)]);
+            if (!TRAIN || r < 4) bias[r] = to_f32(b1[min(j, H - 1)]);
         }
         if (ch + 1 < nch) load_w(j0 + FFN16_CHUNK);
         __syncthreads();
@@ -304,14 +210,42 @@ __global__ __launch_bounds__(256, DB <= 5 ? 2 : 1) void ffn_residual_bf16_kernel
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
             float v[4];
+            if constexpr (TRAIN) {
+                // zs = bf16(h) into the chunk's tile, a = gelu(h) * M1: this lane's token at four consecutive hidden columns
+                uint32_t w[4];
+                ffn16_draws4(tr.drop, 0, tok, j0 + cw * 32 + 8 * g + 4 * hh, w);
+                float z[4];
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int r = 4 * g + e;
-                v[e] = real[r] && tok_ok ? gelu<float>(h[r] + bias[r]) : 0.0f;
+                for (int e = 0; e < 4; ++e) {
+                    const int r = 4 * g + e;
+                    z[e] = h[r] + bias[r];
+                    v[e] = real[r] && tok_ok ? masked(tr.drop, 0, w[e], gelu<float>(z[e])) : 0.0f;
+                }
+                if (g < 3) {                                 // the next group's b1: four values in flight, not sixteen held through the draws
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) bias[4 * g + 4 + e] = to_f32(b1[min(j0 + cw * 32 + 8 * (g + 1) + 4 * hh + e, H - 1)]);
+                }
+                *(uint2*)(Zs + (rt * 32 + l31) * FFN16_LDZ + cw * 32 + 8 * g + 4 * hh) = make_uint2(cvt_pk_bf16(z[0], z[1]), cvt_pk_bf16(z[2], z[3]));
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int r = 4 * g + e;
+                    v[e] = real[r] && tok_ok ? gelu<float>(h[r] + bias[r]) : 0.0f;
+                }
             }
             *(uint2*)(grow + cw * 32 + 8 * g + 4 * hh) = make_uint2(cvt_pk_bf16(v[0], v[1]), cvt_pk_bf16(v[2], v[3]));
         }
         __syncthreads();                                     // Gs is written
+        if constexpr (TRAIN) {
+            // the zs tile to memory as whole 128-byte lines: 8 consecutive threads move one token's 64 columns of the chunk
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                const int idx = tid + 256 * i;
+                const int r = idx >> 3, c = 8 * (idx & 7);
+                if (row0 + r < ntok && j0 + c < H)            // hidden is a multiple of 8: a piece lies inside it or past it
+                    *(u32x4*)(tr.zs + (size_t)(row0 + r) * H + j0 + c) = *(const u32x4*)(Zs + r * FFN16_LDZ + c);
+            }
+        }
         // ---- layer 2: out^T blocks cw, cw + 2, .. on the running accumulators ----------------------------------------------------------
 #pragma unroll
         for (int s = 0; s < FFN16_CHUNK / 16; ++s) {
@@ -328,7 +262,30 @@ __global__ __launch_bounds__(256, DB <= 5 ? 2 : 1) void ffn_residual_bf16_kernel
     }
 
     // ---- x + (acc + b2) * scale: register group g of block i holds the columns (cw + 2 i) * 32 + 8 g + 4 hh .. + 3 of this token ---------
-    if (tok_ok) {
+    if constexpr (TRAIN) {
+        // y = acc + b2 (saved, rounded to T), out = x + (y * M2) * scale; the quad shares its draws, so every lane walks the columns
+#pragma unroll
+        for (int i = 0; i < NB; ++i)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const int n = (cw + 2 * i) * 32 + 8 * g + 4 * hh;
+                if (cw + 2 * i < DB) {                       // wave-uniform
+                    uint32_t w[4];
+                    ffn16_draws4(tr.drop, 1, tok, min(n, D - 4), w);
+                    if (tok_ok && n < D) {
+                        float xv[4], y[4], o[4];
+                        ffn16_load4f(x + xo + n, ovec, xv);
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) {
+                            y[e] = acc[i][4 * g + e] + to_f32(b2[n + e]);
+                            o[e] = xv[e] + masked(tr.drop, 1, w[e], y[e]) * to_f32(scale[n + e]);
+                        }
+                        ffn16_store4(tr.ys + (size_t)tok * D + n, true, y);      // ys is dense and 256-byte aligned
+                        ffn16_store4(out + oo + n, ovec, o);
+                    }
+                }
+            }
+    } else if (tok_ok) {
 #pragma unroll
         for (int i = 0; i < NB; ++i)
 #pragma unroll
@@ -375,6 +332,54 @@ static void ffn16_launch(const T* x, T* out, long long n0, long long n1, long lo
         SEMICRF_FFN16_CASE(5); SEMICRF_FFN16_CASE(6); SEMICRF_FFN16_CASE(7); SEMICRF_FFN16_CASE(8);
     }
 #undef SEMICRF_FFN16_CASE
+}
+
+// ---- the training mode: the same geometry, the zs tile more in LDS; the saved buffer is laid out as ffn_bf16_train_math.h says -------------
+template <typename T, int DB>
+static void ffn16_train_launch_one(const T* x, T* out, long long ntok, long long n1, long long xs0, long long xs1, long long os0, long long os1,
+                                   int D, int H, const T* W1, const T* b1, const T* W2, const T* b2, const T* scale, float eps, int vec, int ovec,
+                                   const Ffn16Train<T>& tr, hipStream_t stream)
+{
+    static PerDeviceOnce once;
+    if (once.first())
+        (void)hipFuncSetAttribute((const void*)ffn_residual_bf16_kernel<T, DB, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)lds_bytes_bf16_train(DB * 32));
+    hipLaunchKernelGGL((ffn_residual_bf16_kernel<T, DB, true>), dim3((unsigned)((ntok + FFN16_ROWS - 1) / FFN16_ROWS)), dim3(256),
+                       lds_bytes_bf16_train(D), stream, x, out, ntok, n1, xs0, xs1, os0, os1, D, H, W1, b1, W2, b2, scale, eps, vec, ovec, tr);
+}
+
+template <typename T>
+static void ffn16_train_launch(const T* x, T* out, long long n0, long long n1, long long xs0, long long xs1, long long os0, long long os1, int D,
+                               int H, const T* W1, const T* b1, const T* W2, const T* b2, const T* scale, float eps, unsigned long long seed,
+                               double p1, double p2, void* saved, hipStream_t stream)
+{
+    constexpr long long EL = 16 / sizeof(T);
+    const int vec = ((((uintptr_t)x | (uintptr_t)W1 | (uintptr_t)W2) & 15) == 0) && ((xs0 | xs1) & (EL - 1)) == 0;
+    const int ovec = ((((uintptr_t)x | (uintptr_t)out) & (4 * sizeof(T) - 1)) == 0) && ((xs0 | xs1 | os0 | os1) & 3) == 0;
+    const long long ntok = n0 * n1;
+    const Ffn16Train<T> tr{attr_heads::dropout_params(seed, p1, p2), (uint16_t*)saved, (T*)((unsigned char*)saved + train_saved_ys_offset(ntok, H))};
+#define SEMICRF_FFN16_CASE(N) \
+    case N: ffn16_train_launch_one<T, N>(x, out, ntok, n1, xs0, xs1, os0, os1, D, H, W1, b1, W2, b2, scale, eps, vec, ovec, tr, stream); break
+    switch ((D + 31) / 32) {
+        SEMICRF_FFN16_CASE(1); SEMICRF_FFN16_CASE(2); SEMICRF_FFN16_CASE(3); SEMICRF_FFN16_CASE(4);
+        SEMICRF_FFN16_CASE(5); SEMICRF_FFN16_CASE(6); SEMICRF_FFN16_CASE(7); SEMICRF_FFN16_CASE(8);
+    }
+#undef SEMICRF_FFN16_CASE
+}
+
+void launch_ffn_residual_bf16_train(const uint16_t* x, uint16_t* out, long long n0, long long n1, long long xs0, long long xs1, long long os0,
+                                    long long os1, int D, int H, const uint16_t* W1, const uint16_t* b1, const uint16_t* W2, const uint16_t* b2,
+                                    const uint16_t* scale, float eps, unsigned long long seed, double p1, double p2, void* saved, hipStream_t stream)
+{
+    ffn16_train_launch<uint16_t>(x, out, n0, n1, xs0, xs1, os0, os1, D, H, W1, b1, W2, b2, scale, eps, seed, p1, p2, saved, stream);
+}
+
+void launch_ffn_residual_bf16_mixed_train(const float* x, float* out, long long n0, long long n1, long long xs0, long long xs1, long long os0,
+                                          long long os1, int D, int H, const float* W1, const float* b1, const float* W2, const float* b2,
+                                          const float* scale, float eps, unsigned long long seed, double p1, double p2, void* saved,
+                                          hipStream_t stream)
+{
+    ffn16_train_launch<float>(x, out, n0, n1, xs0, xs1, os0, os1, D, H, W1, b1, W2, b2, scale, eps, seed, p1, p2, saved, stream);
 }
 
 void launch_ffn_residual_bf16(const uint16_t* x, uint16_t* out, long long n0, long long n1, long long xs0, long long xs1, long long os0, long long os1,

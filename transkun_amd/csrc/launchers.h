@@ -105,6 +105,25 @@ void launch_ffn_residual_bf16(const uint16_t* x, uint16_t* out, long long n0, lo
 void launch_ffn_residual_bf16_mixed(const float* x, float* out, long long n0, long long n1, long long xs0, long long xs1, long long os0, long long os1,
                                     int D, int H, const float* W1, const float* b1, const float* W2, const float* b2, const float* scale, float eps,
                                     hipStream_t stream);
+// the training mode: `saved` is laid out as ffn_bf16_train_math.h says (zs, then ys)
+void launch_ffn_residual_bf16_train(const uint16_t* x, uint16_t* out, long long n0, long long n1, long long xs0, long long xs1, long long os0,
+                                    long long os1, int D, int H, const uint16_t* W1, const uint16_t* b1, const uint16_t* W2, const uint16_t* b2,
+                                    const uint16_t* scale, float eps, unsigned long long seed, double p1, double p2, void* saved, hipStream_t stream);
+void launch_ffn_residual_bf16_mixed_train(const float* x, float* out, long long n0, long long n1, long long xs0, long long xs1, long long os0,
+                                          long long os1, int D, int H, const float* W1, const float* b1, const float* W2, const float* b2,
+                                          const float* scale, float eps, unsigned long long seed, double p1, double p2, void* saved,
+                                          hipStream_t stream);
+
+// ffn_bf16_bwd.hip
+size_t ffn_bf16_bwd_workspace_bytes(long long ntok, int D, int H);
+void launch_ffn_residual_bf16_bwd(const uint16_t* dout, const uint16_t* x, const void* saved, long long n0, long long n1, long long gs0, long long gs1,
+                                  long long xs0, long long xs1, long long ds0, long long ds1, int D, int H, const uint16_t* W1, const uint16_t* W2,
+                                  const uint16_t* scale, float eps, unsigned long long seed, double p1, double p2, uint16_t* dx, uint16_t* dW1,
+                                  uint16_t* db1, uint16_t* dW2, uint16_t* db2, uint16_t* dscale, void* ws, hipStream_t stream);
+void launch_ffn_residual_bf16_mixed_bwd(const float* dout, const float* x, const void* saved, long long n0, long long n1, long long gs0, long long gs1,
+                                        long long xs0, long long xs1, long long ds0, long long ds1, int D, int H, const float* W1, const float* W2,
+                                        const float* scale, float eps, unsigned long long seed, double p1, double p2, float* dx, float* dW1,
+                                        float* db1, float* dW2, float* db2, float* dscale, void* ws, hipStream_t stream);
 
 // logmel.hip
 void launch_log_mel(const float* frames, long long sn, long long sc, long long sf, int N, int C, int nFrame, int W, const float* windows, int nWin,

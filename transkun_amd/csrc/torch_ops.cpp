@@ -1408,6 +1408,185 @@ void ffn_residual_bf16_mixed_cpu(Tensor x, Tensor W1, Tensor b1, Tensor W2, Tens
     ffn_on_host<float>(a, eps, &semicrf_cpu::ffn_residual_bf16_mixed, "ffn_residual_bf16_mixed");
 }
 
+// ---- the bf16 block in training: four ops, E the element type of the form (uint16_t: bfloat16 tensors, float: the _mixed form) ------------
+// saved: uint8, contiguous, at least semicrf_ffn_residual_bf16_train_saved_bytes(n0 n1, D, hidden) bytes, 16-byte aligned; seed: 64 bits
+template <typename E>
+constexpr ScalarType ffn16_dtype() { return sizeof(E) == 2 ? ScalarType::BFloat16 : ScalarType::Float; }
+inline void ffn16_p_ok(double p_hidden, double p_out)
+{
+    STD_TORCH_CHECK(p_hidden >= 0.0 && p_hidden < 1.0 && p_out >= 0.0 && p_out < 1.0, "semicrf: dropout probabilities must lie in [0, 1)");
+}
+inline bool ffn16_apart(const void* p, size_t np, const void* q, size_t nq)
+{
+    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
+    return a + np <= b || b + nq <= a;
+}
+inline void* ffn16_saved(const Tensor& saved, const FfnArgs& a, size_t* need)
+{
+    *need = semicrf_ffn_residual_bf16_train_saved_bytes(a.n0 * a.n1, a.D, a.H);
+    void* p = bytes(saved, "saved");
+    if (a.n0 == 0 || a.n1 == 0) return p;
+    STD_TORCH_CHECK((size_t)saved.numel() >= *need, "semicrf: `saved` holds ", saved.numel(), " bytes, the call needs ", *need);
+    STD_TORCH_CHECK(((uintptr_t)p & 15) == 0, "semicrf: `saved` must be 16-byte aligned");
+    return p;
+}
+template <typename E, typename F>
+void ffn16_train_fwd_device(F entry, const char* name, const Tensor& x, const Tensor& W1, const Tensor& b1, const Tensor& W2, const Tensor& b2,
+                            const Tensor& scale, double eps, int64_t seed, double p_hidden, double p_out, const Tensor& out, const Tensor& saved)
+{
+    Ctx c(x); c.same(x, W1, b1, W2, b2, scale, out, saved);
+    const FfnArgs a = ffn_args(x, W1, b1, W2, b2, scale, out, ffn16_dtype<E>());
+    void* sp = bytes(saved, "saved");
+    if (a.n0 == 0 || a.n1 == 0) return;
+    check(entry((const E*)a.x, (E*)a.out, sp, (size_t)saved.numel(), a.n0, a.n1, a.st[0], a.st[1], a.st[2], a.st[3], a.D, a.H, (const E*)a.W1,
+                (const E*)a.b1, (const E*)a.W2, (const E*)a.b2, (const E*)a.scale, (float)eps, (uint64_t)seed, p_hidden, p_out, c.stream),
+          name);
+}
+template <typename E, typename F>
+void ffn16_train_fwd_host(F mirror, const char* name, const Tensor& x, const Tensor& W1, const Tensor& b1, const Tensor& W2, const Tensor& b2,
+                          const Tensor& scale, double eps, int64_t seed, double p_hidden, double p_out, const Tensor& out, const Tensor& saved)
+{
+    all_cpu(x, W1, b1, W2, b2, scale, out, saved);
+    const FfnArgs a = ffn_args(x, W1, b1, W2, b2, scale, out, ffn16_dtype<E>());
+    ffn16_p_ok(p_hidden, p_out);
+    size_t need = 0;
+    void* sp = ffn16_saved(saved, a, &need);
+    if (a.n0 == 0 || a.n1 == 0) return;
+    const size_t xext = (size_t)((a.n0 - 1) * a.st[0] + (a.n1 - 1) * a.st[1] + a.D) * sizeof(E);
+    const size_t oext = (size_t)((a.n0 - 1) * a.st[2] + (a.n1 - 1) * a.st[3] + a.D) * sizeof(E);
+    STD_TORCH_CHECK(ffn16_apart(a.x, xext, a.out, oext), "semicrf: ", name, ": `out` overlaps `x`");
+    STD_TORCH_CHECK(ffn16_apart(sp, need, a.x, xext) && ffn16_apart(sp, need, a.out, oext), "semicrf: ", name, ": saved overlaps x or out");
+    mirror((const E*)a.x, (E*)a.out, sp, a.n0, a.n1, a.st[0], a.st[1], a.st[2], a.st[3], a.D, a.H, (const E*)a.W1, (const E*)a.b1, (const E*)a.W2,
+           (const E*)a.b2, (const E*)a.scale, (float)eps, (uint64_t)seed, p_hidden, p_out);
+}
+
+struct Ffn16BwdArgs {
+    const void *g, *x, *W1, *W2, *scale;
+    void *dx, *dW1, *db1, *dW2, *db2, *dscale;
+    int64_t n0, n1, st[6];           // dout, x, dx: two element row strides each
+    int D, H;
+};
+inline Ffn16BwdArgs ffn16_bwd_args(ScalarType dtype, const Tensor& dout, const Tensor& x, const Tensor& W1, const Tensor& W2, const Tensor& scale,
+                                   double p_hidden, double p_out, const Tensor& dx, const Tensor& dW1, const Tensor& db1, const Tensor& dW2,
+                                   const Tensor& db2, const Tensor& dscale)
+{
+    Ffn16BwdArgs a{};
+    const char* const dname = dtype == ScalarType::Float ? "float32" : "bfloat16";
+    const Tensor* views[3] = {&dout, &x, &dx};
+    STD_TORCH_CHECK(x.defined() && x.dim() == 3, "semicrf: `x` must be [n0, n1, D]");
+    STD_TORCH_CHECK(W1.defined() && W1.dim() == 2 && W2.defined() && W2.dim() == 2, "semicrf: `W1` must be [hidden, D], `W2` [D, hidden]");
+    const int64_t D = x.size(2), H = W1.size(0);
+    a.n0 = x.size(0); a.n1 = x.size(1);
+    STD_TORCH_CHECK(D >= 1 && D < (1 << 20) && H >= 1 && H < (1 << 20) && W1.size(1) == D && W2.size(0) == D && W2.size(1) == H,
+                    "semicrf: `W1` / `W2` do not have the shape of the call");
+    STD_TORCH_CHECK(semicrf_ffn_residual_bf16_bwd_supported((int)D, (int)H), "semicrf: ffn_residual_bf16_bwd does not support D=", D, " hidden=", H,
+                    " (semicrf_ffn_residual_bf16_bwd_supported)");
+    ffn16_p_ok(p_hidden, p_out);
+    for (int v = 0; v < 3; ++v) {
+        const Tensor& t = *views[v];
+        STD_TORCH_CHECK(t.defined() && t.dim() == 3 && t.scalar_type() == dtype, "semicrf: `dout`, `x` and `dx` must be ", dname, " [n0, n1, D]");
+        STD_TORCH_CHECK(t.size(0) == a.n0 && t.size(1) == a.n1 && t.size(2) == D && t.stride(2) == 1,
+                        "semicrf: `dout`, `x` and `dx` must share one shape and have a contiguous last dimension");
+        for (int j = 0; j < 2; ++j) {
+            a.st[2 * v + j] = t.size(j) > 1 ? t.stride(j) : 0;
+            STD_TORCH_CHECK(a.st[2 * v + j] >= 0, "semicrf: negative stride");
+        }
+    }
+    STD_TORCH_CHECK((a.n0 <= 1 || a.st[4] >= D) && (a.n1 <= 1 || a.st[5] >= D), "semicrf: `dx` must not repeat or interleave its rows");
+    a.D = (int)D; a.H = (int)H;
+    auto ptr = [&](const Tensor& t, int64_t n, const char* name) -> void* { want(t, dtype, n, name); return t.data_ptr(); };
+    a.W1 = ptr(W1, H * D, "W1"); a.W2 = ptr(W2, D * H, "W2"); a.scale = ptr(scale, D, "scale");
+    a.dW1 = ptr(dW1, H * D, "dW1"); a.db1 = ptr(db1, H, "db1"); a.dW2 = ptr(dW2, D * H, "dW2"); a.db2 = ptr(db2, D, "db2");
+    a.dscale = ptr(dscale, D, "dscale");
+    const int64_t ntok = a.n0 * a.n1;
+    a.g = ntok > 0 ? dout.data_ptr() : nullptr;
+    a.x = ntok > 0 ? x.data_ptr() : nullptr;
+    a.dx = ntok > 0 ? dx.data_ptr() : nullptr;
+    return a;
+}
+template <typename E, typename F>
+void ffn16_bwd_device(F entry, const char* name, const Tensor& dout, const Tensor& x, const Tensor& saved, const Tensor& W1, const Tensor& W2,
+                      const Tensor& scale, double eps, int64_t seed, double p_hidden, double p_out, const Tensor& dx, const Tensor& dW1,
+                      const Tensor& db1, const Tensor& dW2, const Tensor& db2, const Tensor& dscale, const Tensor& ws)
+{
+    Ctx c(x); c.same(x, dout, saved, W1, W2, scale, dx, dW1, db1, dW2, db2, dscale, ws);
+    const Ffn16BwdArgs a = ffn16_bwd_args(ffn16_dtype<E>(), dout, x, W1, W2, scale, p_hidden, p_out, dx, dW1, db1, dW2, db2, dscale);
+    void* sp = bytes(saved, "saved");
+    void* wp = bytes(ws, "ws");
+    if (a.n0 == 0 || a.n1 == 0) return;
+    check(entry((const E*)a.g, (const E*)a.x, sp, (size_t)saved.numel(), a.n0, a.n1, a.st[0], a.st[1], a.st[2], a.st[3], a.st[4], a.st[5], a.D, a.H,
+                (const E*)a.W1, (const E*)a.W2, (const E*)a.scale, (float)eps, (uint64_t)seed, p_hidden, p_out, (E*)a.dx, (E*)a.dW1, (E*)a.db1, (E*)a.dW2,
+                (E*)a.db2, (E*)a.dscale, wp, (size_t)ws.numel(), c.stream),
+          name);
+}
+template <typename E, typename F>
+void ffn16_bwd_host(F mirror, const char* name, const Tensor& dout, const Tensor& x, const Tensor& saved, const Tensor& W1, const Tensor& W2,
+                    const Tensor& scale, double eps, int64_t seed, double p_hidden, double p_out, const Tensor& dx, const Tensor& dW1,
+                    const Tensor& db1, const Tensor& dW2, const Tensor& db2, const Tensor& dscale, const Tensor& ws)
+{
+    all_cpu(x, dout, saved, W1, W2, scale, dx, dW1, db1, dW2, db2, dscale, ws);
+    const Ffn16BwdArgs a = ffn16_bwd_args(ffn16_dtype<E>(), dout, x, W1, W2, scale, p_hidden, p_out, dx, dW1, db1, dW2, db2, dscale);
+    void* sp = bytes(saved, "saved");
+    if (a.n0 == 0 || a.n1 == 0) return;
+    const size_t need = semicrf_ffn_residual_bf16_train_saved_bytes(a.n0 * a.n1, a.D, a.H);
+    STD_TORCH_CHECK((size_t)saved.numel() >= need, "semicrf: `saved` holds ", saved.numel(), " bytes, the call needs ", need);
+    auto ext = [&](int v) { return (size_t)((a.n0 - 1) * a.st[2 * v] + (a.n1 - 1) * a.st[2 * v + 1] + a.D) * sizeof(E); };
+    STD_TORCH_CHECK(ffn16_apart(a.dx, ext(2), a.g, ext(0)) && ffn16_apart(a.dx, ext(2), a.x, ext(1)) && ffn16_apart(a.dx, ext(2), sp, need),
+                    "semicrf: ", name, ": `dx` overlaps dout, x or saved");
+    mirror((const E*)a.g, (const E*)a.x, sp, a.n0, a.n1, a.st[0], a.st[1], a.st[2], a.st[3], a.st[4], a.st[5], a.D, a.H, (const E*)a.W1,
+           (const E*)a.W2, (const E*)a.scale, (float)eps, (uint64_t)seed, p_hidden, p_out, (E*)a.dx, (E*)a.dW1, (E*)a.db1, (E*)a.dW2, (E*)a.db2,
+           (E*)a.dscale);
+}
+
+void ffn_residual_bf16_train_fwd_op(Tensor x, Tensor W1, Tensor b1, Tensor W2, Tensor b2, Tensor scale, double eps, int64_t seed, double p_hidden,
+                                    double p_out, Tensor out, Tensor saved)
+{
+    ffn16_train_fwd_device<uint16_t>(&semicrf_ffn_residual_bf16_train_fwd, "semicrf_ffn_residual_bf16_train_fwd", x, W1, b1, W2, b2, scale, eps, seed,
+                                     p_hidden, p_out, out, saved);
+}
+void ffn_residual_bf16_train_fwd_cpu(Tensor x, Tensor W1, Tensor b1, Tensor W2, Tensor b2, Tensor scale, double eps, int64_t seed, double p_hidden,
+                                     double p_out, Tensor out, Tensor saved)
+{
+    ffn16_train_fwd_host<uint16_t>(&semicrf_cpu::ffn_residual_bf16_train_fwd, "ffn_residual_bf16_train_fwd", x, W1, b1, W2, b2, scale, eps, seed,
+                                   p_hidden, p_out, out, saved);
+}
+void ffn_residual_bf16_mixed_train_fwd_op(Tensor x, Tensor W1, Tensor b1, Tensor W2, Tensor b2, Tensor scale, double eps, int64_t seed,
+                                          double p_hidden, double p_out, Tensor out, Tensor saved)
+{
+    ffn16_train_fwd_device<float>(&semicrf_ffn_residual_bf16_mixed_train_fwd, "semicrf_ffn_residual_bf16_mixed_train_fwd", x, W1, b1, W2, b2, scale, eps,
+                                  seed, p_hidden, p_out, out, saved);
+}
+void ffn_residual_bf16_mixed_train_fwd_cpu(Tensor x, Tensor W1, Tensor b1, Tensor W2, Tensor b2, Tensor scale, double eps, int64_t seed,
+                                           double p_hidden, double p_out, Tensor out, Tensor saved)
+{
+    ffn16_train_fwd_host<float>(&semicrf_cpu::ffn_residual_bf16_mixed_train_fwd, "ffn_residual_bf16_mixed_train_fwd", x, W1, b1, W2, b2, scale, eps,
+                                seed, p_hidden, p_out, out, saved);
+}
+void ffn_residual_bf16_bwd_op(Tensor dout, Tensor x, Tensor saved, Tensor W1, Tensor W2, Tensor scale, double eps, int64_t seed, double p_hidden,
+                              double p_out, Tensor dx, Tensor dW1, Tensor db1, Tensor dW2, Tensor db2, Tensor dscale, Tensor ws)
+{
+    ffn16_bwd_device<uint16_t>(&semicrf_ffn_residual_bf16_bwd, "semicrf_ffn_residual_bf16_bwd", dout, x, saved, W1, W2, scale, eps, seed, p_hidden, p_out,
+                               dx, dW1, db1, dW2, db2, dscale, ws);
+}
+void ffn_residual_bf16_bwd_cpu(Tensor dout, Tensor x, Tensor saved, Tensor W1, Tensor W2, Tensor scale, double eps, int64_t seed, double p_hidden,
+                               double p_out, Tensor dx, Tensor dW1, Tensor db1, Tensor dW2, Tensor db2, Tensor dscale, Tensor ws)
+{
+    ffn16_bwd_host<uint16_t>(&semicrf_cpu::ffn_residual_bf16_bwd, "ffn_residual_bf16_bwd", dout, x, saved, W1, W2, scale, eps, seed, p_hidden, p_out, dx,
+                             dW1, db1, dW2, db2, dscale, ws);
+}
+void ffn_residual_bf16_mixed_bwd_op(Tensor dout, Tensor x, Tensor saved, Tensor W1, Tensor W2, Tensor scale, double eps, int64_t seed, double p_hidden,
+                                    double p_out, Tensor dx, Tensor dW1, Tensor db1, Tensor dW2, Tensor db2, Tensor dscale, Tensor ws)
+{
+    ffn16_bwd_device<float>(&semicrf_ffn_residual_bf16_mixed_bwd, "semicrf_ffn_residual_bf16_mixed_bwd", dout, x, saved, W1, W2, scale, eps, seed,
+                            p_hidden, p_out, dx, dW1, db1, dW2, db2, dscale, ws);
+}
+void ffn_residual_bf16_mixed_bwd_cpu(Tensor dout, Tensor x, Tensor saved, Tensor W1, Tensor W2, Tensor scale, double eps, int64_t seed, double p_hidden,
+                                     double p_out, Tensor dx, Tensor dW1, Tensor db1, Tensor dW2, Tensor db2, Tensor dscale, Tensor ws)
+{
+    ffn16_bwd_host<float>(&semicrf_cpu::ffn_residual_bf16_mixed_bwd, "ffn_residual_bf16_mixed_bwd", dout, x, saved, W1, W2, scale, eps, seed, p_hidden,
+                          p_out, dx, dW1, db1, dW2, db2, dscale, ws);
+}
+
 // ---- the audio front end (semicrf_log_mel) -------------------------------------------------------------------------------------------
 // frames: a [N, C, nFrame, W] VIEW with sample stride 1 (its three other strides are read from the tensor: the overlapping unfold view
 // goes in as it is); windows [nWin, W], tw [W / 2, 2], fb_start / fb_len / fb_off [nMel] int32, fb_val [total], shift / denom [N] when
@@ -1827,6 +2006,15 @@ STABLE_TORCH_LIBRARY(semicrf, m)
           "-> ()");
     m.def("ffn_residual_bf16(Tensor x, Tensor W1, Tensor b1, Tensor W2, Tensor b2, Tensor scale, float eps, Tensor(a!) out) -> ()");
     m.def("ffn_residual_bf16_mixed(Tensor x, Tensor W1, Tensor b1, Tensor W2, Tensor b2, Tensor scale, float eps, Tensor(a!) out) -> ()");
+    m.def("ffn_residual_bf16_train_fwd(Tensor x, Tensor W1, Tensor b1, Tensor W2, Tensor b2, Tensor scale, float eps, int seed, float p_hidden, "
+          "float p_out, Tensor(a!) out, Tensor(b!) saved) -> ()");
+    m.def("ffn_residual_bf16_mixed_train_fwd(Tensor x, Tensor W1, Tensor b1, Tensor W2, Tensor b2, Tensor scale, float eps, int seed, "
+          "float p_hidden, float p_out, Tensor(a!) out, Tensor(b!) saved) -> ()");
+    m.def("ffn_residual_bf16_bwd(Tensor dout, Tensor x, Tensor saved, Tensor W1, Tensor W2, Tensor scale, float eps, int seed, float p_hidden, "
+          "float p_out, Tensor(a!) dx, Tensor(b!) dW1, Tensor(c!) db1, Tensor(d!) dW2, Tensor(e!) db2, Tensor(f!) dscale, Tensor(g!) ws) -> ()");
+    m.def("ffn_residual_bf16_mixed_bwd(Tensor dout, Tensor x, Tensor saved, Tensor W1, Tensor W2, Tensor scale, float eps, int seed, "
+          "float p_hidden, float p_out, Tensor(a!) dx, Tensor(b!) dW1, Tensor(c!) db1, Tensor(d!) dW2, Tensor(e!) db2, Tensor(f!) dscale, "
+          "Tensor(g!) ws) -> ()");
     m.def("log_mel(Tensor frames, Tensor windows, Tensor tw, Tensor fb_start, Tensor fb_len, Tensor fb_off, Tensor fb_val, int max_len, "
           "Tensor shift, Tensor denom, bool has_gain, bool log_flag, float eps, bool to_mono, Tensor(a!) out) -> ()");
     m.def("grad_sqnorm(Tensor flat, int numel, Tensor(a!) partials) -> ()");
@@ -1878,6 +2066,10 @@ STABLE_TORCH_LIBRARY_IMPL(semicrf, CPU, m)
     m.impl("ffn_dropout_mask", TORCH_BOX(&ffn_dropout_mask_cpu));
     m.impl("ffn_residual_bf16", TORCH_BOX(&ffn_residual_bf16_cpu));
     m.impl("ffn_residual_bf16_mixed", TORCH_BOX(&ffn_residual_bf16_mixed_cpu));
+    m.impl("ffn_residual_bf16_train_fwd", TORCH_BOX(&ffn_residual_bf16_train_fwd_cpu));
+    m.impl("ffn_residual_bf16_mixed_train_fwd", TORCH_BOX(&ffn_residual_bf16_mixed_train_fwd_cpu));
+    m.impl("ffn_residual_bf16_bwd", TORCH_BOX(&ffn_residual_bf16_bwd_cpu));
+    m.impl("ffn_residual_bf16_mixed_bwd", TORCH_BOX(&ffn_residual_bf16_mixed_bwd_cpu));
     m.impl("log_mel", TORCH_BOX(&log_mel_cpu));
     m.impl("grad_sqnorm", TORCH_BOX(&grad_sqnorm_cpu));
     m.impl("clip_from_history", TORCH_BOX(&clip_from_history_cpu));
@@ -1935,6 +2127,10 @@ STABLE_TORCH_LIBRARY_IMPL(semicrf, CUDA, m)
     m.impl("ffn_dropout_mask", TORCH_BOX(&ffn_dropout_mask_op));
     m.impl("ffn_residual_bf16", TORCH_BOX(&ffn_residual_bf16_op));
     m.impl("ffn_residual_bf16_mixed", TORCH_BOX(&ffn_residual_bf16_mixed_op));
+    m.impl("ffn_residual_bf16_train_fwd", TORCH_BOX(&ffn_residual_bf16_train_fwd_op));
+    m.impl("ffn_residual_bf16_mixed_train_fwd", TORCH_BOX(&ffn_residual_bf16_mixed_train_fwd_op));
+    m.impl("ffn_residual_bf16_bwd", TORCH_BOX(&ffn_residual_bf16_bwd_op));
+    m.impl("ffn_residual_bf16_mixed_bwd", TORCH_BOX(&ffn_residual_bf16_mixed_bwd_op));
     m.impl("log_mel", TORCH_BOX(&log_mel_op));
     m.impl("grad_sqnorm", TORCH_BOX(&grad_sqnorm_op));
     m.impl("clip_from_history", TORCH_BOX(&clip_from_history_op));
